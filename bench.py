@@ -19,14 +19,18 @@ Scaling.  `--batch_size 64` is the GLOBAL batch, exactly as the reference's flag
 processes batch_size // N impressions per step (trainer.py:218) and the gradients are averaged over the ranks -- the SAME
 optimisation problem at every N, so the headline line is STRONG scaling at global batch 64 (`scaling: "strong"`; BASELINE.json
 configs[3] = per-GPU batch 8 at N = 8: a regime bound by the 128-step dependent chain of the Bi-LSTM and by launch latency,
-not by throughput).  For N > 1 the same run also times WEAK scaling (64 impressions per GPU, global batch 64 N) and reports it
+not by throughput).  For N > 1 a --full run also times WEAK scaling (64 impressions per GPU, global batch 64 N) and reports it
 in the secondary `weak_scaling` object; `--weak` makes that the headline instead (`--no_weak` skips the leg).
 
-Prints ONE JSON line (rank 0): throughput, the roofline of the dominant kernel measured live with HIP events on the launch
-stream (+ `roofline.hbm`: the HBM-bound kernels of the step against the 8 TB/s peak), and a CPU baseline (the oracle with
-ATen's packed-sequence LSTM = the reference's nn.LSTM host path, timed on this box's cores on a bounded sample).
-`--config mhsa` runs BASELINE.json configs[1] (MHSA+MHSA) and adds the attention kernels' MFMA figures (`roofline.mhsa`).
-Exit code 3 if the CU-pair recurrence's exchange ever timed out (values poisoned)."""
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and reports the headline: `metric`, `value`
+(impressions/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the run's configuration.  `--dump-outputs DIR` then writes
+what the last timed step computed as float32 .npy files (dump_outputs); the inputs are seeded, so the same arguments give the same
+inputs in every run.  `--full` adds everything else the line used to carry: the roofline of the dominant kernel measured live with
+HIP events on the launch stream (+ `roofline.hbm`: the HBM-bound kernels of the step against the 8 TB/s peak), the isolated and
+sustained legs, the secondary legs over the other BASELINE.json configs, the exchange figures and the other scaling mode for N > 1,
+and a CPU baseline (the oracle with ATen's packed-sequence LSTM = the reference's nn.LSTM host path, timed on the host's cores on
+a bounded sample).  `--config mhsa` runs BASELINE.json configs[1] (MHSA+MHSA); with --full it adds the attention kernels' MFMA
+figures (`roofline.mhsa`).  Exit code 3 if the CU-pair recurrence's exchange ever timed out (values poisoned)."""
 import argparse
 import json
 import os
@@ -83,6 +87,11 @@ def parse(argv=None):
     ap.add_argument('--cpu_baseline_steps', type=int, default=2)
     ap.add_argument('--plumbing_check', action='store_true', help='CPU only (gloo): run the launcher + the product\'s flat-buffer / '
                     'exchange plumbing (trainer.FlatParams, nnr_amd.dp) on a stand-in module and print one JSON line; no HIP call')
+    ap.add_argument('--full', action='store_true', help='after the headline window, also run every other measurement: roofline (instrumented '
+                    'steps), isolated and sustained legs, secondary legs, exchange / other scaling mode (N > 1) and the CPU baseline; the '
+                    'options above that tune those legs apply only with --full')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', default=None, metavar='DIR', help='write what the last timed step computed '
+                    '(logits, loss, a fixed sample of every parameter after its update) as DIR/<name>.npy, float32')
     a = ap.parse_args(argv)
     if a.config == 'mhsa':
         a.news_encoder = a.user_encoder = 'MHSA'
@@ -143,8 +152,11 @@ def cpu_baseline(cfg, spec, batch_size, steps, headline_batch=0, headline_steps=
     corpus = SynthCorpus(spec)
     rng = np.random.default_rng(11)
     # thread count: the step is a chain of mid-size CPU GEMMs; probe a few intra-op thread counts with one step each (the
-    # first also warms up) and time the sample with the fastest
-    ncpu = os.cpu_count() or 1
+    # first also warms up) and time the sample with the fastest.  The probe stays within the CPUs this process may use (its
+    # affinity mask and OMP_NUM_THREADS when set): os.cpu_count() is the whole host's on a shared machine
+    ncpu = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
+    if os.environ.get('OMP_NUM_THREADS', '').isdigit() and int(os.environ['OMP_NUM_THREADS']) > 0:
+        ncpu = min(ncpu, int(os.environ['OMP_NUM_THREADS']))
     cands = sorted({min(ncpu, c) for c in (8, 16, 32, 64)})
     best, probe = None, {}
     for c in cands:
@@ -334,7 +346,8 @@ def measure_exchange(trainer, torch, dev, world, a):
 
 
 def timed_run(a, trainer, fresh, steps, warmup, prof, dp, torch, dev, world, prime_timing):
-    """W untimed + K timed steps bracketed by barrier + synchronize; returns the MAX over ranks of the elapsed seconds.  The window is
+    """W untimed + K timed steps bracketed by barrier + synchronize; returns the MAX over ranks of the elapsed seconds, the C-ABI calls
+    per timed step and what the last timed step returned (logits, loss: device tensors, complete on return).  The window is
     UN-INSTRUMENTED (no HIP event pair around any call of any timed step; round-5 verdict: two of the ten steps of a secondary leg carried
     per-call events and made the batch-8 leg 15 % pessimistic); the roofline's per-call durations come from instrumented_steps() AFTER it."""
     for i in range(warmup):
@@ -354,8 +367,9 @@ def timed_run(a, trainer, fresh, steps, warmup, prof, dp, torch, dev, world, pri
         marks[0].record()
     t0 = time.perf_counter()
     host = []
+    last = None
     for i in range(steps):
-        trainer.train_step(fresh(warmup + i))
+        last = trainer.train_step(fresh(warmup + i))
         if marks:
             marks[i + 1].record()
             host.append(time.perf_counter() - t0)
@@ -369,7 +383,34 @@ def timed_run(a, trainer, fresh, steps, warmup, prof, dp, torch, dev, world, pri
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     if world > 1:
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
-    return float(tmax), (_lib.CALLS[0] - calls0) / max(1, steps)
+    return float(tmax), (_lib.CALLS[0] - calls0) / max(1, steps), last
+
+
+PARAM_SAMPLE = 4096          # elements per parameter tensor in params_sample.npy (all of a smaller tensor)
+
+
+def dump_outputs(dirname, model, last):
+    """--dump-outputs: what the timed path computed in its last step, as float32 arrays -- `logits` and `loss` (what train_step returned)
+    and `params_sample` (the parameters after that step's update: per parameter in name order, a sample of PARAM_SAMPLE elements at
+    positions seeded by the parameter's name, or the whole tensor when smaller).  Call it before any further step: a replayed step
+    writes its logits / loss into the same buffers every time."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    logits, loss = last
+    parts = []
+    for name, p in sorted(model.named_parameters()):
+        flat = p.detach().reshape(-1)
+        if flat.numel() > PARAM_SAMPLE:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(flat.numel(), PARAM_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        parts.append(flat.float().cpu())
+    arrays = {'logits': logits.float().cpu().numpy(), 'loss': loss.float().cpu().numpy().reshape(1),
+              'params_sample': torch.cat(parts).numpy()}
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + '.npy'), np.ascontiguousarray(v, dtype=np.float32))
+    return {k: list(v.shape) for k, v in arrays.items()}
 
 
 def instrumented_steps(trainer, fresh, n, first, prof, torch):
@@ -444,7 +485,7 @@ def secondary_legs(a, prof, dp, torch, dev, rank_seed=0):
             dc = from_synth(SynthCorpus(spec), 4096, rng, dev, graph='build')
             order = [torch.from_numpy(rng.permutation(4096)[:per_gpu].astype(np.int32)).to(dev) for _ in range(steps + warm)]
             src = lambda i: dc.train_batch(order[i % len(order)])
-            dt, calls = timed_run(a, trainer, src, steps, warm, prof, dp, torch, dev, 1, True)
+            dt, calls, _ = timed_run(a, trainer, src, steps, warm, prof, dp, torch, dev, 1, True)
             sampled = instrumented_steps(trainer, src, max(1, a.roofline_steps), warm + steps, prof, torch)
             roof = prof.roofline(PEAK_F32_TFLOPS, sampled_steps=sampled, ms_per_step=1000 * dt / steps) or {}
             for v in (roof.get('hbm') or {}).values():      # (the committed PMC passes are of the headline command only)
@@ -544,10 +585,15 @@ def main():
 
     headline_batches = batch_source(per_gpu)      # the SAME resident batches serve the timed region, the sustained leg and the isolated leg (a
                                                   # MIND-shaped batch of 64 varies by +-6 % in tokens: other draws are another workload)
-    dt, calls = timed_run(a, trainer, headline_batches, a.steps, a.warmup, prof, dp, torch, dev, world, True)
+    # (prime_timing only with --full: the discarded timing replay of the last warm-up step serves the instrumented steps after the window)
+    dt, calls, last = timed_run(a, trainer, headline_batches, a.steps, a.warmup, prof, dp, torch, dev, world, a.full)
     bx3_seen_headline = dict(ops.BX3_SEEN)
-    sampled = instrumented_steps(trainer, headline_batches, max(1, a.roofline_steps), a.warmup + a.steps, prof, torch)
-    roof = prof.roofline(PEAK_F32_TFLOPS, sampled_steps=sampled, ms_per_step=1000 * dt / a.steps)
+    dumped = dump_outputs(a.dump_outputs, trainer.model, last) if (a.dump_outputs and rank == 0) else None
+    del last
+    roof = None
+    if a.full:
+        sampled = instrumented_steps(trainer, headline_batches, max(1, a.roofline_steps), a.warmup + a.steps, prof, torch)
+        roof = prof.roofline(PEAK_F32_TFLOPS, sampled_steps=sampled, ms_per_step=1000 * dt / a.steps)
     if roof:
         roof['timed_window'] = 'un-instrumented; per-call HIP events from %d extra steps after the window (same resident batches)' % sampled
         # (the committed kernel tables are of the HEADLINE command: other batch sizes / encoder pairs launch the same kernels at other sizes)
@@ -596,29 +642,29 @@ def main():
                                 'how': 'same launches of 2 extra untimed steps, every HIP stream of the step collapsed into one'}
 
     sustained = None
-    if a.sustained_seconds > 0:
+    if a.full and a.sustained_seconds > 0:
         # the driver's K = 20 steps are 0.2 s of GPU time; the same loop for >= 3 s shows the clocks the chip holds under this load
         n_sus = max(a.steps, int(a.sustained_seconds / max(1e-4, dt / a.steps)) + 1)
-        sdt_, _ = timed_run(a, trainer, headline_batches, n_sus, 0, prof, dp, torch, dev, world, False)
+        sdt_, _, _ = timed_run(a, trainer, headline_batches, n_sus, 0, prof, dp, torch, dev, world, False)
         sustained = {'seconds': round(sdt_, 3), 'steps': n_sus, 'ms_per_step': round(1000 * sdt_ / n_sus, 3),
                      'value': round(n_sus * global_batch / sdt_, 2), 'unit': 'impressions/s'}
 
     exchange = None
-    if world > 1:
+    if a.full and world > 1:
         exchange = measure_exchange(trainer, torch, dev, world, a)
 
     other = None
-    if world > 1 and not a.no_weak:
+    if a.full and world > 1 and not a.no_weak:
         # the OTHER scaling mode of the same job, as a secondary object: weak scaling (batch_size impressions per GPU) beside the
         # strong-scaling headline, or -- under --weak -- the reference's global-batch semantics beside the weak headline
         op_, og_ = shard_sizes(a.batch_size, world, not weak)
         if op_ >= 1 and op_ != per_gpu:
-            odt, ocalls = timed_run(a, trainer, batch_source(op_), a.steps, max(3, a.warmup // 2), prof, dp, torch, dev, world, False)
+            odt, ocalls, _ = timed_run(a, trainer, batch_source(op_), a.steps, max(3, a.warmup // 2), prof, dp, torch, dev, world, False)
             other = {'scaling': 'strong' if weak else 'weak', 'global_batch': og_, 'per_gpu_batch': op_, 'value': round(a.steps * og_ / odt, 2),
                      'unit': 'impressions/s', 'ms_per_step': round(1000 * odt / a.steps, 3), 'abi_calls_per_step': round(ocalls, 1)}
 
     secondary = None
-    if world == 1 and not a.no_secondary and headline:
+    if a.full and world == 1 and not a.no_secondary and headline:
         secondary = secondary_legs(a, prof, dp, torch, dev)
 
     exchange_timeouts = ops.lstm_sync_timeouts()      # persistent device counter over EVERY pair-kernel launch of this process
@@ -649,19 +695,22 @@ def main():
                        'launch_path': launch_path(trainer),
                        'gradient_exchange': trainer.exchange.describe() if world > 1 else 'none (1 GPU)',
                        'recurrence_exchange_timeouts': exchange_timeouts},
-            'roofline': roof,
         }
+        if a.full:
+            out['roofline'] = roof
+        if dumped is not None:
+            out['dumped_outputs'] = {'dir': a.dump_outputs, 'arrays': dumped, 'dtype': 'float32'}
         if sustained is not None:
             out['sustained'] = sustained
         if exchange is not None:
             out['exchange'] = exchange
-        if world > 1:
+        if a.full and world > 1:
             out['scaling_ceiling'] = scaling_ceiling(per_gpu, global_batch)
         if other is not None:
             out['weak_scaling' if other['scaling'] == 'weak' else 'strong_scaling'] = other
         if secondary is not None:
             out['secondary'] = secondary
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out['cpu_baseline'] = cpu_baseline(cfg, spec, a.cpu_baseline_batch, a.cpu_baseline_steps,
                                                headline_batch=per_gpu if a.cpu_baseline_headline_steps > 0 else 0, headline_steps=a.cpu_baseline_headline_steps,
                                                headline_threads=a.cpu_baseline_headline_threads)

@@ -85,7 +85,7 @@ def test_gradient_exchange_buckets_cover_the_flat_buffer_exactly_once():
 
 
 def test_secondary_legs_name_every_other_baseline_config():
-    """`bench.py --gpus 1` reports every other BASELINE.json config it can run on one GPU under `secondary` (round-4 verdict, item 3).
+    """`bench.py --gpus 1 --full` reports every other BASELINE.json config it can run on one GPU under `secondary` (round-4 verdict, item 3).
     CPU side of that contract: the leg table matches BASELINE.json's configs (encoder pair, dataset, global batch / GPU count ->
     per-GPU shard, trainer.py:218), the reference's per-dataset overrides apply (config.py:85-94), and the plumbing line says which
     keys a GPU run adds.  (The legs themselves need the MI355X; profiles/r05_bench.json is a driver-shaped run.)"""
@@ -127,3 +127,40 @@ def test_secondary_legs_name_every_other_baseline_config():
         assert line['dtype'] == 'f32' and 'bf16x3' in line['config']['matrix_path']['nt_weight_gemms']
         r = line['roofline']
         assert set(r['rocprof']) >= {'in_step_avg_us', 'solo_avg_us', 'frac_in_step', 'frac_solo'} and r['step']['gflop_executed'] >= r['step']['gflop_algorithmic']
+
+
+def test_plain_run_flags_default_to_the_headline_only():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times the headline only: every other leg waits for --full, and no outputs are
+    written unless --dump-outputs names a directory."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(['--gpus', '1', '--steps', '7', '--warmup', '3'])
+    assert a.steps == 7 and a.warmup == 3 and a.full is False and a.dump_outputs is None
+    a = bench.parse(['--full', '--dump-outputs', 'out'])
+    assert a.full is True and a.dump_outputs == 'out'
+
+
+@pytest.mark.gpu
+def test_plain_run_reports_the_headline_and_dumps_the_last_step(tmp_path):
+    """The plain run on the MI355X: the result line carries the headline keys and nothing of the --full legs, `steps` timed steps,
+    and --dump-outputs writes the last timed step's logits / loss / parameter sample as finite float32 arrays -- the same arrays in a
+    second run with the same arguments (seeded inputs, reproducible gradients)."""
+    import numpy as np
+    outs = []
+    for k in range(2):
+        d = tmp_path / ('run%d' % k)
+        r, out = _run(['--gpus', '1', '--steps', '3', '--warmup', '4', '--dump-outputs', str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert out is not None and out['steps'] == 3 and out['warmup'] == 4
+        assert out['higher_is_better'] is True and out['dtype'] == 'f32' and out['unit'] == 'impressions/s'
+        assert out['ms_per_step'] > 0 and abs(out['value'] - 64 * 1000.0 / out['ms_per_step']) <= 0.01 * out['value']
+        assert not {'roofline', 'sustained', 'secondary', 'cpu_baseline'} & set(out)
+        arrays = {}
+        for name in ('logits', 'loss', 'params_sample'):
+            v = np.load(d / (name + '.npy'))
+            assert v.dtype == np.float32 and np.isfinite(v).all(), name
+            arrays[name] = v
+        assert arrays['logits'].shape == (64, 5) and arrays['loss'].shape == (1,)
+        outs.append(arrays)
+    for name in outs[0]:
+        np.testing.assert_array_equal(outs[0][name], outs[1][name], err_msg=name)

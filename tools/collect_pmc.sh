@@ -4,7 +4,7 @@ TAG=${1:-r03}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/profiles_$TAG
 mkdir -p $OUT
-CMD="python3 $ROOT/bench.py --steps 6 --warmup 3 --no_cpu_baseline --no_isolated --sustained_seconds 0"
+CMD="python3 $ROOT/bench.py --full --steps 6 --warmup 3 --no_cpu_baseline --no_isolated --sustained_seconds 0"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pmc_$TAG
 export NNR_REPLAY=${NNR_REPLAY:-0}

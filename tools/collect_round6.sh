@@ -13,8 +13,8 @@ cd $ROOT
 export PYTHONWARNINGS=ignore
 O=$ROOT/gpurun_out/profiles_$TAG
 mkdir -p $O
-python3 bench.py > $O/bench_first.json 2> $O/bench_first.err
-CMD="python3 $ROOT/bench.py --steps 12 --warmup 4 --no_cpu_baseline --no_isolated --no_secondary --sustained_seconds 0"
+python3 bench.py --full > $O/bench_first.json 2> $O/bench_first.err
+CMD="python3 $ROOT/bench.py --full --steps 12 --warmup 4 --no_cpu_baseline --no_isolated --no_secondary --sustained_seconds 0"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_$TAG
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG/kt -- $CMD > $O/bench_under_kernel_trace.json 2> $O/kt.err
@@ -35,20 +35,20 @@ cp $O/pmc_traffic.json profiles/pmc_traffic.json 2>/dev/null
 python3 tools/kernel_stats_json.py $O/kernel_stats.csv $O/one_stream_kernel_stats.csv $O/kernel_stats.json > $O/kernel_stats.txt 2>&1
 cp $O/kernel_stats.json profiles/kernel_stats.json 2>/dev/null
 # MHSA + MHSA (BASELINE configs[1]): kernel table, matrix-pipe busy counters, then the bench line that quotes them
-MH="python3 $ROOT/bench.py --config mhsa --steps 12 --warmup 4 --no_cpu_baseline --no_isolated --no_secondary --sustained_seconds 0"
+MH="python3 $ROOT/bench.py --full --config mhsa --steps 12 --warmup 4 --no_cpu_baseline --no_isolated --no_secondary --sustained_seconds 0"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG/mhsa -- $MH > $O/bench_mhsa_traced.json 2> $O/mhsa_kt.err
 F=$(find /tmp/prof_$TAG/mhsa -name "*kernel_stats.csv" | head -1); [ -n "$F" ] && cp $F $O/mhsa_kernel_stats.csv
-NNR_REPLAY=0 timeout 900 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d /tmp/prof_${TAG}_mfma -- python3 $ROOT/bench.py --config mhsa --steps 6 --warmup 3 --no_cpu_baseline --no_isolated --no_secondary --sustained_seconds 0 > $O/bench_mhsa_under_pmc.json 2> $O/mfma_pmc.err
+NNR_REPLAY=0 timeout 900 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d /tmp/prof_${TAG}_mfma -- python3 $ROOT/bench.py --full --config mhsa --steps 6 --warmup 3 --no_cpu_baseline --no_isolated --no_secondary --sustained_seconds 0 > $O/bench_mhsa_under_pmc.json 2> $O/mfma_pmc.err
 # the per-GPU shards of configs[3] (batch 8) and configs[4] (batch 16, V = 130 000, MIND-large dropout 0.1): kernel tables
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG/b8 -- python3 $ROOT/bench.py --batch_size 8 --steps 16 --warmup 6 --no_cpu_baseline --no_isolated --no_secondary --sustained_seconds 0 > $O/bench_b8_traced.json 2> $O/b8_kt.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG/b8 -- python3 $ROOT/bench.py --full --batch_size 8 --steps 16 --warmup 6 --no_cpu_baseline --no_isolated --no_secondary --sustained_seconds 0 > $O/bench_b8_traced.json 2> $O/b8_kt.err
 F=$(find /tmp/prof_$TAG/b8 -name "*kernel_stats.csv" | head -1); [ -n "$F" ] && cp $F $O/b8_kernel_stats.csv
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG/v130 -- python3 $ROOT/bench.py --batch_size 16 --vocabulary_size 130000 --steps 16 --warmup 6 --no_cpu_baseline --no_isolated --no_secondary --sustained_seconds 0 > $O/bench_b16_v130000_traced.json 2> $O/v130_kt.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG/v130 -- python3 $ROOT/bench.py --full --batch_size 16 --vocabulary_size 130000 --steps 16 --warmup 6 --no_cpu_baseline --no_isolated --no_secondary --sustained_seconds 0 > $O/bench_b16_v130000_traced.json 2> $O/v130_kt.err
 F=$(find /tmp/prof_$TAG/v130 -name "*kernel_stats.csv" | head -1); [ -n "$F" ] && cp $F $O/b16_v130000_kernel_stats.csv
 cd $ROOT
 python3 tools/pmc_mfma_busy.py /tmp/prof_${TAG}_mfma $O/pmc_mfma_busy.json > $O/pmc_mfma_busy.txt 2>&1
 cp $O/pmc_mfma_busy.json profiles/pmc_mfma_busy.json 2>/dev/null
-B="python3 bench.py --no_cpu_baseline --no_isolated --no_secondary --sustained_seconds 2"
+B="python3 bench.py --full --no_cpu_baseline --no_isolated --no_secondary --sustained_seconds 2"
 $B --prebuilt > $O/bench_prebuilt.json 2>> $O/bench2.err
 for b in 8 16 32 128; do $B --batch_size $b --steps 40 --warmup 8 > $O/bench_b$b.json 2>> $O/bench2.err; done
 $B --steps 40 --warmup 8 > $O/bench_b64.json 2>> $O/bench2.err
@@ -65,12 +65,12 @@ for b in (8, 16, 32, 64, 128):
         ms[str(b)] = d['ms_per_step']
     except Exception as e:
         print('batch', b, 'FAILED', e)
-json.dump({'build_id': _lib.build_id(), 'ms_per_step': ms, 'how': 'bench.py --batch_size B --steps 40 --warmup 8 --no_secondary on one MI355X (un-instrumented 40-step window)'},
+json.dump({'build_id': _lib.build_id(), 'ms_per_step': ms, 'how': 'bench.py --full --batch_size B --steps 40 --warmup 8 --no_secondary on one MI355X (un-instrumented 40-step window)'},
           open('$O/batch_sweep.json', 'w'), indent=1)
 print(ms)
 PY
 cp $O/batch_sweep.json profiles/batch_sweep.json 2>/dev/null
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 timeout 300 python3 tools/tape_timeline.py --batch_size 64 > $O/timeline_b64.txt 2>&1
 timeout 300 python3 tools/tape_timeline.py --batch_size 8 > $O/timeline_b8.txt 2>&1
 timeout 300 python3 tools/phase_table.py --json $O/phase_b64.json > $O/phase_b64.txt 2>&1
