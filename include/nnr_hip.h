@@ -83,7 +83,7 @@ typedef struct nnr_gemm_args {
   float drop_scale;
   int vec_epi;
   int sched;                /* token-reduction (split-K) launches: bits 0-1 how workgroups are dealt to the XCDs, bits 2-7 / 8+ tuning
-                             * overrides of the device-side slice count (NNR_TN_DEAL / NNR_TN_WANT / NNR_TN_STAGES) */
+                             * overrides of the device-side slice count (workgroup target / stages per slice; 0 = defaults) */
   /* reproducible split-K (trans_a = trans_b = 1, split_k > 1, N % 4 == 0): with `slab` set, slice z STORES its partial M x N result to
    * slab[z] and a second launch adds the live slices in slice order into C (and the fused column sums into colsum_out): no f32
    * atomics inside the reduction, bit-identical gradients from run to run (config.py:125-130).  slab_floats >= split_k * (M * N + M). */

@@ -621,7 +621,7 @@ __global__ __launch_bounds__(256, OCC) void gemm_nt_pipe_kernel(nnr_gemm_args g)
   // wholly beyond N (2 of 5 at N = 200: 13 % of the launch's matrix work; 1 of 5 at N = 300, 3 of 5 at N = 900: 5 %) only ever multiplied clamped rows into
   // columns that are never stored.  Those workgroups take a second instantiation of the stage loop that skips them (uniform branches per tile); every
   // accumulator that IS stored sees the same MFMAs in the same order: results are bit-identical.
-  const int nv = (g.sched & 1) ? min(TN, (N - n0 + 15) >> 4) : TN;      // (g.sched bit 0: set by the launcher unless NNR_RAGGED=0 -- A/B)
+  const int nv = (g.sched & 1) ? min(TN, (N - n0 + 15) >> 4) : TN;      // (g.sched bit 0: set by the launcher, kNtRagged)
   auto run = [&](auto full_tag) {
     constexpr bool FULL = decltype(full_tag)::value;
     for (int s = 0; s < S; ++s) {
@@ -910,16 +910,14 @@ __global__ __launch_bounds__(256, OCC) void gemm_nt_pipe2_kernel(nnr_gemm_args g
   gemm_epilogue<TM, TN>(g, acc, lds, C, m0, n0, M, N, z);
 }
 
-static int nt_ragged_bit() {
-  static const int on = [] { const char* e = getenv("NNR_RAGGED"); return (e && atoi(e) == 0) ? 0 : 1; }();      // A/B: 0 = every tile of a ragged last column block / reduction tail is multiplied
-  return on;
-}
+// g.sched bit 0 of the NT pipe kernels: skip the empty fragments of a ragged last column block / reduction tail
+constexpr int kNtRagged = 1;
 
 template <int TM, int TN, int NS, int OCC>
 int launch_pipe2(const nnr_gemm_args& g0, hipStream_t s) {
   constexpr int BM = 64 * TM, BN = 16 * TN;
   nnr_gemm_args g = g0;
-  g.sched = nt_ragged_bit();
+  g.sched = kNtRagged;
   const int nbm = (g.M + BM - 1) / BM, nbn = (g.N + BN - 1) / BN;
   dim3 grid(nbm * nbn, 1, g.batch > 1 ? g.batch : 1), block(256);
   hipLaunchKernelGGL((gemm_nt_pipe2_kernel<TM, TN, NS, OCC>), grid, block, 0, s, g);
@@ -931,7 +929,7 @@ template <int TM, int TN, int BK, int NS, int OCC, int PRIO = 0>
 int launch_pipe(const nnr_gemm_args& g0, hipStream_t s) {
   constexpr int BM = 64 * TM, BN = 16 * TN;
   nnr_gemm_args g = g0;
-  g.sched = nt_ragged_bit();
+  g.sched = kNtRagged;
   const int nbm = (g.M + BM - 1) / BM, nbn = (g.N + BN - 1) / BN;
   dim3 grid(nbm * nbn, 1, g.batch > 1 ? g.batch : 1), block(256);
   hipLaunchKernelGGL((gemm_nt_pipe_kernel<TM, TN, BK, NS, OCC, PRIO>), grid, block, 0, s, g);
@@ -1386,13 +1384,9 @@ __global__ __launch_bounds__(256, OCC) void gemm_tn_pipe_kernel(nnr_gemm_args g)
   gemm_epilogue<TM, TN>(g, acc, lds, g.slab_mode ? g.C + (long)z * M * N : g.C, m0, n0, M, N, z);
 }
 
-// deal mode / slice-count tuning knobs of the split-K token reductions, as the kernels and the slab reduction read them from g.sched
-static int tn_sched_bits() {
-  static const int deal_mode = [] { const char* e = getenv("NNR_TN_DEAL"); return e ? atoi(e) : 1; }();      // A/B: 0 = tiles of a slice spread over the XCDs
-  static const int want_code = [] { const char* e = getenv("NNR_TN_WANT"); return e ? atoi(e) / 64 : 0; }();    // tuning: minimum workgroup count (default 512)
-  static const int stage_code = [] { const char* e = getenv("NNR_TN_STAGES"); return e ? atoi(e) : 0; }();       // tuning: stages per split-K slice (default 96)
-  return (deal_mode & 3) | ((want_code & 63) << 2) | (stage_code << 8);
-}
+// g.sched of the split-K token reductions, as the kernels and the slab reduction read it: deal mode 1 (the tiles of a slice on one XCD),
+// default workgroup target (512) and stages per slice (96)
+constexpr int kTnSched = 1;
 
 template <int TM, int TN, int NS, int OCC, int PRIO = 0>
 int launch_tn_pipe(const nnr_gemm_args& g, hipStream_t s) {
@@ -1400,7 +1394,7 @@ int launch_tn_pipe(const nnr_gemm_args& g, hipStream_t s) {
   const int nbm = (g.M + BM - 1) / BM, nbn = (g.N + BN - 1) / BN;
   dim3 grid(g.split_k > 1 ? nbm * nbn * ((g.split_k + 7) / 8) * 8 : nbm * nbn), block(256);      // split-K: slices are dealt to XCDs (see the kernel)
   nnr_gemm_args gg = g;
-  gg.sched = tn_sched_bits();
+  gg.sched = kTnSched;
   hipLaunchKernelGGL((gemm_tn_pipe_kernel<TM, TN, NS, OCC, PRIO>), grid, block, 0, s, gg);
   NNR_CHECK_LAUNCH();
   return NNR_OK;
@@ -1660,7 +1654,7 @@ int launch_tn_pipe2(const nnr_gemm_args& g, hipStream_t s) {
   const int nbm = (g.M + BM - 1) / BM, nbn = (g.N + BN - 1) / BN;
   dim3 grid(g.split_k > 1 ? nbm * nbn * ((g.split_k + 7) / 8) * 8 : nbm * nbn), block(256);      // split-K: slices are dealt to XCDs (see the kernel)
   nnr_gemm_args gg = g;
-  gg.sched = tn_sched_bits();
+  gg.sched = kTnSched;
   hipLaunchKernelGGL((gemm_tn_pipe2_kernel<TM, TN, NS, OCC>), grid, block, 0, s, gg);
   NNR_CHECK_LAUNCH();
   return NNR_OK;
@@ -1795,14 +1789,12 @@ __global__ __launch_bounds__(64 * NW) void skinny_gemm_kernel(nnr_gemm_args g) {
 int launch_skinny(const nnr_gemm_args& g, hipStream_t s) {
   const int tiles = ((g.M + 15) / 16) * ((g.N + 79) / 80) * (g.batch > 1 ? g.batch : 1);
   dim3 grid(((g.M + 15) / 16) * ((g.N + 79) / 80), 1, g.batch > 1 ? g.batch : 1);
-  static const int force = [] { const char* e = getenv("NNR_SKINNY_WAVES"); return e ? atoi(e) : 0; }();      // A/B: 4 = the round 1-3 kernel everywhere
-  int nw = 4;
-  if (tiles <= 640 && g.K >= 384) nw = 8;              // every workgroup resident at once (43 KB of LDS): 8 waves.  (16 waves for the handful-of-tiles
-                                                       // launches measured no better than 8 -- batch 8: 26.2 vs 23.6 us per launch incl. dispatch gaps, 28.7 with 4)
-  if (force == 4 || force == 8 || force == 16) nw = force;
+  // every workgroup resident at once (43 KB of LDS): 8 waves.  (16 waves for the handful-of-tiles launches measured no better than 8 --
+  // batch 8: 26.2 vs 23.6 us per launch incl. dispatch gaps, 28.7 with 4)
+  const bool w8 = tiles <= 640 && g.K >= 384;
 #define NNR_SKINNY(TBV, NWV) hipLaunchKernelGGL((skinny_gemm_kernel<TBV, NWV>), grid, dim3(64 * NWV), 0, s, g)
-  if (g.trans_b) { if (nw == 16) NNR_SKINNY(true, 16); else if (nw == 8) NNR_SKINNY(true, 8); else NNR_SKINNY(true, 4); }
-  else { if (nw == 16) NNR_SKINNY(false, 16); else if (nw == 8) NNR_SKINNY(false, 8); else NNR_SKINNY(false, 4); }
+  if (g.trans_b) { if (w8) NNR_SKINNY(true, 8); else NNR_SKINNY(true, 4); }
+  else { if (w8) NNR_SKINNY(false, 8); else NNR_SKINNY(false, 4); }
 #undef NNR_SKINNY
   NNR_CHECK_LAUNCH();
   return NNR_OK;
@@ -1954,17 +1946,15 @@ extern "C" int nnr_gemm_f32(const nnr_gemm_args* a, hipStream_t stream) {
     const long wg64 = (long)((g.M + 63) / 64) * ((g.N + 79) / 80) * (g.split_k > 1 ? g.split_k : (g.batch > 1 ? g.batch : 1));
     const bool plain = !g.trans_a && !g.a_idx && !g.b_idx && !g.c_idx && !g.dyn_dev && g.split_k <= 1 && g.k_chunk <= 0 && !g.rowdot_w &&
                        !g.colsum_out && !g.atomic && (g.drop_target == 0 || g.drop_target == 3) && !g.pre_add && !g.gate_bwd;
-    static const bool use_t9 = [] { const char* e = getenv("NNR_NT9"); return !(e && atoi(e) == 0); }();   // A/B
-    static const bool use_pipe = [] { const char* e = getenv("NNR_GEMM_PIPE"); return !(e && atoi(e) == 0); }();   // A/B switch
     if (g.rowdot_w) tile = 3;
     else if (plain && wg64 <= 512 && g.K >= 64) tile = 7;   // small row-parallel launch: 16 x 80 tiles, K split over the 4 waves
-    else if (use_pipe && use_t9 && pipe_ok(g) && !g.a_idx && g.K >= 800 && wg64 > 512) {
+    else if (pipe_ok(g) && !g.a_idx && g.K >= 800 && wg64 > 512) {
       tile = 9;              // long reductions (dX: K = 1664, SUE: K = 900): the
                              // software-pipelined loop with the lean DMA issue, 2 workgroups / CU (130 vs 112 TF, 93 vs 79 TF)
     }
-    else if (use_pipe && pipe_ok(g) && (g.dyn_dev || wg128 >= 640)) tile = 15;   // GPU-filling NT: LDS-DMA staged 128 x 80, BK 16, 4 workgroups / CU
+    else if (pipe_ok(g) && (g.dyn_dev || wg128 >= 640)) tile = 15;   // GPU-filling NT: LDS-DMA staged 128 x 80, BK 16, 4 workgroups / CU
                              // (112 vs 98 TF on the 131 072-row CNE shapes, tools/gemm_pipe_bench.py)
-    else if (use_pipe && pipe_ok(g) && wg64 > 512 && g.K >= 128) tile = 16;      // mid-size NT (SUE: 4 352 x 900 x 900): same tile, two 13 KB stages,
+    else if (pipe_ok(g) && wg64 > 512 && g.K >= 128) tile = 16;      // mid-size NT (SUE: 4 352 x 900 x 900): same tile, two 13 KB stages,
                              // 5-6 workgroups / CU cover the round trips (79 vs 65-72 TF)
     else if (wg64 <= 512 && !g.dyn_dev && g.k_chunk <= 0 && g.K >= 128 && !g.trans_a) tile = 6;   // (not for TN: the small weight-gradient
                              // launches run on the leaf stream BESIDE the recurrence, whose workgroups hold 98 KB of LDS per CU; a 74 KB tile cannot
@@ -1984,7 +1974,7 @@ extern "C" int nnr_gemm_f32(const nnr_gemm_args* a, hipStream_t stream) {
   const long mn4 = ((long)g.M * g.N) >> 2;
   const int blocks = (int)(mn4 / 256 + 1 > 2048 ? 2048 : mn4 / 256 + 1);
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)g.slab, (const float*)g.colsum_out, slab_C, slab_ldc, slab_cs,
-                     g.M, g.N, g.K, g.dyn_dim == 2 ? g.dyn_dev : (const int*)nullptr, g.split_k, tn_sched_bits(), nblk, occ * 256, bk, kind);
+                     g.M, g.N, g.K, g.dyn_dim == 2 ? g.dyn_dev : (const int*)nullptr, g.split_k, kTnSched, nblk, occ * 256, bk, kind);
   NNR_CHECK_LAUNCH();
   return NNR_OK;
 }

@@ -1332,15 +1332,9 @@ template <int UB>
 int launch_pair(const LstmArgs& a, bool backward, int max_tiles, hipStream_t s) {
   const int tiles = max_tiles + (a.quad_T > 0 ? MAXQ : 0);             // quad tiles take the first ids; whatever is not needed exits
   dim3 grid(((tiles + 7) / 8) * 16 * 2 * a.nprob), block(512);         // groups of 8 tiles x 2 halves, see pair_id()
-  static const bool bal = [] { const char* e = getenv("NNR_LSTM_BWD_BAL"); return !(e && atoi(e) == 0); }();      // A/B: 0 = the legacy whole-tile split
-  if (backward) {
-    if constexpr (UB == 13) {
-      if (bal) hipLaunchKernelGGL((lstm_bwd_pair_kernel<UB, true>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((lstm_bwd_pair_kernel<UB, false>), grid, block, 0, s, a);
-    } else {
-      hipLaunchKernelGGL((lstm_bwd_pair_kernel<UB, false>), grid, block, 0, s, a);
-    }
-  } else hipLaunchKernelGGL((lstm_fwd_pair_kernel<UB>), grid, block, 0, s, a);
+  static_assert(UB == 13, "the balanced split of the backward pair kernel is laid out for 13 unit blocks");
+  if (backward) hipLaunchKernelGGL((lstm_bwd_pair_kernel<UB, true>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((lstm_fwd_pair_kernel<UB>), grid, block, 0, s, a);
   NNR_CHECK_LAUNCH();
   return NNR_OK;
 }
@@ -1439,7 +1433,6 @@ static int lstm_run(const nnr_lstm_problem* probs, int nprob, int H, bool backwa
     for (int i = 0; i < nprob; ++i) maxn = max(maxn, a.p[i].n);
     const char* e = getenv("NNR_LSTM_QUAD_T");
     a.quad_T = e ? atoi(e) : (maxn <= 1024 ? 16 : (maxn <= 2048 ? 64 : 96));
-    if (backward) { const char* eb = getenv("NNR_LSTM_QUAD_T_BWD"); if (eb) a.quad_T = atoi(eb); }      // (A/B: own threshold for the backward launches)
   }
   // 2-CU weights-stationary recurrence when the caller provides the exchange workspace
   bool pair = UB == 13 && (H % 2 == 0);

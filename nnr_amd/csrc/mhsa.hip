@@ -721,9 +721,8 @@ static int mhsa_bwd_launch(const float* qkv, const uint8_t* mask, const int* row
   if (rowmap && (!coop || prob)) return NNR_ERR_UNSUPPORTED;
   const size_t shm = ((size_t)waves * (4 * LP * SD + LP * (LP + 1)) + 16) * sizeof(float);
   const int blocks = (n * heads + waves - 1) / waves;
-  static const int persist = [] { const char* e = getenv("NNR_MHSA_PERSIST"); return e ? atoi(e) : 1; }();      // A/B: 0 = one 4-head group per workgroup
   if (pair_off && !(coop && !prob && 32 * dh <= 768)) return NNR_ERR_UNSUPPORTED;      // paired titles: the persistent 4-head kernel only
-  if ((persist || pair_off) && coop && !prob && 32 * dh <= 768) {
+  if (coop && !prob && 32 * dh <= 768) {
     // one workgroup per sample's heads (heads / 4 groups), or fewer groups when that leaves the chip short of workgroups
     const int ngroups = n * heads / 4;
     int gp = heads / 4;

@@ -588,18 +588,11 @@ static int pool_launch(const nnr_pool_args* p, hipStream_t stream) {
   const PoolArgs a = to_args(p);
   const dim3 grid(p->n), block(256);
   const int nv = (p->D + 3) / 4;
-  // A/B switches: NNR_POOL_TEAM bit 0 = forward, bit 1 = backward through the register-resident kernels (0 = one streaming workgroup per sequence,
-  // rounds 1-5); NNR_POOL_R = rows a wave keeps (16: 2 waves / SIMD, single-wave teams up to 16 tokens, shared up to 64; 8: 4 waves / SIMD, 8 / 32)
-  static const int team = [] { const char* e = getenv("NNR_POOL_TEAM"); return e ? atoi(e) : 3; }();
-  static const int rows = [] { const char* e = getenv("NNR_POOL_R"); return e ? atoi(e) : 8; }();
-  if ((team & (BWD ? 2 : 1)) && p->packed && nv <= 128 && p->L <= 128) {
-    if (rows >= 16) {
-      if (nv <= 64) hipLaunchKernelGGL((pool_packed_kernel<BWD, 1, 16>), grid, block, 0, stream, a);
-      else hipLaunchKernelGGL((pool_packed_kernel<BWD, 2, 16>), grid, block, 0, stream, a);
-    } else {
-      if (nv <= 64) hipLaunchKernelGGL((pool_packed_kernel<BWD, 1, 8>), grid, block, 0, stream, a);
-      else hipLaunchKernelGGL((pool_packed_kernel<BWD, 2, 8>), grid, block, 0, stream, a);
-    }
+  // packed streams: the register-resident team kernels, 8 rows per wave (4 waves / SIMD, single-wave teams up to 8 tokens, shared up to 32);
+  // anything else: one streaming workgroup per sequence
+  if (p->packed && nv <= 128 && p->L <= 128) {
+    if (nv <= 64) hipLaunchKernelGGL((pool_packed_kernel<BWD, 1, 8>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((pool_packed_kernel<BWD, 2, 8>), grid, block, 0, stream, a);
     NNR_CHECK_LAUNCH();
     return NNR_OK;
   }

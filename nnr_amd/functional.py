@@ -42,7 +42,7 @@ class MhsaPack:
         self.rowmap = ops.seq_rowmap(self.plan)
         self.cover = cover
         # round 6: two titles of <= 16 positions per 32 x 32 attention problem (the core's matrix work does not depend on a title's length)
-        self.pair = ops.mhsa_pair_map(self.plan, mask) if (ops.MHSA_PAIR and self.plan.L == 32) else None
+        self.pair = ops.mhsa_pair_map(self.plan, mask) if self.plan.L == 32 else None
 
 
 class PackedEmbedDropFn(torch.autograd.Function):
@@ -124,7 +124,7 @@ class PackedAttentionFn(torch.autograd.Function):
         ops.tanh_score_bwd(th, ds, mod.affine2.weight, grad_of(mod.affine2.weight), plan, A)          # th := d(pre-activation)
         gw, gb = grad_of(mod.affine1.weight), grad_of(mod.affine1.bias)
         ops.leaf_deferred(x.device, cap, lambda: ops.linear_bwd_weight(th, x, gw, db=gb, dyn=plan.total), th, x)
-        if ops.USE_WT and cap >= 1024 and (A & 3) == 0:
+        if cap >= 1024 and (A & 3) == 0:
             ops.gemm(th, ops.wt(mod.affine1.weight), dx, M=cap, N=F, K=A, lda=A, ldb=A, ldc=F, accumulate=True, dyn=plan.total, dyn_dim=1)
         else:
             ops.gemm(th, mod.affine1.weight, dx, M=cap, N=F, K=A, lda=A, ldb=F, ldc=F, trans_b=True, accumulate=True, dyn=plan.total, dyn_dim=1)
@@ -212,7 +212,7 @@ class QKVFn(torch.autograd.Function):
             ops.leaf_deferred(x.device, M, lambda: ops.gemm(dqkv, x, gw, M=3 * HD, N=K, K=M, lda=3 * HD, ldb=K, ldc=K, trans_a=True,
                                                          trans_b=True, split_k=ops.split_for(3 * HD, K, M, *ops.tn_tile(3 * HD, K, M)[1:]), atomic=True,
                                                          colsum_out=gb, tile=ops.tn_tile(3 * HD, K, M)[0], **d2), dqkv, x)
-            if ops.USE_WT and M >= 1024 and w.is_contiguous():
+            if M >= 1024 and w.is_contiguous():
                 ops.gemm(dqkv, ops.wt(w), dx, M=M, N=K, K=3 * HD, lda=3 * HD, ldb=3 * HD, ldc=K, **d1)          # NT on [W_Q; W_K; W_V]^T
             else:
                 ops.gemm(dqkv, w, dx, M=M, N=K, K=3 * HD, lda=3 * HD, ldb=K, ldc=K, trans_b=True, **d1)

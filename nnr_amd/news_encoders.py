@@ -27,18 +27,12 @@ from . import ops
 from .layers import Attention, ScaledDotProduct_CandidateAttention, MultiHeadAttention, Conv1D, LSTMParams, grad_of, PARAM_EPOCH
 
 _SITE = dict(title=1, content=2, cat=3, sub=4)
-_TITLE_DX_FIRST = os.environ.get('NNR_TITLE_DX_FIRST', '0') == '1'       # measured: no gain either way (12.39 vs 12.42-12.58 ms/step)
-_TITLE_DX_TILE = int(os.environ.get('NNR_TITLE_DX_TILE', '0'))
 _DP_TABLE_FIRST = int(os.environ.get('NNR_DP_TABLE_FIRST', '0'))       # 1: always, -1: when world_size > 1, 0 (default): never -- no multi-GPU box to measure it on
 
 
 def _dp_world():
     import torch.distributed as dist
     return dist.get_world_size() if dist.is_initialized() else 1
-
-
-_CN_SPLIT = os.environ.get('NNR_CN_SPLIT', '0') == '1'      # c_n projections of a union call as plain skinny GEMM + row gather: measured no gain (11.21-11.27 vs 11.24-11.26 ms)
-_DX_TILE = int(os.environ.get('NNR_DX_TILE', '0'))          # A/B: tile of the content streams' embedding-row gradient GEMM (0 = automatic: 9)
 
 
 class NewsEncoder(nn.Module):
@@ -84,7 +78,7 @@ def _i32(t):
 class _CNEPairFunction(torch.autograd.Function):
     """Candidate call + history call of the SAME encoder in one pass.  Default: both calls planned as ONE packed token stream
     (cne union: every per-token kernel runs once over both calls; the rank pairing of newsEncoders.py:128-129 stays per call
-    through nnr_cne_pair_map).  NNR_CNE_UNION=0: two lock-step calls that only share the recurrence launches."""
+    through nnr_cne_pair_map).  _CNE_UNION = False (tests): two lock-step calls that only share the recurrence launches."""
 
     @staticmethod
     def forward(ctx, anchor, mod, *tensors):
@@ -134,34 +128,22 @@ def cne_forward(mod, title_text, title_mask, content_text, content_mask, categor
 
 _SIDE = {}
 ops.STREAM_CACHES.append(_SIDE)
-_LSTM_FWD_SPLIT = os.environ.get('NNR_LSTM_FWD_SPLIT', '0') == '1'      # A/B: title recurrence launched on the title stream
-_PROJ_ORDER = os.environ.get('NNR_PROJ_ORDER', '0') == '1'      # A/B (round 4, with NNR_LSTM_FWD_SPLIT=1): the content projection waits for the title projection, so the
-                                                                # title recurrence runs UNDER the content projection instead of inside the shared recurrence launch
-_DWHH_FIRST = os.environ.get('NNR_DWHH_FIRST', '0') == '1'      # A/B (round 4): this stream's dW_hh GEMM in front of the embedding-row gradient GEMM + scatter instead of behind them
-_LEAF2_ROWS = int(os.environ.get('NNR_LEAF2_ROWS', '65536'))
-_POOL_FUSED = os.environ.get('NNR_POOL_FUSED', '1') != '0'      # A/B (round 5): the two pools' token gradient in ONE write of dHt (see _cne_bwd_pre)
-_POST_INLINE = os.environ.get('NNR_POST_INLINE', '0') == '1'      # A/B: the content stream's tail GEMMs on one HIP stream
-_DX_SPLIT = os.environ.get('NNR_DX_SPLIT', '1') == '1'      # embedding-row gradient as plain GEMM + scatter kernel (11.46 vs 11.51 ms fused)
-_BWD_SPLIT = os.environ.get('NNR_LSTM_BWD_SPLIT', '1') == '1'      # batch 8: 4.68 (split) vs 4.93 ms; batch 64: no difference
-_PROJ_TILE = int(os.environ.get('NNR_PROJ_TILE', '0'))       # A/B (round 4): tile of the LSTM input projection (N = 1664 = 8 x 208), 0 = automatic (15)
-_DCN_TILE = int(os.environ.get('NNR_DCN_TILE', '0'))         # round 6: tile of the d c_n product in front of the backward recurrence (0 = automatic: 6)
-_GATE_TILE = int(os.environ.get('NNR_GATE_TILE', '0'))       # ... of the gate / attention / their data-gradient GEMMs over the token rows (N = 400 / 200)
-_GATE_FUSED = os.environ.get('NNR_GATE_FUSED', '1') != '0'      # A/B: the gate's backward inside the epilogue of the GEMM that completes dHt
-_CNE_UNION = os.environ.get('NNR_CNE_UNION', '1') != '0'      # A/B switch: candidate + history call as one packed token stream
+_LEAF2_ROWS = 65536         # the title stream's weight gradients on the second leaf stream up to this many content token rows (see _cne_bwd_pre)
+_CNE_UNION = True           # candidate + history call as one packed token stream (tests switch it off: the two-call plugin path)
 
 
 def _side_stream(dev):
     """One extra HIP stream per device for the small (candidate) encoder call."""
     key = (dev.type, dev.index)
     if key not in _SIDE:
-        _SIDE[key] = ops.new_stream(dev, critical=True)
+        _SIDE[key] = ops.new_stream(dev)
     return _SIDE[key]
 
 
 def _title_stream(dev):
     key = (dev.type, dev.index, 2)
     if key not in _SIDE:
-        _SIDE[key] = ops.new_stream(dev, critical=True)
+        _SIDE[key] = ops.new_stream(dev)
     return _SIDE[key]
 
 
@@ -243,7 +225,7 @@ def cne_forward_many(mod, calls):
         # CU, the 29 launches of ~5 us crawled at 70-160 us each and ended level with their first users: profiles/r06_ab.txt, first collection of the round.)
         ops.bx3_prefetch(dev)
     pre = _fork_join(len(calls), dev, lambda i, on_main: _cne_fwd_pre(mod, *calls[i], par=on_main))
-    items = [st for sv in pre for st in (sv['streams'][1],)] + [st for sv in pre for st in (sv['streams'][0],) if not st.get('lstm_done')]   # content streams first
+    items = [sv['streams'][1] for sv in pre] + [sv['streams'][0] for sv in pre]      # content streams first
     for i in range(0, len(items), 4):
         ops.lstm_fwd(items[i:i + 4], H)
     return _fork_join(len(calls), dev, lambda i, on_main: _cne_fwd_post(mod, pre[i], on_main))
@@ -287,7 +269,6 @@ def _cne_fwd_pre(mod, title_text, title_mask, content_text, content_mask, catego
     emb = mod.word_embedding.weight
 
     streams = [None, None]
-    proj_done = {}
 
     def prepare(slot, name, ids, mask, Lx, lstm, Hlin, Mlin, satt, catt):
         parts = list(zip(ids, mask)) if union else [(ids, mask)]
@@ -314,25 +295,15 @@ def _cne_fwd_pre(mod, title_text, title_mask, content_text, content_mask, catego
             # data parallel: the touched-row exchange of the table gradient learns this stream's words -- whenever a backward pass may
             # follow (also an eval-mode gradient check: the backward's table hook is unconditional; round-5 advisor)
             hook(plan.tok, plan.total)
-        if ops.SCATTER_SORTED and mod.training and E <= 320:
+        if mod.training and E <= 320:
             # the backward's embedding-row gradient is a segmented reduction over the rows sorted by word id (reproducible, no atomic
             # ceiling): the sort needs only the planned ids and runs on the leaf stream under the forward pass
             st['tsort'] = ops.TokenSort(plan.tok, plan.total, emb.shape[0])
-        if _PROJ_ORDER and par and name == 'content' and 'ev' in proj_done:
-            torch.cuda.current_stream(dev).wait_event(proj_done['ev'])      # A/B: content projection BEHIND the title projection (see _PROJ_ORDER)
         ops.gemm(st['xd'], w.w_ihp, st['gates'], M=cap, N=2 * w.NP, K=E, lda=E, ldb=E, ldc=2 * w.NP, dyn=plan.total, dyn_dim=1, bias=w.b_p,
-                 flop_scale=4.0 * H / w.NP, tile=_PROJ_TILE)
-        if _PROJ_ORDER and par and name == 'title':
-            proj_done['ev'] = torch.cuda.Event()
-            proj_done['ev'].record()
+                 flop_scale=4.0 * H / w.NP)
         st['cell'] = torch.empty((cap, 2 * w.HP), **f32)
         st['hout'] = torch.empty((cap, H2), **f32)
         st['cn'] = torch.empty((n, H2), **f32)
-        if _LSTM_FWD_SPLIT and par and name == 'title':
-            # the title recurrence (32 steps, a fifth of the tokens) right behind its own projection on the title stream: it runs under
-            # the content stream's projection GEMM instead of adding to the recurrence launch the whole forward pass waits for
-            ops.lstm_fwd([st], H)
-            st['lstm_done'] = True
         streams[slot] = st
 
     # the title and the content stream are independent up to the recurrence: plan + gather + input projection of the
@@ -378,22 +349,16 @@ def _cne_fwd_post(mod, sv, par=False):
     def gate_and_self(st, other):
         plan, cap = st['plan'], st['plan'].cap
         # title_M(sorted_content_m): both indexed by sorted RANK (newsEncoders.py:128-129)
-        if st['pm'] is not None and _CN_SPLIT:
-            # rank pairing over a union of two calls: the plain (skinny, 16 x 80 tiles) projection of every c_n row, then a row gather
-            # through the pairing map -- the row-gathering 64 x 80 GEMM took 50-75 us here and 150 us in the backward pass (right in
-            # front of the backward recurrence, beside the leaf stream's weight-gradient GEMMs)
-            st['mproj'] = ops.embed_gather(ops.linear_fwd(other['cn'], st['Mlin'].weight, st['Mlin'].bias), st['pm'], 0.0, 0)
-        else:
-            st['mproj'] = ops.linear_fwd(other['cn'], st['Mlin'].weight, st['Mlin'].bias, **({} if st['pm'] is None else {'a_idx': st['pm']}))
+        st['mproj'] = ops.linear_fwd(other['cn'], st['Mlin'].weight, st['Mlin'].bias, **({} if st['pm'] is None else {'a_idx': st['pm']}))
         st['G'] = torch.empty((cap, H2), **f32)
         st['Ht'] = torch.empty((cap, H2), **f32)
         ops.gemm(st['hout'], st['Hlin'].weight, st['Ht'], M=cap, N=H2, K=H2, lda=H2, ldb=H2, ldc=H2, dyn=plan.total, dyn_dim=1,
                  rowvec=st['mproj'], ldrv=H2, rowvec_map=plan.row_seq, act=ops.ACT_SIGMOID, aux_out=st['G'], ldaux=H2,
-                 mul=st['hout'], ldmul=H2, tile=_GATE_TILE)
+                 mul=st['hout'], ldmul=H2)
         st['th'] = torch.empty((cap, A), **f32)
         sa = st['satt']
         ops.gemm(st['Ht'], sa.affine1.weight, st['th'], M=cap, N=A, K=H2, lda=H2, ldb=H2, ldc=A, dyn=plan.total, dyn_dim=1,
-                 bias=sa.affine1.bias, act=ops.ACT_TANH, tile=_GATE_TILE)
+                 bias=sa.affine1.bias, act=ops.ACT_TANH)
         st['alpha_s'] = torch.empty(cap, **f32)
         st['selfv'] = torch.empty((n, H2), **f32)
         if A <= 256 and A % 4 == 0:
@@ -457,31 +422,21 @@ def cne_backward_many(mod, pairs):
 def _cne_bwd_rest(mod, pairs, H, dev, leaf):
     _fork_join(len(pairs), dev, lambda i, on_main: _cne_bwd_pre(mod, pairs[i][0], pairs[i][1], on_main, leaf))
 
-    # recurrence backward: ONE launch over every token stream (longest tiles of all streams first, lstm.hip pair_id), then the
-    # token-reduction GEMMs per stream kind -- the title streams' on the side stream next to the content streams'.  All
-    # parameter-gradient accumulation below is atomic.  NNR_LSTM_BWD_SPLIT=1: one launch per stream kind on two HIP streams
-    # (round 1's layout: the title recurrence then queues behind the content stream's GEMMs for CUs).
+    # recurrence backward: one launch per stream kind on two HIP streams -- the title streams' on the side stream next to the content
+    # streams' --, each followed by that kind's token-reduction GEMMs (batch 8: 4.68 vs 4.93 ms with ONE launch over every token stream;
+    # batch 64: no difference).  All parameter-gradient accumulation below is atomic.
     main = torch.cuda.current_stream(dev)
     side = _side_stream(dev)
-    if _BWD_SPLIT:
-        def run_kind(kind):
-            ops.lstm_bwd([sv['streams'][kind] for sv, _ in pairs], H)
-            for sv, _ in pairs:
-                _cne_bwd_post(mod, sv, sv['streams'][kind], leaf if kind == 1 else None)
 
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            run_kind(0)
-        run_kind(1)
-        main.wait_stream(side)
-        return
-    ops.lstm_bwd([sv['streams'][1] for sv, _ in pairs] + [sv['streams'][0] for sv, _ in pairs], H)
+    def run_kind(kind):
+        ops.lstm_bwd([sv['streams'][kind] for sv, _ in pairs], H)
+        for sv, _ in pairs:
+            _cne_bwd_post(mod, sv, sv['streams'][kind], leaf if kind == 1 else None)
+
     side.wait_stream(main)
     with torch.cuda.stream(side):
-        for sv, _ in pairs:
-            _cne_bwd_post(mod, sv, sv['streams'][0], None)
-    for sv, _ in pairs:
-        _cne_bwd_post(mod, sv, sv['streams'][1], leaf)
+        run_kind(0)
+    run_kind(1)
     main.wait_stream(side)
 
 
@@ -508,21 +463,16 @@ def _cne_bwd_pre(mod, sv, drep, par=False, leaf=None):
     def alt_leaf(st):
         return st['name'] == 'title' and c_['plan'].cap <= _LEAF2_ROWS
 
-    # ---- cross attention pools: dv -> K / Q params and the gradient of the OTHER stream's self vector.  Round 5 (_POOL_FUSED): this pass no
-    # longer writes dHt -- it leaves its per-token d score (ds_c) behind, and the self pool's backward below writes
-    # dHt = alpha_s d self + alpha_c d cross + scale ds_c v in ONE store (before: store here, read-modify-write there: 5 passes over
-    # [tokens, 400] for the two pools instead of 3; the cross pool must still run first, its dv feeds the other stream's self vector)
+    # ---- cross attention pools: dv -> K / Q params and the gradient of the OTHER stream's self vector.  This pass does not write dHt:
+    # it leaves its per-token d score (ds_c) behind, and the self pool's backward below writes dHt = alpha_s d self + alpha_c d cross +
+    # scale ds_c v in ONE store (3 passes over [tokens, 400] for the two pools instead of 5; the cross pool must still run first, its dv
+    # feeds the other stream's self vector)
     def cross_bwd(st, other, col0):
         plan, ca, cap = st['plan'], st['catt'], st['plan'].cap
         dv = torch.empty((n, H2), **f32)
-        if _POOL_FUSED:
-            st['ds_c'] = torch.empty(cap, **f32)
-            ops.pool_bwd(x=st['Ht'], ldx=H2, D=H2, n=n, Lx=st['L'], plan=plan, v=st['v'], ldv=H2, scale=1.0 / math.sqrt(A),
-                         alpha=st['alpha_c'], dout=drep[:, col0:], lddo=D, dscore=st['ds_c'], dv=dv, lddv=H2)
-        else:
-            st['dHt'] = torch.empty((cap, H2), **f32)
-            ops.pool_bwd(x=st['Ht'], ldx=H2, D=H2, n=n, Lx=st['L'], plan=plan, v=st['v'], ldv=H2, scale=1.0 / math.sqrt(A),
-                         alpha=st['alpha_c'], dout=drep[:, col0:], lddo=D, dx=st['dHt'], lddx=H2, dv=dv, lddv=H2)
+        st['ds_c'] = torch.empty(cap, **f32)
+        ops.pool_bwd(x=st['Ht'], ldx=H2, D=H2, n=n, Lx=st['L'], plan=plan, v=st['v'], ldv=H2, scale=1.0 / math.sqrt(A),
+                     alpha=st['alpha_c'], dout=drep[:, col0:], lddo=D, dscore=st['ds_c'], dv=dv, lddv=H2)
         dqv = torch.empty((n, A), **f32)
         ops.gemm(dv, ca.K.weight, dqv, M=n, N=A, K=H2, lda=H2, ldb=H2, ldc=A)                 # dqv = dv . K^T
         leaf(lambda: (ops.linear_bwd_weight(st['qv'], dv, grad_of(ca.K.weight)),             # dK[A,H2] += qv^T dv
@@ -535,46 +485,32 @@ def _cne_bwd_pre(mod, sv, drep, par=False, leaf=None):
     def self_gate_bwd(st, other, col0):
         plan, sa, cap = st['plan'], st['satt'], st['plan'].cap
         ds = torch.empty(cap, **f32)
-        if _POOL_FUSED:
-            st['dHt'] = torch.empty((cap, H2), **f32)
-            ops.pool_bwd(x=st['Ht'], ldx=H2, D=H2, n=n, Lx=st['L'], plan=plan, score=None, alpha=st['alpha_s'],
-                         dout=drep[:, col0:], lddo=D, dout2=st['dself_x'], lddo2=H2, dx=st['dHt'], lddx=H2, dscore=ds,
-                         alpha_b=st['alpha_c'], dout_b=drep[:, col0:], lddo_b=D, dscore_b=st['ds_c'], v_b=st['v'], ldv_b=H2, scale_b=1.0 / math.sqrt(A))
-            st['ds_c'] = None
-        else:
-            ops.pool_bwd(x=st['Ht'], ldx=H2, D=H2, n=n, Lx=st['L'], plan=plan, score=None, alpha=st['alpha_s'],
-                         dout=drep[:, col0:], lddo=D, dout2=st['dself_x'], lddo2=H2, dx=st['dHt'], lddx=H2, dx_accumulate=True, dscore=ds)
+        st['dHt'] = torch.empty((cap, H2), **f32)
+        ops.pool_bwd(x=st['Ht'], ldx=H2, D=H2, n=n, Lx=st['L'], plan=plan, score=None, alpha=st['alpha_s'],
+                     dout=drep[:, col0:], lddo=D, dout2=st['dself_x'], lddo2=H2, dx=st['dHt'], lddx=H2, dscore=ds,
+                     alpha_b=st['alpha_c'], dout_b=drep[:, col0:], lddo_b=D, dscore_b=st['ds_c'], v_b=st['v'], ldv_b=H2, scale_b=1.0 / math.sqrt(A))
+        st['ds_c'] = None
         th = st['th']
         ops.tanh_score_bwd(th, ds, sa.affine2.weight, grad_of(sa.affine2.weight), plan, A)    # th := dpre
         st['dH'] = torch.empty((cap, H2), **f32)
         dpre = torch.empty((cap, H2), **f32)             # (not Ht's buffer: the deferred weight-gradient GEMM below still reads it)
-        if _GATE_FUSED:
-            # the GEMM that completes dHt (+= d tanh-projection . W1) applies the gate's backward in its epilogue: Ht = hout * G ->
-            # dH = dHt * G, d pre = dHt * hout * G * (1 - G) -- one launch and one pass over dHt less on the dependent chain (round 4)
-            ops.gemm(th, ops.wt(sa.affine1.weight), st['dH'], M=cap, N=H2, K=A, lda=A, ldb=A, ldc=H2, dyn=plan.total, dyn_dim=1,
-                     pre_add=st['dHt'], ldpre=H2, gate_bwd=True, mul=st['G'], ldmul=H2, resid=st['hout'], ldres=H2, aux_out=dpre, ldaux=H2,
-                     tile=_GATE_TILE)
-        else:
-            ops.gemm(th, ops.wt(sa.affine1.weight), st['dHt'], M=cap, N=H2, K=A, lda=A, ldb=A, ldc=H2, accumulate=True,      # NT on W1^T
-                     dyn=plan.total, dyn_dim=1)
-            ops.gate_bwd(st['dHt'], st['hout'], st['G'], st['dH'], dpre, plan, H2)               # gate: Ht = hout * G
+        # the GEMM that completes dHt (+= d tanh-projection . W1) applies the gate's backward in its epilogue: Ht = hout * G ->
+        # dH = dHt * G, d pre = dHt * hout * G * (1 - G) -- one launch and one pass over dHt less on the dependent chain (round 4)
+        ops.gemm(th, ops.wt(sa.affine1.weight), st['dH'], M=cap, N=H2, K=A, lda=A, ldb=A, ldc=H2, dyn=plan.total, dyn_dim=1,
+                 pre_add=st['dHt'], ldpre=H2, gate_bwd=True, mul=st['G'], ldmul=H2, resid=st['hout'], ldres=H2, aux_out=dpre, ldaux=H2)
         leaf(lambda: ops.linear_bwd_weight(th, st['Ht'], grad_of(sa.affine1.weight), dyn=plan.total, db=grad_of(sa.affine1.bias)), th, st['Ht'], alt=alt_leaf(st))
         ops.gemm(dpre, ops.wt(st['Hlin'].weight), st['dH'], M=cap, N=H2, K=H2, lda=H2, ldb=H2, ldc=H2, accumulate=True,   # NT on W_H^T
-                 dyn=plan.total, dyn_dim=1, tile=_GATE_TILE)
+                 dyn=plan.total, dyn_dim=1)
         leaf(lambda: ops.linear_bwd_weight(dpre, st['hout'], grad_of(st['Hlin'].weight), dyn=plan.total), dpre, st['hout'], alt=alt_leaf(st))
         dP = torch.empty((n, H2), **f32)                  # d mproj[rank]
         ops.packed_seq_sum(dpre, H2, plan, dP)
         pm, opm = st['pm'], other['pm']                   # union of two calls: mproj[s] = M(cn_other[pm[s]])  (pm^-1 = other's pm)
         leaf(lambda: ops.linear_bwd_weight(dP, other['cn'], grad_of(st['Mlin'].weight), db=grad_of(st['Mlin'].bias),
                                            **({} if pm is None else {'b_idx': pm})), dP, alt=alt_leaf(st))
-        # (NNR_DCN_TILE: this [n, 400] x [400, 400] product runs beside the leaf stream's weight-gradient GEMMs, whose workgroups hold 120 KB of a
-        #  CU's LDS, and its 74 KB tile waits for them: 277 us in the step against 40 us alone.  The 19 KB register-staged tile (2) halves its
-        #  in-step time and leaves the step where it was -- the chain waits for the same leaf work one call later; profiles/r06_ab.txt call 24)
-        dcn_kw = {'tile': _DCN_TILE} if _DCN_TILE else {}
-        if opm is not None and _CN_SPLIT:
-            other['dcn'] = ops.embed_gather(ops.linear_bwd_data(dP, st['Mlin'].weight, **dcn_kw), opm, 0.0, 0)            # [n, H2], rank-indexed
-        else:
-            other['dcn'] = ops.linear_bwd_data(dP, st['Mlin'].weight, **dcn_kw, **({} if opm is None else {'a_idx': opm}))   # [n, H2], rank-indexed
+        # (this [n, 400] x [400, 400] product runs beside the leaf stream's weight-gradient GEMMs and its automatic 74 KB tile waits for them:
+        #  277 us in the step against 40 us alone.  The 19 KB register-staged tile halves its in-step time but leaves the step where it was --
+        #  the chain waits for the same leaf work one call later; profiles/r06_ab.txt call 24 --, so the automatic choice stays)
+        other['dcn'] = ops.linear_bwd_data(dP, st['Mlin'].weight, **({} if opm is None else {'a_idx': opm}))   # [n, H2], rank-indexed
         st['dHt'] = None
 
     _two_chains(dev, par, lambda: self_gate_bwd(t_, c_, 0), lambda: self_gate_bwd(c_, t_, H2))
@@ -623,25 +559,17 @@ def _cne_bwd_post(mod, sv, st, leaf=None):
             hook(mod.__dict__.get('_table_scatters', 2))
 
     def dx_scatter():
-        # d(embedding rows): dX = dgates . W_ihp (NT on the transposed packed weight), scattered (atomic) into the table
-        # gradient through the dropout mask.  The title streams' launch runs BESIDE the content recurrence, whose workgroups
-        # hold 98 KB of LDS per CU: there the 40 KB tile (tile 15) can move in next to them, the 80 KB one (the automatic
-        # choice for this long reduction) cannot and crawls (384 us for 4 GFLOP, measured).
-        if _DX_SPLIT:
-            # plain-store GEMM into the cell-state buffer (dead after the recurrence backward; xd / hout are still being read by the
-            # weight-gradient GEMMs on the leaf stream) + the row-scatter kernel: the atomic epilogue of the fused form costs the GEMM
-            # 18 % (764 vs 624 us alone, tools/dx_epilogue_bench.py)
-            # (the cell buffer is [cap, 2*HP]: large enough only when 2*HP >= E -- not at --hidden_dim <= 144 with E = 300)
-            dx = st['cell'].view(-1)[:cap * E].view(cap, E) if st['cell'].numel() >= cap * E else torch.empty((cap, E), **f32)
-            ops.gemm(dg, w.w_ihp_t, dx, M=cap, N=E, K=2 * NP, lda=2 * NP, ldb=2 * NP, ldc=E, dyn=plan.total, dyn_dim=1,
-                     tile=_DX_TILE if leaf is not None else _TITLE_DX_TILE, flop_scale=4.0 * H / NP)
-            if st.get('tsort') is not None:
-                ops.embed_scatter_sorted(dx, st['tsort'], grad_of(emb), p, st['seed'])
-            else:
-                ops.embed_scatter(dx, plan.tok, grad_of(emb), p, st['seed'], dyn=plan.total)
-            return
-        ops.gemm(dg, w.w_ihp_t, grad_of(emb), M=cap, N=E, K=2 * NP, lda=2 * NP, ldb=2 * NP, ldc=E, c_idx=plan.tok, atomic=True,
-                 drop=(4, p, st['seed'], E), dyn=plan.total, dyn_dim=1, tile=0 if leaf is not None else _TITLE_DX_TILE, flop_scale=4.0 * H / NP)
+        # d(embedding rows): dX = dgates . W_ihp (NT on the transposed packed weight), scattered into the table gradient through the
+        # dropout mask.  Plain-store GEMM into the cell-state buffer (dead after the recurrence backward; xd / hout are still being read
+        # by the weight-gradient GEMMs on the leaf stream) + the row-scatter kernel: the atomic epilogue of the fused form costs the GEMM
+        # 18 % (764 vs 624 us alone, tools/dx_epilogue_bench.py; step 11.46 vs 11.51 ms)
+        # (the cell buffer is [cap, 2*HP]: large enough only when 2*HP >= E -- not at --hidden_dim <= 144 with E = 300)
+        dx = st['cell'].view(-1)[:cap * E].view(cap, E) if st['cell'].numel() >= cap * E else torch.empty((cap, E), **f32)
+        ops.gemm(dg, w.w_ihp_t, dx, M=cap, N=E, K=2 * NP, lda=2 * NP, ldb=2 * NP, ldc=E, dyn=plan.total, dyn_dim=1, flop_scale=4.0 * H / NP)
+        if st.get('tsort') is not None:
+            ops.embed_scatter_sorted(dx, st['tsort'], grad_of(emb), p, st['seed'])
+        else:
+            ops.embed_scatter(dx, plan.tok, grad_of(emb), p, st['seed'], dyn=plan.total)
 
     # Data parallelism (world > 1), NNR_DP_TABLE_FIRST (opt-in: its benefit needs >= 2 GPUs to measure): the word-embedding table is 70 % of the
     # gradient bytes and its bucket can only leave after the LAST embedding-row scatter.  Both token streams then compute their
@@ -661,31 +589,20 @@ def _cne_bwd_post(mod, sv, st, leaf=None):
         ops.lstm_unpack_grads(dw_ihp, db_p, dw_hhp, H, E, [grad_of(q) for q in st['lstm'].param_list()], zero_src=True)
         return
     if leaf is None:
-        # title streams (side stream, beside the content recurrence): the scatter GEMM first -- it is the largest launch and the
-        # one the tail of the step would otherwise still be waiting for
-        if _TITLE_DX_FIRST:
-            dx_scatter()
-            table_hook()
+        # title streams (side stream, beside the content recurrence): the weight gradients, then the scatter GEMM (scatter first:
+        # no gain either way, 12.39 vs 12.42-12.58 ms/step)
         dw_ih(); dw_hh(0); dw_hh(1)
-    else:
-        # two balanced halves: leaf stream dW_ih + dW_hh(reverse), this stream the scatter GEMM + dW_hh(forward)
-        if _POST_INLINE:
-            dx_scatter()
-            table_hook()
-            dw_ih(); dw_hh(0); dw_hh(1)
-        else:
-            leaf(lambda: (dw_ih(), dw_hh(1)), dw_ihp, db_p, dw_hhp)
-            if _DWHH_FIRST:
-                dw_hh(0)
-            dx_scatter()
-            table_hook()
-            if not _DWHH_FIRST:
-                dw_hh(0)
-            leaf.sync()
-    ops.lstm_unpack_grads(dw_ihp, db_p, dw_hhp, H, E, [grad_of(q) for q in st['lstm'].param_list()], zero_src=True)
-    if leaf is None and not _TITLE_DX_FIRST:
+        ops.lstm_unpack_grads(dw_ihp, db_p, dw_hhp, H, E, [grad_of(q) for q in st['lstm'].param_list()], zero_src=True)
         dx_scatter()
         table_hook()
+        return
+    # two balanced halves: leaf stream dW_ih + dW_hh(reverse), this stream the scatter GEMM + dW_hh(forward)
+    leaf(lambda: (dw_ih(), dw_hh(1)), dw_ihp, db_p, dw_hhp)
+    dx_scatter()
+    table_hook()
+    dw_hh(0)
+    leaf.sync()
+    ops.lstm_unpack_grads(dw_ihp, db_p, dw_hhp, H, E, [grad_of(q) for q in st['lstm'].param_list()], zero_src=True)
 
 
 @torch.no_grad()
@@ -807,13 +724,10 @@ class CNE(NewsEncoder):
 
 
 # ================================================================================================== MHSA / CNN
-_MHSA_PACKED = os.environ.get('NNR_MHSA_PACKED', '1') != '0'      # A/B (round 5): MHSA news encoder over packed token rows
-
-
 def mhsa_packed(enc, title_text):
-    """Packed rows need the 4-head cooperative attention core (heads % 4 == 0, head_dim % 4 == 0, titles of at most 32 positions) and
-    device tensors; anything else takes the dense path."""
-    return (_MHSA_PACKED and title_text.is_cuda and enc.head_num % 4 == 0 and enc.head_dim % 4 == 0 and enc.head_dim <= 32
+    """MHSA news encoder over packed token rows (round 5).  Packed rows need the 4-head cooperative attention core (heads % 4 == 0,
+    head_dim % 4 == 0, titles of at most 32 positions) and device tensors; anything else takes the dense path."""
+    return (title_text.is_cuda and enc.head_num % 4 == 0 and enc.head_dim % 4 == 0 and enc.head_dim <= 32
             and enc.max_sentence_length <= 32 and enc.word_embedding_dim % 4 == 0)
 
 

@@ -75,8 +75,7 @@ def _s():
 # not reusable until its event completes: the allocator then grows with hipMalloc and the step time turned bimodal,
 # 14 ms or 50-67 ms per step -- measured when the 2.7 GB gate buffer was recorded.)
 _LEAF = {}
-_NO_DEFER = os.environ.get('NNR_LEAF_DEFER', '1') == '0'
-SIDE_CALL = os.environ.get('NNR_SIDE_CALL', '1') != '0'      # model.Model.forward: candidate encoder call on a side stream
+SIDE_CALL = True            # model.Model.forward: candidate encoder call on a side stream (tests switch it off)
 EXTRA_STREAMS = []          # every HIP stream this package created (side, title, leaf): see join_extra_streams()
 
 
@@ -94,50 +93,23 @@ def set_one_stream(flag):
     del EXTRA_STREAMS[:]
 
 
-def new_stream(dev, critical=False):
-    """critical: a stream that carries a piece of the dependent chain (candidate call, title chain) rather than leaf work.
-    (Measured and rejected: giving the critical streams a high HIP stream priority -- 13.43 vs 13.05 ms/step.)"""
+def new_stream(dev):
+    """A new HIP stream of the package (one per role: side, title, leaf, ...).  (Measured and rejected: a high HIP stream priority for
+    the streams that carry a piece of the dependent chain -- 13.43 vs 13.05 ms/step, later no difference.)"""
     if ONE_STREAM[0]:
         return torch.cuda.current_stream(dev)
-    # NNR_PRIO=1 (A/B, round 3 -- the whole step is now enqueued at once by the native replay, so the hardware queues arbitrate): the
-    # chain-carrying side streams get HIP's high priority.  Measured: no difference (11.20 / 10.80 vs 11.33 / 10.75 ms, 20 steps /
-    # sustained).  Running the MAIN chain on a high-priority stream as well did not finish (the pair recurrence's partner workgroups
-    # of lower-priority launches wait behind it): not offered.
     # HIP binds a stream to one of its 4 hardware queues (GPU_MAX_HW_QUEUES; 5 and up fall off a cliff: 13 ms per batch-64 step, 6.5 per batch-8 step) and
     # the step runs on 5-6 streams, so some share a queue; WHICH ones do depends on the order the process created and first used its streams, and it
     # decides up to 7 % of the latency-bound batch-8 step: 3.10-3.20 ms in the natural order of a fresh process, 3.3-4.1 ms with 1-4 idle streams in front
     # of the set or of one of its streams; at batch 64 every pattern tried is within 0.08 ms of the natural one (profiles/r06_ab.txt calls 42-46).
-    # NNR_STREAM_BURN=a,b,...: the A/B knob -- a, b, ... idle streams (used once) in front of the 1st, 2nd, ... stream of the set.
-    k = len(EXTRA_STREAMS)
-    if _STREAM_BURN:
-        from . import tape as _tape
-        assert _tape.ACTIVE[0] is None, 'NNR_STREAM_BURN: a stream was created while a launch tape records'
-        for _ in range(_STREAM_BURN[k] if k < len(_STREAM_BURN) else 0):
-            _bind(torch.cuda.Stream(device=dev), dev)
-    st = torch.cuda.Stream(device=dev, priority=-1) if (critical and STREAM_PRIO >= 1) else torch.cuda.Stream(device=dev)
-    if _STREAM_BURN:
-        _bind(st, dev)                                # first use = creation
+    st = torch.cuda.Stream(device=dev)
     EXTRA_STREAMS.append(st)
     return st
-
-
-_BURNT = []
-
-
-def _bind(st, dev):
-    with torch.cuda.stream(st):
-        torch.empty(64, device=dev).zero_()           # (a torch kernel, not a C-ABI call)
-    _BURNT.append(st)
-
-
-STREAM_PRIO = int(os.environ.get('NNR_PRIO', '0'))
-_STREAM_BURN = [int(x) for x in os.environ.get('NNR_STREAM_BURN', '').split(',') if x.strip()]
 
 
 STREAM_CACHES.append(_LEAF)
 _LEAF_ALT = {}
 STREAM_CACHES.append(_LEAF_ALT)
-LEAF2 = os.environ.get('NNR_LEAF2', '1') != '0'      # a second leaf stream for the title token stream's weight-gradient GEMMs (A/B)
 
 
 def join_extra_streams(dev=None):
@@ -192,7 +164,7 @@ class leaf_scope:
             fn()
             return
         st = self.leaf
-        if alt and LEAF2 and not ONE_STREAM[0]:
+        if alt and not ONE_STREAM[0]:
             if self.leaf2 is None:
                 key = (self.dev.type, self.dev.index)
                 if key not in _LEAF_ALT:
@@ -235,8 +207,8 @@ def leaf_deferred(dev, rows, fn, *tensors):
     """Inside an autograd backward function: run `fn` (a weight-gradient launch, atomic accumulation) on the leaf stream
     behind the current stream's work, and join it when THIS backward pass ends (autograd's end-of-pass callback), so the data
     gradient chain on the main stream does not wait for it.  `tensors` (the inputs fn reads) are held until that join.
-    NNR_LEAF_DEFER=0 runs fn inline."""
-    if _NO_DEFER or _DEFER.get('off') or max(rows, STEP_ROWS[0]) < LEAF_MIN_ROWS:
+    _DEFER['off'] (tests) runs fn inline."""
+    if _DEFER.get('off') or max(rows, STEP_ROWS[0]) < LEAF_MIN_ROWS:
         fn()
         return
     key = (dev.type, dev.index)
@@ -270,7 +242,6 @@ def tape_keep(*tensors):
 
 
 _WT = {}
-USE_WT = os.environ.get('NNR_WT', '1') != '0'      # A/B switch: data-gradient GEMMs as NT products on cached W^T
 
 
 class _WtEntry:
@@ -322,7 +293,7 @@ def wt_prefetch(dev):
     start of a training forward pass: the copies are needed by the BACKWARD pass only, so they leave the critical chain --
     made lazily, the first user's stream does the copy and users on the other streams wait for it (measured: a 383 us stall
     of the history call's backward behind the candidate call's)."""
-    if not USE_WT or not _WT or torch.cuda.is_current_stream_capturing():      # (under hipGraph capture the copies are refreshed lazily by wt():
+    if not _WT or torch.cuda.is_current_stream_capturing():      # (under hipGraph capture the copies are refreshed lazily by wt():
         return                                                               # ending a capture that holds this fork segfaults in the HIP runtime)
     from .layers import PARAM_EPOCH
     live = [(k, e, e.ref()) for k, e in _WT.items()]
@@ -351,34 +322,20 @@ def wt_prefetch(dev):
         e.epoch, e.version, e.event, e.stream = PARAM_EPOCH[0], w._version, ev, cur
 
 
-# LDS-DMA staged weight-gradient tiles (csrc/gemm.hip: gemm_tn_pipe_kernel): (tile id, rows, cols, workgroups to aim for)
-TN_PIPE = os.environ.get('NNR_TN_PIPE', '1') != '0'
-_TN_SQUARE = os.environ.get('NNR_TN_SQUARE', '1') == '1'      # LDS-DMA tile for the 900 x 900 weight gradients of the user encoder (same step time, 8 instead of 12 atomic slices)
-_TN_WIDE = os.environ.get('NNR_TN_WIDE', '1') == '1'      # 128 x 160 tile for the 1664 x 300 weight gradient: counter traffic 2.0x -> 1.5x of its operands, step +0.05 ms
-_TN_SMALL_LDS = os.environ.get('NNR_TN_SMALL_LDS', '0') == '1'      # 1: 53 KB 128 x 80 tiles everywhere.  Mid-round they won (12.35 vs 12.52 ms:
-                                                                    # they fitted beside a 98 KB recurrence workgroup); since the recurrence holds
-                                                                    # 120-130 KB and the split-K slices come in whole waves, the 78 KB 128 x 208
-                                                                    # tile for N = 200 / 400 is ahead again (11.38 vs 11.43 ms, 4 rounds each)
-
-
-_TN_T64 = int(os.environ.get('NNR_TN_T64', '3'))      # A/B (round 4): bit 0 = 64 x 208 tile for the M = 200 / 400 gate / attention weight gradients, bit 1 = for the gathered dW_hh (M = 832)
-
-
 def tn_tile(M, N, K, gather=False):
     """Tile of a token-reduction (weight-gradient) GEMM C[M,N] += A[K,M]^T B[K,N] and the tile dims its split-K factor is sized
-    for.  Measured on the step's shapes (tools/gemm_pipe_bench.py tn, TFLOP/s old -> new): 1664x300 82 -> 96 (128x80),
-    832x200 with gathered rows 68 -> 86, 400x400 75 -> 82, 200x400 62 -> 73 (128x208); short reductions and the 900x900 SUE
-    layers stay on the register-staged 64x80 tile."""
-    if _TN_SQUARE and TN_PIPE and K >= 2048 and M >= 512 and N >= 512 and not gather and not ((M & 3) or (N & 3)):
+    for: the LDS-DMA staged tiles of csrc/gemm.hip (gemm_tn_pipe_kernel) as (tile id, rows, cols, workgroups to aim for).  Measured
+    on the step's shapes (tools/gemm_pipe_bench.py tn, TFLOP/s old -> new): 1664x300 82 -> 96 (128x80), 832x200 with gathered rows
+    68 -> 86, 400x400 75 -> 82, 200x400 62 -> 73 (128x208); short reductions stay on the register-staged 64x80 tile.  (The 53 KB
+    128 x 80 tile everywhere lost to the 78 KB 128 x 208 one for N = 200 / 400 once the recurrence held 120-130 KB: 11.43 vs 11.38 ms.)"""
+    if K >= 2048 and M >= 512 and N >= 512 and not gather and not ((M & 3) or (N & 3)):
         return 26, 128, 80, 2048          # SUE's 900 x 900 x 4 352 weight gradients: 8 slices of 544 rows instead of 12 of 363 on the 64 x 80 tile
-    if not TN_PIPE or K < 8192 or (M & 3) or (N & 3) or (M >= 512 and N >= 512):
+    if K < 8192 or (M & 3) or (N & 3) or (M >= 512 and N >= 512):
         return 0, 64, 80, 2048
-    if _TN_WIDE and not gather and M >= 1024 and 160 < N <= 320:
-        return 30, 128, 160, 2048         # dW_ih (1664 x 300): two 160-column blocks instead of four 80-column ones: A (d gates) is fetched twice, not 4x
-    if _TN_SMALL_LDS:
-        return (20 if gather else 26), 128, 80, 2048
+    if not gather and M >= 1024 and 160 < N <= 320:
+        return 30, 128, 160, 2048         # dW_ih (1664 x 300): operand counter traffic 2.0x -> 1.5x -- A (d gates) is fetched twice, not 4x
     if N <= 208 or (N > 320 and N <= 416):
-        if (_TN_T64 & 2) if gather else ((_TN_T64 & 1) and M % 128 != 0):
+        if gather or M % 128 != 0:
             return 32, 64, 208, 640       # gen-2 loop, 64 x 208: M = 200 / 400 / 832 in 4 / 7 / 13 row tiles (256 / 448 / 832 rows of MFMA work, not 256 / 512 / 896)
         return 27, 128, 208, 640          # gen-2 loop, 128 x 208 (one token row per DMA instruction: takes gathered rows)
     if gather:
@@ -404,14 +361,14 @@ def split_for(m, n, k, tile_m=64, tile_n=80, target_blocks=2048, kmin=256):
 # (profiles/r06_bx3_phases.md: -0.33 ms of the 10.27 ms headline step, every class positive).  NNR_BX3=0 = the pure fp32-MFMA path
 # (bench.py keeps it as a `secondary` leg of the same workload so that both numbers are driver-timed).
 BX3 = [os.environ.get('NNR_BX3', '1') == '1']
-_BX3_MIN_ROWS = int(os.environ.get('NNR_BX3_MIN_ROWS', '2048'))
-_BX3_TILE = int(os.environ.get('NNR_BX3_TILE', '50'))          # A/B: 50 = 128 x 80 (2 workgroups / CU), 51 = 64 x 80 (3), 52 = 128 x 64, 53 = 256 x 80 (1)
+_BX3_MIN_ROWS = 2048
+_BX3_TILE = 50          # 128 x 80, 2 workgroups / CU (tile 51, 64 x 80 with 3 per CU, stays for explicit callers)
 # shape classes the bf16x3 kernel takes (round 6: decided per class by same-box in-step A/Bs, profiles/r06_bx3_phases.md):
 #   dx   = long reductions (K >= 1024: the embedding-row gradient dX = dGates . W_ih, K = 2 NP = 1664)
 #   sue  = K >= 800 (the user encoder's 900 x 900 layers)
 #   proj = N >= 1024 (the LSTM input projection x . W_ih^T, N = 1664)
 #   gate = everything else (gate / attention projections, K, N = 200 .. 400)
-_BX3_CLASSES = set(c for c in os.environ.get('NNR_BX3_CLASSES', 'dx,sue,proj,gate').split(',') if c)
+_BX3_CLASSES = {'dx', 'sue', 'proj', 'gate'}      # (step.matrix_path narrows it per model and step size)
 
 
 def bx3_class(N, K):
@@ -438,15 +395,12 @@ def mark_weight(*tensors, prefetchable=False):
             t._nnr_prefetch = True
 
 
-BX3_PREFETCH = os.environ.get('NNR_BX3_PREFETCH', '1') != '0'
-
-
 def bx3_prefetch(dev):
     """Re-split, on the leaf stream at the start of a training step (right behind wt_prefetch's transposes, same stream), the bf16 images of
     every weight bx3_images() has served before and that changed since (i.e. after an optimizer step): parameters and their cached transposes.
     Made lazily, each split is a 3-30 us launch on the stream of its first user -- five of them sat on the step's dependent chain in front of
     their GEMMs (profiles/r06_ab.txt: split_bf16x3_kernel 21 / 11 / 34 / 28 / 14 us on the main streams)."""
-    if not (BX3[0] and BX3_PREFETCH) or not _B3 or torch.cuda.is_current_stream_capturing():
+    if not BX3[0] or not _B3 or torch.cuda.is_current_stream_capturing():
         return
     from .layers import PARAM_EPOCH
     stale = []
@@ -611,11 +565,6 @@ def gemm(A, B, C_=None, *, M, N, K, lda, ldb, ldc=0, trans_a=False, trans_b=Fals
         t = 7
     elif pipe_nt and a_idx is None and K >= 800 and wg64 > 512:
         t = 9
-        if dyn is None and batch <= 1 and os.environ.get('NNR_NT64', '0') == '1':
-            nbm = (M + 127) // 128
-            t80, t64 = nbm * ((N + 79) // 80), nbm * ((N + 63) // 64)
-            if t80 < 1024 and ((t64 + 255) // 256) * 64 * 100 < ((t80 + 255) // 256) * 80 * 92:
-                t = 31
     elif pipe_nt and (dyn is not None or wg128 >= 640):
         t = 15
     elif pipe_nt and wg64 > 512 and K >= 128:
@@ -674,7 +623,7 @@ def linear_bwd_data(dy, w, out=None, accumulate=False, **kw):
     K = w.shape[1]
     if out is None:
         out = torch.empty((M, K), device=dy.device, dtype=torch.float32)
-    if USE_WT and M >= 1024 and w.is_contiguous() and (N & 3) == 0:
+    if M >= 1024 and w.is_contiguous() and (N & 3) == 0:
         gemm(dy, wt(w), out, M=M, N=K, K=N, lda=dy.stride(0), ldb=N, ldc=out.stride(0), accumulate=accumulate, **kw)      # NT on W^T
     else:
         gemm(dy, w, out, M=M, N=K, K=N, lda=dy.stride(0), ldb=w.stride(0), ldc=out.stride(0), trans_b=True, accumulate=accumulate, **kw)
@@ -704,7 +653,7 @@ def rowdot(x, w, out, dyn=None, rows=None):
 
 _SLOT_WS = {}
 _SLAB_WS = {}
-TN_SLAB = os.environ.get('NNR_TN_SLAB', '1') != '0'      # split-K weight gradients through slabs + a fixed-order reduction (0: f32 atomics)
+TN_SLAB = True      # split-K weight gradients through slabs + a fixed-order reduction (False, tests: f32 atomics)
 # fixed-order stream-K for the one-to-two-wave NT launches of the user encoder (csrc/gemm.hip: gemm_nt_sk_kernel; round 5, verdict item 1b)
 def _slab_ws(dev, floats):
     """Split-K slab workspace of the CURRENT stream (nnr_gemm_args.slab): a launch's slices store their partial results there and the
@@ -1147,12 +1096,9 @@ def fusion_rows_fwd(cat_table, sub_table, cat0, sub0, cat1, sub1, out_view, ldo,
                                         C.c_uint32(seed_sub & 0xFFFFFFFF), _s()), 'nnr_fusion_rows_fwd')
 
 
-DETERMINISTIC = os.environ.get('NNR_DETERMINISTIC', '1') != '0'      # reproducible forms of the small reductions (category tables, proxy nodes)
-
-
 def fusion_rows_bwd(cat0, sub0, cat1, sub1, cd, sd, dout_view, lddo, dcat_table, dsub_table, p, seed_cat, seed_sub):
     n0, n1 = cat0.numel(), (cat1.numel() if cat1 is not None else 0)
-    if DETERMINISTIC and cd <= 128 and sd <= 128:
+    if cd <= 128 and sd <= 128:                   # reproducible form (slot rows + fixed-order sum); wider tables: f32 atomics
         L.check(L.lib().nnr_fusion_rows_bwd_det(_p(cat0), _p(sub0), n0, _p(cat1), _p(sub1), n1, cd, sd, dcat_table.shape[0], dsub_table.shape[0],
                                                 _p(dout_view), lddo, _p(dcat_table), _p(dsub_table), C.c_float(p), C.c_uint32(seed_cat & 0xFFFFFFFF),
                                                 C.c_uint32(seed_sub & 0xFFFFFFFF), _s()), 'nnr_fusion_rows_bwd_det')
@@ -1269,9 +1215,6 @@ def mhsa_bwd_packed(qkv, mask, rowmap, plan, dout, heads, dh, dqkv, p=0.0, seed=
                                             _p(dqkv), C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _s()), 'nnr_mhsa_bwd_packed')
 
 
-MHSA_PAIR = os.environ.get('NNR_MHSA_PAIR', '1') != '0'      # round 6: two titles of <= 16 positions per 32 x 32 attention problem (csrc/mhsa.hip: mhsa_pairing)
-
-
 def mhsa_pair_map(plan, mask):
     """(vrowmap [n, 32] int32, vmask [n, 32] uint8) of the paired attention core over `plan` (a packed call with L = 32) and the ORIGINAL key mask."""
     if mask.dtype == torch.bool:
@@ -1330,9 +1273,6 @@ def _embed_scatter(dout, idx, dtable, p, seed, dyn, n, dim):
         return
     L.check(L.lib().nnr_embed_scatter(_p(dout), _p(idx), C.c_long(n), dim, _p(dtable), C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _s()),
             'nnr_embed_scatter')
-
-
-SCATTER_SORTED = os.environ.get('NNR_SCATTER_SORTED', '1') != '0'      # embedding-row gradient as a sorted segmented reduction (0: f32-atomic scatter)
 
 
 class TokenSort:

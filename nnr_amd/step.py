@@ -7,18 +7,13 @@ news_encoders / user_encoders / model (tests/test_hip_tape_gpu.py compares the t
 autograd's bookkeeping, its gradient-accumulation / fill / cat kernels, and every host-side tensor op that is not a call into
 libnnr_hip.so.  That makes the step RECORDABLE: nnr_amd.tape captures the calls of one such step and replays them natively."""
 import contextlib
-import os
 
 import torch
 
 from . import ops
-from .news_encoders import cne_forward_many, cne_backward_many, _CNE_UNION
+from .news_encoders import cne_forward_many, cne_backward_many
 
-_BX3_MHSA = os.environ.get('NNR_BX3_MHSA', '0') == '1'              # A/B: every class of ops._BX3_CLASSES in the MHSA step too
-_CNE_STEP_ROWS = os.environ.get('NNR_CNE_STEP_ROWS', '0') == '1'      # A/B: post the history call's token rows (Model.forward's rule) instead of 0
-_BX3_MIN_SEQS = int(os.environ.get('NNR_BX3_MIN_SEQS', '1408'))         # CNE + SUE: bf16x3 from this many news-encoder sequences per step on (batch 32: 1 760)
-_BX3_MHSA_CLASSES = set(c for c in os.environ.get('NNR_BX3_MHSA_CLASSES', 'dx').split(',') if c)
-_MHSA_NATIVE = os.environ.get('NNR_MHSA_NATIVE', '1') != '0'      # A/B: MHSA+MHSA through autograd (round 3) instead of the native step
+_BX3_MIN_SEQS = 1408        # CNE + SUE: bf16x3 from this many news-encoder sequences per step on (batch 32: 1 760)
 
 
 def kind(model):
@@ -29,7 +24,7 @@ def kind(model):
         return None
     if type(model.news_encoder) is NE.CNE and type(model.user_encoder) is UE.SUE and model.news_encoder.tie_order == 'stable' and NE._CNE_UNION:
         return 'cne_sue'
-    if type(model.news_encoder) is NE.MHSA and type(model.user_encoder) is UE.MHSA and _MHSA_NATIVE:
+    if type(model.news_encoder) is NE.MHSA and type(model.user_encoder) is UE.MHSA:
         return 'mhsa'
     return None
 
@@ -52,7 +47,7 @@ def bx3_classes(model, seqs=None):
     if not ops.BX3[0]:
         return set()
     if type(getattr(model, 'news_encoder', None)) is NE.MHSA:
-        return set(ops._BX3_CLASSES) if _BX3_MHSA else set(_BX3_MHSA_CLASSES)
+        return {'dx'}
     if seqs is not None and seqs < _BX3_MIN_SEQS:
         return set()
     return set(ops._BX3_CLASSES)
@@ -257,9 +252,9 @@ def _forward_backward_cne_sue(trainer, model, ne, ue, batch, dev, f32):
     with torch.no_grad():
         # ops.leaf_deferred's "is the step big enough to defer small reductions" input.  This step never posted it and ran on whatever the process's last
         # OTHER step had left there (0 in a fresh process -- what every A/B of this step was tuned on --, 102 400 behind an MHSA step): posted now, so
-        # that the step does not depend on its predecessors.  (Measured neutral either way, call 49; it is NOT why bench.py's batch-8 leg runs 7 % behind
-        # its stand-alone command -- see ops.new_stream.)
-        ops.STEP_ROWS[0] = user_title_text.numel() if _CNE_STEP_ROWS else 0
+        # that the step does not depend on its predecessors.  (Posting the history call's token rows instead -- Model.forward's rule -- measured neutral,
+        # call 49; it is NOT why bench.py's batch-8 leg runs 7 % behind its stand-alone command -- see ops.new_stream.)
+        ops.STEP_ROWS[0] = 0
         ops.wt_prefetch(dev)                          # W^T copies the backward pass multiplies by, on the leaf stream
         cand = (news_title_text, news_title_mask, news_content_text, news_content_mask, news_category, news_subCategory)
         hist = (user_title_text, user_title_mask, user_content_text, user_content_mask, user_category, user_subCategory)

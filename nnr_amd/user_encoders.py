@@ -11,8 +11,6 @@ SUE (userEncoders.py:42-98):
 Backward is hand-written against the same kernels; parameter gradients accumulate into `param.grad`."""
 import math
 
-import os
-
 import torch
 import torch.nn as nn
 
@@ -56,23 +54,18 @@ class _SUEFunction(torch.autograd.Function):
         return dhist, dcand, None, None, None, None
 
 
-_SUE_JOIN = os.environ.get('NNR_SUE_JOIN', '0') == '1'      # 0 (default) = this encoder's weight-gradient GEMMs (leaf stream) are joined at the end of the step; 1 = the main
-                                                             # stream waits for them when this encoder's backward returns (what a data-parallel early bucket needs: forced there).
-                                                             # Round 4, same box: batch 8 3.20-3.21 vs 3.33-3.40 ms (the main stream sat idle for ~200 us behind four 65 us GEMMs),
-                                                             # batch 16 4.35-4.40 vs 4.42-4.44, batch 64 10.43-10.49 vs 10.47-10.55 (an earlier A/B at batch 64 alone read neutral)
-_GCN_FUSED = os.environ.get('NNR_GCN_FUSED', '1') != '0'      # A/B: dedicated per-user aggregate kernel vs the batched tile GEMM
-_SUE_SIDE = os.environ.get('NNR_SUE_SIDE', '1') != '0'        # round 4: the candidate-side projections (inputs: the candidates only) and the candidate gradient's
-                                                              # accumulations (read by nobody before the news encoder's backward) leave SUE's dependent chain for a side stream
+# round 4: the candidate-side projections (inputs: the candidates only) and the candidate gradient's accumulations (read by nobody before the news
+# encoder's backward) leave SUE's dependent chain for a side stream
 _SIDE = {}
 ops.STREAM_CACHES.append(_SIDE)
 
 
 def _sue_side(dev):
-    if not _SUE_SIDE or ops.ONE_STREAM[0]:
+    if ops.ONE_STREAM[0]:
         return None
     key = (dev.type, dev.index)
     if key not in _SIDE:
-        _SIDE[key] = ops.new_stream(dev, critical=True)
+        _SIDE[key] = ops.new_stream(dev)
     return _SIDE[key]
 
 
@@ -99,7 +92,7 @@ def gcn_forward(gcn, x0, graph, seed0, training):
             ln = layer.layer_normalization
             ops.layernorm_fwd(u, ln.weight, ln.bias, ln.eps, xhat, rstd, r, x if gcn.residual else None, y, pl, seed0 + l)
             lns.append((xhat, rstd))
-        elif _GCN_FUSED and G <= 128 and D % 4 == 0:
+        elif G <= 128 and D % 4 == 0:                                              # dedicated per-user aggregate kernel
             ops.gcn_aggregate_fwd(graph, z, layer.W.bias, x if gcn.residual else None, r, y, B, G, D, True, pl, seed0 + l)
             lns.append(None)
         else:
@@ -123,7 +116,7 @@ def gcn_backward(gcn, gsv, dy, graph, leaf):
         pl = (gcn.dropout_rate if gsv['training'] else 0.0) if l + 1 < Lg else 0.0
         dS = torch.empty((B, G, D), **f32)
         dx = torch.empty((B, G, D), **f32)
-        if _GCN_FUSED and G <= 128 and D % 4 == 0 and gsv['lns'][l] is None:
+        if G <= 128 and D % 4 == 0 and gsv['lns'][l] is None:
             # mask + ReLU gradient applied while dY is loaded, then dZ_b = A_b^T dS_b, one launch (csrc/gcn.hip)
             dz = torch.empty((B, G, D), **f32)
             ops.gcn_aggregate_bwd(graph, dy, gsv['rs'][l], dS, dx if gcn.residual else None, dz, B, G, D, pl, gsv['seed0'] + l)
@@ -256,9 +249,10 @@ def sue_backward(mod, sv, dout, dhist_out=None, dcand_accum=None):
     hook = mod.__dict__.get('_grads_ready_hook')
     # a data-parallel trainer starts reducing this encoder's gradients right after this function (early bucket): then they must be
     # ordered on the current stream when it returns.  Otherwise nobody needs them before the optimizer: the leaf stream is joined at
-    # the end of the backward pass, and the news encoder's backward starts without waiting for the last weight-gradient GEMMs
+    # the end of the backward pass, and the news encoder's backward starts without waiting for the last weight-gradient GEMMs (round 4, joined
+    # vs deferred: batch 8 3.33-3.40 vs 3.20-3.21 ms -- the main stream sat idle for ~200 us behind four 65 us GEMMs --, batch 64 10.47-10.55 vs 10.43-10.49)
     exchange = getattr(hook, '__self__', None)
-    need_now = _SUE_JOIN or (exchange is not None and exchange.active()) or not ops._DEFER.get('step_joins')      # (only the native step ends with its own join)
+    need_now = (exchange is not None and exchange.active()) or not ops._DEFER.get('step_joins')      # (only the native step ends with its own join)
     with ops.leaf_scope(dev, defer_join=not need_now) as leaf:
         res = _sue_backward_body(mod, sv, dout, leaf, B, Hn, D, N, Kc, G, Cn, A, p, seed, dev, f32, cand2, ia, dhist_out, dcand_accum)
     # (joined form) every parameter gradient of this encoder is now ordered on the current stream:

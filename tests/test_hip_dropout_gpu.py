@@ -84,7 +84,7 @@ def test_cne_sue_dropout_on_two_steps_use_fresh_masks():
 
 
 def test_cne_plugin_api_two_separate_calls_dropout_on(monkeypatch):
-    """NNR_CNE_UNION=0 / the plugin API: candidate call and history call are separate encoder calls with separate seeds."""
+    """_CNE_UNION = False / the plugin API: candidate call and history call are separate encoder calls with separate seeds."""
     from nnr_amd import news_encoders as NE
     monkeypatch.setattr(NE, '_CNE_UNION', False)
     cfg = _cne_cfg(batch_size=3)

@@ -23,3 +23,16 @@ def test_another_hardware_queue_count_is_kept_and_warned_about():
     assert r.returncode == 0 and r.stdout.strip() == '8' and 'GPU_MAX_HW_QUEUES=8' in r.stderr and 'SLOWER' in r.stderr
     r = _run('import nnr_amd', GPU_MAX_HW_QUEUES='4')
     assert r.returncode == 0 and r.stderr.strip() == ''
+
+
+def test_environment_variables_read_by_the_package_are_the_ones_readme_lists():
+    """Every NNR_* variable the package reads (Python `os.environ` / native `getenv`) has a row in README.md's table, and every row is read."""
+    import glob
+    import re
+    read = set()
+    for path in glob.glob(os.path.join(ROOT, 'nnr_amd', '**', '*.py'), recursive=True) + glob.glob(os.path.join(ROOT, 'nnr_amd', 'csrc', '*.hip')):
+        with open(path) as f:
+            read |= set(re.findall(r'''(?:environ\.get\(|environ\[|getenv\()\s*['"](NNR_[A-Z0-9_]+)['"]''', f.read()))
+    with open(os.path.join(ROOT, 'README.md')) as f:
+        listed = set(re.findall(r'^\| `(NNR_[A-Z0-9_]+)` \|', f.read(), flags=re.M))
+    assert read and read == listed, ('read, not listed: %s; listed, not read: %s' % (sorted(read - listed), sorted(listed - read)))

@@ -52,7 +52,6 @@ B="python3 bench.py --full --no_cpu_baseline --no_isolated --no_secondary --sust
 $B --prebuilt > $O/bench_prebuilt.json 2>> $O/bench2.err
 for b in 8 16 32 128; do $B --batch_size $b --steps 40 --warmup 8 > $O/bench_b$b.json 2>> $O/bench2.err; done
 $B --steps 40 --warmup 8 > $O/bench_b64.json 2>> $O/bench2.err
-NNR_BX3=0 NNR_POOL_TEAM=0 $B --steps 40 --warmup 8 > $O/bench_b64_f32_old_pools.json 2>> $O/bench2.err
 $B --config mhsa > $O/bench_mhsa.json 2>> $O/bench2.err
 python3 - <<PY
 import json, sys
@@ -82,7 +81,7 @@ timeout 600 python3 tools/replay_soak.py --steps 1500 > $O/soak.json 2> $O/soak.
 tail -c 300 $O/soak.json
 python3 - <<PY
 import json
-for n in ['bench_first', 'bench', 'bench_prebuilt', 'bench_b8', 'bench_b16', 'bench_b32', 'bench_b64', 'bench_b64_f32_old_pools', 'bench_b128', 'bench_mhsa']:
+for n in ['bench_first', 'bench', 'bench_prebuilt', 'bench_b8', 'bench_b16', 'bench_b32', 'bench_b64', 'bench_b128', 'bench_mhsa']:
     try:
         d = json.loads([l for l in open('$O/%s.json' % n) if l.startswith('{')][-1])
         r = d['roofline']

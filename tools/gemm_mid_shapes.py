@@ -14,13 +14,11 @@ for label, N, K in (('QKV', 1200, 500), ('out proj', 500, 400), ('att affine', 2
     ops.mark_weight(b)
     res = []
     for tile in (0, 2, 4, 5, 6, 7, 15, 16, 50, 51):
-        prev = ops.BX3[0]
-        ops.BX3[0] = tile in (50, 51)
-        kw = {} if tile in (50, 51) else {'tile': tile}
+        kw = {'tile': tile}
         if tile in (50, 51):
-            os.environ['NNR_BX3_TILE'] = str(tile)
-            ops._BX3_TILE = tile
-            ops._BX3_CLASSES = set(['dx', 'sue', 'proj', 'gate', 'other', ops.bx3_class(N, K)])
+            kw['b3'] = ops.bx3_images(b, N, K, K)      # the bf16x3 tiles read the weight's pre-split images
+        prev = ops.BX3[0]
+        ops.BX3[0] = False                             # (tile 0 = the automatic fp32 choice)
         f = lambda: ops.gemm(a, b, c, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, **kw)
         try:
             ms = timeit(f, iters=30)

@@ -2,8 +2,7 @@
 """The attention pools of CNE (csrc/pool.hip) alone, at the in-step shapes of a batch-64 step: 3 520 sequences (3 200 history + 320 candidate
 news), D = 400, title stream (L = 32, ~11.5 tokens) and content stream (L = 128, ~43 tokens, padded history slots = 1 token).  The four calls a
 token stream makes per step: self pool forward (score = w2 . tanh rows), cross pool forward (dot score), cross pool backward (d score + dv,
-no dx), self pool backward with the cross pool's terms folded into the one write of dx.  Prints us per call and GB/s of the algorithmic bytes;
-`--check` compares NNR_POOL_TEAM=1 (register-resident rows, round 6) with =0 (one streaming workgroup per sequence) in two child processes.
+no dx), self pool backward with the cross pool's terms folded into the one write of dx.  Prints us per call and GB/s of the algorithmic bytes.
 
     python tools/pool_bench.py [--stream content|title] [--dump out.pt]"""
 import argparse
@@ -55,8 +54,8 @@ calls = {
     'self_bwd (x read + dx written: 3.2 KB/token)': (lambda: ops.pool_bwd(score=None, alpha=alpha_s, dout=dout, lddo=2 * D, dout2=dself_x, lddo2=D, dx=dHt, lddx=D, dscore=ds,
                                                                          alpha_b=alpha_c, dout_b=dout, lddo_b=2 * D, dscore_b=ds_c, v_b=v, ldv_b=D, scale_b=scale, **kw), 8.0 * D + 16),
 }
-print('%s stream: %d sequences, L %d, %d live tokens (mean %.1f), <= 16 tokens: %d, 17..64: %d, > 64: %d; NNR_POOL_TEAM=%s' % (
-    a.stream, n, L, total, total / n, int((lens <= 16).sum()), int(((lens > 16) & (lens <= 64)).sum()), int((lens > 64).sum()), os.environ.get('NNR_POOL_TEAM', '1')))
+print('%s stream: %d sequences, L %d, %d live tokens (mean %.1f), <= 16 tokens: %d, 17..64: %d, > 64: %d' % (
+    a.stream, n, L, total, total / n, int((lens <= 16).sum()), int(((lens > 16) & (lens <= 64)).sum()), int((lens > 64).sum())))
 for name, (fn, per_tok) in calls.items():
     for _ in range(3):
         fn()
