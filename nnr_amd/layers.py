@@ -8,11 +8,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-
-
-# Bumped by every optimizer step that updates parameters through raw pointers (nnr_amd.trainer): derived weight layouts
-# (e.g. the packed LSTM fragments) are cached against it, together with torch's own version counters.
-PARAM_EPOCH = [0]
+from .ops import PARAM_EPOCH      # noqa: F401  (the derived-weight cache's epoch, importable here as before)
 
 
 def grad_of(p):

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .layers import Attention, ScaledDotProduct_CandidateAttention, MultiHeadAttention, Conv1D, LSTMParams, grad_of, PARAM_EPOCH
+from .layers import Attention, ScaledDotProduct_CandidateAttention, MultiHeadAttention, Conv1D, LSTMParams, grad_of
 
 _SITE = dict(title=1, content=2, cat=3, sub=4)
 _DP_TABLE_FIRST = int(os.environ.get('NNR_DP_TABLE_FIRST', '0'))       # 1: always, -1: when world_size > 1, 0 (default): never -- no multi-GPU box to measure it on
@@ -200,24 +200,14 @@ def cne_forward_many(mod, calls):
     """Run several independent CNE calls in lock-step: everything is per call except the Bi-LSTM recurrence, which is ONE
     launch over all streams of all calls (it is latency-bound by its longest sequence, not throughput-bound).  The per-call
     phases of the first (small) call run on a second HIP stream, filling the gaps of the big call's kernels."""
-    H = mod.hidden_dim
+    H, E = mod.hidden_dim, mod.word_embedding_dim
     dev = (calls[0][0][0] if isinstance(calls[0][0], tuple) else calls[0][0]).device
     if len(calls) > 1:
-        mod._packed_weights('title', mod.title_lstm)    # (re)pack on the main stream BEFORE forking: both calls read them
-        mod._packed_weights('content', mod.content_lstm)
+        ops.lstm_pack(mod.title_lstm, H, E)             # (re)pack on the main stream BEFORE forking: both calls read them
+        ops.lstm_pack(mod.content_lstm, H, E)
     else:
-        # one call (the union of candidate and history call): the two re-packs need nothing of this step but the parameters, so they
-        # run on the leaf stream next to the planner / row gather of the chains; each chain waits for them in front of its projection
-        key = (dev.type, dev.index)
-        if key not in ops._LEAF:
-            ops._LEAF[key] = ops.new_stream(dev)
-        leaf = ops._LEAF[key]
-        leaf.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(leaf):
-            mod._packed_weights('title', mod.title_lstm)
-            mod._packed_weights('content', mod.content_lstm)
-            mod.__dict__['_packed_ev'] = torch.cuda.Event()
-            mod.__dict__['_packed_ev'].record()
+        # one call (the union of candidate and history call): the two re-packs run on the leaf stream next to the planner / row gather
+        ops.lstm_prefetch(dev, (mod.title_lstm, mod.content_lstm), H, E)
     if mod.training:
         # the bf16 images of the parameters (and of their cached transposes) the gate / attention / user-encoder GEMMs will read: re-split on the LEAF
         # stream HERE -- behind the weight packing (which the input projection waits for: in front of it the splits cost +0.3 ms) and in FRONT of the
@@ -280,11 +270,8 @@ def _cne_fwd_pre(mod, title_text, title_mask, content_text, content_mask, catego
         if union and name == 'content':
             plan_ev = torch.cuda.Event()
             plan_ev.record()
-        w = mod._packed_weights(name, lstm)
+        w = ops.lstm_pack(lstm, H, E)
         cap = plan.cap
-        pev = mod.__dict__.get('_packed_ev')
-        if pev is not None:
-            torch.cuda.current_stream(dev).wait_event(pev)
         st = dict(name=name, L=Lx, plan=plan, plan_ev=plan_ev, w=w, lstm=lstm, Hlin=Hlin, Mlin=Mlin, satt=satt, catt=catt, seed=seed + _SITE[name])
         st['gates'] = torch.empty((cap, 2 * w.NP), **f32)
         # dropout(embedding rows) materialised ONCE per token (6 TB/s gather): fused into the GEMM's A loader the counter hash
@@ -700,17 +687,6 @@ class CNE(NewsEncoder):
         self.content_self_attention.initialize()
         self.title_cross_attention.initialize()
         self.content_cross_attention.initialize()
-
-    def _packed_weights(self, name, lstm):
-        """nn.LSTM parameters in the recurrent kernels' layouts, re-packed when the parameters change (once per optimizer
-        step: both encoder calls of a step share them)."""
-        cache = self.__dict__.setdefault('_pack_cache', {})
-        key = (PARAM_EPOCH[0],) + tuple((q.data_ptr(), q._version) for q in lstm.param_list())
-        hit = cache.get(name)
-        if hit is None or hit[0] != key:
-            hit = (key, ops.LstmPacked(lstm.param_list(), self.hidden_dim, self.word_embedding_dim))
-            cache[name] = hit
-        return hit[1]
 
     def forward(self, title_text, title_mask, title_entity, content_text, content_mask, content_entity, category, subCategory, user_embedding):
         # title_entity / content_entity / user_embedding are accepted and ignored, as in the reference (newsEncoders.py:102-141)

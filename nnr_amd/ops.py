@@ -9,6 +9,7 @@ import torch
 
 from . import _lib as L
 from . import profile as _prof
+from . import tape as _tape
 
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
 K_CHUNK = 1024      # reduction rows per slice of the token-reduction (weight-gradient) GEMMs, see nnr_gemm_args.k_chunk
@@ -112,6 +113,15 @@ _LEAF_ALT = {}
 STREAM_CACHES.append(_LEAF_ALT)
 
 
+def leaf_stream(dev, alt=False):
+    """The leaf stream of `dev` (alt: the second one, see leaf_scope), created on first use."""
+    table = _LEAF_ALT if alt else _LEAF
+    key = (dev.type, dev.index)
+    if key not in table:
+        table[key] = new_stream(dev)
+    return table[key]
+
+
 def join_extra_streams(dev=None):
     """Make the current stream wait for everything enqueued on the package's own streams.  Every backward function joins
     the streams it used before it returns; the trainer calls this once more before the gradient exchange / optimizer
@@ -149,10 +159,7 @@ class leaf_scope:
     def __enter__(self):
         self.keep = []
         if self.enable:
-            key = (self.dev.type, self.dev.index)
-            if key not in _LEAF:
-                _LEAF[key] = new_stream(self.dev)
-            self.leaf = _LEAF[key]
+            self.leaf = leaf_stream(self.dev)
             self.leaf2 = None
             self.main = torch.cuda.current_stream(self.dev)
         return self
@@ -166,10 +173,7 @@ class leaf_scope:
         st = self.leaf
         if alt and not ONE_STREAM[0]:
             if self.leaf2 is None:
-                key = (self.dev.type, self.dev.index)
-                if key not in _LEAF_ALT:
-                    _LEAF_ALT[key] = new_stream(self.dev)
-                self.leaf2 = _LEAF_ALT[key]
+                self.leaf2 = leaf_stream(self.dev, alt=True)
             st = self.leaf2
         st.wait_stream(torch.cuda.current_stream(self.dev))     # the producer of the inputs (may be a side stream)
         self.keep.extend(tensors)
@@ -211,10 +215,7 @@ def leaf_deferred(dev, rows, fn, *tensors):
     if _DEFER.get('off') or max(rows, STEP_ROWS[0]) < LEAF_MIN_ROWS:
         fn()
         return
-    key = (dev.type, dev.index)
-    if key not in _LEAF:
-        _LEAF[key] = new_stream(dev)
-    leaf, main = _LEAF[key], torch.cuda.current_stream(dev)
+    leaf, main = leaf_stream(dev), torch.cuda.current_stream(dev)
     leaf.wait_stream(main)
     _DEFER['keep'].extend(tensors)
     _DEFER['calls'] += 1
@@ -235,91 +236,185 @@ def tape_keep(*tensors):
     module-level tables (W^T copies and their descriptor table, slot / exchange workspaces, packed-gradient accumulators) are replaced
     when a table is rebuilt -- e.g. after other models of the process were garbage-collected -- and a tape must not be left pointing
     at freed memory.  No-op when nothing records."""
-    from . import tape as _tape
     t = _tape.ACTIVE[0]
     if t is not None:
         t.keep.extend(x for x in tensors if x is not None)
 
 
-_WT = {}
+# ---------------------------------------------------------------------------------------------- derived weights
+# W^T copies (wt), bf16x3 images (bx3_images) and packed LSTM layouts (lstm_pack): buffers computed from the parameters, in one cache.
+#   identity   entry key (kind, source); the source is held by weak reference and a tensor source's pointer is checked on every lookup (the
+#              caching allocator hands a freed tensor's address to the next tensor of that size -- found with bf16x3 on: 10 GPU tests
+#              multiplied by the previous test's weights).  The buffers keep their addresses while the source lives: refreshes refill them.
+#   freshness  refreshed when the stamp moved: PARAM_EPOCH (every optimizer step that writes the parameters through raw pointers), the tape
+#              that records (a recorded step must hold the refresh of every derived buffer it reads, or its replays would run on the
+#              parameters of the recording step), and per source its (pointer, version counter) or, for a derived source, that entry's
+#              generation (bumped by every refresh: the images of a W^T copy follow the copy however the parameter changed).
+#   streams    a refresh runs on the stream of the first user, or on the leaf stream in a prefetch, and records an event that users on other
+#              streams wait for (without it the history call read images the candidate call was still writing: 7.7e-2 gradient error in the
+#              two-ranks-on-one-GPU test).  Refilling in place is safe: the last step's readers joined the main stream before the optimizer.
+PARAM_EPOCH = [0]
+_DERIVED = {}               # (kind, id(source)) -> _Derived
+_OWNED = {}                 # id(derived buffer) -> its entry (which holds the buffer: the id cannot be reused while it is listed)
+_DERIVED_SWEEP = 256        # a new entry beyond this many first drops every entry whose source has died
+_WT_DESCS = [None, None]    # (descriptors, device-resident nnr_transpose_batch table) of the last W^T prefetch
 
 
-class _WtEntry:
-    __slots__ = ('ref', 'ptr', 'epoch', 'version', 't', 'event', 'stream')
+class _Derived:
+    __slots__ = ('ref', 'ptr', 'spec', 'out', 'bufs', 'prefetch', 'stamp', 'gen', 'event', 'stream', 'served')
 
 
-_WT_TABLE = {'ids': None, 'dev': None, 'count': 0}      # device-resident descriptor table of the registered transposes
+def is_weight(t):
+    """A parameter or a buffer of the derived-weight cache: rewritten only when the parameters change, so its bf16x3 images can be cached
+    (an activation buffer is rewritten through the C-ABI without any version bump)."""
+    return isinstance(t, torch.nn.Parameter) or id(t) in _OWNED
+
+
+def _drop(key):
+    for b in _DERIVED.pop(key).bufs:
+        _OWNED.pop(id(b), None)
+
+
+def _derived(kind, src, spec, make, prefetch):
+    """The entry of (kind, src) with layout `spec`; a new one (make(): a tensor, or an object listing its tensors in `bufs`) when there is none
+    or it was made for another object, address or layout.  prefetch: the entry may be refreshed by its kind's prefetch at the start of a step."""
+    key = (kind, id(src))
+    ptr = src.data_ptr() if torch.is_tensor(src) else None
+    e = _DERIVED.get(key)
+    if e is not None and e.ref() is src and e.ptr == ptr and e.spec == spec:
+        return e
+    if e is not None:
+        _drop(key)
+    if len(_DERIVED) > _DERIVED_SWEEP:
+        for k in [k for k, v in _DERIVED.items() if v.ref() is None]:
+            _drop(k)
+    e = _DERIVED[key] = _Derived()
+    e.ref, e.ptr, e.spec, e.prefetch = weakref.ref(src), ptr, spec, prefetch
+    e.out = make()
+    e.bufs = (e.out,) if torch.is_tensor(e.out) else e.out.bufs
+    e.stamp, e.gen, e.event, e.stream, e.served = None, 0, None, None, False
+    for b in e.bufs:
+        _OWNED[id(b)] = e
+    return e
+
+
+def _stamp(sources):
+    t = _tape.ACTIVE[0]
+    s = [PARAM_EPOCH[0], None if t is None else weakref.ref(t)]
+    for x in sources:
+        o = _OWNED.get(id(x))
+        s.append(o.gen if o is not None else (x.data_ptr(), x._version))
+    return tuple(s)
+
+
+def _refreshed(jobs, stream):
+    """jobs = [(entry, stamp)] were just refilled on the current stream (raw handle `stream`): one event for all of them."""
+    ev = torch.cuda.Event()
+    ev.record()
+    for e, stamp in jobs:
+        e.stamp, e.gen, e.event, e.stream = stamp, e.gen + 1, ev, stream
+
+
+def _serve(e, sources, fill):
+    """Hand out entry `e` (computed from `sources`) to a launch on the current stream: refilled here by fill() when stale, else ordered behind
+    its last refresh."""
+    e.served = True
+    tape_keep(*e.bufs)
+    stamp, cur = _stamp(sources), _s().value
+    if e.stamp != stamp:
+        fill()
+        _refreshed([(e, stamp)], cur)
+    elif e.stream != cur:
+        torch.cuda.current_stream(e.bufs[0].device).wait_event(e.event)
+
+
+def _stale(kind):
+    """[(entry, source, stamp)] of the prefetchable entries of `kind` that were served since the last prefetch (not another model's) and are
+    stale."""
+    jobs = []
+    for (k, _), e in _DERIVED.items():
+        src = e.ref() if k == kind and e.prefetch and e.served else None
+        if src is not None and src.data_ptr() == e.ptr:
+            stamp = _stamp((src,))
+            if e.stamp != stamp:
+                jobs.append((e, src, stamp))
+    return jobs
+
+
+def _on_leaf(dev, jobs, launch):
+    """launch() -- the refresh of jobs = [(entry, source(s), stamp)] -- on the leaf stream, behind the current stream's work (the optimizer step
+    that changed the parameters), with one event for all of them."""
+    leaf = leaf_stream(dev)
+    leaf.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(leaf):
+        launch()
+        _refreshed([(e, stamp) for e, _, stamp in jobs], _s().value)
+    for e, _, _ in jobs:
+        e.served = False
 
 
 def wt(w):
-    """W^T (contiguous [cols, rows]) of a 2-D contiguous PARAMETER, cached until the parameter changes (optimizer step:
-    layers.PARAM_EPOCH; in-place edits: the tensor's version counter).  With it every data-gradient GEMM dX = dY . W becomes
-    an NT product (both operands K-contiguous) and runs on the LDS-DMA staged kernels; the transposes are a few hundred KB per
-    step against GBs of activations.  A stale copy is refreshed on the stream of the first user; a user on another HIP stream
-    waits for the producer's event.  In training, Model.forward refreshes ALL registered copies in one launch on the leaf
-    stream (wt_prefetch), so the backward pass only ever finds fresh ones."""
-    from .layers import PARAM_EPOCH
-    # identity of the cached object: the tensor OBJECT (weak reference) + its pointer.  A pointer alone is not an identity --
-    # the caching allocator hands a freed parameter's address to the next model's parameter of the same shape.
-    e = _WT.get(id(w))
-    cur = torch._C._cuda_getCurrentRawStream(_DEV_INDEX[0] if _DEV_INDEX else torch.cuda.current_device())
-    if e is not None and e.epoch == PARAM_EPOCH[0] and e.version == w._version and e.ptr == w.data_ptr() and e.ref() is w:
-        if e.stream != cur:
-            torch.cuda.current_stream(w.device).wait_event(e.event)
-        tape_keep(e.t)
-        return e.t
+    """W^T (contiguous [cols, rows]) of a 2-D contiguous weight.  With it every data-gradient GEMM dX = dY . W becomes an NT product (both
+    operands K-contiguous) and runs on the LDS-DMA staged kernels; the transposes are a few hundred KB per step against GBs of activations.
+    In training, Model.forward / the native step refresh the stale copies of every parameter in one launch on the leaf stream (wt_prefetch),
+    so the backward pass only ever finds fresh ones."""
     rows, cols = w.shape
-    if e is None or e.ref() is not w or e.ptr != w.data_ptr() or e.t.shape != (cols, rows):
-        if len(_WT) > 256:                                   # entries of dead tensors (temporary views, discarded models)
-            for k in [k for k, v in _WT.items() if v.ref() is None]:
-                del _WT[k]
-        e = _WtEntry()
-        e.ref, e.ptr = weakref.ref(w), w.data_ptr()
-        e.t = torch.empty((cols, rows), device=w.device, dtype=torch.float32)      # kept across refreshes: stable address
-        _WT[id(w)] = e
-        _WT_TABLE['ids'] = None
-        mark_weight(e.t, prefetchable=True)
-    tape_keep(e.t)
-    transpose2d(w, e.t, rows, cols)
-    e.event = torch.cuda.Event()
-    e.event.record()
-    e.epoch, e.version, e.stream = PARAM_EPOCH[0], w._version, cur
-    return e.t
+    e = _derived('wt', w, (rows, cols), lambda: torch.empty((cols, rows), device=w.device, dtype=torch.float32), isinstance(w, torch.nn.Parameter))
+    _serve(e, (w,), lambda: transpose2d(w, e.out, rows, cols))
+    return e.out
 
 
 def wt_prefetch(dev):
-    """Refresh, on the leaf stream and in ONE launch (nnr_transpose_batch over a device-resident descriptor table), the
-    transposes of every parameter wt() has served before and that changed since (i.e. after an optimizer step).  Called at the
-    start of a training forward pass: the copies are needed by the BACKWARD pass only, so they leave the critical chain --
-    made lazily, the first user's stream does the copy and users on the other streams wait for it (measured: a 383 us stall
-    of the history call's backward behind the candidate call's)."""
-    if not _WT or torch.cuda.is_current_stream_capturing():      # (under hipGraph capture the copies are refreshed lazily by wt():
-        return                                                               # ending a capture that holds this fork segfaults in the HIP runtime)
-    from .layers import PARAM_EPOCH
-    live = [(k, e, e.ref()) for k, e in _WT.items()]
-    live = [(k, e, w) for k, e, w in live if w is not None and isinstance(w, torch.nn.Parameter) and e.ptr == w.data_ptr()]
-    if not live or all(e.epoch == PARAM_EPOCH[0] and e.version == w._version for _, e, w in live):
+    """Refresh, on the leaf stream and in ONE launch (nnr_transpose_batch over a device-resident descriptor table), the stale W^T copies of the
+    parameters wt() served since the last prefetch (i.e. after an optimizer step).  Called at the start of a training forward pass: the copies
+    are needed by the BACKWARD pass only, so they leave the critical chain -- made lazily, the first user's stream does the copy and users on
+    the other streams wait for it (measured: a 383 us stall of the history call's backward behind the candidate call's)."""
+    if torch.cuda.is_current_stream_capturing():        # (under hipGraph capture the copies are refreshed lazily by wt(): ending a
+        return                                          # capture that holds this fork segfaults in the HIP runtime)
+    jobs = _stale('wt')
+    if not jobs:
         return
-    ids = tuple(k for k, _, _ in live)
-    if _WT_TABLE['ids'] != ids:
-        arr = (L.TransposeDesc * len(live))()
-        for d, (_, e, w) in zip(arr, live):
-            d.inp, d.out, d.rows, d.cols = w.data_ptr(), e.t.data_ptr(), w.shape[0], w.shape[1]
-        host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-        _WT_TABLE.update(ids=ids, dev=host.to(dev), count=len(live))
-    key = (dev.type, dev.index)
-    if key not in _LEAF:
-        _LEAF[key] = new_stream(dev)
-    leaf = _LEAF[key]
-    leaf.wait_stream(torch.cuda.current_stream(dev))       # behind the optimizer step that changed the parameters
-    tape_keep(_WT_TABLE['dev'], *[e.t for _, e, _ in live])
-    with torch.cuda.stream(leaf):
-        L.check(L.lib().nnr_transpose_batch(_p(_WT_TABLE['dev']), _WT_TABLE['count'], _s()), 'nnr_transpose_batch')
-        ev = torch.cuda.Event()
-        ev.record()
-        cur = torch._C._cuda_getCurrentRawStream(_DEV_INDEX[0] if _DEV_INDEX else torch.cuda.current_device())
-    for _, e, w in live:
-        e.epoch, e.version, e.event, e.stream = PARAM_EPOCH[0], w._version, ev, cur
+    descs = tuple((w.data_ptr(), e.out.data_ptr(), w.shape[0], w.shape[1]) for e, w, _ in jobs)
+    if _WT_DESCS[0] != descs:
+        arr = (L.TransposeDesc * len(descs))()
+        for d, (src, out, rows, cols) in zip(arr, descs):
+            d.inp, d.out, d.rows, d.cols = src, out, rows, cols
+        _WT_DESCS[:] = [descs, torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)]
+    table = _WT_DESCS[1]
+    tape_keep(table, *[e.out for e, _, _ in jobs])
+    _on_leaf(dev, jobs, lambda: L.check(L.lib().nnr_transpose_batch(_p(table), len(descs), _s()), 'nnr_transpose_batch'))
+
+
+def _pack_entry(lstm, p, H, E):
+    return _derived('lstm', lstm, (H, E), lambda: LstmPacked(p, H, E, fill=False), False)
+
+
+def lstm_pack(lstm, H, E):
+    """The parameters of `lstm` (layers.LSTMParams) in the recurrent kernels' layouts (LstmPacked), refilled in place when they changed (once
+    per optimizer step: both encoder calls of a step share them)."""
+    p = lstm.param_list()
+    e = _pack_entry(lstm, p, H, E)
+    _serve(e, p, lambda: e.out.pack(p))
+    return e.out
+
+
+def lstm_prefetch(dev, lstms, H, E):
+    """Refresh the stale packs of `lstms` on the leaf stream, one event for all: they need nothing of the step but the parameters, so they run
+    next to the planner / row gather of the chains; each chain waits for them in front of its input projection (lstm_pack)."""
+    jobs = []
+    for lstm in lstms:
+        p = lstm.param_list()
+        e = _pack_entry(lstm, p, H, E)
+        stamp = _stamp(p)
+        if e.stamp != stamp:
+            jobs.append((e, p, stamp))
+
+    def launch():
+        for e, p, _ in jobs:
+            tape_keep(*e.bufs)
+            e.out.pack(p)
+    if jobs:
+        _on_leaf(dev, jobs, launch)
 
 
 def tn_tile(M, N, K, gather=False):
@@ -355,8 +450,8 @@ def split_for(m, n, k, tile_m=64, tile_n=80, target_blocks=2048, kmin=256):
 # ---------------------------------------------------------------------------------------------- bf16x3 NT GEMMs (the default matrix path since round 6)
 # The GPU-filling NT launches whose B operand is a weight (a parameter, a cached transpose, the packed LSTM input weights) run on
 # csrc/gemm.hip:gemm_nt_bx3_kernel: fp32 arithmetic as six exact bf16 x bf16 products with fp32 accumulation: the same
-# fp32 inputs, fp32 outputs, and a third of the fp32-MFMA kernel's error against fp64.  The weight's three bf16 images are cached per (storage,
-# shape) and re-split when the parameters changed (layers.PARAM_EPOCH) -- one small launch per weight and step, recorded in the launch tape
+# fp32 inputs, fp32 outputs, and a third of the fp32-MFMA kernel's error against fp64.  The weight's three bf16 images are derived weights (see
+# above): re-split when the weight changed -- one small launch per weight and step, recorded in the launch tape
 # like any other call.  Round 5 measured it (off); round 6 made it the default after five interleaved same-box pairs + a per-shape-class A/B
 # (profiles/r06_bx3_phases.md: -0.33 ms of the 10.27 ms headline step, every class positive).  NNR_BX3=0 = the pure fp32-MFMA path
 # (bench.py keeps it as a `secondary` leg of the same workload so that both numbers are driver-timed).
@@ -381,87 +476,41 @@ def bx3_class(N, K):
     return 'gate'
 
 
-_B3 = {}
 BX3_SEEN = {}                                                  # diagnostics: (M, N, K, 'weight' | 'other') -> launches that met every other condition
 
 
-def mark_weight(*tensors, prefetchable=False):
-    """`tensors` are derived weights (a cached transpose, a packed layout): rewritten only when the parameters change (layers.PARAM_EPOCH).
-    prefetchable: the tensor is refreshed on the leaf stream at the START of a step (wt_prefetch's transposes), so bx3_prefetch may re-split
-    it there; the packed LSTM weights are re-packed inside the forward pass and are split by their first user instead."""
-    for t in tensors:
-        t._nnr_weight = True
-        if prefetchable:
-            t._nnr_prefetch = True
+def _split_bf16x3(B, N, K, ldb, img):
+    ldo = img.shape[2]
+    L.check(L.lib().nnr_split_bf16x3(_p(B), N, K, ldb, ldo, _p(img), C.c_long(N * ldo), _s()), 'nnr_split_bf16x3')
 
 
 def bx3_prefetch(dev):
-    """Re-split, on the leaf stream at the start of a training step (right behind wt_prefetch's transposes, same stream), the bf16 images of
-    every weight bx3_images() has served before and that changed since (i.e. after an optimizer step): parameters and their cached transposes.
-    Made lazily, each split is a 3-30 us launch on the stream of its first user -- five of them sat on the step's dependent chain in front of
-    their GEMMs (profiles/r06_ab.txt: split_bf16x3_kernel 21 / 11 / 34 / 28 / 14 us on the main streams)."""
-    if not BX3[0] or not _B3 or torch.cuda.is_current_stream_capturing():
+    """Re-split, on the leaf stream at the start of a training step (right behind wt_prefetch's transposes, same stream), the stale bf16 images
+    of every parameter and cached transpose bx3_images() served since the last prefetch (i.e. after an optimizer step).  Made lazily, each split
+    is a 3-30 us launch on the stream of its first user -- five of them sat on the step's dependent chain in front of their GEMMs
+    (profiles/r06_ab.txt: split_bf16x3_kernel 21 / 11 / 34 / 28 / 14 us on the main streams).  The images of the packed LSTM weights, re-packed
+    inside the forward pass, are split by their first user."""
+    if not BX3[0] or torch.cuda.is_current_stream_capturing():
         return
-    from .layers import PARAM_EPOCH
-    stale = []
-    for e in _B3.values():
-        B = e[3]()
-        if B is None or e[4][0] != B.data_ptr() or not (isinstance(B, torch.nn.Parameter) or getattr(B, '_nnr_prefetch', False)):
-            continue
-        if not e[7] or (e[1] == PARAM_EPOCH[0] and e[2] == B._version):
-            continue                                  # (not served since the last prefetch -- another model's weight -- or still fresh)
-        e[7] = False
-        stale.append((e, B))
-    if not stale:
-        return
-    key = (dev.type, dev.index)
-    if key not in _LEAF:
-        _LEAF[key] = new_stream(dev)
-    leaf = _LEAF[key]
-    leaf.wait_stream(torch.cuda.current_stream(dev))       # behind the optimizer step that changed the parameters
-    with torch.cuda.stream(leaf):
-        for e, B in stale:
-            _, N, K, ldb = e[4]
-            ldo = e[0].shape[2]
-            tape_keep(e[0], B)                    # (B: a parameter -- inside the trainer's flat buffer -- or a long-lived cached transpose)
-            L.check(L.lib().nnr_split_bf16x3(_p(B), N, K, ldb, ldo, _p(e[0]), C.c_long(N * ldo), _s()), 'nnr_split_bf16x3')
-        ev = torch.cuda.Event()
-        ev.record()
-        cur = torch._C._cuda_getCurrentRawStream(_DEV_INDEX[0] if _DEV_INDEX else torch.cuda.current_device())
-    for e, B in stale:
-        e[1], e[2], e[5], e[6] = PARAM_EPOCH[0], B._version, ev, cur
+    jobs = _stale('bx3')
+
+    def launch():
+        for e, B, _ in jobs:
+            tape_keep(e.out, B)                   # (B: a parameter -- inside the trainer's flat buffer -- or a long-lived cached transpose)
+            _split_bf16x3(B, *e.spec, e.out)
+    if jobs:
+        _on_leaf(dev, jobs, launch)
 
 
 def bx3_images(B, N, K, ldb):
-    """(images [3, N, ldo] bf16-as-int16, image stride in elements, ldo) of the [N, K] weight `B`, re-split when the parameters changed.
-    Identity of a cached entry = the tensor OBJECT (weak reference) + its pointer + the parameter epoch + the tensor's version counter: a
-    pointer alone is not an identity (the caching allocator hands a freed model's addresses to the next model -- found by running the GPU
-    suite with NNR_BX3=1: 10 tests multiplied by the previous test's weights).  The split runs on the stream of the first user; a user
-    on another HIP stream waits for the producer's event, as wt() does (the candidate and the history calls of one step share every
-    weight and run on two streams: without the wait the second one can read images that are still being written -- found by the
-    two-ranks-on-one-GPU test under NNR_BX3=1, 7.7e-2 gradient error)."""
-    from .layers import PARAM_EPOCH
-    e = _B3.get(id(B))
+    """(images [3, N, ldo] bf16-as-int16, image stride in elements, ldo) of the [N, K] weight `B` (a derived-weight-cache entry: re-split when
+    `B` changed)."""
     ldo = (K + 7) // 8 * 8
-    cur = torch._C._cuda_getCurrentRawStream(_DEV_INDEX[0] if _DEV_INDEX else torch.cuda.current_device())
-    if e is not None and (e[3]() is not B or e[4] != (B.data_ptr(), N, K, ldb)):
-        e = None
-    if e is None:
-        if len(_B3) > 512:
-            for k in [k for k, v in _B3.items() if v[3]() is None]:
-                del _B3[k]
-        e = _B3[id(B)] = [torch.empty((3, N, ldo), device=B.device, dtype=torch.int16), -1, None, weakref.ref(B), (B.data_ptr(), N, K, ldb), None, None, True]
-    tape_keep(e[0])
-    e[7] = True                                   # served since the last bx3_prefetch: worth re-splitting ahead of the next step's first user
-    if e[1] != PARAM_EPOCH[0] or e[2] != B._version:
-        # (write-after-read: last step's readers on every stream joined the main stream before the optimizer step that changed the epoch)
-        L.check(L.lib().nnr_split_bf16x3(_p(B), N, K, ldb, ldo, _p(e[0]), C.c_long(N * ldo), _s()), 'nnr_split_bf16x3')
-        e[5] = torch.cuda.Event()
-        e[5].record()
-        e[1], e[2], e[6] = PARAM_EPOCH[0], B._version, cur
-    elif e[6] != cur:
-        torch.cuda.current_stream(B.device).wait_event(e[5])
-    return e[0], N * ldo, ldo
+    owner = _OWNED.get(id(B))
+    e = _derived('bx3', B, (N, K, ldb), lambda: torch.empty((3, N, ldo), device=B.device, dtype=torch.int16),
+                 isinstance(B, torch.nn.Parameter) or (owner is not None and owner.prefetch))
+    _serve(e, (B,), lambda: _split_bf16x3(B, N, K, ldb, e.out))
+    return e.out, N * ldo, ldo
 
 
 def _bx3_wanted(A, B, M, N, K, lda, ldb, trans_a, trans_b, a_idx, b_idx, c_idx, split_k, k_chunk, rowdot_w, colsum_out, atomic, batch, dyn_dim, drop):
@@ -531,9 +580,8 @@ def gemm(A, B, C_=None, *, M, N, K, lda, ldb, ldc=0, trans_a=False, trans_b=Fals
         g.gate_bwd = 1
     if b3 is None and BX3[0] and tile in (0, 9, 15, 16) and _bx3_wanted(A, B, M, N, K, lda, ldb, trans_a, trans_b, a_idx, b_idx, c_idx, split_k, k_chunk, rowdot_w,
                                                                     colsum_out, atomic, batch, dyn_dim, drop):
-        # (NNR_BX3, default on): this NT launch on the BF16 matrix pipe, weights pre-split.  Only when B IS a weight: a parameter or a
-        # marked derived weight -- an activation buffer is rewritten through the C-ABI without any version bump, so its cached images would go stale
-        is_w = isinstance(B, torch.nn.Parameter) or getattr(B, '_nnr_weight', False)
+        # (NNR_BX3, default on): this NT launch on the BF16 matrix pipe, weights pre-split.  Only when B IS a weight (is_weight)
+        is_w = is_weight(B)
         key = (M, N, K, 'weight' if is_w else 'other')
         BX3_SEEN[key] = BX3_SEEN.get(key, 0) + 1
         if is_w and bx3_class(N, K) in _BX3_CLASSES:
@@ -741,20 +789,24 @@ def lstm_dims(H):
 
 
 class LstmPacked:
-    """nn.LSTM parameters re-laid out for the recurrent kernels (csrc/lstm.hip)."""
+    """nn.LSTM parameters `p` (in nn.LSTM order) re-laid out for the recurrent kernels (csrc/lstm.hip); pack(p) refills the buffers in place
+    (fill=False: allocate only)."""
 
-    def __init__(self, p, H, E):
+    def __init__(self, p, H, E, fill=True):
         ub, hp, np_ = lstm_dims(H)
-        dev = p[0].device
-        f = dict(device=dev, dtype=torch.float32)
+        f = dict(device=p[0].device, dtype=torch.float32)
         self.UB, self.HP, self.NP, self.H, self.E = ub, hp, np_, H, E
         self.w_ihp = torch.empty((2 * np_, E), **f)
         self.b_p = torch.empty(2 * np_, **f)
         self.wf = torch.empty(2 * ub * 4 * ub * 256, **f)
         self.wb = torch.empty(2 * ub * (np_ // 16) * 256, **f)
         self.w_ihp_t = torch.empty((E, 2 * np_), **f)             # [E, 2*NP]: K-contiguous B operand of the dX GEMM (NT form)
-        mark_weight(self.w_ihp, self.w_ihp_t)
-        L.check(L.lib().nnr_lstm_pack_weights(*[_p(t) for t in p], H, E, _p(self.w_ihp), _p(self.b_p), _p(self.wf), _p(self.wb),
+        self.bufs = (self.w_ihp, self.b_p, self.wf, self.wb, self.w_ihp_t)
+        if fill:
+            self.pack(p)
+
+    def pack(self, p):
+        L.check(L.lib().nnr_lstm_pack_weights(*[_p(t) for t in p], self.H, self.E, _p(self.w_ihp), _p(self.b_p), _p(self.wf), _p(self.wb),
                                               _p(self.w_ihp_t), _s()), 'nnr_lstm_pack_weights')
 
 
@@ -1288,10 +1340,7 @@ class TokenSort:
         nb = int(L.lib().nnr_token_sort_workspace_bytes(C.c_long(cap), self.vocab))
         temp = torch.empty(max(nb, 256), device=dev, dtype=torch.uint8)
         self.partial = torch.empty(int(L.lib().nnr_embed_scatter_sorted_workspace_floats(C.c_long(cap))), device=dev, dtype=torch.float32)
-        key = (dev.type, dev.index)
-        if key not in _LEAF:
-            _LEAF[key] = new_stream(dev)
-        leaf = _LEAF[key]
+        leaf = leaf_stream(dev)
         leaf.wait_stream(torch.cuda.current_stream(dev))          # behind the planner that wrote `tok` / `total`
         with torch.cuda.stream(leaf):
             L.check(L.lib().nnr_token_sort(_p(tok), C.c_long(cap), _p(total), self.vocab, _p(buf[:cap]), _p(buf[cap:2 * cap]), _p(self.keys), _p(self.rows),

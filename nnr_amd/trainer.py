@@ -9,7 +9,6 @@ import torch.nn as nn
 
 from . import dp, ops
 from . import profile as _prof
-from .layers import PARAM_EPOCH
 from .model import negative_log_softmax
 
 # NNR_NATIVE_STEP=0: always the autograd path (loss.backward() through the encoders' autograd Functions).
@@ -193,12 +192,8 @@ class Trainer:
         """Clear the flat gradient buffer on the leaf stream: nothing writes a gradient before the backward pass, so the 100 MB fill
         leaves the head of the step's dependent chain (forward_backward waits for it via wait_grad_zeroed)."""
         dev = self.flat.grad.device
-        main = torch.cuda.current_stream(dev)
-        key = (dev.type, dev.index)
-        if key not in ops._LEAF:
-            ops._LEAF[key] = ops.new_stream(dev)
-        leaf = ops._LEAF[key]
-        leaf.wait_stream(main)                          # behind the previous step's optimizer (it reads the gradients)
+        leaf = ops.leaf_stream(dev)
+        leaf.wait_stream(torch.cuda.current_stream(dev))        # behind the previous step's optimizer (it reads the gradients)
         with torch.cuda.stream(leaf):
             self.flat.zero_grad()
             self._zeroed = torch.cuda.Event()
@@ -251,7 +246,7 @@ class Trainer:
             tape.replay(values, batch, timing=timing)
             if timing:
                 self._snapshot_sizes(tape)
-            PARAM_EPOCH[0] += 1
+            ops.PARAM_EPOCH[0] += 1
             self.last_path = 'replay'
             # tape.out are the recorded step's OWN logits / loss buffers, overwritten by the next replay: hand out copies, as the
             # call-by-call and autograd paths hand out fresh tensors (a loop that keeps `loss` for later -- epoch-loss lists, logging
@@ -336,7 +331,7 @@ class Trainer:
         ops.sumsq(self.flat.grad, self.sumsq)
         ops.clip_adam(self.flat.flat, self.flat.grad, self.m, self.v, self.sumsq, grad_scale, self.gradient_clip_norm, self.lr, 0.9, 0.999,
                       1e-8, self.weight_decay, self.step_count)
-        PARAM_EPOCH[0] += 1           # parameters changed behind torch's back: invalidate cached weight layouts
+        ops.PARAM_EPOCH[0] += 1       # parameters changed behind torch's back: invalidate the derived weights
 
     def skipped_steps(self, reset=False):
         """Optimizer steps dropped so far because the gradient norm was not finite (nnr_clip_adam leaves parameters and moments

@@ -1435,3 +1435,24 @@ def test_transpose_batch_and_weight_transpose_cache():
     assert torch.equal(ops.wt(w2), w2.detach().t().contiguous())
 
 
+def test_bx3_images_of_a_weight_transpose_follow_a_torch_optimizer_step(monkeypatch):
+    """The bf16x3 images of a cached W^T are derived from the copy, not from the parameter.  A torch optimizer step moves the parameter's
+    version counter but not PARAM_EPOCH: wt() rewrites the copy in place, and the copy's images must be re-split too, or the next dX GEMM on
+    the bf16x3 path multiplies by the old weights."""
+    from nnr_amd import ops
+    d = dev()
+    M, N, K = 4096, 256, 256
+    monkeypatch.setattr(ops, 'BX3', [True])
+    w = torch.nn.Parameter(rnd(N, K, seed=31, scale=0.1).to(d))
+    dy = rnd(M, N, seed=32).to(d)
+    seen = ops.BX3_SEEN.get((M, K, N, 'weight'), 0)
+    ops.linear_bwd_data(dy, w)
+    w.grad = torch.ones_like(w)
+    torch.optim.SGD([w], lr=1.0, foreach=False).step()      # every weight moves by 1.0: far beyond the bf16x3 error
+    out = ops.linear_bwd_data(dy, w)
+    assert ops.BX3_SEEN.get((M, K, N, 'weight'), 0) == seen + 2       # both products took the bf16x3 path
+    ops.BX3[0] = False
+    ref = ops.linear_bwd_data(dy, w)
+    close(out, ref, tol=2e-5 * max(1.0, math.sqrt(N / 100.0)), what='dX after a torch optimizer step')
+
+

@@ -251,6 +251,38 @@ def test_tape_footprint_budget_keeps_the_step_call_by_call(monkeypatch):
         assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize('batch_size', [8, 64])
+def test_eval_before_the_recording_step_keeps_replays_equal_to_call_by_call(batch_size):
+    """An eval forward between the last optimizer step and the step that records the tape refreshes derived weights at the current parameters:
+    the packed LSTM weights and, at M >= 2048, bf16x3 images.  The recording step must still contain their refresh launches: without them its
+    replays run on the parameters of the recording step, or the recording is discarded because it reads buffers made outside it.  The step
+    records, and replay equals call by call bit for bit: every step's logits and the final parameters.
+    (Batch 8 covers the packs only: its training step runs no bf16x3 GEMM, step.bx3_classes; batch 64 covers the images as well.)"""
+    from nnr_amd.trainer import Trainer
+    cfg = make_config(['--news_encoder=CNE', '--user_encoder=SUE'], corpus_sizes=dict(vocabulary_size=900), tie_order='stable', batch_size=batch_size)
+    corpus = SynthCorpus(SynthSpec(vocabulary_size=900, news_pool=500, seed=6))
+    batches = [to_torch(corpus.batch(batch_size, np.random.default_rng(31 + i)), 'cuda') for i in range(5)]
+    res = {}
+    for replay in (True, False):
+        model, _ = _models(cfg, seed=7)
+        tr = Trainer(model, cfg, replay=replay)
+        logits, paths = [], []
+        for i, b in enumerate(batches):
+            if i == 2:
+                model.eval()
+                with torch.no_grad():
+                    model(*b)
+                model.train()
+            logits.append(tr.train_step(b)[0].clone())
+            paths.append(tr.last_path)
+        res[replay] = (logits, paths, tr.flat.flat.clone())
+        del tr, model
+    assert res[True][1] == ['native', 'native', 'record', 'replay', 'replay'] and res[False][1] == ['native'] * 5, (res[True][1], res[False][1])
+    for step, (a, b) in enumerate(zip(res[True][0], res[False][0])):
+        assert torch.equal(a, b), step
+    assert torch.equal(res[True][2], res[False][2])
+
+
 @pytest.mark.parametrize('batch_size', [3, 64])
 def test_mhsa_pair_native_step_equals_autograd_and_replays_against_oracle(batch_size):
     """BASELINE.json configs[1] (MHSA + MHSA; newsEncoders.py:187-200, userEncoders.py:164-173): (1) the native step (nnr_amd.step.
