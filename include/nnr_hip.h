@@ -329,6 +329,22 @@ int nnr_sue_intra_bwd(const float* kf, const float* qc, const float* g, const lo
                       int N, int Hn, int C, int A, int D, float* dg, float* dkf, float* dqc, float* ds_ws /* [B*N*Hn] scratch */,
                       hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------------ candidate-aware additive attention
+ * CATT (userEncoders.py:213-220, act = 1 relu) and layers.CandidateAttention / MultipleCandidateAttention (layers.py:225-232, 254-262,
+ * act = 2 tanh), csrc/cand_attn.hip:  a[b,n,h] = w2 . act(P[b,n,:] + Q[b,h,:]);  alpha[b,n,:] = softmax_h(mask[b,h] ? a : -1e9);
+ * out[b,n,:] = sum_h alpha[b,n,h] feat[b,h,:].   P [B*N, A] = query projection + bias, Q [B*H, A] = feature projection, w2 [A],
+ * feat [B, H, D] with row stride ldf, mask uint8 [B, H] or NULL (no masking), alpha [B, N, H], out / dout [B, N, D]; all fp32.
+ * The score's bias is no argument: it cancels in the softmax and its gradient is zero.
+ * Backward: dP [B*N, A], dQ [B*H, A] and dfeat [B, H, D] are written (dfeat added into when dfeat_accumulate), dw2 [A] is ADDED into;
+ * ws: nnr_cand_attn_ws_floats(B, N, H, A) floats of scratch owned by the calling stream.  Same inputs, same bits (no float atomics
+ * into shared destinations but nnr_colsum's one add per column).  NNR_ERR_UNSUPPORTED when N*A + A + N*H floats exceed 64 KB of LDS. */
+int nnr_cand_attn_ws_floats(int B, int N, int H, int A);
+int nnr_cand_attn_fwd(const float* P, const float* Q, const float* w2, const float* feat, int ldf, const uint8_t* mask, int B, int N,
+                      int H, int A, int D, int act, float* alpha, float* out, hipStream_t stream);
+int nnr_cand_attn_bwd(const float* P, const float* Q, const float* w2, const float* feat, int ldf, const uint8_t* mask, const float* alpha,
+                      const float* dout, int B, int N, int H, int A, int D, int act, float* dP, float* dQ, float* dfeat,
+                      int dfeat_accumulate, float* ws, float* dw2_accum, hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------ device-resident corpus
  * (SURVEY.md section 8 f-1 / f-2).  The corpus tables MIND_Corpus builds (MIND_corpus.py:261-268, 336-353) live in HBM;
  * a training batch is described by behaviour indices + the (1 + K) sampled news ids of each behaviour.

@@ -162,6 +162,88 @@ class _CandidateAttentionFn(torch.autograd.Function):
         return dx.view(n, Lx, F), dq, None, None
 
 
+# ------------------------------------------------------------------------------------------------ candidate-aware additive attention
+class _CandAttnFn(torch.autograd.Function):
+    """alpha[b,n,:] = softmax_h(w2 . act(Wq query[b,n] + bq + Wf feature[b,h])), out[b,n] = alpha[b,n] . feature[b]: two projection GEMMs and the
+    fused kernel of csrc/cand_attn.hip (the [B, N, H, A] hidden tensor of the reference is never stored; the backward pass recomputes the
+    activations).  feature [B, H, F], query [B, N, Qd], mask [B, H] or None -> [B, N, F].  `mod` supplies the weights through
+    _cand_attn_weights() -> (Wq [A, Qd], bq, Wf [A, F], w2 [A], act) and their gradient buffers through _cand_attn_grads() in the same order
+    (row-strided views are fine: CATT's Wq | Wf are the two halves of ONE Linear(2D, A))."""
+
+    @staticmethod
+    def forward(ctx, feature, query, mod, mask):
+        B, H, F = feature.shape
+        N, Qd = query.shape[1], query.shape[2]
+        wq, bq, wf, w2, act = mod._cand_attn_weights()
+        A = w2.numel()
+        x = feature.contiguous()
+        q = query.contiguous().view(B * N, Qd)
+        if mask is not None:
+            mask = (mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0).contiguous()
+        f32 = dict(device=x.device, dtype=torch.float32)
+        P = ops.linear_fwd(q, wq, bq)                                                           # [B*N, A]
+        Q = ops.linear_fwd(x.view(B * H, F), wf)                                                # [B*H, A]
+        alpha = torch.empty((B, N, H), **f32)
+        out = torch.empty((B, N, F), **f32)
+        ops.cand_attn_fwd(P, Q, w2, x, mask, B, N, H, A, F, act, alpha, out)
+        ctx.mod, ctx.saved = mod, (x, q, P, Q, alpha, mask, (B, N, H, A, F, Qd))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        mod = ctx.mod
+        x, q, P, Q, alpha, mask, (B, N, H, A, F, Qd) = ctx.saved
+        ctx.saved = None
+        wq, _, wf, w2, act = mod._cand_attn_weights()
+        gwq, gbq, gwf, gw2 = mod._cand_attn_grads()
+        f32 = dict(device=x.device, dtype=torch.float32)
+        dP = torch.empty((B * N, A), **f32)
+        dQ = torch.empty((B * H, A), **f32)
+        dx = torch.empty((B, H, F), **f32)
+        ops.cand_attn_bwd(P, Q, w2, x, mask, alpha, dout.contiguous(), B, N, H, A, F, act, dP, dQ, dx, gw2)
+        ops.linear_bwd_data(dQ, wf, out=dx.view(B * H, F), accumulate=True)                      # the feature's share through Wf
+        dq = ops.linear_bwd_data(dP, wq)
+        ops.linear_bwd_weight(dP, q, gwq)
+        ops.bias_grad(dP, gbq)
+        ops.linear_bwd_weight(dQ, x.view(B * H, F), gwf)
+        return dx, dq.view(B, N, Qd), None, None
+
+
+class CandidateAttention(nn.Module):
+    """layers.py:206-232: additive attention over `feature` with ONE query per sample (tanh)."""
+
+    def __init__(self, feature_dim: int, query_dim: int, attention_dim: int):
+        super().__init__()
+        self.feature_affine = nn.Linear(feature_dim, attention_dim, bias=False)
+        self.query_affine = nn.Linear(query_dim, attention_dim, bias=True)
+        self.attention_affine = nn.Linear(attention_dim, 1, bias=False)
+
+    def initialize(self):
+        nn.init.xavier_uniform_(self.feature_affine.weight, gain=nn.init.calculate_gain('tanh'))
+        nn.init.xavier_uniform_(self.query_affine.weight, gain=nn.init.calculate_gain('tanh'))
+        nn.init.zeros_(self.query_affine.bias)
+        nn.init.xavier_uniform_(self.attention_affine.weight)
+
+    def _cand_attn_weights(self):
+        return self.query_affine.weight, self.query_affine.bias, self.feature_affine.weight, self.attention_affine.weight.view(-1), ops.ACT_TANH
+
+    def _cand_attn_grads(self):
+        return (grad_of(self.query_affine.weight), grad_of(self.query_affine.bias), grad_of(self.feature_affine.weight),
+                grad_of(self.attention_affine.weight).view(-1))
+
+    def forward(self, feature, query, mask=None):
+        """feature [n, L, F], query [n, Qd], mask [n, L] -> [n, F]"""
+        return _CandAttnFn.apply(feature, query.unsqueeze(dim=1), self, mask).squeeze(dim=1)
+
+
+class MultipleCandidateAttention(CandidateAttention):
+    """layers.py:235-262: the same with several queries per sample."""
+
+    def forward(self, feature, query, mask=None):
+        """feature [n, L, F], query [n, Nq, Qd], mask [n, L] -> [n, Nq, F]"""
+        return _CandAttnFn.apply(feature, query, self, mask)
+
+
 class MultiHeadAttention(nn.Module):
     """layers.py:102-148 (parameter holder + forward over the MFMA attention kernel, see news_encoders.MHSA)."""
 

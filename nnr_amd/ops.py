@@ -1108,6 +1108,29 @@ def _sue_intra_bwd(kf, qc, g, cidx, alpha, dfeat, B, N, Hn, Cn, A, D, dg, dkf, d
                                       _p(ws), _s()), 'nnr_sue_intra_bwd')
 
 
+def _u8(mask):
+    return None if mask is None else (mask.view(torch.uint8) if mask.dtype == torch.bool else mask)
+
+
+def cand_attn_fwd(P, Q, w2, feat, mask, B, N, H, A, D, act, alpha, out):
+    """Candidate-aware additive attention (csrc/cand_attn.hip): P [B*N, A], Q [B*H, A], w2 [A], feat [B, H, D], mask [B, H] bool / uint8 or
+    None -> alpha [B, N, H], out [B, N, D]."""
+    # per sample: both projections + features + mask read; weights [N, H] + outputs [N, D] written
+    with _hbm_span('cand_attn_fwd', 4.0 * (N * A + H * A + H * D + N * H + N * D) + 1.0 * H, B, fixed=4.0 * A):
+        L.check(L.lib().nnr_cand_attn_fwd(_p(P), _p(Q), _p(w2), _p(feat), feat.stride(1), _p(_u8(mask)), B, N, H, A, D, act, _p(alpha), _p(out),
+                                          _s()), 'nnr_cand_attn_fwd')
+
+
+def cand_attn_bwd(P, Q, w2, feat, mask, alpha, dout, B, N, H, A, D, act, dP, dQ, dfeat, dw2, accumulate=False):
+    """dP [B*N, A], dQ [B*H, A], dfeat [B, H, D] (added into when `accumulate`) are written, dw2 [A] is added into."""
+    ws = torch.empty(L.lib().nnr_cand_attn_ws_floats(B, N, H, A), device=P.device, dtype=torch.float32)
+    # per sample: projections, features, weights, d outputs read; d projections, d features written (+ the workspace's da and dw2 rows, both ways)
+    with _hbm_span('cand_attn_bwd', 4.0 * (2 * N * A + 2 * H * A + (3 if accumulate else 2) * H * D + 3 * N * H + N * D + 2 * N * A) + 1.0 * H, B,
+                   fixed=8.0 * A):
+        L.check(L.lib().nnr_cand_attn_bwd(_p(P), _p(Q), _p(w2), _p(feat), feat.stride(1), _p(_u8(mask)), _p(alpha), _p(dout), B, N, H, A, D, act,
+                                          _p(dP), _p(dQ), _p(dfeat), int(accumulate), _p(ws), _p(dw2), _s()), 'nnr_cand_attn_bwd')
+
+
 def logits_loss_fwd(user, cand, B, N, D, logits, loss, dlogits):
     L.check(L.lib().nnr_logits_loss_fwd(_p(user), _p(cand), B, N, D, _p(logits), _p(loss), _p(dlogits), _s()), 'nnr_logits_loss_fwd')
 

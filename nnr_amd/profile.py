@@ -141,13 +141,17 @@ HBM_KERNELS = {
     'sue_intra_fwd': (('sue_intra_fwd_kernel',), 1), 'sue_intra_bwd': (('sue_intra_bwd_ds_kernel', 'sue_intra_bwd_dg_kernel'), 2),
     'clip_adam': (('adam_kernel',), 1), 'sumsq': (('sumsq_kernel',), 1),
 }
+# families that no launch of the headline step belongs to (the committed counter pass, profiles/pmc_traffic.json, is of that step)
+HBM_KERNELS_OTHER = {
+    'cand_attn_fwd': (('cand_attn_fwd_kernel',), 1), 'cand_attn_bwd': (('cand_attn_bwd_da_kernel', 'cand_attn_bwd_dx_kernel'), 2),
+}
 PEAK_HBM_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 TB/s achievable by a float4 copy)
 
 
 def pmc_traffic_family(family):
     """Counter HBM bytes per CALL of an HBM-bound family from the committed PMC passes (same build only), or None."""
     d = _pmc_file()
-    spec = HBM_KERNELS.get(family)
+    spec = HBM_KERNELS.get(family) or HBM_KERNELS_OTHER.get(family)
     if d is None or spec is None:
         return None
     names, per_call = spec

@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .layers import Attention, ScaledDotProduct_CandidateAttention, MultiHeadAttention, GCN, grad_of
+from .layers import Attention, ScaledDotProduct_CandidateAttention, MultiHeadAttention, GCN, grad_of, _CandAttnFn
 from .news_encoders import NewsEncoder
 
 
@@ -425,3 +425,43 @@ class ATT(UserEncoder):
                     user_history_category_indices, candidate_news_representation):
         from . import functional as Fn
         return Fn.ExpandFn.apply(self.attention(history_embedding), candidate_news_representation.size(1))
+
+
+class CATT(UserEncoder):
+    """userEncoders.py:194-221: candidate-aware additive attention over the click history, one user vector per candidate.
+    relu(affine1([cand ; hist])) = relu(Wc cand + b1 + Wh hist) with Wc | Wh the two column halves of affine1.weight (views, no copies: the
+    state_dict stays the reference's), so the [B, N, H, 2D] concatenation never exists (layers._CandAttnFn).  A user without history gets the
+    reference's uniform weights over all H padded slots.  affine2.bias cancels in the softmax: it exists, and its gradient is exactly zero."""
+
+    def __init__(self, news_encoder: NewsEncoder, config):
+        super().__init__(news_encoder, config)
+        self.affine1 = nn.Linear(self.news_embedding_dim * 2, config.attention_dim, bias=True)
+        self.affine2 = nn.Linear(config.attention_dim, 1, bias=True)
+        self.max_history_num = config.max_history_num
+
+    def initialize(self):
+        nn.init.xavier_uniform_(self.affine1.weight, gain=nn.init.calculate_gain('relu'))
+        nn.init.zeros_(self.affine1.bias)
+        nn.init.xavier_uniform_(self.affine2.weight)
+        nn.init.zeros_(self.affine2.bias)
+
+    def _cand_attn_weights(self):
+        D, w = self.news_embedding_dim, self.affine1.weight.detach()
+        return w[:, :D], self.affine1.bias, w[:, D:], self.affine2.weight.view(-1), ops.ACT_RELU
+
+    def _cand_attn_grads(self):
+        D, g = self.news_embedding_dim, grad_of(self.affine1.weight)
+        grad_of(self.affine2.bias)                              # (stays zero)
+        return g[:, :D], grad_of(self.affine1.bias), g[:, D:], grad_of(self.affine2.weight).view(-1)
+
+    def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask, user_content_entity,
+                user_category, user_subCategory, user_history_mask, user_history_graph, user_history_category_mask,
+                user_history_category_indices, user_embedding, candidate_news_representation):
+        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
+                                              user_content_entity, user_category, user_subCategory, user_embedding)
+        return self.encode_user(history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
+                                user_history_category_indices, candidate_news_representation)
+
+    def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
+                    user_history_category_indices, candidate_news_representation):
+        return _CandAttnFn.apply(history_embedding, candidate_news_representation, self, user_history_mask)

@@ -30,7 +30,7 @@ from make_goldens import stable_sort_patch          # noqa: E402
 from oracle.nnr_oracle import default_config        # noqa: E402  (attribute bag only)
 
 
-def run(tag, news, user, stable):
+def run(tag, news, user, stable, min_gap=None):
     rng = np.random.default_rng(21)
     cwd = os.getcwd()
     with tempfile.TemporaryDirectory() as tmp:
@@ -104,6 +104,14 @@ def run(tag, news, user, stable):
         finally:
             torch.Tensor.cuda, torch.cuda.empty_cache = orig_cuda, orig_empty
             os.chdir(cwd)
+    if min_gap is not None:                             # the fixture must decide the ranks: no two scores of an impression closer than this
+        o, gaps = 0, []
+        for n in out['sizes']:
+            if n > 1:
+                gaps.append(float(np.diff(np.sort(out['scores'][o:o + n])).min()))
+            o += n
+        assert min(gaps) > min_gap, (tag, min(gaps))
+        print(tag, 'min within-impression score gap %.3e' % min(gaps))
     np.savez_compressed(os.path.join(OUT, 'eval_%s.npz' % tag), **out)
     print(tag, 'samples', out['scores'].shape[0], 'impressions', out['sizes'].shape[0], 'metrics', out['metrics'], 'score range', out['scores'].min(), out['scores'].max())
 
@@ -139,3 +147,6 @@ if __name__ == '__main__':
     run('tiny_CNN_ATT', 'CNN', 'ATT', False)
     with stable_sort_patch():
         run('tiny_CNE_SUE_stable', 'CNE', 'SUE', True)
+    run('tiny_CNN_CATT', 'CNN', 'CATT', False, min_gap=1e-3)
+    with stable_sort_patch():
+        run('tiny_CNE_CATT_stable', 'CNE', 'CATT', True, min_gap=1e-3)

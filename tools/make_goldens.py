@@ -9,6 +9,7 @@ touch the arithmetic:
   * NewsEncoder.__init__ unpickles the word table from CWD -> a synthetic table is written to a temp CWD.
 
 Usage:  python tools/make_goldens.py            (rewrites every fixture)
+        python tools/make_goldens.py catt       (the CATT user encoder and the candidate-attention layers)
 """
 import os
 import pickle
@@ -230,7 +231,61 @@ def dropout_cases():
     run_case('drop_tiny_CNN_ATT', cfg, tiny_spec(cfg, 8), batch_size=3, seed=47, mode='train', gain=2.0, adam_steps=1, dropout_seed=3)
 
 
+def layer_cand_attn():
+    """layers.CandidateAttention (layers.py:206-232) and layers.MultipleCandidateAttention (:235-262) of the reference on their own: inputs,
+    outputs and every gradient of out.square().sum(), with a mask (one all-zero row, one all-one row, two ragged ones) and with mask=None."""
+    import layers as ref_layers                 # the reference's layers.py
+    rng = np.random.default_rng(53)
+    n, Lx, Fd, Qd, A, Nq = 4, 7, 24, 24, 12, 3
+    feature = (0.25 * rng.standard_normal((n, Lx, Fd))).astype(np.float32)      # (gradients of O(1): the fixture's own fp32 rounding stays below 1e-6)
+    mask = np.array([[0] * 7, [1] * 7, [1, 1, 1, 0, 0, 0, 0], [1, 0, 1, 1, 1, 0, 0]], dtype=np.int64)
+    out = {'feature': feature, 'mask': mask}
+    for kind, cls, qshape in (('single', ref_layers.CandidateAttention, (n, Qd)), ('multi', ref_layers.MultipleCandidateAttention, (n, Nq, Qd))):
+        mod = cls(Fd, Qd, A)
+        mod.initialize()
+        st = make_state({k: tuple(v.shape) for k, v in mod.named_parameters()}, 59, 1.5)
+        with torch.no_grad():
+            for k, p in mod.named_parameters():
+                p.copy_(torch.from_numpy(st[k]))
+                out['%s/param/%s' % (kind, k)] = st[k]
+        out[kind + '/param_names'] = np.array(list(mod.state_dict().keys())).astype(str)
+        query = (0.5 * rng.standard_normal(qshape)).astype(np.float32)
+        out[kind + '/query'] = query
+        for mtag, m in (('mask', torch.from_numpy(mask)), ('nomask', None)):
+            f, q = torch.from_numpy(feature.copy()).requires_grad_(), torch.from_numpy(query.copy()).requires_grad_()
+            mod.zero_grad()
+            o = mod(f, q, m)
+            o.square().sum().backward()
+            pre = '%s/%s/' % (kind, mtag)
+            out[pre + 'out'] = o.detach().numpy().copy()
+            out[pre + 'grad/feature'], out[pre + 'grad/query'] = f.grad.numpy().copy(), q.grad.numpy().copy()
+            for k, p in mod.named_parameters():
+                out[pre + 'grad/param/' + k] = p.grad.detach().numpy().copy()
+    np.savez_compressed(os.path.join(OUT, 'layer_cand_attn.npz'), **out)
+    print('layer_cand_attn: %d arrays' % len(out))
+
+
+def catt_cases():
+    """The CATT user encoder (userEncoders.py:194-221) under the CNE and CNN news encoders (`python tools/make_goldens.py catt`).  The tiny CNE
+    case must hold users without any history (uniform attention over the padded slots); with the reference's own initialisation CATT's
+    gradients are 0.3 % of the total norm, hence gain 2.0 for the CNN case too."""
+    with stable_sort_patch():
+        cfg = tiny_cfg('CNE', 'CATT')
+        run_case('tiny_CNE_CATT_stable', cfg, tiny_spec(cfg, 3), batch_size=8, seed=19, mode='train', gain=2.0)
+        lens = np.load(os.path.join(OUT, 'tiny_CNE_CATT_stable.npz'))['in/user_history_mask'].astype(bool).sum(axis=1)
+        assert int((lens == 0).sum()) >= 2 and int(lens.max()) >= 4, lens
+        print('tiny_CNE_CATT_stable history lengths', lens.tolist())
+        cfg = full_cfg('CNE', 'CATT', V=400)
+        run_case('full_CNE_CATT_g1p0_stable', cfg, full_spec(cfg, 9), batch_size=2, seed=17, mode='train', gain=1.0, full_arrays=False)
+    cfg = tiny_cfg('CNN', 'CATT')
+    run_case('tiny_CNN_CATT', cfg, tiny_spec(cfg, 3), batch_size=3, seed=11, mode='train', gain=2.0)
+    layer_cand_attn()
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == 'catt':
+        torch.set_num_threads(8)
+        return catt_cases()
     if len(sys.argv) > 1 and sys.argv[1] == 'extra':
         torch.set_num_threads(8)
         return extra_cases()
