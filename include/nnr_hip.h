@@ -345,6 +345,28 @@ int nnr_cand_attn_bwd(const float* P, const float* Q, const float* w2, const flo
                       const float* dout, int B, int N, int H, int A, int D, int act, float* dP, float* dQ, float* dfeat,
                       int dfeat_accumulate, float* ws, float* dw2_accum, hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------------ OMAP (Hi-Fi Ark) user encoder
+ * userEncoders.py:357-374, csrc/omap.hip.  hist [B, H, D] with row stride ldf (X), cand [B, N, D] (C), mask uint8 [B, H] or NULL (no
+ * masking), W [D, K], s = sqrt(D):   alpha = softmax_j(mask[b,j] ? X X^T / s : -1e9) [B, H, H];  Y = X + alpha X [B, H, D];
+ * beta = softmax_k(mask[b,i] ? Y W / s : -1e9) [B, H, K] (a padded row carries 1 / K and contributes to every archive);  R = beta^T Y
+ * [B, K, D];  gamma = softmax_k(C R^T / s) [B, N, K];  out = gamma R [B, N, D].  A user without history has alpha = 1 / H.  All fp32; the
+ * [H, H, D] products run on the exact-fp32 MFMA.  alpha, Y, beta, R and gamma are written by the forward call and read by the backward one.
+ * Backward: dhist [B, H, D] contiguous (added into when dhist_accumulate) and dcand [B, N, D] are written, dW [D, K] is ADDED into; masked
+ * scores pass no gradient (db = 0 on padded rows, dS = 0 on masked keys, also for a user without history).  ws: nnr_omap_ws_floats(B, N, H,
+ * D, K) floats of scratch owned by the calling stream, for either call.  Same inputs, same bits: no float atomics.
+ * NNR_ERR_UNSUPPORTED (from nnr_omap_ws_floats too, before any launch) when H > 96, K > 16 or (H + N) * K > 4096.
+ * The regulariser coef * ||(W^T W) o (J_K - I_K)||_F: nnr_omap_reg_fwd writes the 0-dim loss and keeps Off [K * K] and Omega in off
+ * [K * K + 1]; nnr_omap_reg_bwd ADDS gup[0] * coef * 2 W Off / Omega into dW (gup: device pointer to the upstream gradient; nothing is
+ * added when Omega == 0, torch's subgradient).  Neither synchronises with the host. */
+int nnr_omap_ws_floats(int B, int N, int H, int D, int K);
+int nnr_omap_fwd(const float* hist, int ldf, const float* cand, const uint8_t* mask, const float* W, int B, int N, int H, int D, int K,
+                 float* alpha, float* Y, float* beta, float* R, float* gamma, float* out, float* ws, hipStream_t stream);
+int nnr_omap_bwd(const float* hist, int ldf, const float* cand, const uint8_t* mask, const float* W, const float* alpha, const float* Y,
+                 const float* beta, const float* R, const float* gamma, const float* dout, int B, int N, int H, int D, int K, float* dhist,
+                 int dhist_accumulate, float* dcand, float* dW_accum, float* ws, hipStream_t stream);
+int nnr_omap_reg_fwd(const float* W, int D, int K, float coef, float* off, float* loss, hipStream_t stream);
+int nnr_omap_reg_bwd(const float* W, const float* off, const float* gup, int D, int K, float coef, float* dW_accum, hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------ device-resident corpus
  * (SURVEY.md section 8 f-1 / f-2).  The corpus tables MIND_Corpus builds (MIND_corpus.py:261-268, 336-353) live in HBM;
  * a training batch is described by behaviour indices + the (1 + K) sampled news ids of each behaviour.

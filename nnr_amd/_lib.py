@@ -68,6 +68,7 @@ SYMBOLS = [
     'nnr_token_sort_workspace_bytes', 'nnr_token_sort', 'nnr_embed_scatter_sorted_workspace_floats', 'nnr_embed_scatter_sorted', 'nnr_fusion_rows_bwd_det',
     'nnr_rows_touch', 'nnr_rows_compact', 'nnr_rows_pack', 'nnr_rows_unpack',
     'nnr_cand_attn_ws_floats', 'nnr_cand_attn_fwd', 'nnr_cand_attn_bwd',
+    'nnr_omap_ws_floats', 'nnr_omap_fwd', 'nnr_omap_bwd', 'nnr_omap_reg_fwd', 'nnr_omap_reg_bwd',
 ]
 
 

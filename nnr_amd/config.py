@@ -15,12 +15,12 @@ _FLAGS = [
     ('cnn_method', str, 'naive'), ('cnn_kernel_num', int, 400), ('cnn_window_size', int, 3), ('attention_dim', int, 200),
     ('head_num', int, 20), ('head_dim', int, 20), ('user_embedding_dim', int, 50), ('category_embedding_dim', int, 50),
     ('subCategory_embedding_dim', int, 50), ('dropout_rate', float, 0.2), ('gcn_normalization_type', str, 'symmetric'), ('gcn_layer_num', int, 4), ('hidden_dim', int, 200),
-    ('click_predictor', str, 'dot_product'),
+    ('click_predictor', str, 'dot_product'), ('OMAP_head_num', int, 3), ('HiFi_Ark_regularizer_coefficient', float, 0.1),
 ]
 _BOOL_FLAGS = ['no_self_connection', 'no_adjacent_normalization', 'no_gcn_residual', 'gcn_layer_norm']
 
 NEWS_ENCODERS = ['CNE', 'CNN', 'MHSA']          # in scope; the reference lists 15
-USER_ENCODERS = ['SUE', 'MHSA', 'ATT', 'CATT']  # in scope; the reference lists 11
+USER_ENCODERS = ['SUE', 'MHSA', 'ATT', 'CATT', 'OMAP']  # in scope; the reference lists 11
 
 
 def build_parser():

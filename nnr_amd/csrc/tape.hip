@@ -51,6 +51,7 @@ const Entry REGISTRY[] = {
   R(nnr_token_sort), R(nnr_embed_scatter_sorted), R(nnr_fusion_rows_bwd_det),
   R(nnr_rows_touch), R(nnr_rows_compact), R(nnr_rows_pack), R(nnr_rows_unpack),
   R(nnr_cand_attn_fwd), R(nnr_cand_attn_bwd),
+  R(nnr_omap_fwd), R(nnr_omap_bwd), R(nnr_omap_reg_fwd), R(nnr_omap_reg_bwd),
 };
 #undef R
 constexpr int NREG = (int)(sizeof(REGISTRY) / sizeof(REGISTRY[0]));

@@ -92,8 +92,10 @@ class Model(nn.Module):
             self.user_encoder = userEncoders.ATT(self.news_encoder, config)
         elif config.user_encoder == 'CATT':
             self.user_encoder = userEncoders.CATT(self.news_encoder, config)
+        elif config.user_encoder == 'OMAP':
+            self.user_encoder = userEncoders.OMAP(self.news_encoder, config)
         else:
-            raise Exception(config.user_encoder + ' is not on the MI355X hot path (in scope: SUE, MHSA, ATT, CATT; SURVEY.md section 8a)')
+            raise Exception(config.user_encoder + ' is not on the MI355X hot path (in scope: SUE, MHSA, ATT, CATT, OMAP; SURVEY.md section 8a)')
         self.model_name = config.news_encoder + '-' + config.user_encoder
         self.news_embedding_dim = self.news_encoder.news_embedding_dim
         self.dropout = nn.Dropout(p=config.dropout_rate)                    # (model.py:77: part of the attribute surface; only the

@@ -1131,6 +1131,48 @@ def cand_attn_bwd(P, Q, w2, feat, mask, alpha, dout, B, N, H, A, D, act, dP, dQ,
                                           _p(dP), _p(dQ), _p(dfeat), int(accumulate), _p(ws), _p(dw2), _s()), 'nnr_cand_attn_bwd')
 
 
+def omap_ws(B, N, H, D, K, device):
+    n = L.lib().nnr_omap_ws_floats(B, N, H, D, K)
+    if n < 0:
+        raise L.NnrHipError('nnr_omap_ws_floats failed with code %d (B %d, N %d, H %d, D %d, K %d)' % (n, B, N, H, D, K))
+    return torch.empty(n, device=device, dtype=torch.float32)
+
+
+def omap_fwd(hist, cand, mask, W, B, N, H, D, K, alpha, Y, beta, R, gamma, out):
+    """The OMAP user encoder (csrc/omap.hip): hist [B, H, D] (row stride allowed), cand [B, N, D], mask [B, H] bool / uint8 or None, W [D, K]
+    -> alpha [B, H, H], Y [B, H, D], beta [B, H, K], R [B, K, D], gamma [B, N, K], out [B, N, D]."""
+    ws = omap_ws(B, N, H, D, K, hist.device)
+    # per user: X read by the score and the mix launch, alpha written and read, Y written and read, candidates, archives (written, read),
+    # outputs, the small tensors; W once
+    with _hbm_span('omap_fwd', 4.0 * (2 * H * D + 2 * H * H + 2 * H * D + N * D + 2 * K * D + N * D + 2 * H * K + N * K) + 1.0 * H, B,
+                   fixed=4.0 * D * K):
+        L.check(L.lib().nnr_omap_fwd(_p(hist), hist.stride(1), _p(cand), _p(_u8(mask)), _p(W), B, N, H, D, K, _p(alpha), _p(Y), _p(beta), _p(R),
+                                     _p(gamma), _p(out), _p(ws), _s()), 'nnr_omap_fwd')
+
+
+def omap_bwd(hist, cand, mask, W, alpha, Y, beta, R, gamma, dout, B, N, H, D, K, dhist, dcand, dW, accumulate=False):
+    """dhist [B, H, D] (added into when `accumulate`) and dcand [B, N, D] are written, dW [D, K] is added into."""
+    ws = omap_ws(B, N, H, D, K, hist.device)
+    # per user: X twice, Y twice, alpha twice, G both ways, d outputs + candidates + archives, dR both ways (read twice), d candidates,
+    # d history (read first when it accumulates), the user's dW rows both ways
+    with _hbm_span('omap_bwd', 4.0 * (2 * H * D + 2 * H * D + 2 * H * H + 2 * H * H + 2 * N * D + K * D + 3 * K * D + N * D +
+                                      (2 if accumulate else 1) * H * D + 2 * D * K + 3 * H * K) + 1.0 * H, B, fixed=12.0 * D * K):
+        L.check(L.lib().nnr_omap_bwd(_p(hist), hist.stride(1), _p(cand), _p(_u8(mask)), _p(W), _p(alpha), _p(Y), _p(beta), _p(R), _p(gamma),
+                                     _p(dout), B, N, H, D, K, _p(dhist), int(accumulate), _p(dcand), _p(dW), _p(ws), _s()), 'nnr_omap_bwd')
+
+
+def omap_reg_fwd(W, coef, off, loss):
+    """loss (0-dim) = coef * ||(W^T W) o (J - I)||_F; off [K * K + 1] keeps the off-diagonal part and the norm for omap_reg_bwd."""
+    D, K = W.shape
+    L.check(L.lib().nnr_omap_reg_fwd(_p(W), D, K, C.c_float(coef), _p(off), _p(loss), _s()), 'nnr_omap_reg_fwd')
+
+
+def omap_reg_bwd(W, off, gup, coef, dW):
+    """dW += gup * coef * 2 W Off / Omega (gup: 0-dim device tensor; nothing at Omega == 0)."""
+    D, K = W.shape
+    L.check(L.lib().nnr_omap_reg_bwd(_p(W), _p(off), _p(gup), D, K, C.c_float(coef), _p(dW), _s()), 'nnr_omap_reg_bwd')
+
+
 def logits_loss_fwd(user, cand, B, N, D, logits, loss, dlogits):
     L.check(L.lib().nnr_logits_loss_fwd(_p(user), _p(cand), B, N, D, _p(logits), _p(loss), _p(dlogits), _s()), 'nnr_logits_loss_fwd')
 

@@ -144,6 +144,8 @@ HBM_KERNELS = {
 # families that no launch of the headline step belongs to (the committed counter pass, profiles/pmc_traffic.json, is of that step)
 HBM_KERNELS_OTHER = {
     'cand_attn_fwd': (('cand_attn_fwd_kernel',), 1), 'cand_attn_bwd': (('cand_attn_bwd_da_kernel', 'cand_attn_bwd_dx_kernel'), 2),
+    'omap_fwd': (('omap_alpha_kernel', 'omap_mix_kernel', 'omap_pool_kernel'), 3),
+    'omap_bwd': (('omap_bwd_pool_kernel', 'omap_bwd_dalpha_kernel', 'omap_bwd_dx_kernel', 'omap_dw_reduce_kernel'), 4),
 }
 PEAK_HBM_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 TB/s achievable by a float4 copy)
 

@@ -181,6 +181,11 @@ class Trainer:
         with native_step.matrix_path(model, batch):      # (same kernels as the native step of this model would run)
             logits = model(*batch)
             loss = negative_log_softmax(logits)
+            # the encoders' regularisers (trainer.py:109-114); None for every encoder but OMAP
+            if model.news_encoder.auxiliary_loss is not None:
+                loss = loss + model.news_encoder.auxiliary_loss.mean()
+            if model.user_encoder.auxiliary_loss is not None:
+                loss = loss + model.user_encoder.auxiliary_loss.mean()
             loss.backward()
         ops.join_extra_streams()
         scale = self.exchange.finish()

@@ -465,3 +465,90 @@ class CATT(UserEncoder):
     def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
                     user_history_category_indices, candidate_news_representation):
         return _CandAttnFn.apply(history_embedding, candidate_news_representation, self, user_history_mask)
+
+
+class _OmapFn(torch.autograd.Function):
+    """hist [B, H, D], cand [B, N, D], mask [B, H] -> [B, N, D] on the kernels of csrc/omap.hip (three launches forward, four backward).  alpha,
+    Y = X + alpha X, beta, the archives and gamma are saved; dW goes straight into W.grad."""
+
+    @staticmethod
+    def forward(ctx, hist, cand, mod, mask):
+        B, H, D = hist.shape
+        N, K = cand.shape[1], mod.OMAP_head_num
+        x = hist if hist.stride(2) == 1 and hist.stride(0) == H * hist.stride(1) else hist.contiguous()
+        c = cand.contiguous()
+        if mask is not None:
+            mask = (mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0).contiguous()
+        W = mod.W.detach()
+        f32 = dict(device=x.device, dtype=torch.float32)
+        alpha, Y, beta = torch.empty((B, H, H), **f32), torch.empty((B, H, D), **f32), torch.empty((B, H, K), **f32)
+        R, gamma, out = torch.empty((B, K, D), **f32), torch.empty((B, N, K), **f32), torch.empty((B, N, D), **f32)
+        ops.omap_fwd(x, c, mask, W, B, N, H, D, K, alpha, Y, beta, R, gamma, out)
+        ctx.mod, ctx.saved = mod, (x, c, mask, alpha, Y, beta, R, gamma, (B, N, H, D, K))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        mod = ctx.mod
+        x, c, mask, alpha, Y, beta, R, gamma, (B, N, H, D, K) = ctx.saved
+        ctx.saved = None
+        f32 = dict(device=x.device, dtype=torch.float32)
+        dx, dc = torch.empty((B, H, D), **f32), torch.empty((B, N, D), **f32)
+        ops.omap_bwd(x, c, mask, mod.W.detach(), alpha, Y, beta, R, gamma, dout.contiguous(), B, N, H, D, K, dx, dc, grad_of(mod.W))
+        return dx, dc, None, None
+
+
+class _OmapRegFn(torch.autograd.Function):
+    """coef * ||(W^T W) o (J - I)||_F as a 0-dim device tensor; its backward adds the gradient into W.grad, scaled by the upstream gradient
+    on the device (no host read of the norm in either direction)."""
+
+    @staticmethod
+    def forward(ctx, W, mod):
+        K = W.shape[1]
+        off = torch.empty(K * K + 1, device=W.device, dtype=torch.float32)
+        loss = torch.empty((), device=W.device, dtype=torch.float32)
+        ops.omap_reg_fwd(W.detach(), mod.HiFi_Ark_regularizer_coefficient, off, loss)
+        ctx.mod, ctx.off = mod, off
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        mod = ctx.mod
+        ops.omap_reg_bwd(mod.W.detach(), ctx.off, g.contiguous().float(), mod.HiFi_Ark_regularizer_coefficient, grad_of(mod.W))
+        return None, None
+
+
+class OMAP(UserEncoder):
+    """userEncoders.py:335-375, the Hi-Fi Ark baseline: self-attention over the history with a residual, K archives pooled by a softmax over
+    the heads, one user vector per candidate from a softmax over the archives.  Observable quirks kept: a padded history row has beta = 1/K and
+    adds Y[i] / K to every archive; a user without history has alpha = 1/H; masked scores pass no gradient.  In train mode every call
+    rewrites `auxiliary_loss` = coefficient * ||(W^T W) o (J_K - I_K)||_F (a 0-dim tensor that carries its own backward); in eval mode it is
+    left as it was.  state_dict: W (J_k / I_k are plain attributes, as in the reference)."""
+
+    def __init__(self, news_encoder: NewsEncoder, config):
+        super().__init__(news_encoder, config)
+        self.max_history_num = config.max_history_num
+        self.OMAP_head_num = int(config.OMAP_head_num)
+        self.HiFi_Ark_regularizer_coefficient = float(config.HiFi_Ark_regularizer_coefficient)
+        self.scalar = math.sqrt(float(self.news_embedding_dim))
+        self.W = nn.parameter.Parameter(torch.zeros([self.news_embedding_dim, self.OMAP_head_num]))
+        self.J_k = torch.ones([self.OMAP_head_num, self.OMAP_head_num])
+        self.I_k = torch.eye(self.OMAP_head_num)
+
+    def initialize(self):
+        nn.init.orthogonal_(self.W.data)
+
+    def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask, user_content_entity,
+                user_category, user_subCategory, user_history_mask, user_history_graph, user_history_category_mask,
+                user_history_category_indices, user_embedding, candidate_news_representation):
+        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
+                                              user_content_entity, user_category, user_subCategory, user_embedding)
+        return self.encode_user(history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
+                                user_history_category_indices, candidate_news_representation)
+
+    def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
+                    user_history_category_indices, candidate_news_representation):
+        user_representation = _OmapFn.apply(history_embedding, candidate_news_representation, self, user_history_mask)
+        if self.training:
+            self.auxiliary_loss = _OmapRegFn.apply(self.W, self)
+        return user_representation

@@ -30,7 +30,8 @@ from make_goldens import stable_sort_patch          # noqa: E402
 from oracle.nnr_oracle import default_config        # noqa: E402  (attribute bag only)
 
 
-def run(tag, news, user, stable, min_gap=None):
+def run(tag, news, user, stable, min_gap=None, **cfg_over):
+    """`cfg_over`: flags default_config lacks (OMAP_head_num, HiFi_Ark_regularizer_coefficient: config.py:74-75)."""
     rng = np.random.default_rng(21)
     cwd = os.getcwd()
     with tempfile.TemporaryDirectory() as tmp:
@@ -48,7 +49,7 @@ def run(tag, news, user, stable, min_gap=None):
                                  category_embedding_dim=4, subCategory_embedding_dim=4, negative_sample_num=2, head_num=2, head_dim=4,
                                  cnn_kernel_num=12, gcn_layer_num=2, dropout_rate=0.2, entity_embedding_dim=100, context_embedding_dim=100,
                                  no_self_connection=False, no_adjacent_normalization=False, gcn_normalization_type='symmetric',
-                                 train_root='../MIND-tiny/train', dev_root='../MIND-tiny/dev', test_root='../MIND-tiny/test')
+                                 train_root='../MIND-tiny/train', dev_root='../MIND-tiny/dev', test_root='../MIND-tiny/test', **cfg_over)
             torch.manual_seed(5)
             corpus = MIND_corpus.MIND_Corpus(cfg)
             m = ref_model.Model(cfg)
@@ -150,3 +151,7 @@ if __name__ == '__main__':
     run('tiny_CNN_CATT', 'CNN', 'CATT', False, min_gap=1e-3)
     with stable_sort_patch():
         run('tiny_CNE_CATT_stable', 'CNE', 'CATT', True, min_gap=1e-3)
+    omap = dict(OMAP_head_num=3, HiFi_Ark_regularizer_coefficient=0.1)
+    run('tiny_CNN_OMAP', 'CNN', 'OMAP', False, min_gap=1e-3, **omap)
+    with stable_sort_patch():
+        run('tiny_CNE_OMAP_stable', 'CNE', 'OMAP', True, min_gap=1e-3, **omap)

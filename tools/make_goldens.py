@@ -6,10 +6,16 @@ the fixtures hold inputs and expected outputs (arrays) only.  Accommodations, no
 touch the arithmetic:
   * torch_scatter (third-party, absent) -> tools/ref_shims/torch_scatter.py (pure torch composite);
   * config.Config() cannot be built without a GPU/dataset -> a SimpleNamespace with the same attributes;
-  * NewsEncoder.__init__ unpickles the word table from CWD -> a synthetic table is written to a temp CWD.
+  * NewsEncoder.__init__ unpickles the word table from CWD -> a synthetic table is written to a temp CWD;
+  * the loss is the trainer's (trainer.py:109-114): the encoders' `auxiliary_loss.mean()` is added when it is not None.  It is None for
+    every encoder pair but those with the OMAP user encoder, whose fixtures also store the term as `auxiliary_loss`;
+  * OMAP.initialize() calls `self.J_k.cuda()` and drops the result (userEncoders.py:348-349), which raises without a GPU: the `omap`
+    cases build the model with torch.Tensor.cuda patched to the identity (as tools/make_eval_goldens.py does);
+  * `OMAP_head_num` / `HiFi_Ark_regularizer_coefficient` (config.py:74-75) enter the attribute bag through tiny_cfg / full_cfg keywords.
 
 Usage:  python tools/make_goldens.py            (rewrites every fixture)
         python tools/make_goldens.py catt       (the CATT user encoder and the candidate-attention layers)
+        python tools/make_goldens.py omap       (the OMAP user encoder)
 """
 import os
 import pickle
@@ -131,6 +137,11 @@ def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True
         inp = to_torch(batch)                   # fresh copies: the model mutates masks in place
         logits = m(*inp)
         loss = (-torch.log_softmax(logits, dim=1).select(dim=1, index=0)).mean()   # trainer.py:64-66
+        aux = [e.auxiliary_loss.mean() for e in (m.news_encoder, m.user_encoder) if e.auxiliary_loss is not None]   # trainer.py:109-114
+        for a in aux:
+            loss = loss + a
+        if aux and step == 0:
+            out['auxiliary_loss'] = np.float32(float(sum(a.detach() for a in aux)))
         opt.zero_grad()
         loss.backward()
         if step == 0:
@@ -191,9 +202,9 @@ def tiny_spec(cfg, seed):
                      title_len_mean=3.0, content_len_mean=5.0, empty_content_frac=0.2, empty_history_frac=0.2, seed=seed)
 
 
-def full_cfg(news, user, V):
+def full_cfg(news, user, V, **kw):
     return default_config(news_encoder=news, user_encoder=user, dataset='200k', vocabulary_size=V, dropout_rate=0.0,
-                          gcn_layer_num=4, lr=1e-3)
+                          gcn_layer_num=4, lr=1e-3, **kw)
 
 
 def full_spec(cfg, seed):
@@ -282,7 +293,56 @@ def catt_cases():
     layer_cand_attn()
 
 
+class cuda_identity_patch:
+    """torch.Tensor.cuda -> identity (OMAP.initialize() calls it on a plain attribute and drops the result)."""
+
+    def __enter__(self):
+        self.orig = torch.Tensor.cuda
+        torch.Tensor.cuda = lambda self, *a, **k: self
+
+    def __exit__(self, *a):
+        torch.Tensor.cuda = self.orig
+
+
+def omap_cases():
+    """The OMAP user encoder (userEncoders.py:335-375) under the CNE and CNN news encoders (`python tools/make_goldens.py omap`), reference
+    flag defaults (3 heads, coefficient 0.1).  Weights come from make_state, not from the reference's orthogonal initialisation: there the
+    regulariser's norm is fp32 rounding noise and its gradient a noise direction.  The tiny CNE case must hold users without history
+    (alpha = 1/H) and padded rows (beta = 1/K).  Every fixture must make the auxiliary term and W's gradient count: asserted below.
+    The full-size case runs at gain 0.35, not 1.0: an archive sums 50 history rows, so at gain 1.0 max|user_rep| is 5.06 and the reference's
+    own fp32 forward is 2.4e-6 (5-6 ulp) away from float64 -- over the absolute 1e-6 at which tests/test_omap_host.py pins the restatement to
+    it.  max|user_rep| is 4.95 x gain (measured at 0.5 ... 1.0); below 2 six ulp are 7e-7, hence a gain under 0.40."""
+    omap = dict(OMAP_head_num=3, HiFi_Ark_regularizer_coefficient=0.1)
+
+    def check(tag):
+        z = np.load(os.path.join(OUT, tag + '.npz'))
+        aux, loss = float(z['auxiliary_loss']), float(z['loss'])
+        click = loss - aux
+        share = float(z['gradnorm/user_encoder.W']) / float(z['grad_total_norm'])
+        print('%s: click loss %.4f, auxiliary term %.4f (%.2fx), |dW| / |g| = %.3f' % (tag, click, aux, aux / click, share))
+        assert 0.05 * click <= aux <= 2.0 * click, (tag, aux, click)
+        assert share >= 0.01, (tag, share)
+
+    with cuda_identity_patch():
+        with stable_sort_patch():
+            cfg = tiny_cfg('CNE', 'OMAP', **omap)
+            run_case('tiny_CNE_OMAP_stable', cfg, tiny_spec(cfg, 3), batch_size=8, seed=19, mode='train', gain=2.0)
+            lens = np.load(os.path.join(OUT, 'tiny_CNE_OMAP_stable.npz'))['in/user_history_mask'].astype(bool).sum(axis=1)
+            assert int((lens == 0).sum()) >= 2 and int(lens.max()) >= 4, lens
+            print('tiny_CNE_OMAP_stable history lengths', lens.tolist())
+            check('tiny_CNE_OMAP_stable')
+            cfg = full_cfg('CNE', 'OMAP', V=400, **omap)
+            run_case('full_CNE_OMAP_g0p35_stable', cfg, full_spec(cfg, 9), batch_size=2, seed=17, mode='train', gain=0.35, full_arrays=False)
+            check('full_CNE_OMAP_g0p35_stable')
+        cfg = tiny_cfg('CNN', 'OMAP', **omap)
+        run_case('tiny_CNN_OMAP', cfg, tiny_spec(cfg, 3), batch_size=3, seed=11, mode='train', gain=2.0)
+        check('tiny_CNN_OMAP')
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == 'omap':
+        torch.set_num_threads(8)
+        return omap_cases()
     if len(sys.argv) > 1 and sys.argv[1] == 'catt':
         torch.set_num_threads(8)
         return catt_cases()
