@@ -52,24 +52,139 @@ class PoolArgs(C.Structure):
                 ('alpha_b', vp), ('dout_b', vp), ('lddo_b', ci), ('dscore_b', vp), ('v_b', vp), ('ldv_b', ci), ('scale_b', cf)]
 
 
-# every symbol include/nnr_hip.h declares (tests check the .so exports all of them)
-SYMBOLS = [
-    'nnr_version', 'nnr_gemm_f32', 'nnr_split_bf16x3', 'nnr_seq_plan', 'nnr_seq_plan_pair', 'nnr_cne_pair_map', 'nnr_lstm_dims', 'nnr_lstm_pack_weights', 'nnr_lstm_unpack_grads',
-    'nnr_lstm_fwd', 'nnr_lstm_bwd', 'nnr_lstm_sync_bytes', 'nnr_lstm_sync_diag_offset', 'nnr_lstm_set_timeout_counter', 'nnr_attn_pool_fwd', 'nnr_attn_pool_bwd', 'nnr_gate_bwd', 'nnr_packed_seq_sum',
-    'nnr_tanh_score_bwd', 'nnr_slot_workspace_floats', 'nnr_colsum', 'nnr_rowdot', 'nnr_small_embed_fwd', 'nnr_small_embed_bwd', 'nnr_add', 'nnr_add_atomic', 'nnr_add2d', 'nnr_expand_rows_fwd', 'nnr_expand_rows_bwd', 'nnr_dropout',
-    'nnr_layernorm_fwd', 'nnr_layernorm_bwd', 'nnr_relu_bwd', 'nnr_relu_drop_bwd', 'nnr_gcn_aggregate_fwd', 'nnr_gcn_aggregate_bwd', 'nnr_sue_x0_fwd', 'nnr_sue_x0_bwd', 'nnr_sue_slice_fwd', 'nnr_sue_slice_bwd',
-    'nnr_sue_intra_fwd', 'nnr_sue_intra_bwd', 'nnr_logits_loss_fwd', 'nnr_logits_fwd', 'nnr_nls_loss', 'nnr_logits_bwd', 'nnr_sumsq', 'nnr_sumsq_part', 'nnr_clip_adam',
-    'nnr_mhsa_fwd', 'nnr_mhsa_bwd', 'nnr_mhsa_fwd_packed', 'nnr_mhsa_bwd_packed', 'nnr_mhsa_pair_map', 'nnr_mhsa_fwd_paired', 'nnr_mhsa_bwd_paired', 'nnr_mask_cover', 'nnr_seq_rowmap', 'nnr_embed_gather', 'nnr_embed_scatter', 'nnr_embed_scatter_dyn', 'nnr_transpose2d', 'nnr_transpose_batch', 'nnr_corpus_batch', 'nnr_history_graph', 'nnr_rank_metrics',
-    'nnr_dp_unique_id', 'nnr_dp_init', 'nnr_dp_allreduce', 'nnr_dp_broadcast', 'nnr_dp_destroy', 'nnr_dp_emulate_ranks', 'nnr_dp_busy',
-    'nnr_fill_zero', 'nnr_copy_bytes', 'nnr_fill_column_u8', 'nnr_adam_skipped_steps', 'nnr_adam_skipped_peek', 'nnr_fusion_rows_fwd', 'nnr_fusion_rows_bwd', 'nnr_click_loss',
-    'nnr_tape_create', 'nnr_tape_destroy', 'nnr_tape_fn_id', 'nnr_tape_fn_nargs', 'nnr_tape_call', 'nnr_tape_wait_stream', 'nnr_tape_event_record',
-    'nnr_tape_event_wait', 'nnr_tape_segment', 'nnr_tape_patch', 'nnr_tape_finalize', 'nnr_tape_info', 'nnr_tape_replay', 'nnr_tape_prepare_timing', 'nnr_tape_timings', 'nnr_tape_timeline',
-    'nnr_tape_last_error',
-    'nnr_token_sort_workspace_bytes', 'nnr_token_sort', 'nnr_embed_scatter_sorted_workspace_floats', 'nnr_embed_scatter_sorted', 'nnr_fusion_rows_bwd_det',
-    'nnr_rows_touch', 'nnr_rows_compact', 'nnr_rows_pack', 'nnr_rows_unpack',
-    'nnr_cand_attn_ws_floats', 'nnr_cand_attn_fwd', 'nnr_cand_attn_bwd',
-    'nnr_omap_ws_floats', 'nnr_omap_fwd', 'nnr_omap_bwd', 'nnr_omap_reg_fwd', 'nnr_omap_reg_bwd',
-]
+# The C-ABI, stated once: entry point -> 'return kind, then the kind of every parameter in header order' (tests/test_cabi_exports.py
+# compares every word with include/nnr_hip.h).  lib() derives argtypes / restype from it, so call sites pass plain Python values, and the
+# tape (nnr_amd/tape.py) encodes a recorded call by these kinds.  i32 int | i64 long, int64_t | u64 size_t, uint64_t | f32 float |
+# seed uint32_t (every scalar one is a dropout seed) | ptr data pointer | handle nnr_tape*, nnr_dp_ctx* (opaque host objects, also as **
+# out-parameters) | cstr char* | stream hipStream_t | a mirror class's name: pointer to that struct.
+SIGNATURES = {
+    'nnr_version': 'i32',
+    'nnr_gemm_f32': 'i32 GemmArgs stream',
+    'nnr_split_bf16x3': 'i32 ptr i32 i32 i32 i32 ptr i64 stream',
+    'nnr_seq_plan': 'i32 ptr ptr i32 i32 ptr ptr ptr ptr ptr ptr ptr ptr ptr ptr ptr stream',
+    'nnr_seq_plan_pair': 'i32 ptr ptr i32 ptr ptr i32 i32 ptr ptr ptr ptr ptr ptr ptr ptr ptr ptr ptr stream',
+    'nnr_cne_pair_map': 'i32 ptr ptr i32 i32 ptr ptr ptr stream',
+    'nnr_mask_cover': 'i32 ptr i32 i32 ptr stream',
+    'nnr_seq_rowmap': 'i32 ptr ptr ptr i32 i32 ptr stream',
+    'nnr_lstm_dims': 'i32 i32 ptr ptr ptr',
+    'nnr_lstm_pack_weights': 'i32 ptr ptr ptr ptr ptr ptr ptr ptr i32 i32 ptr ptr ptr ptr ptr stream',
+    'nnr_lstm_unpack_grads': 'i32 ptr ptr ptr i32 i32 ptr ptr ptr ptr ptr ptr ptr ptr i32 i32 stream',
+    'nnr_lstm_sync_bytes': 'u64 i32',
+    'nnr_lstm_sync_diag_offset': 'u64 i32',
+    'nnr_lstm_set_timeout_counter': 'i32 ptr',
+    'nnr_lstm_fwd': 'i32 LstmProblem i32 i32 stream',
+    'nnr_lstm_bwd': 'i32 LstmProblem i32 i32 stream',
+    'nnr_attn_pool_fwd': 'i32 PoolArgs stream',
+    'nnr_attn_pool_bwd': 'i32 PoolArgs stream',
+    'nnr_gate_bwd': 'i32 ptr ptr ptr ptr ptr ptr i32 i32 stream',
+    'nnr_packed_seq_sum': 'i32 ptr i32 ptr ptr i32 ptr stream',
+    'nnr_slot_workspace_floats': 'i32 i32',
+    'nnr_tanh_score_bwd': 'i32 ptr ptr ptr ptr ptr i32 i32 ptr stream',
+    'nnr_colsum': 'i32 ptr i32 ptr i32 i32 ptr ptr stream',
+    'nnr_rowdot': 'i32 ptr i32 ptr ptr i32 i32 ptr stream',
+    'nnr_small_embed_fwd': 'i32 ptr ptr i32 i32 ptr i32 f32 seed stream',
+    'nnr_small_embed_bwd': 'i32 ptr i32 i32 ptr i32 ptr f32 seed stream',
+    'nnr_embed_gather': 'i32 ptr ptr i64 ptr i32 ptr f32 seed stream',
+    'nnr_embed_scatter': 'i32 ptr ptr i64 i32 ptr f32 seed stream',
+    'nnr_embed_scatter_dyn': 'i32 ptr ptr i64 ptr i32 ptr f32 seed stream',
+    'nnr_token_sort_workspace_bytes': 'u64 i64 i32',
+    'nnr_token_sort': 'i32 ptr i64 ptr i32 ptr ptr ptr ptr ptr u64 stream',
+    'nnr_embed_scatter_sorted_workspace_floats': 'u64 i64',
+    'nnr_embed_scatter_sorted': 'i32 ptr ptr ptr i64 i32 i32 ptr f32 seed ptr stream',
+    'nnr_transpose2d': 'i32 ptr ptr i64 i32 i32 stream',
+    'nnr_transpose_batch': 'i32 TransposeDesc i32 stream',
+    'nnr_add': 'i32 ptr ptr i64 f32 stream',
+    'nnr_add_atomic': 'i32 ptr ptr i64 f32 stream',
+    'nnr_add2d': 'i32 ptr i32 ptr i32 i32 i32 f32 i32 stream',
+    'nnr_expand_rows_fwd': 'i32 ptr ptr i32 i32 i32 stream',
+    'nnr_expand_rows_bwd': 'i32 ptr ptr i32 i32 i32 stream',
+    'nnr_dropout': 'i32 ptr ptr i64 f32 seed stream',
+    'nnr_relu_bwd': 'i32 ptr ptr ptr i64 stream',
+    'nnr_gcn_aggregate_fwd': 'i32 ptr ptr ptr ptr ptr ptr i32 i32 i32 i32 f32 seed stream',
+    'nnr_gcn_aggregate_bwd': 'i32 ptr ptr ptr ptr ptr ptr i32 i32 i32 f32 seed stream',
+    'nnr_relu_drop_bwd': 'i32 ptr ptr ptr ptr i64 f32 seed stream',
+    'nnr_mhsa_fwd': 'i32 ptr ptr i32 i32 i32 i32 f32 ptr ptr f32 seed stream',
+    'nnr_mhsa_bwd': 'i32 ptr ptr ptr ptr i32 i32 i32 i32 f32 ptr f32 seed stream',
+    'nnr_mhsa_fwd_packed': 'i32 ptr ptr ptr i32 i32 i32 i32 f32 ptr f32 seed stream',
+    'nnr_mhsa_bwd_packed': 'i32 ptr ptr ptr ptr i32 i32 i32 i32 f32 ptr f32 seed stream',
+    'nnr_mhsa_pair_map': 'i32 ptr ptr ptr ptr i32 i32 ptr ptr stream',
+    'nnr_mhsa_fwd_paired': 'i32 ptr ptr ptr ptr i32 i32 i32 f32 ptr f32 seed stream',
+    'nnr_mhsa_bwd_paired': 'i32 ptr ptr ptr ptr ptr i32 i32 i32 f32 ptr f32 seed stream',
+    'nnr_sue_x0_fwd': 'i32 ptr ptr ptr i32 i32 i32 i32 f32 seed ptr stream',
+    'nnr_sue_x0_bwd': 'i32 ptr ptr ptr ptr i32 i32 i32 i32 f32 seed stream',
+    'nnr_sue_slice_fwd': 'i32 ptr ptr ptr i32 i32 i32 i32 stream',
+    'nnr_sue_slice_bwd': 'i32 ptr ptr i32 i32 i32 i32 stream',
+    'nnr_sue_intra_fwd': 'i32 ptr ptr ptr ptr i32 i32 i32 i32 i32 i32 ptr ptr stream',
+    'nnr_sue_intra_bwd': 'i32 ptr ptr ptr ptr ptr ptr i32 i32 i32 i32 i32 i32 ptr ptr ptr ptr stream',
+    'nnr_cand_attn_ws_floats': 'i32 i32 i32 i32 i32',
+    'nnr_cand_attn_fwd': 'i32 ptr ptr ptr ptr i32 ptr i32 i32 i32 i32 i32 i32 ptr ptr stream',
+    'nnr_cand_attn_bwd': 'i32 ptr ptr ptr ptr i32 ptr ptr ptr i32 i32 i32 i32 i32 i32 ptr ptr ptr i32 ptr ptr stream',
+    'nnr_omap_ws_floats': 'i32 i32 i32 i32 i32 i32',
+    'nnr_omap_fwd': 'i32 ptr i32 ptr ptr ptr i32 i32 i32 i32 i32 ptr ptr ptr ptr ptr ptr ptr stream',
+    'nnr_omap_bwd': 'i32 ptr i32 ptr ptr ptr ptr ptr ptr ptr ptr ptr i32 i32 i32 i32 i32 ptr i32 ptr ptr ptr stream',
+    'nnr_omap_reg_fwd': 'i32 ptr i32 i32 f32 ptr ptr stream',
+    'nnr_omap_reg_bwd': 'i32 ptr ptr ptr i32 i32 f32 ptr stream',
+    'nnr_corpus_batch': 'i32 CorpusTables BatchOut ptr ptr i32 i32 i32 stream',
+    'nnr_history_graph': 'i32 ptr ptr i32 i32 i32 i32 ptr ptr ptr stream',
+    'nnr_rank_metrics': 'i32 ptr ptr ptr i32 ptr ptr stream',
+    'nnr_logits_loss_fwd': 'i32 ptr ptr i32 i32 i32 ptr ptr ptr stream',
+    'nnr_logits_fwd': 'i32 ptr ptr i32 i32 i32 ptr stream',
+    'nnr_nls_loss': 'i32 ptr i32 i32 ptr ptr stream',
+    'nnr_logits_bwd': 'i32 ptr ptr ptr i32 i32 i32 ptr ptr i32 stream',
+    'nnr_layernorm_fwd': 'i32 ptr ptr ptr f32 i64 i32 ptr ptr ptr ptr ptr f32 seed stream',
+    'nnr_layernorm_bwd': 'i32 ptr ptr ptr ptr i64 i32 ptr ptr ptr stream',
+    'nnr_sumsq': 'i32 ptr i64 ptr stream',
+    'nnr_sumsq_part': 'i32 ptr i64 ptr ptr i32 stream',
+    'nnr_clip_adam': 'i32 ptr ptr ptr ptr i64 ptr f32 f32 f32 f32 f32 f32 f32 i32 stream',
+    'nnr_adam_skipped_steps': 'i32 ptr i32',
+    'nnr_adam_skipped_peek': 'i32 ptr',
+    'nnr_dp_unique_id': 'i32 ptr',
+    'nnr_dp_init': 'i32 ptr i32 i32 handle',
+    'nnr_dp_allreduce': 'i32 handle ptr u64 stream',
+    'nnr_dp_broadcast': 'i32 handle ptr u64 i32 stream',
+    'nnr_dp_destroy': 'i32 handle',
+    'nnr_dp_emulate_ranks': 'i32 handle i32',
+    'nnr_dp_busy': 'i32 ptr i64 i32 i32 stream',
+    'nnr_rows_touch': 'i32 ptr i64 ptr i32 ptr stream',
+    'nnr_rows_compact': 'i32 ptr i32 ptr ptr stream',
+    'nnr_rows_pack': 'i32 ptr ptr i32 i32 ptr stream',
+    'nnr_rows_unpack': 'i32 ptr ptr i32 i32 ptr stream',
+    'nnr_fusion_rows_fwd': 'i32 ptr ptr ptr ptr i32 ptr ptr i32 i32 i32 ptr i32 f32 seed seed stream',
+    'nnr_fusion_rows_bwd': 'i32 ptr ptr i32 ptr ptr i32 i32 i32 ptr i32 ptr ptr f32 seed seed stream',
+    'nnr_fusion_rows_bwd_det': 'i32 ptr ptr i32 ptr ptr i32 i32 i32 i32 i32 ptr i32 ptr ptr f32 seed seed stream',
+    'nnr_click_loss': 'i32 ptr ptr i32 i32 i32 ptr ptr ptr ptr ptr ptr stream',
+    'nnr_fill_zero': 'i32 ptr u64 stream',
+    'nnr_copy_bytes': 'i32 ptr ptr u64 stream',
+    'nnr_fill_column_u8': 'i32 ptr i32 i32 i32 i32 stream',
+    'nnr_tape_create': 'i32 handle',
+    'nnr_tape_destroy': 'i32 handle',
+    'nnr_tape_fn_id': 'i32 cstr',
+    'nnr_tape_fn_nargs': 'i32 i32',
+    'nnr_tape_call': 'i32 handle i32 stream ptr i32 ptr ptr ptr i32 i32 ptr ptr',
+    'nnr_tape_wait_stream': 'i32 handle stream stream',
+    'nnr_tape_event_record': 'i32 handle u64 stream',
+    'nnr_tape_event_wait': 'i32 handle stream u64',
+    'nnr_tape_segment': 'i32 handle',
+    'nnr_tape_patch': 'i32 handle u64 i32 i32 i64',
+    'nnr_tape_finalize': 'i32 handle',
+    'nnr_tape_prepare_timing': 'i32 handle i32',
+    'nnr_tape_info': 'i32 handle ptr ptr ptr ptr ptr',
+    'nnr_tape_replay': 'i32 handle i32 ptr i32 ptr i32 i32',
+    'nnr_tape_timings': 'i32 handle i32 ptr i32',
+    'nnr_tape_timeline': 'i32 handle i32 ptr ptr ptr i32',
+    'nnr_tape_last_error': 'i32 handle ptr ptr cstr i32',
+}
+SYMBOLS = list(SIGNATURES)
+STRUCTS = {'nnr_gemm_args': GemmArgs, 'nnr_lstm_problem': LstmProblem, 'nnr_pool_args': PoolArgs, 'nnr_transpose_desc': TransposeDesc,
+           'nnr_corpus_tables': CorpusTables, 'nnr_batch_out': BatchOut}
+DEVICE_STRUCTS = {'TransposeDesc'}     # descriptor tables that live in DEVICE memory: passed (and recorded) like any data pointer
+_CTYPES = {'i32': ci, 'i64': cl, 'u64': C.c_size_t, 'f32': cf, 'seed': cu32, 'ptr': vp, 'handle': vp, 'cstr': C.c_char_p, 'stream': vp}
+_CTYPES.update((c.__name__, vp if c.__name__ in DEVICE_STRUCTS else C.POINTER(c)) for c in STRUCTS.values())
+
+
+def kinds(name):
+    """Parameter kinds of an entry point, in header order (the return kind is SIGNATURES[name].split()[0])."""
+    return SIGNATURES[name].split()[1:]
 
 
 class NnrHipError(RuntimeError):
@@ -99,12 +214,10 @@ def lib():
         # foreign to the second one (each call fails with NNR_ERR_LAUNCH) -- found by running build() and smoke() in ONE process.
         import torch  # noqa: F401
         _lib = C.CDLL(LIB_PATH)
-        for s in SYMBOLS:
-            getattr(_lib, s).restype = ci
-        _lib.nnr_lstm_sync_bytes.restype = C.c_size_t
-        _lib.nnr_lstm_sync_diag_offset.restype = C.c_size_t
-        _lib.nnr_token_sort_workspace_bytes.restype = C.c_size_t
-        _lib.nnr_embed_scatter_sorted_workspace_floats.restype = C.c_size_t
+        for name, sig in SIGNATURES.items():
+            ret, *params = [_CTYPES[k] for k in sig.split()]
+            fn = getattr(_lib, name)
+            fn.restype, fn.argtypes = ret, params
     return _lib
 
 

@@ -49,13 +49,13 @@ class NativeExchange:
         L.check(L.lib().nnr_dp_init(uid, rank, world, C.byref(self.ctx)), 'nnr_dp_init')
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return torch.cuda.current_stream().cuda_stream
 
     def allreduce(self, flat):
-        self.L.check(self.L.lib().nnr_dp_allreduce(self.ctx, C.c_void_p(flat.data_ptr()), C.c_size_t(flat.numel()), self._stream()), 'nnr_dp_allreduce')
+        self.L.check(self.L.lib().nnr_dp_allreduce(self.ctx, flat.data_ptr(), flat.numel(), self._stream()), 'nnr_dp_allreduce')
 
     def broadcast(self, flat, root=0):
-        self.L.check(self.L.lib().nnr_dp_broadcast(self.ctx, C.c_void_p(flat.data_ptr()), C.c_size_t(flat.numel()), root, self._stream()), 'nnr_dp_broadcast')
+        self.L.check(self.L.lib().nnr_dp_broadcast(self.ctx, flat.data_ptr(), flat.numel(), root, self._stream()), 'nnr_dp_broadcast')
 
     def close(self):
         if self.ctx:
@@ -420,7 +420,7 @@ class GradientExchange:
         V = self.table_shape[0]
         if flags.is_cuda:
             from . import _lib as L, ops
-            L.check(L.lib().nnr_rows_touch(ops._p(tok), C.c_long(tok.numel()), ops._p(total), V, ops._p(flags), ops._s()), 'nnr_rows_touch')
+            L.check(L.lib().nnr_rows_touch(ops._p(tok), tok.numel(), ops._p(total), V, ops._p(flags), ops._s()), 'nnr_rows_touch')
             ev = torch.cuda.Event()
             ev.record()
             self._noted.append(ev)

@@ -2,8 +2,6 @@
 (evaluate.py:32-89).  Dev / test samples are (impression, candidate) pairs; the model scores each with news_num = 1
 (util.py:43-50), candidates are ranked inside their impression and AUC / MRR / nDCG@5 / nDCG@10 are averaged over
 impressions.  Batches come from a DeviceCorpus (id-only), scores never leave HBM until the four means are read back."""
-import ctypes as C
-
 import numpy as np
 import torch
 

@@ -52,7 +52,7 @@ def _p(t):
         return None
     if not t.is_cuda:
         raise L.NnrHipError('nnr_amd ops need device tensors (no CPU fallback on the product path)')
-    return C.c_void_p(t.data_ptr())
+    return t.data_ptr()
 
 
 _DEV_INDEX = []
@@ -63,7 +63,7 @@ def _s():
     ~9 us of host time per call -- device-index and availability checks --, 170 calls per step; the raw getter ~0.3 us.)"""
     if not _DEV_INDEX:
         _DEV_INDEX.append(torch.cuda.current_device())      # one process per GPU: fixed after set_device
-    return C.c_void_p(torch._C._cuda_getCurrentRawStream(_DEV_INDEX[0]))
+    return torch._C._cuda_getCurrentRawStream(_DEV_INDEX[0])
 
 
 # ---------------------------------------------------------------------------------------------- leaf work on its own stream
@@ -320,7 +320,7 @@ def _serve(e, sources, fill):
     its last refresh."""
     e.served = True
     tape_keep(*e.bufs)
-    stamp, cur = _stamp(sources), _s().value
+    stamp, cur = _stamp(sources), _s()
     if e.stamp != stamp:
         fill()
         _refreshed([(e, stamp)], cur)
@@ -348,7 +348,7 @@ def _on_leaf(dev, jobs, launch):
     leaf.wait_stream(torch.cuda.current_stream(dev))
     with torch.cuda.stream(leaf):
         launch()
-        _refreshed([(e, stamp) for e, _, stamp in jobs], _s().value)
+        _refreshed([(e, stamp) for e, _, stamp in jobs], _s())
     for e, _, _ in jobs:
         e.served = False
 
@@ -481,7 +481,7 @@ BX3_SEEN = {}                                                  # diagnostics: (M
 
 def _split_bf16x3(B, N, K, ldb, img):
     ldo = img.shape[2]
-    L.check(L.lib().nnr_split_bf16x3(_p(B), N, K, ldb, ldo, _p(img), C.c_long(N * ldo), _s()), 'nnr_split_bf16x3')
+    L.check(L.lib().nnr_split_bf16x3(_p(B), N, K, ldb, ldo, _p(img), N * ldo, _s()), 'nnr_split_bf16x3')
 
 
 def bx3_prefetch(dev):
@@ -544,7 +544,7 @@ def gemm(A, B, C_=None, *, M, N, K, lda, ldb, ldc=0, trans_a=False, trans_b=Fals
     if b_idx is not None:
         g.b_idx = b_idx.data_ptr()
     if drop is not None and drop[1] > 0.0:
-        g.drop_target, g.drop_p, g.drop_seed, g.drop_cols = drop[0], float(drop[1]), int(drop[2]) & 0xFFFFFFFF, int(drop[3])
+        g.drop_target, g.drop_p, g.drop_seed, g.drop_cols = drop[0], float(drop[1]), int(drop[2]), int(drop[3])
     if bias is not None:
         g.bias = bias.data_ptr()
     if rowvec is not None:
@@ -721,7 +721,7 @@ def _slot_ws(dev, n):
     """Slot workspace of the CURRENT stream (see nnr_slot_workspace_floats): kernels of one stream run in order and each call
     overwrites the slot rows it reads, so one buffer per stream serves every call; grown when a wider vector comes along."""
     key = torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device())
-    need = L.lib().nnr_slot_workspace_floats(int(n))
+    need = L.lib().nnr_slot_workspace_floats(n)
     ws = _SLOT_WS.get(key)
     if ws is None or ws.numel() < need:
         ws = torch.zeros(max(need, 32 * 1024), device=dev, dtype=torch.float32)
@@ -813,8 +813,8 @@ class LstmPacked:
 def lstm_unpack_grads(dw_ihp, db_p, dw_hhp, H, E, grads, zero_src=False):
     """grads: 8 tensors in nn.LSTM order (w_ih, w_hh, b_ih, b_hh, then *_reverse); accumulated into with f32 atomics
     (parameter gradients may be accumulated from several HIP streams at once).  zero_src: leave the packed buffers zeroed."""
-    L.check(L.lib().nnr_lstm_unpack_grads(_p(dw_ihp), _p(db_p), _p(dw_hhp), H, E, *[_p(t) for t in grads], 1, int(zero_src), _s()),
-            'nnr_lstm_unpack_grads')
+    L.check(L.lib().nnr_lstm_unpack_grads(_p(dw_ihp), _p(db_p), _p(dw_hhp), H, E, *[_p(t) for t in grads], 1, zero_src, _s()),
+                                          'nnr_lstm_unpack_grads')
 
 
 LSTM_PAIR = os.environ.get('NNR_LSTM_PAIR', '1') != '0'      # 2-CU weights-stationary recurrence (lstm.hip) when H = 200
@@ -830,13 +830,13 @@ def _timeout_counter(dev):
     if t is None:
         t = torch.zeros(1, dtype=torch.int32, device=dev)
         _TMO[key] = t
-        L.check(L.lib().nnr_lstm_set_timeout_counter(C.c_void_p(t.data_ptr())), 'nnr_lstm_set_timeout_counter')
+        L.check(L.lib().nnr_lstm_set_timeout_counter(t.data_ptr()), 'nnr_lstm_set_timeout_counter')
     return t
 
 
 def dp_busy(buf, workgroups, iters):
     """Diagnostics: `workgroups` resident 512-thread workgroups sweeping `buf` on the CURRENT stream (a stand-in for RCCL's ring kernels)."""
-    L.check(L.lib().nnr_dp_busy(_p(buf), C.c_long(buf.numel()), int(workgroups), int(iters), _s()), 'nnr_dp_busy')
+    L.check(L.lib().nnr_dp_busy(_p(buf), buf.numel(), workgroups, iters, _s()), 'nnr_dp_busy')
 
 
 def lstm_sync_timeouts(reset=False):
@@ -957,13 +957,13 @@ def pool_bwd(**kw):
 # ---------------------------------------------------------------------------------------------- elementwise
 def add_(y, x, alpha=1.0):
     assert y.is_contiguous() and x.is_contiguous() and y.numel() == x.numel()
-    L.check(L.lib().nnr_add(_p(y), _p(x), C.c_long(y.numel()), C.c_float(alpha), _s()), 'nnr_add')
+    L.check(L.lib().nnr_add(_p(y), _p(x), y.numel(), alpha, _s()), 'nnr_add')
     return y
 
 
 def add_atomic_(y, x, alpha=1.0):
     assert y.is_contiguous() and x.is_contiguous() and y.numel() == x.numel()
-    L.check(L.lib().nnr_add_atomic(_p(y), _p(x), C.c_long(y.numel()), C.c_float(alpha), _s()), 'nnr_add_atomic')
+    L.check(L.lib().nnr_add_atomic(_p(y), _p(x), y.numel(), alpha, _s()), 'nnr_add_atomic')
     return y
 
 
@@ -984,7 +984,7 @@ def expand_rows_bwd(dy):
 
 
 def add2d(y, ldy, x, ldx, rows, cols, alpha=1.0, accumulate=False):
-    L.check(L.lib().nnr_add2d(_p(y), ldy, _p(x), ldx, rows, cols, C.c_float(alpha), int(accumulate), _s()), 'nnr_add2d')
+    L.check(L.lib().nnr_add2d(_p(y), ldy, _p(x), ldx, rows, cols, alpha, accumulate, _s()), 'nnr_add2d')
 
 
 def gate_bwd(dHt, H, G, dH, dpre, plan, cols):
@@ -1009,73 +1009,66 @@ def tanh_score_bwd(th, ds, w2, dw2, plan, A):
 
 def small_embed_fwd(table, idx, out_view, ldo, p, seed):
     n, dim = idx.numel(), table.shape[1]
-    L.check(L.lib().nnr_small_embed_fwd(_p(table), _p(idx), n, dim, _p(out_view), ldo, C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _s()),
-            'nnr_small_embed_fwd')
+    L.check(L.lib().nnr_small_embed_fwd(_p(table), _p(idx), n, dim, _p(out_view), ldo, p, seed, _s()), 'nnr_small_embed_fwd')
 
 
 def small_embed_bwd(idx, dim, dout_view, lddo, dtable, p, seed):
-    L.check(L.lib().nnr_small_embed_bwd(_p(idx), idx.numel(), dim, _p(dout_view), lddo, _p(dtable), C.c_float(p),
-                                        C.c_uint32(seed & 0xFFFFFFFF), _s()), 'nnr_small_embed_bwd')
+    L.check(L.lib().nnr_small_embed_bwd(_p(idx), idx.numel(), dim, _p(dout_view), lddo, _p(dtable), p, seed, _s()), 'nnr_small_embed_bwd')
 
 
 def dropout(x, p, seed, out=None):
     if out is None:
         out = torch.empty_like(x)
-    L.check(L.lib().nnr_dropout(_p(x), _p(out), C.c_long(x.numel()), C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _s()), 'nnr_dropout')
+    L.check(L.lib().nnr_dropout(_p(x), _p(out), x.numel(), p, seed, _s()), 'nnr_dropout')
     return out
 
 
 def layernorm_fwd(u, gamma, beta, eps, xhat, rstd, r_out, resid, y, p, seed):
     """y = dropout(relu(LayerNorm(u) * gamma + beta) + resid) over the last dimension of a contiguous [rows, D] u."""
     rows, D = u.numel() // u.shape[-1], u.shape[-1]
-    L.check(L.lib().nnr_layernorm_fwd(_p(u), _p(gamma), _p(beta), C.c_float(eps), C.c_long(rows), D, _p(xhat), _p(rstd), _p(r_out), _p(resid),
-                                      _p(y), C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _s()), 'nnr_layernorm_fwd')
+    L.check(L.lib().nnr_layernorm_fwd(_p(u), _p(gamma), _p(beta), eps, rows, D, _p(xhat), _p(rstd), _p(r_out), _p(resid), _p(y), p, seed, _s()),
+                                      'nnr_layernorm_fwd')
 
 
 def layernorm_bwd(dv, xhat, rstd, gamma, du, dgamma, dbeta):
     rows, D = dv.numel() // dv.shape[-1], dv.shape[-1]
-    L.check(L.lib().nnr_layernorm_bwd(_p(dv), _p(xhat), _p(rstd), _p(gamma), C.c_long(rows), D, _p(du), _p(dgamma), _p(dbeta), _s()),
-            'nnr_layernorm_bwd')
+    L.check(L.lib().nnr_layernorm_bwd(_p(dv), _p(xhat), _p(rstd), _p(gamma), rows, D, _p(du), _p(dgamma), _p(dbeta), _s()), 'nnr_layernorm_bwd')
 
 
 def relu_bwd(dy, y, dx=None):
     if dx is None:
         dx = torch.empty_like(dy)
-    L.check(L.lib().nnr_relu_bwd(_p(dy), _p(y), _p(dx), C.c_long(dy.numel()), _s()), 'nnr_relu_bwd')
+    L.check(L.lib().nnr_relu_bwd(_p(dy), _p(y), _p(dx), dy.numel(), _s()), 'nnr_relu_bwd')
     return dx
 
 
 def relu_drop_bwd(dy, r, ds, dx, p, seed):
-    L.check(L.lib().nnr_relu_drop_bwd(_p(dy), _p(r), _p(ds), _p(dx), C.c_long(dy.numel()), C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF),
-                                      _s()), 'nnr_relu_drop_bwd')
+    L.check(L.lib().nnr_relu_drop_bwd(_p(dy), _p(r), _p(ds), _p(dx), dy.numel(), p, seed, _s()), 'nnr_relu_drop_bwd')
 
 
 # ---------------------------------------------------------------------------------------------- SUE / loss / optimiser
 def gcn_aggregate_fwd(graph, z, bias, resid, r_out, y, B, G, D, relu, p, seed):
     arrays = 3 + (1 if resid is not None else 0)                                  # z, (resid) read; r, y written
     with _hbm_span('gcn_aggregate_fwd', 4.0 * (G * D * arrays + G * G), B):
-        L.check(L.lib().nnr_gcn_aggregate_fwd(_p(graph), _p(z), _p(bias), _p(resid), _p(r_out), _p(y), B, G, D, int(relu), C.c_float(p),
-                                              C.c_uint32(int(seed) & 0xFFFFFFFF), _s()), 'nnr_gcn_aggregate_fwd')
+        L.check(L.lib().nnr_gcn_aggregate_fwd(_p(graph), _p(z), _p(bias), _p(resid), _p(r_out), _p(y), B, G, D, relu, p, seed, _s()),
+                                              'nnr_gcn_aggregate_fwd')
 
 
 def gcn_aggregate_bwd(graph, dy, r, ds, dx0, dz, B, G, D, p, seed):
     arrays = 4 + (1 if dx0 is not None else 0)                                    # dy, r read; dS, dz, (dx0) written
     with _hbm_span('gcn_aggregate_bwd', 4.0 * (G * D * arrays + G * G), B):
-        L.check(L.lib().nnr_gcn_aggregate_bwd(_p(graph), _p(dy), _p(r), _p(ds), _p(dx0), _p(dz), B, G, D, C.c_float(p),
-                                              C.c_uint32(int(seed) & 0xFFFFFFFF), _s()), 'nnr_gcn_aggregate_bwd')
+        L.check(L.lib().nnr_gcn_aggregate_bwd(_p(graph), _p(dy), _p(r), _p(ds), _p(dx0), _p(dz), B, G, D, p, seed, _s()), 'nnr_gcn_aggregate_bwd')
 
 
 def sue_x0_fwd(hist, proxy, x0, B, Hn, Kc, D, p, seed, cmask_fix=None):
     """cmask_fix: the [B, Kc + 1] cluster mask; its last column is set in place by the same launch (userEncoders.py:73)."""
     if cmask_fix is not None:
         assert cmask_fix.is_contiguous() and cmask_fix.element_size() == 1 and tuple(cmask_fix.shape) == (B, Kc + 1)
-    L.check(L.lib().nnr_sue_x0_fwd(_p(hist), _p(proxy), _p(x0), B, Hn, Kc, D, C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _p(cmask_fix), _s()),
-            'nnr_sue_x0_fwd')
+    L.check(L.lib().nnr_sue_x0_fwd(_p(hist), _p(proxy), _p(x0), B, Hn, Kc, D, p, seed, _p(cmask_fix), _s()), 'nnr_sue_x0_fwd')
 
 
 def sue_x0_bwd(dx0, dhist, dproxy, B, Hn, Kc, D, p, seed, dx0_add=None):
-    L.check(L.lib().nnr_sue_x0_bwd(_p(dx0), _p(dx0_add), _p(dhist), _p(dproxy), B, Hn, Kc, D, C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _s()),
-            'nnr_sue_x0_bwd')
+    L.check(L.lib().nnr_sue_x0_bwd(_p(dx0), _p(dx0_add), _p(dhist), _p(dproxy), B, Hn, Kc, D, p, seed, _s()), 'nnr_sue_x0_bwd')
 
 
 def sue_slice_fwd(gcn, x0, gfeat, B, Hn, G, D):
@@ -1128,7 +1121,7 @@ def cand_attn_bwd(P, Q, w2, feat, mask, alpha, dout, B, N, H, A, D, act, dP, dQ,
     with _hbm_span('cand_attn_bwd', 4.0 * (2 * N * A + 2 * H * A + (3 if accumulate else 2) * H * D + 3 * N * H + N * D + 2 * N * A) + 1.0 * H, B,
                    fixed=8.0 * A):
         L.check(L.lib().nnr_cand_attn_bwd(_p(P), _p(Q), _p(w2), _p(feat), feat.stride(1), _p(_u8(mask)), _p(alpha), _p(dout), B, N, H, A, D, act,
-                                          _p(dP), _p(dQ), _p(dfeat), int(accumulate), _p(ws), _p(dw2), _s()), 'nnr_cand_attn_bwd')
+                                          _p(dP), _p(dQ), _p(dfeat), accumulate, _p(ws), _p(dw2), _s()), 'nnr_cand_attn_bwd')
 
 
 def omap_ws(B, N, H, D, K, device):
@@ -1157,20 +1150,20 @@ def omap_bwd(hist, cand, mask, W, alpha, Y, beta, R, gamma, dout, B, N, H, D, K,
     # d history (read first when it accumulates), the user's dW rows both ways
     with _hbm_span('omap_bwd', 4.0 * (2 * H * D + 2 * H * D + 2 * H * H + 2 * H * H + 2 * N * D + K * D + 3 * K * D + N * D +
                                       (2 if accumulate else 1) * H * D + 2 * D * K + 3 * H * K) + 1.0 * H, B, fixed=12.0 * D * K):
-        L.check(L.lib().nnr_omap_bwd(_p(hist), hist.stride(1), _p(cand), _p(_u8(mask)), _p(W), _p(alpha), _p(Y), _p(beta), _p(R), _p(gamma),
-                                     _p(dout), B, N, H, D, K, _p(dhist), int(accumulate), _p(dcand), _p(dW), _p(ws), _s()), 'nnr_omap_bwd')
+        L.check(L.lib().nnr_omap_bwd(_p(hist), hist.stride(1), _p(cand), _p(_u8(mask)), _p(W), _p(alpha), _p(Y), _p(beta), _p(R), _p(gamma), _p(dout),
+                                     B, N, H, D, K, _p(dhist), accumulate, _p(dcand), _p(dW), _p(ws), _s()), 'nnr_omap_bwd')
 
 
 def omap_reg_fwd(W, coef, off, loss):
     """loss (0-dim) = coef * ||(W^T W) o (J - I)||_F; off [K * K + 1] keeps the off-diagonal part and the norm for omap_reg_bwd."""
     D, K = W.shape
-    L.check(L.lib().nnr_omap_reg_fwd(_p(W), D, K, C.c_float(coef), _p(off), _p(loss), _s()), 'nnr_omap_reg_fwd')
+    L.check(L.lib().nnr_omap_reg_fwd(_p(W), D, K, coef, _p(off), _p(loss), _s()), 'nnr_omap_reg_fwd')
 
 
 def omap_reg_bwd(W, off, gup, coef, dW):
     """dW += gup * coef * 2 W Off / Omega (gup: 0-dim device tensor; nothing at Omega == 0)."""
     D, K = W.shape
-    L.check(L.lib().nnr_omap_reg_bwd(_p(W), _p(off), _p(gup), D, K, C.c_float(coef), _p(dW), _s()), 'nnr_omap_reg_bwd')
+    L.check(L.lib().nnr_omap_reg_bwd(_p(W), _p(off), _p(gup), D, K, coef, _p(dW), _s()), 'nnr_omap_reg_bwd')
 
 
 def logits_loss_fwd(user, cand, B, N, D, logits, loss, dlogits):
@@ -1186,7 +1179,7 @@ def nls_loss(logits, B, N, loss, dlogits):
 
 
 def logits_bwd(dlogits, user, cand, B, N, D, duser, dcand, accumulate=False):
-    L.check(L.lib().nnr_logits_bwd(_p(dlogits), _p(user), _p(cand), B, N, D, _p(duser), _p(dcand), int(accumulate), _s()), 'nnr_logits_bwd')
+    L.check(L.lib().nnr_logits_bwd(_p(dlogits), _p(user), _p(cand), B, N, D, _p(duser), _p(dcand), accumulate, _s()), 'nnr_logits_bwd')
 
 
 def sumsq(g, out):
@@ -1196,32 +1189,31 @@ def sumsq(g, out):
 
 
 def _sumsq(g, out):
-    L.check(L.lib().nnr_sumsq(_p(g), C.c_long(g.numel()), _p(out), _s()), 'nnr_sumsq')
+    L.check(L.lib().nnr_sumsq(_p(g), g.numel(), _p(out), _s()), 'nnr_sumsq')
 
 
 def sumsq_part(g, out, add_in=None, slot=0):
     """out[0] = sum g^2 (+ add_in[0]) over one span of the flat gradient (fixed-order sum; `slot`: scratch set, one per concurrent stream)."""
     with _hbm_span('sumsq', 4.0, g.numel()):
-        L.check(L.lib().nnr_sumsq_part(_p(g), C.c_long(g.numel()), _p(out), _p(add_in), int(slot), _s()), 'nnr_sumsq_part')
+        L.check(L.lib().nnr_sumsq_part(_p(g), g.numel(), _p(out), _p(add_in), slot, _s()), 'nnr_sumsq_part')
 
 
 def fusion_rows_fwd(cat_table, sub_table, cat0, sub0, cat1, sub1, out_view, ldo, p, seed_cat, seed_sub):
     """feature_fusion's category / subCategory rows of one encoder call (cat1 = sub1 = None) or of the union of two calls."""
     n0, n1 = cat0.numel(), (cat1.numel() if cat1 is not None else 0)
     L.check(L.lib().nnr_fusion_rows_fwd(_p(cat_table), _p(sub_table), _p(cat0), _p(sub0), n0, _p(cat1), _p(sub1), n1, cat_table.shape[1],
-                                        sub_table.shape[1], _p(out_view), ldo, C.c_float(p), C.c_uint32(seed_cat & 0xFFFFFFFF),
-                                        C.c_uint32(seed_sub & 0xFFFFFFFF), _s()), 'nnr_fusion_rows_fwd')
+                                        sub_table.shape[1], _p(out_view), ldo, p, seed_cat, seed_sub, _s()), 'nnr_fusion_rows_fwd')
 
 
 def fusion_rows_bwd(cat0, sub0, cat1, sub1, cd, sd, dout_view, lddo, dcat_table, dsub_table, p, seed_cat, seed_sub):
     n0, n1 = cat0.numel(), (cat1.numel() if cat1 is not None else 0)
     if cd <= 128 and sd <= 128:                   # reproducible form (slot rows + fixed-order sum); wider tables: f32 atomics
         L.check(L.lib().nnr_fusion_rows_bwd_det(_p(cat0), _p(sub0), n0, _p(cat1), _p(sub1), n1, cd, sd, dcat_table.shape[0], dsub_table.shape[0],
-                                                _p(dout_view), lddo, _p(dcat_table), _p(dsub_table), C.c_float(p), C.c_uint32(seed_cat & 0xFFFFFFFF),
-                                                C.c_uint32(seed_sub & 0xFFFFFFFF), _s()), 'nnr_fusion_rows_bwd_det')
+                                                _p(dout_view), lddo, _p(dcat_table), _p(dsub_table), p, seed_cat, seed_sub, _s()),
+                                                'nnr_fusion_rows_bwd_det')
         return
     L.check(L.lib().nnr_fusion_rows_bwd(_p(cat0), _p(sub0), n0, _p(cat1), _p(sub1), n1, cd, sd, _p(dout_view), lddo, _p(dcat_table), _p(dsub_table),
-                                        C.c_float(p), C.c_uint32(seed_cat & 0xFFFFFFFF), C.c_uint32(seed_sub & 0xFFFFFFFF), _s()), 'nnr_fusion_rows_bwd')
+                                        p, seed_cat, seed_sub, _s()), 'nnr_fusion_rows_bwd')
 
 
 def click_loss(user, cand, B, N, D, logits, loss, dlogits, duser, dcand, terms_ws):
@@ -1236,9 +1228,8 @@ def clip_adam(p, g, m, v, sumsq_buf, grad_scale, clip, lr, beta1, beta2, eps, wd
 
 
 def _clip_adam(p, g, m, v, sumsq_buf, grad_scale, clip, lr, beta1, beta2, eps, wd, step):
-    L.check(L.lib().nnr_clip_adam(_p(p), _p(g), _p(m), _p(v), C.c_long(p.numel()), _p(sumsq_buf), C.c_float(grad_scale), C.c_float(clip),
-                                  C.c_float(lr), C.c_float(beta1), C.c_float(beta2), C.c_float(eps), C.c_float(wd), int(step), _s()),
-            'nnr_clip_adam')
+    L.check(L.lib().nnr_clip_adam(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(sumsq_buf), grad_scale, clip, lr, beta1, beta2, eps, wd, step, _s()),
+                                  'nnr_clip_adam')
 
 
 def mhsa_fwd(qkv, mask, n, Lq, heads, dh, out, prob, p=0.0, seed=0):
@@ -1265,8 +1256,7 @@ def _mhsa_span(family, n, Lq, heads, dh, flop_units, arrays):
 
 
 def _mhsa_fwd(qkv, mask, n, Lq, heads, dh, out, prob, p, seed):
-    L.check(L.lib().nnr_mhsa_fwd(_p(qkv), _p(mask), n, Lq, heads, dh, C.c_float(1.0 / math.sqrt(dh)), _p(out), _p(prob),
-                                 C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _s()), 'nnr_mhsa_fwd')
+    L.check(L.lib().nnr_mhsa_fwd(_p(qkv), _p(mask), n, Lq, heads, dh, 1.0 / math.sqrt(dh), _p(out), _p(prob), p, seed, _s()), 'nnr_mhsa_fwd')
 
 
 def mhsa_bwd(qkv, mask, prob, dout, n, Lq, heads, dh, dqkv, p=0.0, seed=0):
@@ -1278,8 +1268,8 @@ def mhsa_bwd(qkv, mask, prob, dout, n, Lq, heads, dh, dqkv, p=0.0, seed=0):
 
 
 def _mhsa_bwd(qkv, mask, prob, dout, n, Lq, heads, dh, dqkv, p, seed):
-    L.check(L.lib().nnr_mhsa_bwd(_p(qkv), _p(mask), _p(prob), _p(dout), n, Lq, heads, dh, C.c_float(1.0 / math.sqrt(dh)), _p(dqkv),
-                                 C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _s()), 'nnr_mhsa_bwd')
+    L.check(L.lib().nnr_mhsa_bwd(_p(qkv), _p(mask), _p(prob), _p(dout), n, Lq, heads, dh, 1.0 / math.sqrt(dh), _p(dqkv), p, seed, _s()),
+                                 'nnr_mhsa_bwd')
 
 
 def mask_cover(mask):
@@ -1320,16 +1310,16 @@ def mhsa_fwd_packed(qkv, mask, rowmap, plan, heads, dh, out, p=0.0, seed=0):
     if mask is not None and mask.dtype == torch.bool:
         mask = mask.view(torch.uint8)
     with _mhsa_span_packed('mhsa_fwd', plan, heads, dh, 4.0, 4.0):
-        L.check(L.lib().nnr_mhsa_fwd_packed(_p(qkv), _p(mask), _p(rowmap), plan.n, plan.L, heads, dh, C.c_float(1.0 / math.sqrt(dh)), _p(out),
-                                            C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _s()), 'nnr_mhsa_fwd_packed')
+        L.check(L.lib().nnr_mhsa_fwd_packed(_p(qkv), _p(mask), _p(rowmap), plan.n, plan.L, heads, dh, 1.0 / math.sqrt(dh), _p(out), p, seed, _s()),
+                                            'nnr_mhsa_fwd_packed')
 
 
 def mhsa_bwd_packed(qkv, mask, rowmap, plan, dout, heads, dh, dqkv, p=0.0, seed=0):
     if mask is not None and mask.dtype == torch.bool:
         mask = mask.view(torch.uint8)
     with _mhsa_span_packed('mhsa_bwd', plan, heads, dh, 10.0, 7.0):
-        L.check(L.lib().nnr_mhsa_bwd_packed(_p(qkv), _p(mask), _p(rowmap), _p(dout), plan.n, plan.L, heads, dh, C.c_float(1.0 / math.sqrt(dh)),
-                                            _p(dqkv), C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _s()), 'nnr_mhsa_bwd_packed')
+        L.check(L.lib().nnr_mhsa_bwd_packed(_p(qkv), _p(mask), _p(rowmap), _p(dout), plan.n, plan.L, heads, dh, 1.0 / math.sqrt(dh), _p(dqkv), p,
+                                            seed, _s()), 'nnr_mhsa_bwd_packed')
 
 
 def mhsa_pair_map(plan, mask):
@@ -1346,15 +1336,15 @@ def mhsa_pair_map(plan, mask):
 def mhsa_fwd_paired(qkv, pair, plan, heads, dh, out, p=0.0, seed=0):
     vrow, vmask = pair
     with _mhsa_span_packed('mhsa_fwd', plan, heads, dh, 4.0, 4.0):
-        L.check(L.lib().nnr_mhsa_fwd_paired(_p(qkv), _p(vmask), _p(vrow), _p(plan.off), plan.n, heads, dh, C.c_float(1.0 / math.sqrt(dh)), _p(out),
-                                            C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _s()), 'nnr_mhsa_fwd_paired')
+        L.check(L.lib().nnr_mhsa_fwd_paired(_p(qkv), _p(vmask), _p(vrow), _p(plan.off), plan.n, heads, dh, 1.0 / math.sqrt(dh), _p(out), p, seed,
+                                            _s()), 'nnr_mhsa_fwd_paired')
 
 
 def mhsa_bwd_paired(qkv, pair, plan, dout, heads, dh, dqkv, p=0.0, seed=0):
     vrow, vmask = pair
     with _mhsa_span_packed('mhsa_bwd', plan, heads, dh, 10.0, 7.0):
-        L.check(L.lib().nnr_mhsa_bwd_paired(_p(qkv), _p(vmask), _p(vrow), _p(plan.off), _p(dout), plan.n, heads, dh, C.c_float(1.0 / math.sqrt(dh)),
-                                            _p(dqkv), C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _s()), 'nnr_mhsa_bwd_paired')
+        L.check(L.lib().nnr_mhsa_bwd_paired(_p(qkv), _p(vmask), _p(vrow), _p(plan.off), _p(dout), plan.n, heads, dh, 1.0 / math.sqrt(dh), _p(dqkv), p,
+                                            seed, _s()), 'nnr_mhsa_bwd_paired')
 
 
 def mhsa_prob_size(n, Lq, heads):
@@ -1372,8 +1362,7 @@ def embed_gather(table, idx, p, seed, out=None, dyn=None):
 
 
 def _embed_gather(table, idx, p, seed, out, dyn, n, dim):
-    L.check(L.lib().nnr_embed_gather(_p(table), _p(idx), C.c_long(n), _p(dyn), dim, _p(out), C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _s()),
-            'nnr_embed_gather')
+    L.check(L.lib().nnr_embed_gather(_p(table), _p(idx), n, _p(dyn), dim, _p(out), p, seed, _s()), 'nnr_embed_gather')
     return out
 
 
@@ -1385,11 +1374,9 @@ def embed_scatter(dout, idx, dtable, p, seed, dyn=None):
 
 def _embed_scatter(dout, idx, dtable, p, seed, dyn, n, dim):
     if dyn is not None:
-        L.check(L.lib().nnr_embed_scatter_dyn(_p(dout), _p(idx), C.c_long(n), _p(dyn), dim, _p(dtable), C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF),
-                                              _s()), 'nnr_embed_scatter_dyn')
+        L.check(L.lib().nnr_embed_scatter_dyn(_p(dout), _p(idx), n, _p(dyn), dim, _p(dtable), p, seed, _s()), 'nnr_embed_scatter_dyn')
         return
-    L.check(L.lib().nnr_embed_scatter(_p(dout), _p(idx), C.c_long(n), dim, _p(dtable), C.c_float(p), C.c_uint32(seed & 0xFFFFFFFF), _s()),
-            'nnr_embed_scatter')
+    L.check(L.lib().nnr_embed_scatter(_p(dout), _p(idx), n, dim, _p(dtable), p, seed, _s()), 'nnr_embed_scatter')
 
 
 class TokenSort:
@@ -1402,14 +1389,14 @@ class TokenSort:
         i32 = dict(device=dev, dtype=torch.int32)
         buf = torch.empty(4 * cap, **i32)                        # keys_tmp | rows_tmp | keys_sorted | rows_sorted
         self.keys, self.rows = buf[2 * cap:3 * cap], buf[3 * cap:]
-        nb = int(L.lib().nnr_token_sort_workspace_bytes(C.c_long(cap), self.vocab))
+        nb = L.lib().nnr_token_sort_workspace_bytes(cap, self.vocab)
         temp = torch.empty(max(nb, 256), device=dev, dtype=torch.uint8)
-        self.partial = torch.empty(int(L.lib().nnr_embed_scatter_sorted_workspace_floats(C.c_long(cap))), device=dev, dtype=torch.float32)
+        self.partial = torch.empty(L.lib().nnr_embed_scatter_sorted_workspace_floats(cap), device=dev, dtype=torch.float32)
         leaf = leaf_stream(dev)
         leaf.wait_stream(torch.cuda.current_stream(dev))          # behind the planner that wrote `tok` / `total`
         with torch.cuda.stream(leaf):
-            L.check(L.lib().nnr_token_sort(_p(tok), C.c_long(cap), _p(total), self.vocab, _p(buf[:cap]), _p(buf[cap:2 * cap]), _p(self.keys), _p(self.rows),
-                                           _p(temp), C.c_size_t(temp.numel()), _s()), 'nnr_token_sort')
+            L.check(L.lib().nnr_token_sort(_p(tok), cap, _p(total), self.vocab, _p(buf[:cap]), _p(buf[cap:2 * cap]), _p(self.keys), _p(self.rows),
+                                           _p(temp), temp.numel(), _s()), 'nnr_token_sort')
             self.event = torch.cuda.Event()
             self.event.record()
         self._keep = (buf, temp)
@@ -1420,14 +1407,14 @@ def embed_scatter_sorted(dout, ts, dtable, p, seed):
     dim = dtable.shape[1]
     torch.cuda.current_stream(dout.device).wait_event(ts.event)
     with _hbm_span('embed_scatter', 2 * 4.0 * dim + 8.0, ts.cap, dyn=ts.total, tag='sorted cap%d' % ts.cap):
-        L.check(L.lib().nnr_embed_scatter_sorted(_p(dout), _p(ts.keys), _p(ts.rows), C.c_long(ts.cap), ts.vocab, dim, _p(dtable), C.c_float(p),
-                                                 C.c_uint32(seed & 0xFFFFFFFF), _p(ts.partial), _s()), 'nnr_embed_scatter_sorted')
+        L.check(L.lib().nnr_embed_scatter_sorted(_p(dout), _p(ts.keys), _p(ts.rows), ts.cap, ts.vocab, dim, _p(dtable), p, seed, _p(ts.partial),
+                                                 _s()), 'nnr_embed_scatter_sorted')
 
 
 def fill_zero(t):
     """t.zero_() as an entry point of the library (hipMemsetAsync on the current stream): part of the launch tape."""
     assert t.is_contiguous()
-    L.check(L.lib().nnr_fill_zero(_p(t), C.c_size_t(t.numel() * t.element_size()), _s()), 'nnr_fill_zero')
+    L.check(L.lib().nnr_fill_zero(_p(t), t.numel() * t.element_size(), _s()), 'nnr_fill_zero')
     return t
 
 
@@ -1435,7 +1422,7 @@ def copy_bytes(dst, src):
     """dst <- src (device to device, same byte size, both contiguous)."""
     nb = src.numel() * src.element_size()
     assert dst.is_contiguous() and src.is_contiguous() and dst.numel() * dst.element_size() == nb
-    L.check(L.lib().nnr_copy_bytes(_p(dst), _p(src), C.c_size_t(nb), _s()), 'nnr_copy_bytes')
+    L.check(L.lib().nnr_copy_bytes(_p(dst), _p(src), nb, _s()), 'nnr_copy_bytes')
     return dst
 
 
@@ -1443,8 +1430,8 @@ def fill_column_u8(mask, col, value):
     """mask[:, col] = value for a contiguous 2-D bool / uint8 tensor (userEncoders.py:73)."""
     assert mask.dim() == 2 and mask.is_contiguous() and mask.element_size() == 1
     rows, cols = mask.shape
-    L.check(L.lib().nnr_fill_column_u8(_p(mask), rows, cols, col % cols, int(value), _s()), 'nnr_fill_column_u8')
+    L.check(L.lib().nnr_fill_column_u8(_p(mask), rows, cols, col % cols, value, _s()), 'nnr_fill_column_u8')
 
 
 def transpose2d(x, out, rows, cols, accumulate=False):
-    L.check(L.lib().nnr_transpose2d(_p(x), _p(out), C.c_long(rows), cols, int(accumulate), _s()), 'nnr_transpose2d')
+    L.check(L.lib().nnr_transpose2d(_p(x), _p(out), rows, cols, accumulate, _s()), 'nnr_transpose2d')

@@ -7,8 +7,8 @@ runs captures
     wrapped for the duration of the recording;
   * every device buffer the step allocates (`torch.empty / zeros / empty_like / zeros_like` results are kept alive by the tape, so
     the recorded addresses stay valid and are never handed to anybody else);
-  * what changes from step to step: dropout seeds and Adam's step number (value patches, recognised by argument type and
-    value), pointers into the batch tensors (input patches, recognised by address range);
+  * what changes from step to step: dropout seeds and Adam's step number (value patches, recognised by the parameter's declared
+    kind in _lib.SIGNATURES and its value), pointers into the batch tensors (input patches, recognised by address range);
   * host callbacks (`host_call`): points where the host has work of its own (torch.distributed's all-reduce); they split the
     tape into segments and are re-run between the segments of a replay, under the HIP stream that was current when recorded.
 `Tape.replay(values, inputs)` then costs one C-ABI call per segment.  No CPU fallback: without the library nothing records."""
@@ -21,15 +21,10 @@ from . import _lib as L
 from . import profile as _prof
 
 MASK64 = (1 << 64) - 1
-# entry points that are host-side queries / set-up (no stream argument): passed through, never recorded
-_PASS = {'nnr_version', 'nnr_lstm_dims', 'nnr_lstm_sync_bytes', 'nnr_lstm_sync_diag_offset', 'nnr_lstm_set_timeout_counter',
-         'nnr_slot_workspace_floats', 'nnr_dp_unique_id', 'nnr_dp_init', 'nnr_dp_destroy', 'nnr_dp_emulate_ranks', 'nnr_adam_skipped_steps', 'nnr_adam_skipped_peek',
-         'nnr_token_sort_workspace_bytes', 'nnr_embed_scatter_sorted_workspace_floats'}
-_INT_TYPES = (C.c_int, C.c_long, C.c_size_t, C.c_uint32, C.c_ulong, C.c_int64, C.c_uint64)
 ACTIVE = [None]            # the tape that is recording right now
 VALUE_KINDS = {'news_seed': 0, 'user_seed': 1, 'adam_step': 2}
-_VALUE_ARGS = {('nnr_clip_adam', 13): 'adam_step'}            # (entry point, argument index) -> value kind, for plain integers
-_HANDLE_ARGS = {'nnr_dp_allreduce', 'nnr_dp_broadcast'}       # their FIRST pointer is an opaque host handle (the communicator), not device memory
+ADAM_STEP_ARG = ('nnr_clip_adam', 13)      # the one plain integer that changes from step to step: the parameter the header calls `step`
+_BLOB_KINDS = {c.__name__ for c in L.STRUCTS.values()} - L.DEVICE_STRUCTS      # host structs: copied into the tape
 
 
 NEWS_SEED_STRIDE = 104729      # NewsEncoder._next_seed: the per-call seed advances by this much (news_encoders.py)
@@ -67,8 +62,8 @@ class _Proxy:
         fn = self._cache.get(name)
         if fn is None:
             real = getattr(self._real, name)
-            if name in _PASS or name.startswith('nnr_tape_'):
-                fn = real
+            if name.startswith('nnr_tape_') or not L.SIGNATURES.get(name, '').endswith(' stream'):
+                fn = real          # the tape's own entry points and host-side queries / set-up (no stream argument): never recorded
             else:
                 tape = self._tape
 
@@ -128,14 +123,14 @@ class Tape:
             ev_record(ev, stream)
             if not tape._in_host_call:
                 tape.keep.append(ev)
-                L.check(tape.lib.nnr_tape_event_record(tape.h, C.c_uint64(id(ev)), C.c_void_p(stream.cuda_stream)), 'nnr_tape_event_record')
+                L.check(tape.lib.nnr_tape_event_record(tape.h, id(ev), stream.cuda_stream), 'nnr_tape_event_record')
 
         def wait(ev, stream=None):
             if stream is None:
                 stream = torch.cuda.current_stream()
             ev_wait(ev, stream)
             if not tape._in_host_call:
-                rc = tape.lib.nnr_tape_event_wait(tape.h, C.c_void_p(stream.cuda_stream), C.c_uint64(id(ev)))
+                rc = tape.lib.nnr_tape_event_wait(tape.h, stream.cuda_stream, id(ev))
                 if rc != 0:
                     # an event recorded before this step began (e.g. a cached W^T copy): complete by the time any replay starts, because
                     # every step ends with all of its streams joined into the stream the next one starts on
@@ -209,9 +204,9 @@ class Tape:
                 return True
         return False
 
-    def _check_ptr(self, name, where, ptr):
+    def _check_ptr(self, name, where, ptr, violations):
         if ptr and self._input_of(ptr) is None and not self._vouched(ptr):
-            self.violations.append((name, where, ptr))
+            violations.append((name, where, ptr))
 
     def _seed_kind(self, v):
         for name in ('news_seed', 'user_seed'):
@@ -222,47 +217,49 @@ class Tape:
                 return VALUE_KINDS[name], d      # the SECOND news-encoder call of the step (MHSA step: candidates, then history)
         raise TapeError('a uint32 argument (%d) that is not derived from this step\'s dropout seeds reached a recorded call' % v)
 
-    def _add_call(self, name, args):
-        fid, nargs = self._fn(name)
-        if len(args) != nargs + 1:
-            raise TapeError('%s: %d arguments recorded, the entry point takes %d + stream' % (name, len(args), nargs))
-        stream = args[-1]
-        slots = (C.c_uint64 * max(1, nargs))()
-        blobs = []                           # (slot, ctypes object, nbytes)
-        patches = []                         # ('slot' | blob index, byte offset inside, kind, width, addend)
-        for i, a in enumerate(args[:-1]):
-            if a is None:
-                v = 0
-            elif isinstance(a, int):
-                v = a & MASK64
-                kind = _VALUE_ARGS.get((name, i))
-                if kind is not None:
-                    patches.append(('slot', 8 * i, VALUE_KINDS[kind], 4, 0))
-            elif isinstance(a, C.c_void_p):
-                v = a.value or 0
-                hit = self._input_of(v) if v else None
-                if hit is not None:
-                    patches.append(('slot', 8 * i, 1000 + hit[0], 8, hit[1]))
-                elif v and not (i == 0 and name in _HANDLE_ARGS):
-                    self._check_ptr(name, i, v)
-            elif isinstance(a, C.c_float):
-                v = struct.unpack('<I', struct.pack('<f', a.value))[0]
-            elif isinstance(a, C.c_uint32):
-                v = a.value
+    def encode(self, name, args):
+        """What one call puts on the tape, by the DECLARED kind of each parameter (_lib.SIGNATURES): args (plain Python values, as the
+        binding takes them; the trailing stream included) -> (slot words, blobs [(slot, ctypes object, nbytes)], patches [('slot' | blob
+        index, byte offset inside, kind, width, addend)], violations).  Changes nothing on the tape."""
+        kinds = L.kinds(name)
+        if len(args) != len(kinds):
+            raise TapeError('%s: %d arguments recorded, the entry point takes %d + stream' % (name, len(args), len(kinds) - 1))
+        slots, blobs, patches, violations = [], [], [], []
+        for i, (kind, a) in enumerate(zip(kinds[:-1], args)):
+            if kind in _BLOB_KINDS:
+                obj = a._obj if hasattr(a, '_obj') else a          # C.byref(struct), or an array of structs
+                blobs.append((i, obj, C.sizeof(obj)))
+                self._blob_patches(obj, 0, len(blobs) - 1, patches, violations, name)
+                slots.append(0)
+                continue
+            v = getattr(a, 'value', a) or 0          # NULL is None; tests and tools may still pass ctypes scalars
+            if kind == 'f32':
+                v = struct.unpack('<I', struct.pack('<f', v))[0]
+            elif kind == 'seed':
+                v &= 0xFFFFFFFF                      # the one place a seed is masked: the eager call leaves that to c_uint32
                 if v:
                     k, d = self._seed_kind(v)
                     patches.append(('slot', 8 * i, k, 4, d))
-            elif isinstance(a, _INT_TYPES):
-                v = a.value & MASK64
-            elif isinstance(a, (C.Structure, C.Array)) or hasattr(a, '_obj'):
-                obj = a._obj if hasattr(a, '_obj') else a
-                v = 0
-                bi = len(blobs)
-                blobs.append((i, obj, C.sizeof(obj)))
-                self._blob_patches(obj, 0, bi, patches, name)
-            else:
-                raise TapeError('%s: argument %d of type %s cannot be recorded' % (name, i, type(a).__name__))
-            slots[i] = v
+            elif kind in ('i32', 'i64', 'u64'):
+                v &= MASK64
+                if (name, i) == ADAM_STEP_ARG:
+                    patches.append(('slot', 8 * i, VALUE_KINDS['adam_step'], 4, 0))
+            elif kind == 'ptr' or kind in L.DEVICE_STRUCTS:
+                hit = self._input_of(v) if v else None
+                if hit is not None:
+                    patches.append(('slot', 8 * i, 1000 + hit[0], 8, hit[1]))
+                else:
+                    self._check_ptr(name, i, v, violations)
+            elif kind != 'handle':                   # (an opaque host object: neither patched nor checked)
+                raise TapeError('%s: argument %d of kind %s cannot be recorded' % (name, i, kind))
+            slots.append(v)
+        return slots, blobs, patches, violations
+
+    def _add_call(self, name, args):
+        fid, nargs = self._fn(name)
+        words, blobs, patches, violations = self.encode(name, args)
+        self.violations += violations
+        slots = (C.c_uint64 * max(1, nargs))(*words)
         tag = -1
         if self._pending_tag is None and TAG_ALL[0]:
             self._pending_tag = (name[4:], _no_flops)          # diagnostics (tools/tape_timeline.py): every call carries timing events
@@ -276,20 +273,20 @@ class Tape:
         bbytes = (C.c_size_t * max(1, nb))(*[b[2] for b in blobs])
         slot_off = C.c_size_t()
         blob_off = (C.c_size_t * max(1, nb))()
-        rc = self.lib.nnr_tape_call(self.h, fid, stream, slots, nargs, bslot, bptr, bbytes, nb, tag, C.byref(slot_off), blob_off)
+        rc = self.lib.nnr_tape_call(self.h, fid, args[-1], slots, nargs, bslot, bptr, bbytes, nb, tag, C.byref(slot_off), blob_off)
         if rc < 0:
             raise TapeError('nnr_tape_call(%s) failed with %d' % (name, rc))
         for where, off, kind, width, addend in patches:
             base = slot_off.value if where == 'slot' else blob_off[where]
-            L.check(self.lib.nnr_tape_patch(self.h, C.c_size_t(base + off), kind, width, C.c_int64(addend)), 'nnr_tape_patch')
+            L.check(self.lib.nnr_tape_patch(self.h, base + off, kind, width, addend), 'nnr_tape_patch')
         self.calls += 1
 
-    def _blob_patches(self, obj, base, bi, patches, name=''):
+    def _blob_patches(self, obj, base, bi, patches, violations, name=''):
         if isinstance(obj, C.Array):
             step = C.sizeof(obj._type_)
             if issubclass(obj._type_, C.Structure):
                 for j in range(len(obj)):
-                    self._blob_patches(obj[j], base + j * step, bi, patches, name)
+                    self._blob_patches(obj[j], base + j * step, bi, patches, violations, name)
             return
         for fname, ftype in obj._fields_:
             off = base + getattr(type(obj), fname).offset
@@ -299,7 +296,7 @@ class Tape:
                 if hit is not None:
                     patches.append((bi, off, 1000 + hit[0], 8, hit[1]))
                 elif v:
-                    self._check_ptr(name, fname, v)
+                    self._check_ptr(name, fname, v, violations)
             elif ftype is C.c_uint32 and fname.endswith('seed'):
                 v = getattr(obj, fname)
                 if v and (not hasattr(obj, 'drop_target') or obj.drop_target):

@@ -346,7 +346,7 @@ class Trainer:
         import ctypes as C
         from . import _lib as L
         v = C.c_uint()
-        L.check(L.lib().nnr_adam_skipped_steps(C.byref(v), int(reset)), 'nnr_adam_skipped_steps')
+        L.check(L.lib().nnr_adam_skipped_steps(C.byref(v), reset), 'nnr_adam_skipped_steps')
         return int(v.value)
 
     def skipped_peek(self):

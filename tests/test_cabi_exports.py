@@ -16,35 +16,6 @@ def _declared():
     return sorted(set(re.findall(r'^\s*(?:int|size_t)\s+(nnr_\w+)\s*\(', src, flags=re.M)))
 
 
-def test_library_exports_every_declared_symbol():
-    from nnr_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    decl = _declared()
-    assert len(decl) >= 30
-    for name in decl:
-        assert hasattr(lib, name), 'symbol %s declared in include/nnr_hip.h but not exported' % name
-    assert sorted(_lib.SYMBOLS) == decl, 'nnr_amd/_lib.py:SYMBOLS must list exactly the header\'s entry points'
-    assert lib.nnr_version() >= 1
-
-
-def test_ctypes_structs_match_c_layout(tmp_path):
-    from nnr_amd import _lib
-    src = tmp_path / 'sz.cpp'
-    src.write_text('#include "%s"\n#include <stdio.h>\n#include <stddef.h>\nint main(){printf("%%zu %%zu %%zu %%zu %%zu %%zu %%zu %%zu %%zu\\n",'
-                   'sizeof(nnr_gemm_args),sizeof(nnr_lstm_problem),sizeof(nnr_pool_args),offsetof(nnr_gemm_args,tile),'
-                   'offsetof(nnr_pool_args,lddv),sizeof(nnr_corpus_tables),sizeof(nnr_batch_out),offsetof(nnr_corpus_tables,K1),'
-                   'offsetof(nnr_lstm_problem,sync));}\n' % HEADER)
-    exe = tmp_path / 'sz'
-    subprocess.check_call(['hipcc', '-o', str(exe), str(src)], stderr=subprocess.DEVNULL)
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    want = [ctypes.sizeof(_lib.GemmArgs), ctypes.sizeof(_lib.LstmProblem), ctypes.sizeof(_lib.PoolArgs), _lib.GemmArgs.tile.offset,
-            _lib.PoolArgs.lddv.offset, ctypes.sizeof(_lib.CorpusTables), ctypes.sizeof(_lib.BatchOut), _lib.CorpusTables.K1.offset,
-            _lib.LstmProblem.sync.offset]
-    assert got == want
-
-
 def _params(name):
     """Parameter list of an entry point as declared in the header (comments stripped)."""
     src = re.sub(r'/\*.*?\*/', ' ', open(HEADER).read(), flags=re.S)
@@ -52,6 +23,73 @@ def _params(name):
     assert m, name
     body = ' '.join(m.group(1).split())
     return [] if body in ('', 'void') else [q.strip() for q in body.split(',')]
+
+
+def _kind(param):
+    """Kind (nnr_amd/_lib.py:SIGNATURES) that a parameter's C declaration maps to."""
+    from nnr_amd import _lib
+    if param.startswith('hipStream_t'):
+        return 'stream'
+    if '*' in param:
+        base = param[:param.index('*')].replace('const', '').strip()
+        if base in ('nnr_tape', 'nnr_dp_ctx'):
+            return 'handle'
+        if base == 'char':
+            return 'cstr'
+        return _lib.STRUCTS[base].__name__ if base in _lib.STRUCTS else 'ptr'
+    ctype = param.rsplit(None, 1)[0].replace('const', '').strip()
+    return {'int': 'i32', 'long': 'i64', 'int64_t': 'i64', 'size_t': 'u64', 'uint64_t': 'u64', 'float': 'f32', 'uint32_t': 'seed'}[ctype]
+
+
+def test_library_exports_every_declared_symbol():
+    """The .so exports every entry point of the header, and _lib.SIGNATURES -- from which the binding's argtypes / restype and the
+    tape's encoding derive -- states exactly the header's entry points, each with the header's return type and parameter types."""
+    from nnr_amd import _lib, tape
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    decl = _declared()
+    assert len(decl) >= 30
+    for name in decl:
+        assert hasattr(lib, name), 'symbol %s declared in include/nnr_hip.h but not exported' % name
+    assert sorted(_lib.SIGNATURES) == decl, 'nnr_amd/_lib.py:SIGNATURES must list exactly the header\'s entry points'
+    assert _lib.SYMBOLS == list(_lib.SIGNATURES)
+    src = open(HEADER).read()
+    for name in decl:
+        ret = re.search(r'^\s*(int|size_t)\s+%s\s*\(' % name, src, flags=re.M).group(1)
+        assert _lib.SIGNATURES[name].split() == [{'int': 'i32', 'size_t': 'u64'}[ret]] + [_kind(q) for q in _params(name)], name
+    name, index = tape.ADAM_STEP_ARG
+    assert _params(name)[index].split()[-1] == 'step' and _lib.kinds(name)[index] == 'i32'
+    bound = _lib.lib()
+    for name in decl:
+        assert len(getattr(bound, name).argtypes) == len(_params(name)), name
+    assert bound.nnr_lstm_sync_bytes.restype is ctypes.c_size_t and bound.nnr_version.restype is ctypes.c_int
+    assert lib.nnr_version() >= 1
+
+
+def _c_fields(cls):
+    return [('in' if f == 'inp' else f) for f, _ in cls._fields_]
+
+
+def test_ctypes_structs_match_c_layout(tmp_path):
+    """sizeof and every field's offsetof of every mirrored struct, against a C program generated from the mirrors' _fields_ (Python's
+    `inp` is C's `in`)."""
+    from nnr_amd import _lib
+    exprs, want = [], []
+    for cname, cls in sorted(_lib.STRUCTS.items()):
+        exprs.append('sizeof(%s)' % cname)
+        want.append(ctypes.sizeof(cls))
+        for (pyname, _), cfield in zip(cls._fields_, _c_fields(cls)):
+            exprs.append('offsetof(%s,%s)' % (cname, cfield))
+            want.append(getattr(cls, pyname).offset)
+    assert len(_lib.STRUCTS) == 6 and len(want) > 150
+    src = tmp_path / 'sz.cpp'
+    src.write_text('#include "%s"\n#include <stdio.h>\n#include <stddef.h>\nint main(){size_t v[]={%s};'
+                   'for(size_t i=0;i<sizeof(v)/sizeof(v[0]);i++)printf("%%zu\\n",v[i]);}\n' % (HEADER, ','.join(exprs)))
+    exe = tmp_path / 'sz'
+    subprocess.check_call(['hipcc', '-o', str(exe), str(src)], stderr=subprocess.DEVNULL)
+    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    assert got == want, [e for e, g, w in zip(exprs, got, want) if g != w]
 
 
 def test_tape_registry_matches_the_header():

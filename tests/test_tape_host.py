@@ -16,9 +16,7 @@ ERR_ARG = -1
 
 
 def _lib():
-    lib = L.lib()
-    lib.nnr_tape_patch.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int64]
-    return lib
+    return L.lib()
 
 
 def _call(lib, h, name, slots, stream=0, blobs=(), tag=-1):
@@ -216,3 +214,58 @@ def test_rejected_call_leaves_the_tape_untouched():
     assert _call(lib, h, 'nnr_gemm_f32', [0], blobs=[(0, g)])[0] == 0
     assert lib.nnr_tape_finalize(h) == 0 and _replay(lib, h, 0) == 0
     assert lib.nnr_tape_destroy(h) == 0
+
+
+def test_binding_passes_declared_widths_and_refuses_other_types():
+    """The binding's argtypes come from _lib.SIGNATURES.  Width: nnr_fill_zero refuses NULL with a non-zero size before any HIP call, so
+    NULL with bytes = 2^32 returns NNR_ERR_ARG only if all 64 bits of the size_t arrive (an int without argtypes is cut to a C int: 0 bytes,
+    NNR_OK).  Type: ctypes refuses a float for an int and a c_int for a long before the library is entered."""
+    lib = L.lib()
+    assert lib.nnr_fill_zero(None, 1 << 32, None) == ERR_ARG
+    assert L.kinds('nnr_add2d')[1] == 'i32' and L.kinds('nnr_add')[2] == 'i64'
+    with pytest.raises(C.ArgumentError):
+        lib.nnr_add2d(None, 1.5, None, 1, 1, 1, 1.0, 0, None)                      # a Python float for an i32 parameter
+    with pytest.raises(C.ArgumentError):
+        lib.nnr_add(None, None, C.c_int(4), 1.0, None)                             # a c_int instance for an i64 parameter
+
+
+def test_encoder_walks_the_declared_kinds():
+    """Tape.encode on plain Python arguments, nothing recorded or replayed: (slot words, blobs, patches, violations) follow the kind
+    _lib.SIGNATURES declares for each parameter, not the Python type the caller happened to pass."""
+    from nnr_amd import tape as T
+    batch, flat = torch.zeros(64), torch.zeros(64)
+    news, user = 1000, 5000
+    t = T.Tape([batch], {'news_seed': news, 'user_seed': user}, known=[flat])
+    uk, inp = T.VALUE_KINDS['user_seed'], batch.data_ptr()
+    # nnr_dropout(x ptr, y ptr, n i64, p f32, seed, stream): an i64 beyond 32 bits, float bits, a seed patch, an input patch with its offset
+    slots, blobs, patches, violations = t.encode('nnr_dropout', (inp + 24, flat.data_ptr(), (1 << 33) + 5, 0.5, user + 3, None))
+    assert slots == [inp + 24, flat.data_ptr(), (1 << 33) + 5, 0x3f000000, user + 3] and blobs == [] and violations == []
+    assert sorted(patches) == [('slot', 0, 1000, 8, 24), ('slot', 32, uk, 4, 3)]
+    # an unmasked seed is the same seed; seed 0 (no dropout) is a constant
+    assert t.encode('nnr_dropout', (inp + 24, flat.data_ptr(), (1 << 33) + 5, 0.5, (1 << 32) + user + 3, None)) == (slots, blobs, patches, violations)
+    slots0, _, patches0, _ = t.encode('nnr_dropout', (None, None, 7, 0, 0, None))
+    assert slots0 == [0, 0, 7, 0, 0] and patches0 == []
+    # a pointer nothing vouches for; one past the end of an input is not inside it
+    _, _, patches, violations = t.encode('nnr_fill_zero', (0x7f0000002000, 0, None))
+    assert patches == [] and violations == [('nnr_fill_zero', 0, 0x7f0000002000)]
+    assert t.encode('nnr_fill_zero', (inp + 4 * batch.numel(), 0, None))[3] == [('nnr_fill_zero', 0, inp + 4 * batch.numel())]
+    # a handle (the communicator of nnr_dp_allreduce) is a host object: neither patched nor checked, wherever it points
+    for handle in (0x7f0000003000, inp):
+        slots, _, patches, violations = t.encode('nnr_dp_allreduce', (handle, flat.data_ptr(), 64, None))
+        assert slots == [handle, flat.data_ptr(), 64] and patches == [] and violations == []
+    # Adam's step number is the one plain integer that is patched; negative ints keep their 64-bit two's complement
+    slots, _, patches, _ = t.encode('nnr_clip_adam', (None,) * 4 + (64, None) + (1.0,) * 7 + (17, None))
+    assert slots[13] == 17 and patches == [('slot', 8 * 13, T.VALUE_KINDS['adam_step'], 4, 0)]
+    assert t.encode('nnr_fill_column_u8', (None, 1, 1, -1, 1, None))[0][3] == (1 << 64) - 1
+    # a struct kind is copied as a blob and its fields are patched / checked as before
+    g = L.GemmArgs()
+    g.A, g.B, g.C, g.drop_target, g.drop_seed = inp + 8, flat.data_ptr(), 0x7f0000001000, 3, news + 1
+    slots, blobs, patches, violations = t.encode('nnr_gemm_f32', (C.byref(g), None))
+    assert slots == [0] and blobs == [(0, g, C.sizeof(g))] and violations == [('nnr_gemm_f32', 'C', 0x7f0000001000)]
+    assert sorted(patches) == [(0, L.GemmArgs.A.offset, 1000, 8, 8), (0, L.GemmArgs.drop_seed.offset, T.VALUE_KINDS['news_seed'], 4, 1)]
+    with pytest.raises(T.TapeError, match='arguments'):
+        t.encode('nnr_fill_zero', (None, 0))                                       # the stream is missing
+    with pytest.raises(T.TapeError, match='dropout seeds'):
+        t.encode('nnr_dropout', (None, None, 7, 0.5, 99999, None))
+    assert t.violations == [] and t.info()['calls'] == 0                           # encode() left the tape alone
+    t.close()
