@@ -233,6 +233,14 @@ int nnr_small_embed_fwd(const float* table, const int* idx, int n, int dim, floa
                         hipStream_t stream);                                     /* newsEncoders.py:51-53 */
 int nnr_small_embed_bwd(const int* idx, int n, int dim, const float* dout, int lddo, float* dtable_accum, float p, uint32_t seed,
                         hipStream_t stream);
+/* The user-id embedding table of the personalised encoders (model.py:122-125): out[b,:] = dropout(table[ids[b],:]), mask keyed by the
+ * output element b*dim + c; dtable[u,:] += sum over b with ids[b] == u, in ascending b, of mask * dout[b,:] (one writer per row: no float
+ * atomics, same inputs same bits).  table / dtable [rows, dim], ids int64 [B].  An id outside [0, rows) yields a zero row and contributes no
+ * gradient; nothing outside the rows x dim table is read or written. */
+int nnr_user_rows_fwd(const float* table, int rows, const int64_t* ids, int B, int dim, float* out, float p, uint32_t seed,
+                      hipStream_t stream);
+int nnr_user_rows_bwd(const float* dout, const int64_t* ids, int B, int rows, int dim, float* dtable_accum, float p, uint32_t seed,
+                      hipStream_t stream);
 /* nn.Embedding forward / backward for a dense id tensor (newsEncoders.py:117-118, 163, 193) with the in-place dropout fused:
  * out[row,:] = dropout(table[idx[row],:]) (negative idx: zero row); dtable[idx[row],:] += mask * dout[row,:] (f32 atomics). */
 int nnr_embed_gather(const float* table, const int* idx, long n, const int* n_dev /* optional live row count */, int dim, float* out,
@@ -344,6 +352,22 @@ int nnr_cand_attn_fwd(const float* P, const float* Q, const float* w2, const flo
 int nnr_cand_attn_bwd(const float* P, const float* Q, const float* w2, const float* feat, int ldf, const uint8_t* mask, const float* alpha,
                       const float* dout, int B, int N, int H, int A, int D, int act, float* dP, float* dQ, float* dfeat,
                       int dfeat_accumulate, float* ws, float* dw2_accum, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------ per-title personalised attention
+ * PNE's word-level attention (newsEncoders.py:359-360), csrc/pers_attn.hip: layers.CandidateAttention with the query taken through an
+ * index map.  a[i,t] = w2 . tanh(Qf[i,t,:] + P[uidx[i],:]);  alpha[i,:] = softmax_t(mask[i,t] ? a : -1e9) (no live position: 1/L over all
+ * L);  out[i,:] = sum_t alpha[i,t] feat[i,t,:].  Qf [n*L, A] = feature projection, P [U, A] = query projection + bias, uidx int32 [n]
+ * (an entry outside [0, U): P = 0 for that title, and it joins no dP row), w2 [A], feat [n, L, F] with row stride ldf, mask uint8 [n, L]
+ * or NULL, alpha [n, L], out / dout [n, F]; all fp32.  Backward: dP [U, A] (a user without titles: a zero row), dQf [n*L, A] (zero rows
+ * where masked) and dfeat [n, L, F] are written, dw2 [A] is ADDED into; ws: nnr_pers_attn_ws_floats(n, L, A) floats of scratch owned by
+ * the calling stream.  Same inputs, same bits.  NNR_ERR_UNSUPPORTED when L > 64 or A > 1024 (A > 256 on the scalar-lane path, taken
+ * when A, F or ldf is no multiple of 4 or a base pointer is not 16-byte aligned). */
+int nnr_pers_attn_ws_floats(int n, int L, int A);
+int nnr_pers_attn_fwd(const float* Qf, const float* P, const int* uidx, int U, const float* w2, const float* feat, int ldf,
+                      const uint8_t* mask, int n, int L, int A, int F, float* alpha, float* out, hipStream_t stream);
+int nnr_pers_attn_bwd(const float* Qf, const float* P, const int* uidx, int U, const float* w2, const float* feat, int ldf,
+                      const uint8_t* mask, const float* alpha, const float* dout, int n, int L, int A, int F, float* dP, float* dQf,
+                      float* dfeat, float* ws, float* dw2_accum, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------ OMAP (Hi-Fi Ark) user encoder
  * userEncoders.py:357-374, csrc/omap.hip.  hist [B, H, D] with row stride ldf (X), cand [B, N, D] (C), mask uint8 [B, H] or NULL (no

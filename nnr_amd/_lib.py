@@ -84,6 +84,8 @@ SIGNATURES = {
     'nnr_rowdot': 'i32 ptr i32 ptr ptr i32 i32 ptr stream',
     'nnr_small_embed_fwd': 'i32 ptr ptr i32 i32 ptr i32 f32 seed stream',
     'nnr_small_embed_bwd': 'i32 ptr i32 i32 ptr i32 ptr f32 seed stream',
+    'nnr_user_rows_fwd': 'i32 ptr i32 ptr i32 i32 ptr f32 seed stream',
+    'nnr_user_rows_bwd': 'i32 ptr ptr i32 i32 i32 ptr f32 seed stream',
     'nnr_embed_gather': 'i32 ptr ptr i64 ptr i32 ptr f32 seed stream',
     'nnr_embed_scatter': 'i32 ptr ptr i64 i32 ptr f32 seed stream',
     'nnr_embed_scatter_dyn': 'i32 ptr ptr i64 ptr i32 ptr f32 seed stream',
@@ -119,6 +121,9 @@ SIGNATURES = {
     'nnr_cand_attn_ws_floats': 'i32 i32 i32 i32 i32',
     'nnr_cand_attn_fwd': 'i32 ptr ptr ptr ptr i32 ptr i32 i32 i32 i32 i32 i32 ptr ptr stream',
     'nnr_cand_attn_bwd': 'i32 ptr ptr ptr ptr i32 ptr ptr ptr i32 i32 i32 i32 i32 i32 ptr ptr ptr i32 ptr ptr stream',
+    'nnr_pers_attn_ws_floats': 'i32 i32 i32 i32',
+    'nnr_pers_attn_fwd': 'i32 ptr ptr ptr i32 ptr ptr i32 ptr i32 i32 i32 i32 ptr ptr stream',
+    'nnr_pers_attn_bwd': 'i32 ptr ptr ptr i32 ptr ptr i32 ptr ptr ptr i32 i32 i32 i32 ptr ptr ptr ptr ptr stream',
     'nnr_omap_ws_floats': 'i32 i32 i32 i32 i32 i32',
     'nnr_omap_fwd': 'i32 ptr i32 ptr ptr ptr i32 i32 i32 i32 i32 ptr ptr ptr ptr ptr ptr ptr stream',
     'nnr_omap_bwd': 'i32 ptr i32 ptr ptr ptr ptr ptr ptr ptr ptr ptr i32 i32 i32 i32 i32 ptr i32 ptr ptr ptr stream',

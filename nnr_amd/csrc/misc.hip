@@ -216,6 +216,38 @@ __global__ __launch_bounds__(256) void small_embed_bwd_kernel(const int* __restr
   }
 }
 
+// ---- the user-id embedding table of the personalised encoders (model.py:122: dropout(user_embedding(user_ID))): out[b, :] = drop(table[ids[b]]),
+// mask keyed by the output element b * dim + c.  An id outside [0, rows) reads as a zero row: nothing outside the table is touched.
+__global__ void user_rows_fwd_kernel(const float* __restrict__ table, int rows, const int64_t* __restrict__ ids, int B, int dim,
+                                     float* __restrict__ out, uint32_t seed, uint32_t thr, float scale) {
+  const long total = (long)B * dim;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int b = i / dim, c = i - (long)b * dim;
+    const int64_t id = ids[b];
+    const bool ok = id >= 0 && id < rows && nnr_keep(seed, (uint64_t)i, thr);
+    out[i] = ok ? table[id * dim + c] * scale : 0.f;
+  }
+}
+// backward: dtable[u, c] += sum over b with ids[b] == u, in ascending b, of mask * dout[b, c].  The thread of the FIRST occurrence of an id
+// owns that id's row (B is a batch size: the quadratic scan is a few thousand compares), so every destination has one writer: no float
+// atomics, the same inputs give the same bits.  An id outside [0, rows) contributes nothing.
+__global__ void user_rows_bwd_kernel(const float* __restrict__ dout, const int64_t* __restrict__ ids, int B, int rows, int dim,
+                                     float* __restrict__ dtable, uint32_t seed, uint32_t thr, float scale) {
+  const long total = (long)B * dim;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int b = i / dim, c = i - (long)b * dim;
+    const int64_t id = ids[b];
+    if (id < 0 || id >= rows) continue;
+    bool first = true;
+    for (int j = 0; j < b; ++j) first = first && ids[j] != id;
+    if (!first) continue;
+    float acc = 0.f;
+    for (int j = b; j < B; ++j)
+      if (ids[j] == id && nnr_keep(seed, (uint64_t)((long)j * dim + c), thr)) acc += dout[(long)j * dim + c] * scale;
+    dtable[id * dim + c] += acc;
+  }
+}
+
 // ---- embedding-row gather (nn.Embedding forward, newsEncoders.py:117-118,163,193) with fused dropout.
 // One wave per row: the index is wave-uniform, the row is read as contiguous 16-byte lanes (a 300-float row = 75 float4 =
 // two fully coalesced 1 KiB / 176 B wave accesses).  Pure HBM/L2 streaming: out bytes written once, table rows read once.
@@ -1017,6 +1049,19 @@ extern "C" int nnr_small_embed_bwd(const int* idx, int n, int dim, const float* 
   return NNR_OK;
 }
 
+
+extern "C" int nnr_user_rows_fwd(const float* table, int rows, const int64_t* ids, int B, int dim, float* out, float p, uint32_t seed,
+                                 hipStream_t stream) {
+  if (!table || !ids || !out || rows < 1 || B < 1 || dim < 1) return NNR_ERR_ARG;
+  const float sc = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  EW_LAUNCH(user_rows_fwd_kernel, (long)B * dim, table, rows, ids, B, dim, out, seed, nnr_drop_thresh(p), sc);
+}
+extern "C" int nnr_user_rows_bwd(const float* dout, const int64_t* ids, int B, int rows, int dim, float* dtable, float p, uint32_t seed,
+                                 hipStream_t stream) {
+  if (!dout || !ids || !dtable || rows < 1 || B < 1 || dim < 1) return NNR_ERR_ARG;
+  const float sc = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  EW_LAUNCH(user_rows_bwd_kernel, (long)B * dim, dout, ids, B, rows, dim, dtable, seed, nnr_drop_thresh(p), sc);
+}
 
 extern "C" int nnr_embed_gather(const float* table, const int* idx, long n, const int* n_dev, int dim, float* out, float p, uint32_t seed,
                                 hipStream_t stream) {

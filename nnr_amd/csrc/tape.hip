@@ -52,6 +52,7 @@ const Entry REGISTRY[] = {
   R(nnr_rows_touch), R(nnr_rows_compact), R(nnr_rows_pack), R(nnr_rows_unpack),
   R(nnr_cand_attn_fwd), R(nnr_cand_attn_bwd),
   R(nnr_omap_fwd), R(nnr_omap_bwd), R(nnr_omap_reg_fwd), R(nnr_omap_reg_bwd),
+  R(nnr_user_rows_fwd), R(nnr_user_rows_bwd), R(nnr_pers_attn_fwd), R(nnr_pers_attn_bwd),
 };
 #undef R
 constexpr int NREG = (int)(sizeof(REGISTRY) / sizeof(REGISTRY[0]));

@@ -69,7 +69,10 @@ def compute_scores_cached(model, corpus, batch_size):
         if need_graph:
             from .corpus import history_graph
             graph, cmask, cidx = history_graph(t['news_category'][hist[idx]].contiguous(), hmask.contiguous(), corpus.category_num, corpus.norm_name)
-        user = ue.encode_user(h, hmask, graph, cmask, cidx, c)
+        if getattr(ue, 'needs_user_embedding', False):           # (eval mode: the user rows without dropout)
+            user = ue.encode_user(h, hmask, graph, cmask, cidx, c, model.user_rows(t['beh_user'][idx].long()))
+        else:
+            user = ue.encode_user(h, hmask, graph, cmask, cidx, c)
         scores[start:start + idx.numel()] = _DotProductFn.apply(user, c).squeeze(dim=1)
     model.train(was_training)
     LAST_STATS.update(mode='cached', encoder_rows=int(used.numel()), per_sample_rows=int(corpus.num * (hist.shape[1] + 1)))

@@ -27,6 +27,24 @@ class EmbedDropFn(torch.autograd.Function):
         return None, None, None, None
 
 
+class UserRowsFn(torch.autograd.Function):
+    """dropout(user_embedding(user_ID))  (model.py:122) for int64 ids [B]: the id is checked against the table size, and the backward sums
+    duplicate ids in batch order without float atomics (csrc/misc.hip user_rows_*), so the table gradient is the same bits every run."""
+
+    @staticmethod
+    def forward(ctx, table, ids, p, seed):
+        idx = ids.reshape(-1)
+        idx = (idx if idx.dtype == torch.int64 else idx.to(torch.int64)).contiguous()
+        out = ops.user_rows_fwd(table, idx, p, seed)
+        ctx.table, ctx.idx, ctx.p, ctx.seed = table, idx, p, seed
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        ops.user_rows_bwd(dout.contiguous(), ctx.idx, grad_of(ctx.table), ctx.p, ctx.seed)
+        return None, None, None, None
+
+
 # ---------------------------------------------------------------------------------------------- MHSA news encoder over PACKED token rows
 # (round 5)  The reference's MHSA news encoder multiplies all n * L padded positions through W_Q / W_K / W_V and the additive attention's
 # affine1 (newsEncoders.py:187-200, layers.py:134-136,168); ~64 % of those rows are padding whose keys are masked (-1e9) and whose pooled

@@ -209,6 +209,68 @@ class _CandAttnFn(torch.autograd.Function):
         return dx, dq.view(B, N, Qd), None, None
 
 
+class _PersAttnUnsupported(Exception):
+    pass
+
+
+class _PersAttnFn(torch.autograd.Function):
+    """layers.CandidateAttention with the query taken through an index map: feature [n, L, F], query [U, Qd], uidx int32 [n] (title i attends
+    with query uidx[i]), mask [n, L] or None -> [n, F], on csrc/pers_attn.hip.  The query projection and its gradient exist for U rows, not n;
+    the [n, L, A] hidden tensor is never stored (the backward pass recomputes the activations).  `mod` supplies weights and gradient buffers
+    as for _CandAttnFn (tanh only).  Raises _PersAttnUnsupported, before anything is computed, for a shape the kernel does not take:
+    personalized_attention() then runs _CandAttnFn on the expanded query rows."""
+
+    @staticmethod
+    def forward(ctx, feature, query, uidx, mod, mask):
+        n, Lx, F = feature.shape
+        U, Qd = query.shape
+        wq, bq, wf, w2, act = mod._cand_attn_weights()
+        assert act == ops.ACT_TANH
+        A = w2.numel()
+        x = feature.contiguous()
+        q = query.contiguous()
+        uidx = (uidx if uidx.dtype == torch.int32 else uidx.to(torch.int32)).contiguous()
+        if mask is not None:
+            mask = (mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0).contiguous()
+        f32 = dict(device=x.device, dtype=torch.float32)
+        P = ops.linear_fwd(q, wq, bq)                                                           # [U, A]
+        Qf = ops.linear_fwd(x.view(n * Lx, F), wf)                                              # [n*L, A]
+        alpha = torch.empty((n, Lx), **f32)
+        out = torch.empty((n, F), **f32)
+        if ops.pers_attn_fwd(Qf, P, uidx, w2, x, mask, n, Lx, A, F, alpha, out) != 0:
+            raise _PersAttnUnsupported()
+        ctx.mod, ctx.saved = mod, (x, q, uidx, P, Qf, alpha, mask, (n, Lx, A, F, U, Qd))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        mod = ctx.mod
+        x, q, uidx, P, Qf, alpha, mask, (n, Lx, A, F, U, Qd) = ctx.saved
+        ctx.saved = None
+        wq, _, wf, w2, _ = mod._cand_attn_weights()
+        gwq, gbq, gwf, gw2 = mod._cand_attn_grads()
+        f32 = dict(device=x.device, dtype=torch.float32)
+        dP = torch.empty((U, A), **f32)
+        dQf = torch.empty((n * Lx, A), **f32)
+        dx = torch.empty((n, Lx, F), **f32)
+        ops.pers_attn_bwd(Qf, P, uidx, w2, x, mask, alpha, dout.contiguous(), n, Lx, A, F, dP, dQf, dx, gw2)
+        ops.linear_bwd_data(dQf, wf, out=dx.view(n * Lx, F), accumulate=True)                   # the feature's share through Wf
+        dq = ops.linear_bwd_data(dP, wq)
+        ops.linear_bwd_weight(dP, q, gwq)
+        ops.bias_grad(dP, gbq)
+        ops.leaf_deferred(x.device, n * Lx, lambda: ops.linear_bwd_weight(dQf, x.view(n * Lx, F), gwf), dQf, x)
+        return dx, dq, None, None, None
+
+
+def personalized_attention(mod, feature, query, uidx, mask=None):
+    """`mod` (a CandidateAttention) over feature [n, L, F] with title i's query = query[uidx[i]] (query [U, Qd], every uidx in [0, U)):
+    the per-title kernel, or -- for a shape it returns NNR_ERR_UNSUPPORTED for -- the candidate-attention kernels on the expanded rows."""
+    try:
+        return _PersAttnFn.apply(feature, query, uidx, mod, mask)
+    except _PersAttnUnsupported:
+        return _CandAttnFn.apply(feature, query.index_select(0, uidx.long()).unsqueeze(dim=1), mod, mask).squeeze(dim=1)
+
+
 class CandidateAttention(nn.Module):
     """layers.py:206-232: additive attention over `feature` with ONE query per sample (tanh)."""
 

@@ -82,8 +82,10 @@ class Model(nn.Module):
             self.news_encoder = newsEncoders.CNN(config, word_table)
         elif config.news_encoder == 'MHSA':
             self.news_encoder = newsEncoders.MHSA(config, word_table)
+        elif config.news_encoder == 'PNE':
+            self.news_encoder = newsEncoders.PNE(config, word_table)
         else:
-            raise Exception(config.news_encoder + ' is not on the MI355X hot path (in scope: CNE, CNN, MHSA; SURVEY.md section 8a)')
+            raise Exception(config.news_encoder + ' is not on the MI355X hot path (in scope: CNE, CNN, MHSA, PNE; SURVEY.md section 8a)')
         if config.user_encoder == 'SUE':
             self.user_encoder = userEncoders.SUE(self.news_encoder, config)
         elif config.user_encoder == 'MHSA':
@@ -94,13 +96,22 @@ class Model(nn.Module):
             self.user_encoder = userEncoders.CATT(self.news_encoder, config)
         elif config.user_encoder == 'OMAP':
             self.user_encoder = userEncoders.OMAP(self.news_encoder, config)
+        elif config.user_encoder == 'PUE':
+            self.user_encoder = userEncoders.PUE(self.news_encoder, config)
         else:
-            raise Exception(config.user_encoder + ' is not on the MI355X hot path (in scope: SUE, MHSA, ATT, CATT, OMAP; SURVEY.md section 8a)')
+            raise Exception(config.user_encoder + ' is not on the MI355X hot path (in scope: SUE, MHSA, ATT, CATT, OMAP, PUE; SURVEY.md section 8a)')
         self.model_name = config.news_encoder + '-' + config.user_encoder
         self.news_embedding_dim = self.news_encoder.news_embedding_dim
-        self.dropout = nn.Dropout(p=config.dropout_rate)                    # (model.py:77: part of the attribute surface; only the
-                                                                              #  out-of-scope mlp / FIM click predictors call it)
-        self.use_user_embedding = False
+        self.dropout = nn.Dropout(p=config.dropout_rate)                    # (model.py:77: part of the attribute surface; the user rows'
+                                                                              #  dropout is fused into their gather, see forward)
+        self.dropout_rate = float(config.dropout_rate)
+        # model.py:79-85: the personalised encoders (NPA) read a trainable table indexed by the batch's user_ID.  No padding_idx: row 0
+        # receives gradient like any other row.
+        self.use_user_embedding = config.news_encoder == 'PNE' or config.user_encoder == 'PUE'
+        if self.use_user_embedding:
+            self.user_embedding = nn.Embedding(num_embeddings=config.user_num, embedding_dim=config.user_embedding_dim)
+            self._user_seed_base = int(getattr(config, 'seed', 0)) * 6151 + 43
+            self._user_calls = 0
         if config.click_predictor != 'dot_product':
             raise Exception('click_predictor=%s is out of scope (dot_product only, model.py:126-127)' % config.click_predictor)
         self.click_predictor = config.click_predictor
@@ -108,12 +119,31 @@ class Model(nn.Module):
     def initialize(self):
         self.news_encoder.initialize()
         self.user_encoder.initialize()
+        if self.use_user_embedding:                                         # model.py:110-112
+            nn.init.uniform_(self.user_embedding.weight, -0.1, 0.1)
+            with torch.no_grad():
+                self.user_embedding.weight[0].zero_()
+
+    def user_rows(self, user_ID):
+        """dropout(user_embedding(user_ID)) (model.py:122), computed once per forward and handed to both news-encoder calls and to the user
+        encoder; None for the encoder pairs that do not read the table."""
+        if not self.use_user_embedding:
+            return None
+        from .functional import UserRowsFn
+        self._user_calls += 1
+        seed = (self._user_seed_base + 7368787 * self._user_calls) & 0x7FFFFFFF
+        return UserRowsFn.apply(self.user_embedding.weight, user_ID, self.dropout_rate if self.training else 0.0, seed)
+
+    def _encode_user(self, user_embedding, *args):
+        if getattr(self.user_encoder, 'needs_user_embedding', False):
+            return self.user_encoder.encode_user(*args, user_embedding)
+        return self.user_encoder.encode_user(*args)
 
     def forward(self, user_ID, user_category, user_subCategory, user_title_text, user_title_mask, user_title_entity, user_content_text,
                 user_content_mask, user_content_entity, user_history_mask, user_history_graph, user_history_category_mask,
                 user_history_category_indices, news_category, news_subCategory, news_title_text, news_title_mask, news_title_entity,
                 news_content_text, news_content_mask, news_content_entity):
-        user_embedding = None
+        user_embedding = self.user_rows(user_ID)
         if self.training and torch.is_grad_enabled() and news_title_text.is_cuda:
             ops.wt_prefetch(news_title_text.device)      # W^T copies the backward pass will want, off the critical chain
         ne = self.news_encoder
@@ -127,18 +157,16 @@ class Model(nn.Module):
             st = ne.__dict__.setdefault('_dedup_stats', [0, 0])
             st[0] += rows
             st[1] += user_title_text.shape[0] * user_title_text.shape[1]
-            user_representation = self.user_encoder.encode_user(history_embedding, user_history_mask, user_history_graph,
-                                                                user_history_category_mask, user_history_category_indices,
-                                                                news_representation)
+            user_representation = self._encode_user(user_embedding, history_embedding, user_history_mask, user_history_graph,
+                                                    user_history_category_mask, user_history_category_indices, news_representation)
         elif hasattr(self.news_encoder, 'forward_pair'):
             # same arithmetic as the two encoder calls of model.py:123-125, issued in lock-step so that launch-latency-bound
             # stages (the Bi-LSTM recurrences) of the candidate call and of the history call share one launch
             news_representation, history_embedding = self.news_encoder.forward_pair(
                 (news_title_text, news_title_mask, news_content_text, news_content_mask, news_category, news_subCategory),
                 (user_title_text, user_title_mask, user_content_text, user_content_mask, user_category, user_subCategory))
-            user_representation = self.user_encoder.encode_user(history_embedding, user_history_mask, user_history_graph,
-                                                                user_history_category_mask, user_history_category_indices,
-                                                                news_representation)
+            user_representation = self._encode_user(user_embedding, history_embedding, user_history_mask, user_history_graph,
+                                                    user_history_category_mask, user_history_category_indices, news_representation)
         else:
             # size class of this step for ops.leaf_deferred: the token rows of the history call
             ops.STEP_ROWS[0] = user_title_text.shape[0] * user_title_text.shape[1] * user_title_text.shape[2]
@@ -155,9 +183,8 @@ class Model(nn.Module):
                 history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text,
                                                       user_content_mask, user_content_entity, user_category, user_subCategory, user_embedding)
                 news_representation = _JoinSideFn.apply(news_representation, side)
-                user_representation = self.user_encoder.encode_user(history_embedding, user_history_mask, user_history_graph,
-                                                                    user_history_category_mask, user_history_category_indices,
-                                                                    news_representation)
+                user_representation = self._encode_user(user_embedding, history_embedding, user_history_mask, user_history_graph,
+                                                        user_history_category_mask, user_history_category_indices, news_representation)
             else:
                 news_representation = self.news_encoder(*cand)
                 user_representation = self.user_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text,

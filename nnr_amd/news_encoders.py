@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .layers import Attention, ScaledDotProduct_CandidateAttention, MultiHeadAttention, Conv1D, LSTMParams, grad_of
+from .layers import Attention, CandidateAttention, ScaledDotProduct_CandidateAttention, MultiHeadAttention, Conv1D, LSTMParams, grad_of, personalized_attention
 
 _SITE = dict(title=1, content=2, cat=3, sub=4)
 _DP_TABLE_FIRST = int(os.environ.get('NNR_DP_TABLE_FIRST', '0'))       # 1: always, -1: when world_size > 1, 0 (default): never -- no multi-GPU box to measure it on
@@ -777,4 +777,50 @@ class CNN(NewsEncoder):
         c = Fn.Conv1dReluFn.apply(w, self.conv.conv, n, Lx)                                                # [n*L, C]
         c = Fn.DropoutFn.apply(c, p, seed + 2)
         rep = self.attention(c.view(n, Lx, self.cnn_kernel_num), mask)
+        return Fn.FuseFn.apply(rep, self, category, subCategory, p, seed).view(B, N, self.news_embedding_dim)
+
+
+class PNE(NewsEncoder):
+    """newsEncoders.py:332-363, NPA's personalised news encoder: CNN's stages with the word-level pool replaced by a CandidateAttention whose
+    query is relu(dense(user_embedding)) -- one additive attention per title with the query of a USER (csrc/pers_attn.hip: P exists for
+    the B users, not for the B * news_num titles).
+
+    Observable quirk kept: newsEncoders.py:359 builds the query rows with `.repeat([news_num, 1])`, so row r of the [B * news_num, ...] title
+    list attends with user r % B -- not with the user r // news_num that owns it.  The two agree only when B == 1 or news_num == 1; with
+    anything else a title is pooled with another sample's query, and evaluation scores depend on the batch size, as the reference's do.
+
+    batch_independent is False: a representation depends on the user (and, through the quirk, on the batch), so evaluate.py does not cache."""
+    batch_independent = False
+
+    def __init__(self, config, word_table=None):
+        super().__init__(config, word_table)
+        self.max_sentence_length = config.max_title_length
+        self.cnn_kernel_num = config.cnn_kernel_num
+        self.personalized_embedding_dim = config.personalized_embedding_dim
+        self.conv = Conv1D(config.cnn_method, config.word_embedding_dim, config.cnn_kernel_num, config.cnn_window_size)
+        self.dense = nn.Linear(config.user_embedding_dim, config.personalized_embedding_dim, bias=True)
+        self.personalizedAttention = CandidateAttention(config.cnn_kernel_num, config.personalized_embedding_dim, config.attention_dim)
+        self.news_embedding_dim = config.cnn_kernel_num + config.category_embedding_dim + config.subCategory_embedding_dim
+
+    def initialize(self):
+        super().initialize()
+        nn.init.xavier_uniform_(self.dense.weight, gain=nn.init.calculate_gain('relu'))
+        nn.init.zeros_(self.dense.bias)
+        self.personalizedAttention.initialize()
+
+    def forward(self, title_text, title_mask, title_entity, content_text, content_mask, content_entity, category, subCategory, user_embedding):
+        from . import functional as Fn
+        if user_embedding is None:
+            raise Exception('PNE needs the user embedding rows (model.Model passes dropout(user_embedding(user_ID)))')
+        B, N = title_text.shape[:2]
+        n, Lx = B * N, self.max_sentence_length
+        p = self.dropout_rate if self.training else 0.0
+        seed = self._next_seed()
+        mask = title_mask.view(n, Lx)
+        w = Fn.EmbedDropFn.apply(self.word_embedding.weight, title_text, p, seed + 1)
+        c = Fn.Conv1dReluFn.apply(w, self.conv.conv, n, Lx)                                                # [n*L, C]
+        c = Fn.DropoutFn.apply(c, p, seed + 2)
+        q_w = Fn.LinearFn.apply(user_embedding, self.dense.weight, self.dense.bias, ops.ACT_RELU, 0.0, 0)    # [B, personalized_embedding_dim]
+        uidx = torch.arange(n, device=title_text.device, dtype=torch.int32) % B                            # the `.repeat` pairing: row r <- user r % B
+        rep = personalized_attention(self.personalizedAttention, c.view(n, Lx, self.cnn_kernel_num), q_w, uidx, mask)
         return Fn.FuseFn.apply(rep, self, category, subCategory, p, seed).view(B, N, self.news_embedding_dim)

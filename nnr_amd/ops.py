@@ -1124,6 +1124,46 @@ def cand_attn_bwd(P, Q, w2, feat, mask, alpha, dout, B, N, H, A, D, act, dP, dQ,
                                           _p(dP), _p(dQ), _p(dfeat), accumulate, _p(ws), _p(dw2), _s()), 'nnr_cand_attn_bwd')
 
 
+def pers_attn_fwd(Qf, P, uidx, w2, feat, mask, n, Lx, A, F, alpha, out, U=None):
+    """Per-title personalised attention (csrc/pers_attn.hip): Qf [n*L, A], P [U, A], uidx int32 [n], w2 [A], feat [n, L, F], mask [n, L] bool /
+    uint8 or None -> alpha [n, L], out [n, F].  Returns the entry point's code for NNR_ERR_UNSUPPORTED (-3) instead of raising."""
+    U = P.shape[0] if U is None else U
+    # per title: the projection rows and feature rows of its live positions (counted as all L), weights + output written; P and w2 once per user
+    with _hbm_span('pers_attn_fwd', 4.0 * (Lx * A + Lx * F + Lx + F) + 1.0 * Lx + 4.0, n, fixed=4.0 * A * (U + 1)):
+        rc = L.lib().nnr_pers_attn_fwd(_p(Qf), _p(P), _p(uidx), U, _p(w2), _p(feat), feat.stride(1), _p(_u8(mask)), n, Lx, A, F, _p(alpha), _p(out), _s())
+    if rc == -3:
+        return rc
+    L.check(rc, 'nnr_pers_attn_fwd')
+    return 0
+
+
+def pers_attn_bwd(Qf, P, uidx, w2, feat, mask, alpha, dout, n, Lx, A, F, dP, dQf, dfeat, dw2, U=None):
+    """dP [U, A], dQf [n*L, A], dfeat [n, L, F] are written, dw2 [A] is added into."""
+    U = dP.shape[0] if U is None else U
+    nws = L.lib().nnr_pers_attn_ws_floats(n, Lx, A)
+    if nws < 0:
+        raise L.NnrHipError('nnr_pers_attn_ws_floats failed with code %d (n %d, L %d, A %d)' % (nws, n, Lx, A))
+    ws = torch.empty(nws, device=Qf.device, dtype=torch.float32)
+    # per title: projection rows + feature rows read, their gradients written, weights, d output, the two workspace rows (both ways)
+    with _hbm_span('pers_attn_bwd', 4.0 * (2 * Lx * A + 2 * Lx * F + Lx + F + 4 * A) + 1.0 * Lx + 4.0, n, fixed=4.0 * A * (2 * U + 2)):
+        L.check(L.lib().nnr_pers_attn_bwd(_p(Qf), _p(P), _p(uidx), U, _p(w2), _p(feat), feat.stride(1), _p(_u8(mask)), _p(alpha), _p(dout), n, Lx, A,
+                                          F, _p(dP), _p(dQf), _p(dfeat), _p(ws), _p(dw2), _s()), 'nnr_pers_attn_bwd')
+
+
+def user_rows_fwd(table, ids, p, seed, rows=None):
+    """out[b] = dropout(table[ids[b]]) for int64 ids [B] (csrc/misc.hip); an id outside [0, rows) gives a zero row."""
+    B, dim = ids.numel(), table.shape[1]
+    out = torch.empty((B, dim), device=table.device, dtype=torch.float32)
+    L.check(L.lib().nnr_user_rows_fwd(_p(table), table.shape[0] if rows is None else rows, _p(ids), B, dim, _p(out), p, seed, _s()), 'nnr_user_rows_fwd')
+    return out
+
+
+def user_rows_bwd(dout, ids, dtable, p, seed, rows=None):
+    """dtable[u] += sum over b with ids[b] == u, in ascending b, of mask * dout[b] (no float atomics)."""
+    B, dim = ids.numel(), dtable.shape[1]
+    L.check(L.lib().nnr_user_rows_bwd(_p(dout), _p(ids), B, dtable.shape[0] if rows is None else rows, dim, _p(dtable), p, seed, _s()), 'nnr_user_rows_bwd')
+
+
 def omap_ws(B, N, H, D, K, device):
     n = L.lib().nnr_omap_ws_floats(B, N, H, D, K)
     if n < 0:

@@ -144,6 +144,7 @@ HBM_KERNELS = {
 # families that no launch of the headline step belongs to (the committed counter pass, profiles/pmc_traffic.json, is of that step)
 HBM_KERNELS_OTHER = {
     'cand_attn_fwd': (('cand_attn_fwd_kernel',), 1), 'cand_attn_bwd': (('cand_attn_bwd_da_kernel', 'cand_attn_bwd_dx_kernel'), 2),
+    'pers_attn_fwd': (('pers_attn_fwd_kernel',), 1), 'pers_attn_bwd': (('pers_attn_bwd_kernel', 'pers_attn_user_sum_kernel'), 2),
     'omap_fwd': (('omap_alpha_kernel', 'omap_mix_kernel', 'omap_pool_kernel'), 3),
     'omap_bwd': (('omap_bwd_pool_kernel', 'omap_bwd_dalpha_kernel', 'omap_bwd_dx_kernel', 'omap_dw_reduce_kernel'), 4),
 }

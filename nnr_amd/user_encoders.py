@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .layers import Attention, ScaledDotProduct_CandidateAttention, MultiHeadAttention, GCN, grad_of, _CandAttnFn
+from .layers import Attention, CandidateAttention, ScaledDotProduct_CandidateAttention, MultiHeadAttention, GCN, grad_of, _CandAttnFn
 from .news_encoders import NewsEncoder
 
 
@@ -552,3 +552,38 @@ class OMAP(UserEncoder):
         if self.training:
             self.auxiliary_loss = _OmapRegFn.apply(self.W, self)
         return user_representation
+
+
+class PUE(UserEncoder):
+    """userEncoders.py:265-284, NPA's personalised user encoder: additive attention over the click history (masked) whose query is
+    relu(dense(user_embedding)), the user vector repeated over the candidates.  B problems of max_history_num slots: the shape
+    layers.CandidateAttention's kernel (csrc/cand_attn.hip) was built for.  encode_user takes the user embedding rows as a seventh argument
+    (needs_user_embedding tells model.Model to pass them)."""
+    needs_user_embedding = True
+
+    def __init__(self, news_encoder: NewsEncoder, config):
+        super().__init__(news_encoder, config)
+        self.dense = nn.Linear(config.user_embedding_dim, config.personalized_embedding_dim, bias=True)
+        self.personalizedAttention = CandidateAttention(self.news_embedding_dim, config.personalized_embedding_dim, config.attention_dim)
+
+    def initialize(self):
+        nn.init.xavier_uniform_(self.dense.weight, gain=nn.init.calculate_gain('relu'))
+        nn.init.zeros_(self.dense.bias)
+        self.personalizedAttention.initialize()
+
+    def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask, user_content_entity,
+                user_category, user_subCategory, user_history_mask, user_history_graph, user_history_category_mask,
+                user_history_category_indices, user_embedding, candidate_news_representation):
+        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
+                                              user_content_entity, user_category, user_subCategory, user_embedding)
+        return self.encode_user(history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
+                                user_history_category_indices, candidate_news_representation, user_embedding)
+
+    def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
+                    user_history_category_indices, candidate_news_representation, user_embedding=None):
+        from . import functional as Fn
+        if user_embedding is None:
+            raise Exception('PUE needs the user embedding rows (model.Model passes dropout(user_embedding(user_ID)))')
+        q_d = Fn.LinearFn.apply(user_embedding, self.dense.weight, self.dense.bias, ops.ACT_RELU, 0.0, 0)     # [B, personalized_embedding_dim]
+        user = self.personalizedAttention(history_embedding, q_d, user_history_mask)                          # [B, news_embedding_dim]
+        return Fn.ExpandFn.apply(user, candidate_news_representation.size(1))

@@ -30,8 +30,10 @@ from make_goldens import stable_sort_patch          # noqa: E402
 from oracle.nnr_oracle import default_config        # noqa: E402  (attribute bag only)
 
 
-def run(tag, news, user, stable, min_gap=None, **cfg_over):
-    """`cfg_over`: flags default_config lacks (OMAP_head_num, HiFi_Ark_regularizer_coefficient: config.py:74-75)."""
+def run(tag, news, user, stable, min_gap=None, batch_size=8, **cfg_over):
+    """`cfg_over`: flags default_config lacks (OMAP_head_num, HiFi_Ark_regularizer_coefficient: config.py:74-75; user_embedding_dim,
+    personalized_embedding_dim: config.py:64-65).  `batch_size` is stored: PNE's scores depend on it (newsEncoders.py:359 pairs title row r
+    of a batch with user r % batch)."""
     rng = np.random.default_rng(21)
     cwd = os.getcwd()
     with tempfile.TemporaryDirectory() as tmp:
@@ -69,7 +71,7 @@ def run(tag, news, user, stable, min_gap=None, **cfg_over):
             scores = []
             fwd = m.forward
             m.forward = lambda *a: (lambda o: (scores.append(o.detach().clone().numpy().reshape(-1)), o)[1])(fwd(*a))
-            auc, mrr, ndcg5, ndcg10 = util.compute_scores(m, corpus, 8, 'dev', 'dev/res/out.txt', 'tiny')
+            auc, mrr, ndcg5, ndcg10 = util.compute_scores(m, corpus, batch_size, 'dev', 'dev/res/out.txt', 'tiny')
             m.forward = fwd
             ranks, labels, sizes = [], [], []
             with open('dev/res/out.txt') as f:
@@ -82,7 +84,7 @@ def run(tag, news, user, stable, min_gap=None, **cfg_over):
                     labels += json.loads(line.strip().split()[1])
             out = dict(scores=np.concatenate(scores).astype(np.float32), ranks=np.array(ranks, dtype=np.int32), labels=np.array(labels, dtype=np.uint8),
                        sizes=np.array(sizes, dtype=np.int32), metrics=np.array([auc, mrr, ndcg5, ndcg10], dtype=np.float64),
-                       dev_indices=np.array(corpus.dev_indices, dtype=np.int32),
+                       dev_indices=np.array(corpus.dev_indices, dtype=np.int32), batch_size=np.int64(batch_size),
                        category_num=np.int64(cfg.category_num), subCategory_num=np.int64(cfg.subCategory_num), vocabulary_size=np.int64(cfg.vocabulary_size),
                        user_num=np.int64(cfg.user_num), entity_size=np.int64(cfg.entity_size),
                        news_category=corpus.news_category, news_subCategory=corpus.news_subCategory, news_title_text=corpus.news_title_text,
@@ -141,8 +143,16 @@ def run_metrics():
     print('metrics_ragged', len(sizes), 'impressions', int(sizes.sum()), 'samples', means)
 
 
+def run_npa():
+    """`python tools/make_eval_goldens.py npa`: PNE + PUE on the user-id embedding path, at batch size 8."""
+    run('tiny_PNE_PUE', 'PNE', 'PUE', False, min_gap=1e-3, batch_size=8, user_embedding_dim=6, personalized_embedding_dim=10)
+
+
 if __name__ == '__main__':
     torch.set_num_threads(4)
+    if len(sys.argv) > 1 and sys.argv[1] == 'npa':
+        run_npa()
+        sys.exit(0)
     run_metrics()
     run('tiny_MHSA_MHSA', 'MHSA', 'MHSA', False)
     run('tiny_CNN_ATT', 'CNN', 'ATT', False)
@@ -155,3 +165,4 @@ if __name__ == '__main__':
     run('tiny_CNN_OMAP', 'CNN', 'OMAP', False, min_gap=1e-3, **omap)
     with stable_sort_patch():
         run('tiny_CNE_OMAP_stable', 'CNE', 'OMAP', True, min_gap=1e-3, **omap)
+    run_npa()

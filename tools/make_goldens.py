@@ -16,6 +16,7 @@ touch the arithmetic:
 Usage:  python tools/make_goldens.py            (rewrites every fixture)
         python tools/make_goldens.py catt       (the CATT user encoder and the candidate-attention layers)
         python tools/make_goldens.py omap       (the OMAP user encoder)
+        python tools/make_goldens.py npa        (the PNE news encoder and the PUE user encoder on the user-id embedding path)
 """
 import os
 import pickle
@@ -105,15 +106,18 @@ class record_dropout:
         self.F.dropout = self.orig
 
 
-def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True, adam_steps=3, dropout_seed=None, _rec_drop=None):
-    """mode: 'train' (dropout_rate must be 0 unless dropout_seed is given) or 'eval' (for MHSA-user's hard-wired F.dropout)."""
+def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True, adam_steps=3, dropout_seed=None, _rec_drop=None, user_ids=None):
+    """mode: 'train' (dropout_rate must be 0 unless dropout_seed is given) or 'eval' (for MHSA-user's hard-wired F.dropout).
+    user_ids: the batch's user_ID (int64 [batch_size]) instead of the synthetic corpus's arange -- the personalised encoders read it."""
     if dropout_seed is not None:
         assert adam_steps == 1 and mode == 'train'
         with record_dropout(dropout_seed) as rec_drop:
-            return run_case(tag, cfg, spec, batch_size, seed, mode, gain, full_arrays, adam_steps, None, _rec_drop=rec_drop)
+            return run_case(tag, cfg, spec, batch_size, seed, mode, gain, full_arrays, adam_steps, None, _rec_drop=rec_drop, user_ids=user_ids)
     torch.manual_seed(seed)
     corpus = SynthCorpus(spec)
     batch = corpus.batch(batch_size, np.random.default_rng(seed + 100))
+    if user_ids is not None:
+        batch['user_ID'] = np.asarray(user_ids, dtype=np.int64).reshape(batch_size)
     rngw = np.random.default_rng(seed + 7)
     table = (rngw.standard_normal((cfg.vocabulary_size, cfg.word_embedding_dim)) * 0.3).astype(np.float32)
     table[0] = 0
@@ -130,6 +134,8 @@ def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True
     rec = {}
     m.news_encoder.register_forward_hook(lambda mod, i, o: rec.setdefault('reps', []).append(o.detach().clone().numpy()))
     m.user_encoder.register_forward_hook(lambda mod, i, o: rec.__setitem__('user_rep', o.detach().clone().numpy()))
+    if cfg.news_encoder == 'PNE':               # the conv stage's output of both encoder calls, as [titles, L, C] (dropout_ is the identity at p = 0)
+        m.news_encoder.conv.register_forward_hook(lambda mod, i, o: rec.setdefault('conv', []).append(o.detach().permute(0, 2, 1).clone().numpy()))
 
     opt = torch.optim.Adam([p for p in m.parameters() if p.requires_grad], lr=cfg.lr, weight_decay=cfg.weight_decay)
     out = {}
@@ -150,6 +156,10 @@ def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True
             out['cand_rep'] = rec['reps'][0]
             out['hist_rep'] = rec['reps'][1]
             out['user_rep'] = rec['user_rep']
+            if 'conv' in rec:
+                out['pne/c_cand'] = rec['conv'][0]
+                if full_arrays:                 # (the history call's is 0.6 MB compressed at full dimensions: the candidate call's alone there)
+                    out['pne/c_hist'] = rec['conv'][1]
             grads = {k: p.grad.detach().clone().numpy() for k, p in m.named_parameters()}
             out['mutated_news_title_mask'] = inp[16].numpy().copy()
             out['mutated_user_history_category_mask'] = inp[11].numpy().copy()
@@ -339,10 +349,71 @@ def omap_cases():
         check('tiny_CNN_OMAP')
 
 
+def npa_cases():
+    """NPA (`python tools/make_goldens.py npa`): the PNE news encoder (newsEncoders.py:332-363) and the PUE user encoder
+    (userEncoders.py:265-284), together and each with an encoder that ignores the user, on the user-id embedding path of model.py:79-85,
+    110-112, 122-125.  make_state weights, as the CATT cases.  The tiny cases have 6 users and a user_ID with a repeated id and id 0 (the
+    table has no padding_idx: row 0 takes gradient); user_embedding_dim 6 and personalized_embedding_dim 10 are no multiples of 4.
+    Asserted below: the fixtures discriminate -- in the tiny cases the table's, the dense layers' and the personalised attentions' gradients
+    are each at least 1 % of the total norm (the full-size case cannot reach that at gain 1.0, see check), and pairing title row r with user r // news_num instead of the reference's r % B (newsEncoders.py:359)
+    misses cand_rep by more than 1e-3."""
+    from npa_ref import pne_title_rep
+    tiny = dict(user_embedding_dim=6, personalized_embedding_dim=10)
+
+    def check(tag, cfg, gain, seed):
+        z = np.load(os.path.join(OUT, tag + '.npz'))
+        total = float(z['grad_total_norm'])
+        watched = [k[len('gradnorm/'):] for k in z.files if k.startswith('gradnorm/') and not k.startswith('gradnorm/user_encoder.news_encoder.')
+                   and ('user_embedding.weight' in k or '.dense.' in k or '.personalizedAttention.' in k) and not k.endswith('.bias')]
+        assert 'user_embedding.weight' in watched and len(watched) >= 4, watched
+        # full dimensions at gain 1.0: the user rows are 0.1 N(0, 1) over 50 columns against conv outputs of O(1), so the query side carries
+        # 0.02-0.3 % of the norm whatever the seed (measured at four); there the floor is the 1e-4 from which the model tests compare a
+        # gradient's direction, and the 1 % floor is the tiny fixtures', whose every gradient is stored in full
+        floor = 0.01 if tag.startswith('tiny_') else 1e-4
+        for k in watched:
+            share = float(z['gradnorm/' + k]) / total
+            print('  %s: |g| / |g_total| = %.4f' % (k, share))
+            assert share >= floor, (tag, k, share)
+        if cfg.news_encoder == 'PNE':
+            B, N = z['in/news_title_text'].shape[:2]
+            from nnr_amd.model import Model     # (the reference's parameter names and shapes: tests/test_npa_host.py)
+            st = make_state({k: tuple(v.shape) for k, v in Model(cfg, torch.zeros(cfg.vocabulary_size, cfg.word_embedding_dim)).named_parameters()}, seed, gain)
+            rows = st['user_embedding.weight'][z['in/user_ID']]
+            C = cfg.cnn_kernel_num
+            mask = z['mutated_news_title_mask'].reshape(B * N, -1)
+            exact = pne_title_rep(z['pne/c_cand'], rows, st, B, N, mask=mask).numpy()
+            wrong = pne_title_rep(z['pne/c_cand'], rows, st, B, N, mask=mask, intended=True).numpy()
+            e0 = float(np.abs(exact - z['cand_rep'].reshape(B * N, -1)[:, :C]).max())
+            e1 = float(np.abs(wrong - z['cand_rep'].reshape(B * N, -1)[:, :C]).max())
+            print('  %s: restatement %.2e from cand_rep, with the intended pairing r // news_num %.2e' % (tag, e0, e1))
+            assert e0 <= 1e-6 and e1 > 1e-3, (tag, e0, e1)
+
+    def run(tag, cfg, spec, batch_size, seed, gain, ids, **kw):
+        run_case(tag, cfg, spec, batch_size=batch_size, seed=seed, mode='train', gain=gain, user_ids=ids, **kw)
+        if tag.startswith('tiny_'):
+            assert 0 in ids and len(set(ids)) < len(ids), ids
+        check(tag, cfg, gain, seed)
+
+    cfg = tiny_cfg('PNE', 'PUE', **tiny)
+    cfg.user_num = 6
+    run('tiny_PNE_PUE', cfg, tiny_spec(cfg, 3), 5, 19, 2.0, [3, 0, 5, 3, 1])
+    cfg = tiny_cfg('PNE', 'ATT', **tiny)
+    cfg.user_num = 6
+    run('tiny_PNE_ATT', cfg, tiny_spec(cfg, 3), 3, 29, 2.0, [2, 0, 2])
+    cfg = tiny_cfg('CNN', 'PUE', **tiny)
+    cfg.user_num = 6
+    run('tiny_CNN_PUE', cfg, tiny_spec(cfg, 3), 3, 31, 2.0, [4, 4, 0])
+    cfg = full_cfg('PNE', 'PUE', V=400, user_num=4, user_embedding_dim=50, personalized_embedding_dim=200)
+    run('full_PNE_PUE_g1p0', cfg, full_spec(cfg, 9), 2, 17, 1.0, [3, 0], full_arrays=False)
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == 'omap':
         torch.set_num_threads(8)
         return omap_cases()
+    if len(sys.argv) > 1 and sys.argv[1] == 'npa':
+        torch.set_num_threads(8)
+        return npa_cases()
     if len(sys.argv) > 1 and sys.argv[1] == 'catt':
         torch.set_num_threads(8)
         return catt_cases()
