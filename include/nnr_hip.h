@@ -288,6 +288,9 @@ int nnr_gcn_aggregate_fwd(const float* graph, const float* z, const float* bias,
 int nnr_gcn_aggregate_bwd(const float* graph, const float* dy, const float* r, float* ds, float* dx0, float* dz, int B, int G, int D, float p,
                           uint32_t seed, hipStream_t stream);
 int nnr_relu_drop_bwd(const float* dy, const float* r, float* ds, float* dx, long n, float p, uint32_t seed, hipStream_t stream);
+/* Backward of y = dropout(sigmoid(z)) given s = sigmoid(z) (the dense layers of the DAE news encoder, newsEncoders.py:389-390):
+ * dz = mask(dy) * s * (1 - s); same mask as nnr_relu_drop_bwd. */
+int nnr_sigmoid_drop_bwd(const float* dy, const float* s, float* dz, long n, float p, uint32_t seed, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------ multi-head self-attention core
  * MultiHeadAttention.forward after the W_Q/W_K/W_V projections (layers.py:137-147) on v_mfma_f32_32x32x2_f32:
@@ -390,6 +393,35 @@ int nnr_omap_bwd(const float* hist, int ldf, const float* cand, const uint8_t* m
                  int dhist_accumulate, float* dcand, float* dW_accum, float* ws, hipStream_t stream);
 int nnr_omap_reg_fwd(const float* W, int D, int K, float coef, float* off, float* loss, hipStream_t stream);
 int nnr_omap_reg_bwd(const float* W, const float* off, const float* gup, int D, int K, float coef, float* dW_accum, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------ bag of words (csrc/bag.hip)
+ * The masked mean of word-embedding rows that opens the DAE (newsEncoders.py:386-387) and Inception (newsEncoders.py:422-425) news
+ * encoders, over the live positions of up to two token streams per news row: ids int32 [n, La] / [n, Lb], masks uint8 [n, La] / [n, Lb]
+ * (ids_b == NULL with Lb == 0: one stream), table [V, E].  An id outside [0, V) counts as a live position with a zero row.
+ *   separate == 0 (DAE):  out[r, off_a : off_a + E] = act((sum over both streams) / (count_a + count_b)); count [n].
+ *   separate == 1 (Inception): the launch first sets mask[r, 0] = 1 IN PLACE on both streams; out[r, off_a : +E] = act(mean of stream a),
+ *   out[r, off_b : +E] = act(mean of stream b); count [2, n] (stream a, then stream b).
+ * act: 0 none, 3 sigmoid.  fp32 sums in a fixed order (stream a ascending, then stream b ascending), plain IEEE division: a row with no
+ * live position gives 0 / 0.  tok (optional) int32 [n, La + Lb] receives the word id of every live position and -1 elsewhere: sorted by
+ * nnr_token_sort (cap = n * (La + Lb), n_dev = NULL) it is the occurrence list the backward call reads.
+ * Backward: dtable[w, :] += sum over the live occurrences (r, pos) of w, in sorted-list order, of g[r] / count, with g[r] = dout[r, off :
+ * off + E] for act 0 and dout * out * (1 - out) for act 3 (out: the forward call's output; may be NULL for act 0).  No [tokens, E]
+ * buffer is read or written; no float atomics: every table row has one writer, so concurrent calls must not share dtable rows.
+ * partial_ws: nnr_bag_mean_bwd_ws_floats(cap) floats.  Same inputs, same bits.
+ * NNR_ERR_UNSUPPORTED when La > 128, Lb > 128 or E > 320.
+ * nnr_row_dist_fwd: dist[r] = ||a[r] - b[r]||_2, aux[r] = coef * dist[r] (newsEncoders.py:391); nnr_row_dist_bwd ADDS u = gup[r] * coef *
+ * (a[r] - b[r]) / dist[r] into da[r] and SUBTRACTS it from db[r] (nothing where dist[r] == 0, torch's subgradient); gup: device [n]. */
+int nnr_bag_mean_fwd(const float* table, int V, int E, const int* ids_a, uint8_t* mask_a, int La, const int* ids_b, uint8_t* mask_b,
+                     int Lb, int n, int separate, int act, float* out, int ldo, int off_a, int off_b, float* count, int* tok,
+                     hipStream_t stream);
+size_t nnr_bag_mean_bwd_ws_floats(long cap);
+int nnr_bag_mean_bwd(const float* dout, int lddo, const float* out, int ldo, int off_a, int off_b, const float* count,
+                     const unsigned* keys_sorted, const int* pos_sorted, long cap, int La, int Lb, int n, int V, int E, int separate,
+                     int act, float* dtable_accum, float* partial_ws, hipStream_t stream);
+int nnr_row_dist_fwd(const float* a, int lda, const float* b, int ldb, int n, int D, float coef, float* dist, float* aux,
+                     hipStream_t stream);
+int nnr_row_dist_bwd(const float* a, int lda, const float* b, int ldb, const float* dist, const float* gup, int n, int D, float coef,
+                     float* da_accum, int ldda, float* db_accum, int lddb, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------ device-resident corpus
  * (SURVEY.md section 8 f-1 / f-2).  The corpus tables MIND_Corpus builds (MIND_corpus.py:261-268, 336-353) live in HBM;

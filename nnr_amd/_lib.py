@@ -105,6 +105,7 @@ SIGNATURES = {
     'nnr_gcn_aggregate_fwd': 'i32 ptr ptr ptr ptr ptr ptr i32 i32 i32 i32 f32 seed stream',
     'nnr_gcn_aggregate_bwd': 'i32 ptr ptr ptr ptr ptr ptr i32 i32 i32 f32 seed stream',
     'nnr_relu_drop_bwd': 'i32 ptr ptr ptr ptr i64 f32 seed stream',
+    'nnr_sigmoid_drop_bwd': 'i32 ptr ptr ptr i64 f32 seed stream',
     'nnr_mhsa_fwd': 'i32 ptr ptr i32 i32 i32 i32 f32 ptr ptr f32 seed stream',
     'nnr_mhsa_bwd': 'i32 ptr ptr ptr ptr i32 i32 i32 i32 f32 ptr f32 seed stream',
     'nnr_mhsa_fwd_packed': 'i32 ptr ptr ptr i32 i32 i32 i32 f32 ptr f32 seed stream',
@@ -129,6 +130,11 @@ SIGNATURES = {
     'nnr_omap_bwd': 'i32 ptr i32 ptr ptr ptr ptr ptr ptr ptr ptr ptr i32 i32 i32 i32 i32 ptr i32 ptr ptr ptr stream',
     'nnr_omap_reg_fwd': 'i32 ptr i32 i32 f32 ptr ptr stream',
     'nnr_omap_reg_bwd': 'i32 ptr ptr ptr i32 i32 f32 ptr stream',
+    'nnr_bag_mean_fwd': 'i32 ptr i32 i32 ptr ptr i32 ptr ptr i32 i32 i32 i32 ptr i32 i32 i32 ptr ptr stream',
+    'nnr_bag_mean_bwd_ws_floats': 'u64 i64',
+    'nnr_bag_mean_bwd': 'i32 ptr i32 ptr i32 i32 i32 ptr ptr ptr i64 i32 i32 i32 i32 i32 i32 i32 ptr ptr stream',
+    'nnr_row_dist_fwd': 'i32 ptr i32 ptr i32 i32 i32 f32 ptr ptr stream',
+    'nnr_row_dist_bwd': 'i32 ptr i32 ptr i32 ptr ptr i32 i32 f32 ptr i32 ptr i32 stream',
     'nnr_corpus_batch': 'i32 CorpusTables BatchOut ptr ptr i32 i32 i32 stream',
     'nnr_history_graph': 'i32 ptr ptr i32 i32 i32 i32 ptr ptr ptr stream',
     'nnr_rank_metrics': 'i32 ptr ptr ptr i32 ptr ptr stream',

@@ -459,6 +459,16 @@ __global__ void relu_drop_bwd_kernel(const float* __restrict__ dy, const float* 
   }
 }
 
+// ---- backward of  y = dropout(sigmoid(z))  given s = sigmoid(z):  dz = mask(dy) * s * (1 - s)
+__global__ void sigmoid_drop_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ s, float* __restrict__ dz, long n, uint32_t seed,
+                                        uint32_t thr, float scale) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float m = nnr_keep(seed, (uint64_t)i, thr) ? scale : 0.f;
+    const float v = s[i];
+    dz[i] = dy[i] * m * v * (1.f - v);
+  }
+}
+
 // ---- standalone dropout  y = mask(x)   (same mask forward / backward)
 __global__ void dropout_kernel(const float* __restrict__ x, float* __restrict__ y, long n, uint32_t seed, uint32_t thr,
                                float scale) {
@@ -1141,6 +1151,11 @@ extern "C" int nnr_relu_drop_bwd(const float* dy, const float* r, float* ds, flo
                                  hipStream_t stream) {
   const float sc = p > 0.f ? 1.f / (1.f - p) : 1.f;
   EW_LAUNCH(relu_drop_bwd_kernel, n, dy, r, ds, dx, n, 0, seed, nnr_drop_thresh(p), sc);
+}
+extern "C" int nnr_sigmoid_drop_bwd(const float* dy, const float* s, float* dz, long n, float p, uint32_t seed, hipStream_t stream) {
+  if (!dy || !s || !dz || n < 0) return NNR_ERR_ARG;
+  const float sc = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  EW_LAUNCH(sigmoid_drop_bwd_kernel, n, dy, s, dz, n, seed, nnr_drop_thresh(p), sc);
 }
 extern "C" int nnr_dropout(const float* x, float* y, long n, float p, uint32_t seed, hipStream_t stream) {
   const float sc = p > 0.f ? 1.f / (1.f - p) : 1.f;

@@ -14,6 +14,9 @@
 //     commute, so the result is bit-reproducible); a run that continues across a chunk boundary is stored as a partial row.
 //   * embed_scatter_sorted_fix_kernel: the wave whose chunk holds the START of a multi-chunk segment adds the partial rows of the
 //     following chunks in chunk order (8 rows in flight) and issues the one atomic add per element.
+// csrc/bag.hip (bag_mean_bwd_kernel / bag_mean_bwd_fix_kernel) carries a second copy of the chunk / partial-slot / fix-walk logic below, with
+// the gradient row reached through the sorted position, plain adds in place of the atomics and no dropout: a change to the boundary rules
+// here (open_left / open_right, the slot of a run, the `own` tests, the 64-chunk window) must be made there too.
 // Traffic: every gradient row is read once, every touched table row written once (+ 2 x 1.25 KB per chunk-crossing run).
 #include <cstring>
 #include <string.h>

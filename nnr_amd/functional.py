@@ -153,25 +153,33 @@ CAPTURE_RELU = [None]      # diagnostics / parity tests: set CAPTURE_RELU[0] = [
 
 
 class LinearFn(torch.autograd.Function):
-    """y = dropout(act(x W^T + b)) for 2-D contiguous x;  act in {none, relu};  dropout mask keyed by the output element."""
+    """y = dropout(act(x W^T + b)) for 2-D contiguous x;  act in {none, relu, sigmoid};  dropout mask keyed by the output element."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, act, p, seed):
+        if act not in (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_SIGMOID):
+            raise ValueError('LinearFn: act must be none, relu or sigmoid')
         x = x.contiguous()
         M, K = x.shape
         N = weight.shape[0]
         y = torch.empty((M, N), device=x.device, dtype=torch.float32)
-        r = torch.empty((M, N), device=x.device, dtype=torch.float32) if (act == ops.ACT_RELU) else None
+        # r = act(.) before the dropout, what the backward mask needs; behind a sigmoid without dropout y itself is that value
+        r = torch.empty((M, N), device=x.device, dtype=torch.float32) if (act == ops.ACT_RELU or (act == ops.ACT_SIGMOID and p > 0)) else None
         ops.gemm(x, weight, y, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, bias=bias, act=act, aux_out=r, ldaux=N, drop=(3, p, seed, N))
-        if CAPTURE_RELU[0] is not None and r is not None:
+        if CAPTURE_RELU[0] is not None and r is not None and act == ops.ACT_RELU:
             CAPTURE_RELU[0].append(r)
+        if act == ops.ACT_SIGMOID and r is None:
+            r = y.detach()               # (a second tensor object on y's storage: ctx must not hold its own output)
         ctx.x, ctx.weight, ctx.bias, ctx.r, ctx.act, ctx.p, ctx.seed = x, weight, bias, r, act, p, seed
         return y
 
     @staticmethod
     def backward(ctx, dy):
         dy = dy.contiguous()
-        if ctx.act == ops.ACT_RELU or ctx.p > 0:
+        if ctx.act == ops.ACT_SIGMOID:
+            dz = torch.empty_like(dy)
+            ops.sigmoid_drop_bwd(dy, ctx.r, dz, ctx.p, ctx.seed)
+        elif ctx.act == ops.ACT_RELU or ctx.p > 0:
             dz = torch.empty_like(dy)
             r = ctx.r if ctx.r is not None else torch.ones_like(dy)
             ops.relu_drop_bwd(dy, r, dz, None, ctx.p, ctx.seed)
@@ -351,6 +359,120 @@ class FuseFn(torch.autograd.Function):
         drep = torch.empty((n, F), device=dout.device, dtype=torch.float32)
         ops.add2d(drep, F, dout, D, n, F)
         return drep, None, None, None, None, None
+
+
+class BagMeanFn(torch.autograd.Function):
+    """act(masked mean of word-embedding rows over the live positions of the title and the abstract together) (newsEncoders.py:386-387,
+    csrc/bag.hip): [n, E] from ids [n, La] / [n, Lb] int32 and masks [n, La] / [n, Lb]; the masks are not modified.  need_grad: the launch
+    also writes the occurrence keys and their sort by word id runs on the leaf stream under the rest of the forward pass.  The table
+    gradient is a reduction with one plain writer per row (no float atomics): always on the leaf stream, where the launches of the
+    candidate call's and the history call's backward nodes cannot overlap."""
+
+    @staticmethod
+    def forward(ctx, table, ids_a, mask_a, ids_b, mask_b, act, need_grad):
+        n, E = ids_a.shape[0], table.shape[1]
+        dev = table.device
+        out = torch.empty((n, E), device=dev, dtype=torch.float32)
+        count = torch.empty(n, device=dev, dtype=torch.float32)
+        plan = ops.BagPlan(n, ids_a.shape[1], ids_b.shape[1], table.shape[0], dev) if need_grad else None
+        if ops.bag_mean_fwd(table, ids_a, mask_a, ids_b, mask_b, False, act, out, E, 0, 0, count, plan) != 0:
+            raise ops.L.NnrHipError('nnr_bag_mean_fwd: unsupported size (a stream of more than 128 positions or word_embedding_dim > 320)')
+        if plan is not None:
+            plan.sort()
+        ctx.table, ctx.saved, ctx.act = table, (out.detach(), count, plan), act
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        out, count, plan = ctx.saved
+        ctx.saved = None
+        dout = dout.contiguous()
+        E, g, act = out.shape[1], grad_of(ctx.table), ctx.act
+        ops.leaf_deferred(dout.device, 0, lambda: ops.bag_mean_bwd(dout, E, out, E, 0, 0, count, plan, False, act, g), dout, out, count, plan, force=True)
+        return None, None, None, None, None, None, None
+
+
+class RowDistFn(torch.autograd.Function):
+    """coef * ||a[r] - b[r]||_2 per row of two [n, D] tensors (newsEncoders.py:391); zero gradient where the two rows are equal."""
+
+    @staticmethod
+    def forward(ctx, a, b, coef):
+        a, b = a.contiguous(), b.contiguous()
+        n = a.shape[0]
+        dist = torch.empty(n, device=a.device, dtype=torch.float32)
+        aux = torch.empty(n, device=a.device, dtype=torch.float32)
+        ops.row_dist_fwd(a, b, coef, dist, aux)
+        ctx.saved, ctx.coef = (a.detach(), b.detach(), dist), coef
+        return aux
+
+    @staticmethod
+    def backward(ctx, gup):
+        a, b, dist = ctx.saved
+        da, db = torch.zeros_like(a), torch.zeros_like(b)
+        ops.row_dist_bwd(a, b, dist, gup.contiguous().float(), ctx.coef, da, db)
+        return da, db, None
+
+
+class InceptionFn(torch.autograd.Function):
+    """The Inception news encoder (newsEncoders.py:421-433) for n news, forward and backward by hand so that the GEMMs' leading dimensions
+    stand in for both torch.cat calls: emb [n, 4E] = [title mean | abstract mean | category row | subCategory row] (csrc/bag.hip in
+    separate mode writes the first two slices, after setting mask[:, 0] = 1 in place), cat3 [n, 3E] = [relu(fc1_3 relu(fc1_2 relu(fc1_1
+    emb))) | relu(fc2 emb) | sum of the four slices of emb], rep = linear_transform(cat3).  Parameter gradients go straight into .grad."""
+
+    @staticmethod
+    def forward(ctx, anchor, enc, tt, tm, ct, cm, cat, sub, need_grad):
+        table = enc.word_embedding.weight
+        n, E, dev = tt.shape[0], table.shape[1], table.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        emb, count = torch.empty((n, 4 * E), **f32), torch.empty(2 * n, **f32)
+        plan = ops.BagPlan(n, tt.shape[1], ct.shape[1], table.shape[0], dev) if need_grad else None
+        if ops.bag_mean_fwd(table, tt, tm, ct, cm, True, ops.ACT_NONE, emb, 4 * E, 0, E, count, plan) != 0:
+            raise ops.L.NnrHipError('nnr_bag_mean_fwd: unsupported size (a stream of more than 128 positions or word_embedding_dim > 320)')
+        if plan is not None:
+            plan.sort()
+        ops.small_embed_fwd(enc.category_embedding.weight, cat, emb[:, 2 * E:], 4 * E, 0.0, 0)
+        ops.small_embed_fwd(enc.subCategory_embedding.weight, sub, emb[:, 3 * E:], 4 * E, 0.0, 0)
+        h1 = ops.linear_fwd(emb, enc.fc1_1.weight, enc.fc1_1.bias, act=ops.ACT_RELU)
+        h2 = ops.linear_fwd(h1, enc.fc1_2.weight, enc.fc1_2.bias, act=ops.ACT_RELU)
+        cat3 = torch.empty((n, 3 * E), **f32)
+        ops.linear_fwd(h2, enc.fc1_3.weight, enc.fc1_3.bias, out=cat3[:, :E], act=ops.ACT_RELU)
+        ops.linear_fwd(emb, enc.fc2.weight, enc.fc2.bias, out=cat3[:, E:2 * E], act=ops.ACT_RELU)
+        s3 = cat3[:, 2 * E:]
+        for k in range(4):                                            # ((title + abstract) + category) + subCategory, the reference's order
+            ops.add2d(s3, 3 * E, emb[:, k * E:], 4 * E, n, E, accumulate=(k > 0))
+        rep = ops.linear_fwd(cat3, enc.linear_transform.weight, enc.linear_transform.bias)
+        ctx.enc, ctx.saved = enc, (emb, count, plan, h1, h2, cat3, cat, sub)
+        return rep
+
+    @staticmethod
+    def backward(ctx, drep):
+        enc = ctx.enc
+        emb, count, plan, h1, h2, cat3, cat, sub = ctx.saved
+        ctx.saved = None
+        drep = drep.contiguous()
+        n, E, dev = emb.shape[0], emb.shape[1] // 4, emb.device
+        lt = enc.linear_transform
+        wg = lambda dy, x, lin: ops.leaf_deferred(dev, n, lambda: ops.linear_bwd_weight(dy, x, grad_of(lin.weight), db=grad_of(lin.bias)), dy, x)
+        wg(drep, cat3, lt)
+        d1, d2, d3 = (ops.linear_bwd_data(drep, lt.weight[:, k * E:(k + 1) * E]) for k in range(3))     # the three column blocks of d cat3
+        dz1 = ops.relu_bwd(d1, cat3[:, :E].contiguous())
+        wg(dz1, h2, enc.fc1_3)
+        dz_h2 = ops.relu_bwd(ops.linear_bwd_data(dz1, enc.fc1_3.weight), h2)
+        wg(dz_h2, h1, enc.fc1_2)
+        dz_h1 = ops.relu_bwd(ops.linear_bwd_data(dz_h2, enc.fc1_2.weight), h1)
+        wg(dz_h1, emb, enc.fc1_1)
+        demb = ops.linear_bwd_data(dz_h1, enc.fc1_1.weight)                                            # [n, 4E]
+        dz2 = ops.relu_bwd(d2, cat3[:, E:2 * E].contiguous())
+        wg(dz2, emb, enc.fc2)
+        ops.linear_bwd_data(dz2, enc.fc2.weight, out=demb, accumulate=True)
+        for k in range(4):
+            ops.add2d(demb[:, k * E:], 4 * E, d3, E, n, E, accumulate=True)
+        ops.small_embed_bwd(cat, E, demb[:, 2 * E:], 4 * E, grad_of(enc.category_embedding.weight), 0.0, 0)
+        ops.small_embed_bwd(sub, E, demb[:, 3 * E:], 4 * E, grad_of(enc.subCategory_embedding.weight), 0.0, 0)
+        g = grad_of(enc.word_embedding.weight)
+        ops.leaf_deferred(dev, 0, lambda: ops.bag_mean_bwd(demb, 4 * E, None, 4 * E, 0, E, count, plan, True, ops.ACT_NONE, g), demb, count, plan,
+                          force=True)
+        return (None,) * 9
 
 
 class ExpandFn(torch.autograd.Function):

@@ -84,8 +84,12 @@ class Model(nn.Module):
             self.news_encoder = newsEncoders.MHSA(config, word_table)
         elif config.news_encoder == 'PNE':
             self.news_encoder = newsEncoders.PNE(config, word_table)
+        elif config.news_encoder == 'DAE':
+            self.news_encoder = newsEncoders.DAE(config, word_table)
+        elif config.news_encoder == 'Inception':
+            self.news_encoder = newsEncoders.Inception(config, word_table)
         else:
-            raise Exception(config.news_encoder + ' is not on the MI355X hot path (in scope: CNE, CNN, MHSA, PNE; SURVEY.md section 8a)')
+            raise Exception(config.news_encoder + ' is not on the MI355X hot path (in scope: CNE, CNN, MHSA, PNE, DAE, Inception; SURVEY.md section 8a)')
         if config.user_encoder == 'SUE':
             self.user_encoder = userEncoders.SUE(self.news_encoder, config)
         elif config.user_encoder == 'MHSA':

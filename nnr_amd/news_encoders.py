@@ -824,3 +824,91 @@ class PNE(NewsEncoder):
         uidx = torch.arange(n, device=title_text.device, dtype=torch.int32) % B                            # the `.repeat` pairing: row r <- user r % B
         rep = personalized_attention(self.personalizedAttention, c.view(n, Lx, self.cnn_kernel_num), q_w, uidx, mask)
         return Fn.FuseFn.apply(rep, self, category, subCategory, p, seed).view(B, N, self.news_embedding_dim)
+
+
+def _bow_streams(title_text, title_mask, content_text, content_mask):
+    """ids [n, L] int32 and mask VIEWS [n, L] of both token streams of a call (views: an in-place mask fix must reach the caller's tensors)."""
+    B, N, La = title_text.shape
+    Lb = content_text.shape[2]
+    n = B * N
+    return (_i32(title_text).reshape(n, La).contiguous(), title_mask.view(n, La), _i32(content_text).reshape(n, Lb).contiguous(),
+            content_mask.view(n, Lb))
+
+
+class DAE(NewsEncoder):
+    """newsEncoders.py:366-394, the denoising auto-encoder of the DAE-GRU baseline: m = sigmoid(mean of the word rows over the live positions
+    of title and abstract together) (csrc/bag.hip, no [tokens, E] buffer), c = dropout(m), h = sigmoid(f1 c), d = sigmoid(f2 h);
+    representation = feature_fusion(h).
+
+    Observable quirks kept: the masks are not modified (a news without a live position is 0 / 0); `auxiliary_loss` = Alpha * ||m - d||_2,
+    a [batch, news_num] device tensor that carries its own backward into m and d, is REWRITTEN by every call, in train and in eval mode.
+    After Model.forward it is therefore the history call's [batch, max_history_num] tensor -- the candidate call's value is dropped and
+    sends no gradient --, also when the candidate call runs on the side stream: that call is issued first, the history call last."""
+    batch_independent = True
+
+    def __init__(self, config, word_table=None):
+        super().__init__(config, word_table)
+        self.Alpha = config.Alpha
+        assert self.Alpha > 0, 'Reconstruction loss weight must be greater than 0'
+        self.f1 = nn.Linear(config.word_embedding_dim, config.hidden_dim, bias=True)
+        self.f2 = nn.Linear(config.hidden_dim, config.word_embedding_dim, bias=True)
+        self.news_embedding_dim = config.hidden_dim + config.category_embedding_dim + config.subCategory_embedding_dim
+
+    def initialize(self):
+        super().initialize()
+        gain = nn.init.calculate_gain('sigmoid')
+        for lin in (self.f1, self.f2):
+            nn.init.xavier_uniform_(lin.weight, gain=gain)
+            nn.init.zeros_(lin.bias)
+
+    def forward(self, title_text, title_mask, title_entity, content_text, content_mask, content_entity, category, subCategory, user_embedding):
+        from . import functional as Fn
+        B, N = title_text.shape[:2]
+        p = self.dropout_rate if self.training else 0.0
+        seed = self._next_seed()
+        table = self.word_embedding.weight
+        tt, tm, ct, cm = _bow_streams(title_text, title_mask, content_text, content_mask)
+        m = Fn.BagMeanFn.apply(table, tt, tm, ct, cm, ops.ACT_SIGMOID, torch.is_grad_enabled() and table.requires_grad)    # [n, E]
+        c = Fn.DropoutFn.apply(m, p, seed + 1) if p > 0 else m                                              # the corrupted embedding
+        h = Fn.LinearFn.apply(c, self.f1.weight, self.f1.bias, ops.ACT_SIGMOID, 0.0, 0)                      # [n, hidden_dim]
+        d = Fn.LinearFn.apply(h, self.f2.weight, self.f2.bias, ops.ACT_SIGMOID, 0.0, 0)                      # [n, E]
+        self.auxiliary_loss = Fn.RowDistFn.apply(m, d, float(self.Alpha)).view(B, N)
+        return Fn.FuseFn.apply(h, self, category, subCategory, p, seed).view(B, N, self.news_embedding_dim)
+
+
+class Inception(NewsEncoder):
+    """newsEncoders.py:397-433, the DFM baseline: title mean, abstract mean, category row and subCategory row side by side, a three-layer
+    and a one-layer ReLU branch plus the plain sum of the four, and a linear layer over the three (functional.InceptionFn).  No dropout
+    anywhere and no feature fusion.  Observable quirk kept: mask[:, :, 0] = 1 is set in place on the caller's title and abstract masks."""
+    batch_independent = True
+
+    def __init__(self, config, word_table=None):
+        super().__init__(config, word_table)
+        assert config.word_embedding_dim == config.category_embedding_dim and config.word_embedding_dim == config.subCategory_embedding_dim, \
+            'embedding dimension must be the same in the Inception module'
+        E = config.word_embedding_dim
+        self.fc1_1 = nn.Linear(E * 4, config.hidden_dim, bias=True)
+        self.fc1_2 = nn.Linear(config.hidden_dim, config.hidden_dim, bias=True)
+        self.fc1_3 = nn.Linear(config.hidden_dim, E, bias=True)
+        self.fc2 = nn.Linear(E * 4, E, bias=True)
+        self.linear_transform = nn.Linear(E * 3, E, bias=True)
+        self.news_embedding_dim = E
+
+    def initialize(self):
+        super().initialize()
+        gain = nn.init.calculate_gain('relu')
+        for lin in (self.fc1_1, self.fc1_2, self.fc1_3, self.fc2):
+            nn.init.xavier_uniform_(lin.weight, gain=gain)
+            nn.init.zeros_(lin.bias)
+        nn.init.xavier_uniform_(self.linear_transform.weight)
+        nn.init.zeros_(self.linear_transform.bias)
+
+    def forward(self, title_text, title_mask, title_entity, content_text, content_mask, content_entity, category, subCategory, user_embedding):
+        from . import functional as Fn
+        B, N = title_text.shape[:2]
+        n = B * N
+        table = self.word_embedding.weight
+        tt, tm, ct, cm = _bow_streams(title_text, title_mask, content_text, content_mask)
+        cat, sub = _i32(category).reshape(n).contiguous(), _i32(subCategory).reshape(n).contiguous()
+        rep = Fn.InceptionFn.apply(table, self, tt, tm, ct, cm, cat, sub, torch.is_grad_enabled() and table.requires_grad)
+        return rep.view(B, N, self.news_embedding_dim)

@@ -207,15 +207,20 @@ STEP_ROWS = [0]             # rows here) or the reduction itself is this long: o
                             # 5 156 deferred; MHSA+MHSA at batch 64: 10 596 inline vs 11 120 with every weight gradient deferred)
 
 
-def leaf_deferred(dev, rows, fn, *tensors):
+def leaf_deferred(dev, rows, fn, *tensors, force=False):
     """Inside an autograd backward function: run `fn` (a weight-gradient launch, atomic accumulation) on the leaf stream
     behind the current stream's work, and join it when THIS backward pass ends (autograd's end-of-pass callback), so the data
     gradient chain on the main stream does not wait for it.  `tensors` (the inputs fn reads) are held until that join.
-    _DEFER['off'] (tests) runs fn inline."""
-    if _DEFER.get('off') or max(rows, STEP_ROWS[0]) < LEAF_MIN_ROWS:
+    _DEFER['off'] (tests) runs fn inline.  force: always on the leaf stream -- for an accumulation that is NOT atomic (bag_mean_bwd: one
+    plain writer per table row), whose launches from backward nodes on different streams (the candidate call's on the side stream)
+    must not overlap: on the one leaf stream they run one after the other."""
+    if not force and (_DEFER.get('off') or max(rows, STEP_ROWS[0]) < LEAF_MIN_ROWS):
         fn()
         return
     leaf, main = leaf_stream(dev), torch.cuda.current_stream(dev)
+    if force and leaf == main:           # (one-stream mode: nothing to serialise; the unforced path is as it always was)
+        fn()
+        return
     leaf.wait_stream(main)
     _DEFER['keep'].extend(tensors)
     _DEFER['calls'] += 1
@@ -1046,6 +1051,11 @@ def relu_drop_bwd(dy, r, ds, dx, p, seed):
     L.check(L.lib().nnr_relu_drop_bwd(_p(dy), _p(r), _p(ds), _p(dx), dy.numel(), p, seed, _s()), 'nnr_relu_drop_bwd')
 
 
+def sigmoid_drop_bwd(dy, s, dz, p, seed):
+    """dz = mask(dy) * s * (1 - s): backward of y = dropout(sigmoid(z)) given s = sigmoid(z)."""
+    L.check(L.lib().nnr_sigmoid_drop_bwd(_p(dy), _p(s), _p(dz), dy.numel(), p, seed, _s()), 'nnr_sigmoid_drop_bwd')
+
+
 # ---------------------------------------------------------------------------------------------- SUE / loss / optimiser
 def gcn_aggregate_fwd(graph, z, bias, resid, r_out, y, B, G, D, relu, p, seed):
     arrays = 3 + (1 if resid is not None else 0)                                  # z, (resid) read; r, y written
@@ -1449,6 +1459,85 @@ def embed_scatter_sorted(dout, ts, dtable, p, seed):
     with _hbm_span('embed_scatter', 2 * 4.0 * dim + 8.0, ts.cap, dyn=ts.total, tag='sorted cap%d' % ts.cap):
         L.check(L.lib().nnr_embed_scatter_sorted(_p(dout), _p(ts.keys), _p(ts.rows), ts.cap, ts.vocab, dim, _p(dtable), p, seed, _p(ts.partial),
                                                  _s()), 'nnr_embed_scatter_sorted')
+
+
+# ---------------------------------------------------------------------------------------------- bag of words (csrc/bag.hip)
+class BagPlan:
+    """Occurrence list of one bag_mean_fwd call for its backward pass: `tok` [n, La + Lb] (written by the forward launch: word id of a live
+    position, -1 elsewhere) sorted by word id on the LEAF stream behind the forward launch (csrc/sort.hip; stable, so a word's
+    occurrences keep the order news row, stream a, stream b, position).  Nothing is read on the host."""
+
+    def __init__(self, n, La, Lb, vocab, dev):
+        self.n, self.La, self.Lb, self.vocab = n, La, Lb, int(vocab)
+        self.cap = cap = n * (La + Lb)
+        i32 = dict(device=dev, dtype=torch.int32)
+        self.tok = torch.empty(cap, **i32)
+        self._buf = torch.empty(4 * cap, **i32)                  # keys_tmp | pos_tmp | keys_sorted | pos_sorted
+        self.keys, self.pos = self._buf[2 * cap:3 * cap], self._buf[3 * cap:]
+        self._temp = torch.empty(max(L.lib().nnr_token_sort_workspace_bytes(cap, self.vocab), 256), device=dev, dtype=torch.uint8)
+        self.partial = torch.empty(L.lib().nnr_bag_mean_bwd_ws_floats(cap), device=dev, dtype=torch.float32)
+        self.event = None
+
+    def sort(self):
+        dev, cap, buf = self.tok.device, self.cap, self._buf
+        leaf = leaf_stream(dev)
+        leaf.wait_stream(torch.cuda.current_stream(dev))          # behind the forward launch that wrote `tok`
+        with torch.cuda.stream(leaf):
+            L.check(L.lib().nnr_token_sort(_p(self.tok), cap, None, self.vocab, _p(buf[:cap]), _p(buf[cap:2 * cap]), _p(self.keys), _p(self.pos),
+                                           _p(self._temp), self._temp.numel(), _s()), 'nnr_token_sort')
+            self.event = torch.cuda.Event()
+            self.event.record()
+        # a graph that is dropped without a backward pass frees these while the sort may still run: the allocator must wait for the leaf
+        # stream before it hands them out again (a few MB, unlike the GB-sized buffers leaf_scope holds by reference instead)
+        for t in (self.tok, self._buf, self._temp):
+            t.record_stream(leaf)
+
+
+def bag_mean_fwd(table, ids_a, mask_a, ids_b, mask_b, separate, act, out, ldo, off_a, off_b, count, plan=None, live=None):
+    """Masked mean of table rows over the live positions of ids_a [n, La] (+ ids_b [n, Lb], optional); see include/nnr_hip.h.  Masks are
+    bool / uint8 [n, L], written in place (column 0) when `separate`.  plan: a BagPlan whose `tok` the launch fills.  live (profiling
+    only): live positions of the call, for the byte count.  Returns the entry point's code for NNR_ERR_UNSUPPORTED (-3) instead of raising."""
+    n, La = ids_a.shape
+    Lb = ids_b.shape[1] if ids_b is not None else 0
+    V, E = table.shape
+    # per news: ids + mask bytes read, one or two output rows + counts written (+ the occurrence keys); per live position one table row
+    per_row = 5.0 * (La + Lb) + 4.0 * E * (2 if separate and ids_b is not None else 1) + 8.0 + (4.0 * (La + Lb) if plan is not None else 0.0)
+    with _hbm_span('bag_mean_fwd', per_row, n, fixed=4.0 * E * (live if live is not None else n * (La + Lb))):
+        rc = L.lib().nnr_bag_mean_fwd(_p(table), V, E, _p(ids_a), _p(_u8(mask_a)), La, _p(ids_b), _p(_u8(mask_b)), Lb, n, int(bool(separate)), act,
+                                      _p(out), ldo, off_a, off_b, _p(count), _p(plan.tok) if plan is not None else None, _s())
+    if rc == -3:
+        return rc
+    L.check(rc, 'nnr_bag_mean_fwd')
+    return 0
+
+
+def bag_mean_bwd(dout, lddo, out, ldo, off_a, off_b, count, plan, separate, act, dtable, live=None):
+    """dtable[w] += sum over w's live occurrences of g[r] / count (reproducible, no float atomics); waits for the plan's sort."""
+    E = dtable.shape[1]
+    torch.cuda.current_stream(dout.device).wait_event(plan.event)
+    # per sorted entry a key + a position; per live occurrence a gradient row (and an output row behind the sigmoid) read from the n
+    # rows of the call, and -- counted once per occurrence, an upper bound -- a table-gradient row read and written
+    rows = 1 if act == ACT_NONE else 2
+    with _hbm_span('bag_mean_bwd', 8.0, plan.cap, fixed=4.0 * E * (rows * plan.n + 2.0 * (live if live is not None else plan.cap))):
+        L.check(L.lib().nnr_bag_mean_bwd(_p(dout), lddo, _p(out), ldo, off_a, off_b, _p(count), _p(plan.keys), _p(plan.pos), plan.cap, plan.La,
+                                         plan.Lb, plan.n, plan.vocab, E, int(bool(separate)), act, _p(dtable), _p(plan.partial), _s()),
+                'nnr_bag_mean_bwd')
+
+
+def row_dist_fwd(a, b, coef, dist, aux, lda=None, ldb=None):
+    """dist[r] = ||a[r] - b[r]||_2, aux[r] = coef * dist[r] for a, b [n, D] (leading dimensions allowed)."""
+    n, D = a.shape
+    with _hbm_span('row_dist_fwd', 2 * 4.0 * D + 8.0, n):
+        L.check(L.lib().nnr_row_dist_fwd(_p(a), a.stride(0) if lda is None else lda, _p(b), b.stride(0) if ldb is None else ldb, n, D, coef,
+                                         _p(dist), _p(aux), _s()), 'nnr_row_dist_fwd')
+
+
+def row_dist_bwd(a, b, dist, gup, coef, da, db):
+    """da[r] += u, db[r] -= u with u = gup[r] * coef * (a[r] - b[r]) / dist[r] (nothing where dist[r] == 0); gup: device [n]."""
+    n, D = a.shape
+    with _hbm_span('row_dist_bwd', 6 * 4.0 * D + 8.0, n):
+        L.check(L.lib().nnr_row_dist_bwd(_p(a), a.stride(0), _p(b), b.stride(0), _p(dist), _p(gup), n, D, coef, _p(da), da.stride(0), _p(db),
+                                         db.stride(0), _s()), 'nnr_row_dist_bwd')
 
 
 def fill_zero(t):

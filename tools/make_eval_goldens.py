@@ -46,12 +46,14 @@ def run(tag, news, user, stable, min_gap=None, batch_size=8, **cfg_over):
         torch.cuda.empty_cache = lambda: None
         try:
             import MIND_corpus, util, model as ref_model        # /root/reference
-            cfg = default_config(news_encoder=news, user_encoder=user, dataset='tiny', word_threshold=1, max_title_length=8,
-                                 max_abstract_length=16, word_embedding_dim=16, hidden_dim=8, attention_dim=8, max_history_num=6,
-                                 category_embedding_dim=4, subCategory_embedding_dim=4, negative_sample_num=2, head_num=2, head_dim=4,
-                                 cnn_kernel_num=12, gcn_layer_num=2, dropout_rate=0.2, entity_embedding_dim=100, context_embedding_dim=100,
-                                 no_self_connection=False, no_adjacent_normalization=False, gcn_normalization_type='symmetric',
-                                 train_root='../MIND-tiny/train', dev_root='../MIND-tiny/dev', test_root='../MIND-tiny/test', **cfg_over)
+            flags = dict(news_encoder=news, user_encoder=user, dataset='tiny', word_threshold=1, max_title_length=8,
+                         max_abstract_length=16, word_embedding_dim=16, hidden_dim=8, attention_dim=8, max_history_num=6,
+                         category_embedding_dim=4, subCategory_embedding_dim=4, negative_sample_num=2, head_num=2, head_dim=4,
+                         cnn_kernel_num=12, gcn_layer_num=2, dropout_rate=0.2, entity_embedding_dim=100, context_embedding_dim=100,
+                         no_self_connection=False, no_adjacent_normalization=False, gcn_normalization_type='symmetric',
+                         train_root='../MIND-tiny/train', dev_root='../MIND-tiny/dev', test_root='../MIND-tiny/test')
+            flags.update(cfg_over)                              # (Inception overrides the two category dimensions)
+            cfg = default_config(**flags)
             torch.manual_seed(5)
             corpus = MIND_corpus.MIND_Corpus(cfg)
             m = ref_model.Model(cfg)
@@ -148,10 +150,20 @@ def run_npa():
     run('tiny_PNE_PUE', 'PNE', 'PUE', False, min_gap=1e-3, batch_size=8, user_embedding_dim=6, personalized_embedding_dim=10)
 
 
+def run_bow():
+    """`python tools/make_eval_goldens.py bow`: the two bag-of-words news encoders under ATT (Alpha: config.py:76; Inception needs the
+    three embedding dimensions equal)."""
+    run('tiny_DAE_ATT', 'DAE', 'ATT', False, min_gap=1e-4, Alpha=0.1)     # (sigmoid features: scores closer together than the others')
+    run('tiny_Inception_ATT', 'Inception', 'ATT', False, min_gap=1e-3, category_embedding_dim=16, subCategory_embedding_dim=16)
+
+
 if __name__ == '__main__':
     torch.set_num_threads(4)
     if len(sys.argv) > 1 and sys.argv[1] == 'npa':
         run_npa()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'bow':
+        run_bow()
         sys.exit(0)
     run_metrics()
     run('tiny_MHSA_MHSA', 'MHSA', 'MHSA', False)
@@ -166,3 +178,4 @@ if __name__ == '__main__':
     with stable_sort_patch():
         run('tiny_CNE_OMAP_stable', 'CNE', 'OMAP', True, min_gap=1e-3, **omap)
     run_npa()
+    run_bow()
