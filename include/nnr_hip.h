@@ -423,6 +423,39 @@ int nnr_row_dist_fwd(const float* a, int lda, const float* b, int ldb, int n, in
 int nnr_row_dist_bwd(const float* a, int lda, const float* b, int ldb, const float* dist, const float* gup, int n, int D, float coef,
                      float* da_accum, int ldda, float* db_accum, int lddb, hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------------ KCNN / DKN (csrc/kcnn.hip)
+ * The kernels around the one convolution product of the KCNN news encoder (newsEncoders.py:203-241, layers.py:47-79 `naive`): n titles of L
+ * positions, E = word_embedding_dim, C = cnn_kernel_num, window w, p = (w - 1) / 2, Lp = L + w - 1.  All fp32, no float atomics anywhere.
+ * nnr_kcnn_image_fwd: the padded image Xp [n][Lp][3][E] = the A operand of the convolution (the window of output position t is the 3 w E
+ *   floats from padded row t on: a product with lda = 3 E < K = 3 w E).  Rows [0, p) and [p + L, Lp) of every title are written as zero;
+ *   row p + t holds [word_table[text[i, t]] | tanh(pre1[i, t]) | tanh(pre2[i, t])] (text int32 [n, L], an id outside [0, V): a zero row;
+ *   pre1 / pre2 [n * L, E]: the projected entity / context rows before the tanh).  16-byte accesses when E % 4 == 0 and every base is
+ *   16-byte aligned, scalar ones otherwise.
+ * nnr_kcnn_image_bwd: from dXp and Xp (both [n][Lp][3][E]) the compact [n * L, E] arrays dx0 = channel 0 of dXp, dpre1 = channel 1 *
+ *   (1 - x1^2), dpre2 likewise; halo rows are not read.
+ * nnr_window_max_fwd: z [n * Lp rows, row stride ldz >= C] = the raw convolution rows (no bias yet; row i * Lp + t = output position t of
+ *   title i), bias [C].  out[i, c] = max(0, max over t in [0, L - w + 1) of fl(z + bias[c])) -- relu, then the maximum over the first
+ *   L - w + 1 positions only (layers.py:77-78) --, arg[i, c] (uint8) = the LOWEST t that attains a positive maximum, 255 when there is none.
+ * nnr_window_max_bwd: dz [lead_rows + n * Lp, C] dense, EVERY element written once: zero in the lead_rows leading rows (the data-gradient
+ *   product reads w - 1 of them), g[i, c] at row lead_rows + i * Lp + arg[i, c], zero elsewhere (also in the rows the maximum never sees).
+ *   db [C] is WRITTEN (not added to): the sum of g[i, c] over the titles with arg != 255 in a fixed order (groups of 8 titles, then the
+ *   groups in order): same inputs, same bits.  ws: nnr_window_max_bwd_ws_floats(n, C) floats owned by the calling stream.
+ * nnr_kcnn_repack, of the Conv2d weight W [C][E][w][3]:  mode 0: out [C][w][3][E] = the B operand of the convolution;  mode 1: out
+ *   [3][E][w][C] with the window reversed, out[j][e][k][c] = W[c][e][w-1-k][j] = the B operand of the data gradient dXp = dz . W (A = dz with
+ *   lda = C < K = w C);  mode 2: the inverse of mode 0 with accumulation, out [C][E][w][3] += in [C][w][3][E] (one plain writer per
+ *   element: concurrent calls must not share `out`).
+ * NNR_ERR_UNSUPPORTED when L + w - 1 > 255, w > 8, E > 1024 or L < w (the reference's slice is empty there). */
+int nnr_kcnn_image_fwd(const float* word_table, int V, const int* text, const float* pre1, const float* pre2, int n, int L, int E, int w,
+                       float* Xp, hipStream_t stream);
+int nnr_kcnn_image_bwd(const float* dXp, const float* Xp, int n, int L, int E, int w, float* dx0, float* dpre1, float* dpre2,
+                       hipStream_t stream);
+int nnr_window_max_fwd(const float* z, int ldz, const float* bias, int n, int C, int L, int w, float* out, uint8_t* arg,
+                       hipStream_t stream);
+size_t nnr_window_max_bwd_ws_floats(int n, int C);
+int nnr_window_max_bwd(const float* g, const uint8_t* arg, int n, int C, int L, int w, int lead_rows, float* dz, float* db, float* ws,
+                       hipStream_t stream);
+int nnr_kcnn_repack(const float* in, float* out, int C, int E, int w, int mode, hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------ device-resident corpus
  * (SURVEY.md section 8 f-1 / f-2).  The corpus tables MIND_Corpus builds (MIND_corpus.py:261-268, 336-353) live in HBM;
  * a training batch is described by behaviour indices + the (1 + K) sampled news ids of each behaviour.

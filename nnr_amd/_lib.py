@@ -135,6 +135,12 @@ SIGNATURES = {
     'nnr_bag_mean_bwd': 'i32 ptr i32 ptr i32 i32 i32 ptr ptr ptr i64 i32 i32 i32 i32 i32 i32 i32 ptr ptr stream',
     'nnr_row_dist_fwd': 'i32 ptr i32 ptr i32 i32 i32 f32 ptr ptr stream',
     'nnr_row_dist_bwd': 'i32 ptr i32 ptr i32 ptr ptr i32 i32 f32 ptr i32 ptr i32 stream',
+    'nnr_kcnn_image_fwd': 'i32 ptr i32 ptr ptr ptr i32 i32 i32 i32 ptr stream',
+    'nnr_kcnn_image_bwd': 'i32 ptr ptr i32 i32 i32 i32 ptr ptr ptr stream',
+    'nnr_window_max_fwd': 'i32 ptr i32 ptr i32 i32 i32 i32 ptr ptr stream',
+    'nnr_window_max_bwd_ws_floats': 'u64 i32 i32',
+    'nnr_window_max_bwd': 'i32 ptr ptr i32 i32 i32 i32 i32 ptr ptr ptr stream',
+    'nnr_kcnn_repack': 'i32 ptr ptr i32 i32 i32 i32 stream',
     'nnr_corpus_batch': 'i32 CorpusTables BatchOut ptr ptr i32 i32 i32 stream',
     'nnr_history_graph': 'i32 ptr ptr i32 i32 i32 i32 ptr ptr ptr stream',
     'nnr_rank_metrics': 'i32 ptr ptr ptr i32 ptr ptr stream',

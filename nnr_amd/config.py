@@ -20,7 +20,7 @@ _FLAGS = [
 ]
 _BOOL_FLAGS = ['no_self_connection', 'no_adjacent_normalization', 'no_gcn_residual', 'gcn_layer_norm']
 
-NEWS_ENCODERS = ['CNE', 'CNN', 'MHSA', 'PNE', 'DAE', 'Inception']       # in scope; the reference lists 15
+NEWS_ENCODERS = ['CNE', 'CNN', 'MHSA', 'PNE', 'DAE', 'Inception', 'KCNN']       # in scope; the reference lists 15
 USER_ENCODERS = ['SUE', 'MHSA', 'ATT', 'CATT', 'OMAP', 'PUE']  # in scope; the reference lists 11
 
 

@@ -54,6 +54,7 @@ const Entry REGISTRY[] = {
   R(nnr_omap_fwd), R(nnr_omap_bwd), R(nnr_omap_reg_fwd), R(nnr_omap_reg_bwd),
   R(nnr_user_rows_fwd), R(nnr_user_rows_bwd), R(nnr_pers_attn_fwd), R(nnr_pers_attn_bwd),
   R(nnr_bag_mean_fwd), R(nnr_bag_mean_bwd), R(nnr_row_dist_fwd), R(nnr_row_dist_bwd), R(nnr_sigmoid_drop_bwd),
+  R(nnr_kcnn_image_fwd), R(nnr_kcnn_image_bwd), R(nnr_window_max_fwd), R(nnr_window_max_bwd), R(nnr_kcnn_repack),
 };
 #undef R
 constexpr int NREG = (int)(sizeof(REGISTRY) / sizeof(REGISTRY[0]));

@@ -475,6 +475,84 @@ class InceptionFn(torch.autograd.Function):
         return (None,) * 9
 
 
+class KcnnFn(torch.autograd.Function):
+    """The KCNN news encoder up to its pooled [n, C] representation (newsEncoders.py:233-238, layers.py:77-78), forward and backward by hand
+    around ONE convolution product (csrc/kcnn.hip):
+      pre_j = table_j[entity] M_j^T + b_j (entity / context rows gathered in the GEMM's A loader);  Xp = the padded image [n, L + w - 1, 3 E]
+      (word rows gathered straight from the table, tanh(pre_j), zero halo rows);  z = Xp' . P^T with Xp' the overlapping-row view of Xp
+      (lda = 3 E < K = 3 w E) and P the repacked Conv2d weight;  out = relu-then-max over the first L - w + 1 positions of z + bias.
+    No dropout and no mask: PAD positions take part with row 0 of each table.  Backward: dense dz (every element written once), dXp = dz' . Q^T
+    (dz' the overlapping-row view with lda = C < K = w C, Q the transposed, window-reversed weight), dP = dz^T . Xp' (split-K through
+    slabs), then the image apart again, the two projections' gradients with the table rows gathered in the B loader, and the three table
+    gradients through the sorted scatter (reproducible, no pile-up of atomics on id 0).  Parameter gradients go straight into .grad."""
+
+    @staticmethod
+    def forward(ctx, anchor, enc, text, entity, n, Lx, need_grad):
+        word, ent_t, ctx_t = enc.word_embedding.weight, enc.entity_embedding.weight, enc.context_embedding.weight
+        conv = enc.knowledge_cnn.conv
+        Cn, E, w, _ = conv.weight.shape
+        dev, rows, Lp = word.device, n * Lx, Lx + w - 1
+        f32 = dict(device=dev, dtype=torch.float32)
+        sorts = None
+        if need_grad:             # both sorts need nothing but the ids: on the leaf stream, under the forward pass
+            sorts = (ops.TokenSort(text, None, word.shape[0]), ops.TokenSort(entity, None, ent_t.shape[0]))
+        pre = []
+        for tab, lin in ((ent_t, enc.M_entity), (ctx_t, enc.M_context)):
+            D = tab.shape[1]
+            y = torch.empty((rows, E), **f32)
+            ops.gemm(tab, lin.weight, y, M=rows, N=E, K=D, lda=D, ldb=D, ldc=E, a_idx=entity, bias=lin.bias)
+            pre.append(y)
+        Xp = torch.empty((n * Lp, 3 * E), **f32)
+        ops.kcnn_image_fwd(word, text, pre[0], pre[1], n, Lx, w, Xp)
+        del pre
+        R = n * Lp - (w - 1)                                          # the last window that lies inside the image starts at row R - 1
+        z = torch.empty((n * Lp, Cn), **f32)                          # (its last w - 1 rows stay unwritten: no maximum reads them)
+        ops.gemm(Xp, ops.kcnn_weight(conv.weight, 0), z, M=R, N=Cn, K=3 * w * E, lda=3 * E, ldb=3 * w * E, ldc=Cn)
+        out = torch.empty((n, Cn), **f32)
+        arg = torch.empty((n, Cn), device=dev, dtype=torch.uint8)
+        ops.window_max_fwd(z, Cn, conv.bias, n, Cn, Lx, w, out, arg)
+        ctx.enc, ctx.saved, ctx.dims = enc, (Xp if need_grad else None, arg, entity, sorts), (n, Lx, E, Cn, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        enc = ctx.enc
+        Xp, arg, entity, (ts_word, ts_ent) = ctx.saved
+        ctx.saved = None
+        n, Lx, E, Cn, w = ctx.dims
+        conv = enc.knowledge_cnn.conv
+        dev, rows, Lp, lead = dout.device, n * Lx, Lx + w - 1, w - 1
+        f32 = dict(device=dev, dtype=torch.float32)
+        dout = dout.contiguous()
+        dzp = torch.empty((lead + n * Lp, Cn), **f32)                 # w - 1 leading zero rows: row r of dz' starts at dz row r - (w - 1)
+        db = torch.empty(Cn, **f32)
+        ops.window_max_bwd(dout, arg, n, Cn, Lx, w, lead, dzp, db)
+        gb, gw = grad_of(conv.bias), grad_of(conv.weight)
+        ops.leaf_deferred(dev, rows, lambda: ops.add_(gb, db), db, force=True)        # (plain read-modify-write: one stream for both calls)
+        dz = dzp[lead:]
+        R = n * Lp - lead
+
+        def weight_grad():
+            dP = torch.zeros((Cn, 3 * w * E), **f32)
+            ops.linear_bwd_weight(dz[:R], Xp.as_strided((R, 3 * w * E), (3 * E, 1)), dP)
+            ops.kcnn_repack(dP, gw, Cn, E, w, 2)
+        ops.leaf_deferred(dev, rows, weight_grad, dzp, Xp, force=True)
+        dXp = torch.empty((n * Lp, 3 * E), **f32)
+        ops.gemm(dzp, ops.kcnn_weight(conv.weight, 1), dXp, M=n * Lp, N=3 * E, K=w * Cn, lda=Cn, ldb=w * Cn, ldc=3 * E)
+        dx0, dp1, dp2 = (torch.empty((rows, E), **f32) for _ in range(3))
+        ops.kcnn_image_bwd(dXp, Xp, n, Lx, E, w, dx0, dp1, dp2)
+        del dXp
+        for tab, lin, dp in ((enc.entity_embedding.weight, enc.M_entity, dp1), (enc.context_embedding.weight, enc.M_context, dp2)):
+            D = tab.shape[1]
+            glw, glb = grad_of(lin.weight), grad_of(lin.bias)
+            ops.leaf_deferred(dev, rows, lambda tab=tab, dp=dp, glw=glw, glb=glb, D=D: ops.gemm(
+                dp, tab, glw, M=E, N=D, K=rows, lda=E, ldb=D, ldc=D, trans_a=True, trans_b=True, b_idx=entity, split_k=ops.split_for(E, D, rows),
+                atomic=True, colsum_out=glb), dp, entity)
+            ops.embed_scatter_sorted(ops.linear_bwd_data(dp, lin.weight), ts_ent, grad_of(tab), 0.0, 0)
+        ops.embed_scatter_sorted(dx0, ts_word, grad_of(enc.word_embedding.weight), 0.0, 0)
+        return (None,) * 7
+
+
 class ExpandFn(torch.autograd.Function):
     """[B, D] -> [B, N, D] (repeat / expand over the candidates, userEncoders.py:172,190); backward sums over N."""
 

@@ -346,6 +346,21 @@ class Conv1D(nn.Module):
                               padding=(cnn_window_size - 1) // 2)
 
 
+class Conv2D_Pool(nn.Module):
+    """layers.py:47-79, 'naive' branch (parameter holder: functional.KcnnFn evaluates relu(conv) and the max over the first
+    length - cnn_window_size + 1 positions)."""
+
+    def __init__(self, cnn_method: str, in_channels: int, cnn_kernel_num: int, cnn_window_size: int, last_channel_num: int):
+        super().__init__()
+        assert cnn_method == 'naive', 'only cnn_method=naive is on the hot path (SURVEY.md section 2, row 5)'
+        self.cnn_method = cnn_method
+        self.in_channels = in_channels
+        self.last_channel_num = last_channel_num
+        self.cnn_window_size = cnn_window_size
+        self.conv = nn.Conv2d(in_channels=in_channels, out_channels=cnn_kernel_num, kernel_size=[cnn_window_size, last_channel_num],
+                              padding=[(cnn_window_size - 1) // 2, 0])
+
+
 class GCNLayer(nn.Module):
     """layers.py:265-292 (parameter holder; SUE's pipeline evaluates relu(A (X W^T) + b) + X)."""
 

@@ -74,7 +74,7 @@ def negative_log_softmax(logits):
 
 
 class Model(nn.Module):
-    def __init__(self, config, word_table=None):
+    def __init__(self, config, word_table=None, entity_table=None, context_table=None):
         super().__init__()
         if config.news_encoder == 'CNE':
             self.news_encoder = newsEncoders.CNE(config, word_table)
@@ -88,8 +88,10 @@ class Model(nn.Module):
             self.news_encoder = newsEncoders.DAE(config, word_table)
         elif config.news_encoder == 'Inception':
             self.news_encoder = newsEncoders.Inception(config, word_table)
+        elif config.news_encoder == 'KCNN':
+            self.news_encoder = newsEncoders.KCNN(config, word_table, entity_table, context_table)
         else:
-            raise Exception(config.news_encoder + ' is not on the MI355X hot path (in scope: CNE, CNN, MHSA, PNE, DAE, Inception; SURVEY.md section 8a)')
+            raise Exception(config.news_encoder + ' is not on the MI355X hot path (in scope: CNE, CNN, MHSA, PNE, DAE, Inception, KCNN; SURVEY.md section 8a)')
         if config.user_encoder == 'SUE':
             self.user_encoder = userEncoders.SUE(self.news_encoder, config)
         elif config.user_encoder == 'MHSA':

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .layers import Attention, CandidateAttention, ScaledDotProduct_CandidateAttention, MultiHeadAttention, Conv1D, LSTMParams, grad_of, personalized_attention
+from .layers import Attention, CandidateAttention, ScaledDotProduct_CandidateAttention, MultiHeadAttention, Conv1D, Conv2D_Pool, LSTMParams, grad_of, personalized_attention
 
 _SITE = dict(title=1, content=2, cat=3, sub=4)
 _DP_TABLE_FIRST = int(os.environ.get('NNR_DP_TABLE_FIRST', '0'))       # 1: always, -1: when world_size > 1, 0 (default): never -- no multi-GPU box to measure it on
@@ -912,3 +912,53 @@ class Inception(NewsEncoder):
         cat, sub = _i32(category).reshape(n).contiguous(), _i32(subCategory).reshape(n).contiguous()
         rep = Fn.InceptionFn.apply(table, self, tt, tm, ct, cm, cat, sub, torch.is_grad_enabled() and table.requires_grad)
         return rep.view(B, N, self.news_embedding_dim)
+
+
+class KCNN(NewsEncoder):
+    """newsEncoders.py:203-241, the knowledge-aware CNN of the DKN baseline: per title position the word row, tanh(M_entity(entity row)) and
+    tanh(M_context(context row)) as the three channels of an image, Conv2d(E -> cnn_kernel_num, kernel [cnn_window_size, 3]) over it, relu, the
+    maximum over positions, feature fusion (functional.KcnnFn, csrc/kcnn.hip: one convolution product on the GEMM family).
+
+    Observable quirks kept: no dropout before the fusion and no mask -- PAD positions take part with row 0 of each table, which is
+    trainable like any other row; both knowledge tables are indexed by the same `title_entity` ids; the maximum runs over the first
+    max_title_length - cnn_window_size + 1 convolution outputs only (layers.py:78).  `title_mask`, the content arguments and
+    `user_embedding` are accepted and ignored.  initialize() leaves the knowledge tables and the convolution as they are."""
+    batch_independent = True
+
+    def __init__(self, config, word_table=None, entity_table=None, context_table=None):
+        super().__init__(config, word_table)
+        self.max_title_length = config.max_title_length
+        self.cnn_kernel_num = config.cnn_kernel_num
+        self.entity_embedding_dim = config.entity_embedding_dim
+        self.context_embedding_dim = config.context_embedding_dim
+        self.entity_embedding = nn.Embedding(num_embeddings=config.entity_size, embedding_dim=self.entity_embedding_dim)
+        self.context_embedding = nn.Embedding(num_embeddings=config.entity_size, embedding_dim=self.context_embedding_dim)
+        for emb, table, fname in ((self.entity_embedding, entity_table, 'entity_embedding-%s.pkl' % config.dataset),
+                                  (self.context_embedding, context_table, 'context_embedding-%s.pkl' % config.dataset)):
+            if table is None and os.path.exists(fname):              # the reference's behaviour (newsEncoders.py:212-215)
+                with open(fname, 'rb') as f:
+                    table = pickle.load(f)
+            if table is not None:
+                emb.weight.data.copy_(table)
+        self.M_entity = nn.Linear(self.entity_embedding_dim, self.word_embedding_dim, bias=True)
+        self.M_context = nn.Linear(self.context_embedding_dim, self.word_embedding_dim, bias=True)
+        self.knowledge_cnn = Conv2D_Pool(config.cnn_method, config.word_embedding_dim, config.cnn_kernel_num, config.cnn_window_size, 3)
+        self.news_embedding_dim = config.cnn_kernel_num + config.category_embedding_dim + config.subCategory_embedding_dim
+
+    def initialize(self):
+        super().initialize()
+        gain = nn.init.calculate_gain('tanh')
+        for lin in (self.M_entity, self.M_context):
+            nn.init.xavier_uniform_(lin.weight, gain=gain)
+            nn.init.zeros_(lin.bias)
+
+    def forward(self, title_text, title_mask, title_entity, content_text, content_mask, content_entity, category, subCategory, user_embedding):
+        from . import functional as Fn
+        B, N = title_text.shape[:2]
+        n, Lx = B * N, self.max_title_length
+        p = self.dropout_rate if self.training else 0.0
+        seed = self._next_seed()
+        table = self.word_embedding.weight
+        text, entity = _i32(title_text).reshape(n * Lx).contiguous(), _i32(title_entity).reshape(n * Lx).contiguous()
+        rep = Fn.KcnnFn.apply(table, self, text, entity, n, Lx, torch.is_grad_enabled() and table.requires_grad)        # [n, C]
+        return Fn.FuseFn.apply(rep, self, category, subCategory, p, seed).view(B, N, self.news_embedding_dim)

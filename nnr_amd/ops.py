@@ -1540,6 +1540,61 @@ def row_dist_bwd(a, b, dist, gup, coef, da, db):
                                          db.stride(0), _s()), 'nnr_row_dist_bwd')
 
 
+# ---------------------------------------------------------------------------------------------- KCNN / DKN (csrc/kcnn.hip)
+KCNN_UNSUPPORTED = 'unsupported size (max_title_length + cnn_window_size - 1 > 255, cnn_window_size > 8 or > max_title_length, or word_embedding_dim > 1024)'
+
+
+def _kcnn_check(rc, what):
+    if rc == -3:
+        raise L.NnrHipError('%s: %s' % (what, KCNN_UNSUPPORTED))
+    L.check(rc, what)
+
+
+def kcnn_image_fwd(table, text, pre1, pre2, n, Lx, w, Xp):
+    """Xp [n, Lx + w - 1, 3, E]: zero halo rows, [word row | tanh(pre1) | tanh(pre2)] per title position (include/nnr_hip.h)."""
+    V, E = table.shape
+    # per padded row 3 E floats written; per title position an id, a table row and two pre-activation rows read
+    with _hbm_span('kcnn_image_fwd', 3 * 4.0 * E, n * (Lx + w - 1), fixed=(3 * 4.0 * E + 4.0) * n * Lx):
+        _kcnn_check(L.lib().nnr_kcnn_image_fwd(_p(table), V, _p(text), _p(pre1), _p(pre2), n, Lx, E, w, _p(Xp), _s()), 'nnr_kcnn_image_fwd')
+
+
+def kcnn_image_bwd(dXp, Xp, n, Lx, E, w, dx0, dpre1, dpre2):
+    """dx0 / dpre1 / dpre2 [n * Lx, E] from the padded gradient image (the tanh derivative from the forward image's channels 1 and 2)."""
+    with _hbm_span('kcnn_image_bwd', (3 + 2 + 3) * 4.0 * E, n * Lx):
+        _kcnn_check(L.lib().nnr_kcnn_image_bwd(_p(dXp), _p(Xp), n, Lx, E, w, _p(dx0), _p(dpre1), _p(dpre2), _s()), 'nnr_kcnn_image_bwd')
+
+
+def window_max_fwd(z, ldz, bias, n, C, Lx, w, out, arg):
+    """out [n, C] = relu-then-max over the first Lx - w + 1 positions of z + bias, arg [n, C] uint8 (255: no positive maximum)."""
+    with _hbm_span('window_max_fwd', 4.0 * C * (Lx - w + 1) + 5.0 * C, n):
+        _kcnn_check(L.lib().nnr_window_max_fwd(_p(z), ldz, _p(bias), n, C, Lx, w, _p(out), _p(arg), _s()), 'nnr_window_max_fwd')
+
+
+def window_max_bwd(g, arg, n, C, Lx, w, lead, dz, db):
+    """dz [lead + n * (Lx + w - 1), C] written densely, db [C] written (fixed-order column sum of the gradients that reached a position)."""
+    ws = torch.empty(max(1, L.lib().nnr_window_max_bwd_ws_floats(n, C)), device=g.device, dtype=torch.float32)
+    tape_keep(ws)
+    with _hbm_span('window_max_bwd', 4.0 * C * (Lx + w - 1) + 5.0 * C, n):
+        _kcnn_check(L.lib().nnr_window_max_bwd(_p(g), _p(arg), n, C, Lx, w, lead, _p(dz), _p(db), _p(ws), _s()), 'nnr_window_max_bwd')
+
+
+def kcnn_repack(src, out, C, E, w, mode):
+    """The Conv2d weight [C, E, w, 3] -> mode 0: [C, w, 3, E] | mode 1: [3, E, w (reversed), C]; mode 2: out [C, E, w, 3] += src [C, w, 3, E]."""
+    assert src.is_contiguous() and out.is_contiguous() and src.numel() == out.numel() == C * E * w * 3
+    _kcnn_check(L.lib().nnr_kcnn_repack(_p(src), _p(out), C, E, w, mode, _s()), 'nnr_kcnn_repack')
+
+
+def kcnn_weight(weight, mode):
+    """P [C, 3 w E] (mode 0) or Q [3 E, w C] (mode 1) of the Conv2d weight [C, E, w, 3]: the B operand of the convolution product or of its
+    data gradient, an entry of the derived-weight cache (repacked once per parameter version, by the first of the two encoder calls that
+    asks; its bf16x3 images follow it)."""
+    C_, E, w, _ = weight.shape
+    shape = (C_, 3 * w * E) if mode == 0 else (3 * E, w * C_)
+    e = _derived('kcnn_q' if mode else 'kcnn_p', weight, (C_, E, w), lambda: torch.empty(shape, device=weight.device, dtype=torch.float32), False)
+    _serve(e, (weight,), lambda: kcnn_repack(weight, e.out, C_, E, w, mode))
+    return e.out
+
+
 def fill_zero(t):
     """t.zero_() as an entry point of the library (hipMemsetAsync on the current stream): part of the launch tape."""
     assert t.is_contiguous()

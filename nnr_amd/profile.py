@@ -147,6 +147,8 @@ HBM_KERNELS_OTHER = {
     'pers_attn_fwd': (('pers_attn_fwd_kernel',), 1), 'pers_attn_bwd': (('pers_attn_bwd_kernel', 'pers_attn_user_sum_kernel'), 2),
     'bag_mean_fwd': (('bag_mean_fwd_kernel',), 1), 'bag_mean_bwd': (('bag_mean_bwd_kernel', 'bag_mean_bwd_fix_kernel'), 2),
     'row_dist_fwd': (('row_dist_fwd_kernel',), 1), 'row_dist_bwd': (('row_dist_bwd_kernel',), 1),
+    'kcnn_image_fwd': (('kcnn_image_fwd_kernel',), 1), 'kcnn_image_bwd': (('kcnn_image_bwd_kernel',), 1),
+    'window_max_fwd': (('window_max_fwd_kernel',), 1), 'window_max_bwd': (('window_max_bwd_kernel', 'window_max_db_kernel'), 2),
     'omap_fwd': (('omap_alpha_kernel', 'omap_mix_kernel', 'omap_pool_kernel'), 3),
     'omap_bwd': (('omap_bwd_pool_kernel', 'omap_bwd_dalpha_kernel', 'omap_bwd_dx_kernel', 'omap_dw_reduce_kernel'), 4),
 }

@@ -157,8 +157,17 @@ def run_bow():
     run('tiny_Inception_ATT', 'Inception', 'ATT', False, min_gap=1e-3, category_embedding_dim=16, subCategory_embedding_dim=16)
 
 
+def run_kcnn():
+    """`python tools/make_eval_goldens.py kcnn`: the KCNN news encoder under CATT.  The tiny tree names an entity in every third title and
+    holds both .vec files: the corpus writes the two knowledge pickles the reference's KCNN reads."""
+    run('tiny_KCNN_CATT', 'KCNN', 'CATT', False, min_gap=1e-3)
+
+
 if __name__ == '__main__':
     torch.set_num_threads(4)
+    if len(sys.argv) > 1 and sys.argv[1] == 'kcnn':
+        run_kcnn()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'npa':
         run_npa()
         sys.exit(0)
@@ -179,3 +188,4 @@ if __name__ == '__main__':
         run('tiny_CNE_OMAP_stable', 'CNE', 'OMAP', True, min_gap=1e-3, **omap)
     run_npa()
     run_bow()
+    run_kcnn()

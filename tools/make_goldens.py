@@ -18,6 +18,7 @@ Usage:  python tools/make_goldens.py            (rewrites every fixture)
         python tools/make_goldens.py omap       (the OMAP user encoder)
         python tools/make_goldens.py npa        (the PNE news encoder and the PUE user encoder on the user-id embedding path)
         python tools/make_goldens.py bow        (the DAE and Inception bag-of-words news encoders)
+        python tools/make_goldens.py kcnn       (the KCNN news encoder of DKN, with entity ids written into the batches)
 """
 import os
 import pickle
@@ -50,6 +51,11 @@ def build_reference_model(cfg, word_table):
                                                          cfg.max_title_length, cfg.max_abstract_length, cfg.dataset)
         with open(name, 'wb') as f:
             pickle.dump(torch.from_numpy(word_table), f)
+        if cfg.news_encoder == 'KCNN':          # newsEncoders.py:212-215 unpickles both knowledge tables too (make_state overwrites them)
+            rngk = np.random.default_rng(cfg.entity_size)
+            for kind, dim in (('entity', cfg.entity_embedding_dim), ('context', cfg.context_embedding_dim)):
+                with open('%s_embedding-%s.pkl' % (kind, cfg.dataset), 'wb') as f:
+                    pickle.dump(torch.from_numpy((0.1 * rngk.standard_normal((cfg.entity_size, dim))).astype(np.float32)), f)
         try:
             m = ref_model.Model(cfg)
         finally:
@@ -107,9 +113,10 @@ class record_dropout:
         self.F.dropout = self.orig
 
 
-def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True, adam_steps=3, dropout_seed=None, _rec_drop=None, user_ids=None, f64_step=False):
+def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True, adam_steps=3, dropout_seed=None, _rec_drop=None, user_ids=None, f64_step=False, entity_seed=None):
     """mode: 'train' (dropout_rate must be 0 unless dropout_seed is given) or 'eval' (for MHSA-user's hard-wired F.dropout).
-    user_ids: the batch's user_ID (int64 [batch_size]) instead of the synthetic corpus's arange -- the personalised encoders read it."""
+    user_ids: the batch's user_ID (int64 [batch_size]) instead of the synthetic corpus's arange -- the personalised encoders read it.
+    entity_seed: write entity ids into the batch's title_entity fields (tests/kcnn_ref.py:fill_entities; the synthetic corpus leaves them zero)."""
     if dropout_seed is not None:
         assert adam_steps == 1 and mode == 'train'
         with record_dropout(dropout_seed) as rec_drop:
@@ -119,6 +126,9 @@ def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True
     batch = corpus.batch(batch_size, np.random.default_rng(seed + 100))
     if user_ids is not None:
         batch['user_ID'] = np.asarray(user_ids, dtype=np.int64).reshape(batch_size)
+    if entity_seed is not None:
+        from kcnn_ref import fill_entities
+        fill_entities(batch, cfg.entity_size, entity_seed)
     rngw = np.random.default_rng(seed + 7)
     table = (rngw.standard_normal((cfg.vocabulary_size, cfg.word_embedding_dim)) * 0.3).astype(np.float32)
     table[0] = 0
@@ -200,6 +210,9 @@ def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True
         m64.train() if mode == 'train' else m64.eval()
         rec64 = []
         m64.news_encoder.register_forward_hook(lambda mod, i, o: rec64.append(o.detach().clone().numpy()))
+        conv64 = []
+        if cfg.news_encoder == 'KCNN':          # the raw convolution outputs of both calls as [titles, positions, C]: the argmax margins
+            m64.news_encoder.knowledge_cnn.conv.register_forward_hook(lambda mod, i, o: conv64.append(o.detach().squeeze(3).permute(0, 2, 1).clone().numpy()))
         logits64 = m64(*to_torch(batch))
         loss64 = (-torch.log_softmax(logits64, dim=1).select(dim=1, index=0)).mean()
         for e in (m64.news_encoder, m64.user_encoder):
@@ -209,6 +222,8 @@ def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True
         loss64.backward()
         out['f64/logits'], out['f64/loss'] = logits64.detach().numpy().copy(), np.float64(float(loss64.detach()))
         out['f64/cand_rep'], out['f64/hist_rep'] = rec64[0], rec64[1]
+        if conv64:
+            out['f64/kcnn/z_cand'], out['f64/kcnn/z_hist'] = conv64[0], conv64[1]
         for k, p in m64.named_parameters():
             out['f64/grad/' + k] = p.grad.detach().numpy().copy()
     out['word_table'] = table if gain is None else np.zeros(0, np.float32)
@@ -479,7 +494,64 @@ def bow_cases():
     check('full_Inception_ATT_g1p0', cfg)
 
 
+KCNN_TINY = dict(entity_size=9, entity_embedding_dim=10, context_embedding_dim=6)     # (neither knowledge dimension a multiple of 4)
+KCNN_MARGIN = 1e-3
+
+
+def kcnn_cases():
+    """The KCNN news encoder (`python tools/make_goldens.py kcnn`; newsEncoders.py:203-241) under the CATT and ATT user encoders, make_state
+    weights (gain 2.0 tiny, 1.0 full), three Adam steps.  The reference's KCNN unpickles both knowledge tables from the working directory:
+    build_reference_model writes random ones beside the word table.  The batches get entity ids (tests/kcnn_ref.py:fill_entities): non-zero
+    on about a fifth of the positions, 9 distinct ids (repeats across titles), a quarter of the titles without any.  The tiny fixtures also
+    hold step 0 of a float64 run of the same classes with the raw convolution outputs of both calls.  Asserted below on the tiny cases: in
+    that float64 run every (title, channel) with a positive maximum has its runner-up at least KCNN_MARGIN of the tensor's scale below it
+    (an fp32 argmax flip cannot excuse a mismatch; tests/test_kcnn_host.py asserts the same) -- the runner-up among the positions whose window
+    has other content: an all-PAD history slot has identical interior windows, equal in any precision and interchangeable --, some maxima sit at the first and at the last
+    pooled position and some (title, channel) pairs have none; the convolution, both projections and all three tables each carry at least
+    1 % of the total gradient norm.  Seeds: the first of those tried that pass."""
+    from kcnn_ref import margins
+
+    def check(tag, cfg):
+        z = np.load(os.path.join(OUT, tag + '.npz'))
+        total = float(z['grad_total_norm'])
+        for k in ('knowledge_cnn.conv.weight', 'M_entity.weight', 'M_context.weight', 'word_embedding.weight', 'entity_embedding.weight', 'context_embedding.weight'):
+            share = float(z['gradnorm/news_encoder.' + k]) / total
+            print('  %s: |g| / |g_total| = %.4f' % (k, share))
+            assert not tag.startswith('tiny_') or share >= 0.01, (tag, k, share)
+        ent = np.concatenate([z['in/news_title_entity'].reshape(-1, cfg.max_title_length), z['in/user_title_entity'].reshape(-1, cfg.max_title_length)])
+        print('  %s: entity ids on %.3f of the positions, %d of %d titles without any' % (tag, float((ent != 0).mean()), int((ent != 0).sum(1).__eq__(0).sum()), len(ent)))
+        assert 0.1 <= float((ent != 0).mean()) <= 0.3 and int(((ent != 0).sum(1) == 0).sum()) >= 2
+        if not tag.startswith('tiny_'):
+            return True
+        ok = True
+        for call, pre in (('cand', 'news'), ('hist', 'user')):
+            zz = torch.from_numpy(z['f64/kcnn/z_' + call])
+            top, gap, arg = margins(zz, cfg.cnn_window_size, z['in/%s_title_text' % pre], z['in/%s_title_entity' % pre])
+            scale = float(torch.relu(zz).max())
+            worst = float(gap[top > 0].min()) / scale
+            T = zz.shape[1] - cfg.cnn_window_size + 1
+            arg = arg[top > 0]
+            print('  %s %s: smallest margin %.2e of the scale %.3f; maxima at t = 0: %d, at t = %d: %d, none: %d' %
+                  (tag, call, worst, scale, int((arg == 0).sum()), T - 1, int((arg == T - 1).sum()), int((top <= 0).sum())))
+            ok = ok and worst >= KCNN_MARGIN and (call == 'cand' or (int((arg == 0).sum()) > 0 and int((arg == T - 1).sum()) > 0 and int((top <= 0).sum()) > 0))
+        return ok
+
+    for tag, user, bs, seed, sseed in (('tiny_KCNN_CATT', 'CATT', 4, KCNN_SEEDS['tiny_KCNN_CATT'], 3), ('tiny_KCNN_ATT', 'ATT', 3, KCNN_SEEDS['tiny_KCNN_ATT'], 3)):
+        cfg = tiny_cfg('KCNN', user, **KCNN_TINY)
+        run_case(tag, cfg, tiny_spec(cfg, sseed), batch_size=bs, seed=seed, mode='train', gain=2.0, f64_step=True, entity_seed=seed + 1)
+        assert check(tag, cfg), tag
+    cfg = full_cfg('KCNN', 'CATT', V=400, entity_size=50, entity_embedding_dim=100, context_embedding_dim=100)
+    run_case('full_KCNN_CATT_g1p0', cfg, full_spec(cfg, 9), batch_size=2, seed=17, mode='train', gain=1.0, full_arrays=False, entity_seed=18)
+    check('full_KCNN_CATT_g1p0', cfg)
+
+
+KCNN_SEEDS = {'tiny_KCNN_CATT': 55, 'tiny_KCNN_ATT': 54}      # (53, 54 and 53 miss the margin: 2.3e-4, 4.3e-4 and 1.8e-4 of the scale)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == 'kcnn':
+        torch.set_num_threads(8)
+        return kcnn_cases()
     if len(sys.argv) > 1 and sys.argv[1] == 'bow':
         torch.set_num_threads(8)
         return bow_cases()
