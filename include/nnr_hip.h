@@ -188,7 +188,8 @@ int nnr_lstm_bwd(const nnr_lstm_problem* probs, int nprob, int H, hipStream_t st
 
 /* ------------------------------------------------------------------------------------------------ attention pooling
  * softmax(mask(score)) . x : the tails of `Attention` (layers.py:169-175) and `ScaledDotProduct_CandidateAttention`
- * (layers.py:197-203), forward and backward; see pool.hip for the layouts. */
+ * (layers.py:197-203), forward and backward; see pool.hip for the layouts.  D <= 1280, L <= 128; D, ldx, ldth and the leading
+ * dimension of every operand whose pointer is set are multiples of 4 (rows move as float4), else NNR_ERR_UNSUPPORTED. */
 typedef struct nnr_pool_args {
   const float* x; int ldx; int D; int n; int L;
   int packed;                                /* 1: time-major packed rows (off/slen/order), 0: dense [n, L, D] */

@@ -564,6 +564,10 @@ static int pool_check(const nnr_pool_args* p) {
   if (!p || !p->x || p->n <= 0) return NNR_ERR_ARG;
   if ((p->D & 3) || p->D > 4 * 64 * MAXV_ALL || (p->ldx & 3)) return NNR_ERR_UNSUPPORTED;
   if (p->L > 64 * MAXT) return NNR_ERR_UNSUPPORTED;
+  // every per-sequence / per-token vector is read or written as float4: a leading dimension that is in use must keep rows 16-byte aligned
+  auto odd = [](const void* ptr, int ld) { return ptr != nullptr && (ld & 3) != 0; };
+  if (odd(p->v, p->ldv) || odd(p->out, p->ldo) || odd(p->add_in, p->ldadd) || odd(p->dout, p->lddo) || odd(p->dout2, p->lddo2) ||
+      odd(p->dx, p->lddx) || odd(p->dv, p->lddv) || odd(p->dout_b, p->lddo_b) || odd(p->v_b, p->ldv_b)) return NNR_ERR_UNSUPPORTED;
   if (p->packed && (!p->off || !p->slen || !p->order)) return NNR_ERR_ARG;
   if (!p->v && !p->score && !p->alpha && !p->th) return NNR_ERR_ARG;
   if (p->th && (!p->w2 || p->A <= 0 || p->A > 256 || (p->A & 3) || (p->ldth & 3))) return NNR_ERR_UNSUPPORTED;
@@ -615,6 +619,6 @@ extern "C" int nnr_attn_pool_bwd(const nnr_pool_args* p, hipStream_t stream) {
   int rc = pool_check(p);
   if (rc != NNR_OK) return rc;
   if (!p->dout || !p->alpha) return NNR_ERR_ARG;
-  if (p->alpha_b && (!p->dout_b || !p->dscore_b || !p->v_b || !p->dx || p->dx_accumulate || (p->lddo_b & 3) || (p->ldv_b & 3))) return NNR_ERR_ARG;
+  if (p->alpha_b && (!p->dout_b || !p->dscore_b || !p->v_b || !p->dx || p->dx_accumulate)) return NNR_ERR_ARG;
   return pool_launch<true>(p, stream);
 }

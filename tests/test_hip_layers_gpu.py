@@ -109,3 +109,83 @@ def test_gcn_standalone_forward_backward(layer_norm, residual):
     rp = dict(ref.named_parameters())
     for k, p in mod.named_parameters():
         _close(p.grad, rp[k].grad, tol=1e-4, what='d ' + k)
+
+
+def _additive_pair(F, A, seed):
+    """The oracle's AdditivePool in float64 (with a non-zero b1) and the package's Attention holding the same parameters."""
+    from nnr_amd.layers import Attention
+    from oracle.nnr_oracle import AdditivePool
+    torch.manual_seed(seed)
+    ref = AdditivePool(F, A).double()
+    ref.initialize()
+    with torch.no_grad():
+        ref.affine1.bias.normal_(0, 0.1)
+    mod = Attention(F, A)
+    mod.load_state_dict({k: v.float() for k, v in ref.state_dict().items()})
+    return ref, mod.cuda()
+
+
+def _additive_param_grads(mod, ref):
+    rp = dict(ref.named_parameters())
+    assert sorted(k for k, _ in mod.named_parameters()) == ['affine1.bias', 'affine1.weight', 'affine2.weight']
+    for k, p in mod.named_parameters():           # dW1, db1, dw2
+        _close(p.grad, rp[k].grad, tol=5e-5, what='d ' + k)
+
+
+@pytest.mark.parametrize('masked', [False, True])
+def test_attention_standalone_forward_backward(masked):
+    """`Attention` (layers.py:151-175) on a dense feature: tanh GEMM, w2 row-dot, the dense pool with mask_div = 1.  The mask has a fully
+    masked row (uniform alpha, no score gradient), a fully live one, one with only the last and one with only the first position live."""
+    import pool_ref as R
+    n, Lx, F, A = 9, 20, 260, 200
+    ref, mod = _additive_pair(F, A, 7)
+    x, dout = torch.randn(n, Lx, F), torch.randn(n, F)
+    mask = R.hole_mask(n, Lx, 11) if masked else None
+    xr = x.double().requires_grad_(True)
+    want = ref(xr, mask)
+    want.backward(dout.double())
+    xg = x.cuda().requires_grad_(True)
+    out = mod(xg, mask.cuda() if masked else None)
+    _close(out, want, what='attention')
+    if masked:
+        _close(out[0], x[0].double().mean(0), what='attention over a fully masked row')
+    out.backward(dout.cuda())
+    torch.cuda.synchronize()
+    _close(xg.grad, xr.grad, tol=5e-5, what='d feature')
+    _additive_param_grads(mod, ref)
+
+
+@pytest.mark.parametrize('A', [200, 264])
+def test_packed_attention_through_mhsa_pack(A):
+    """functional.PackedAttentionFn over the rows functional.MhsaPack keeps (ops.mask_cover of the hole mask), against AdditivePool on the
+    dense input with the original mask.  A = 200: the score is the pool's own th . w2 row-dot; A = 264 (> 256): nnr_rowdot, then the pool
+    with a given score.  Lengths on every body of the packed pool; row 0 is fully masked and keeps all L positions."""
+    import pool_ref as R
+    from nnr_amd import functional as Fn
+    n, Lx, F = 11, 40, 260
+    lens = [40, 33, 32, 9, 20, 8, 5, 1, 8, 2, 3]
+    g = torch.Generator().manual_seed(13)
+    mask = (torch.rand(n, Lx, generator=g) < 0.6) & (torch.arange(Lx)[None, :] < torch.tensor(lens)[:, None])
+    mask[torch.arange(n), torch.tensor(lens) - 1] = True
+    mask[0] = False
+    assert R.cover_lens(mask) == lens and not bool(mask[1:, :].all(dim=1).any())
+    ref, mod = _additive_pair(F, A, 17)
+    x, dout = torch.randn(n, Lx, F, generator=g), torch.randn(n, F, generator=g)
+    xr = x.double().requires_grad_(True)
+    want = ref(xr, mask)
+    want.backward(dout.double())
+    md = mask.cuda()
+    pack = Fn.MhsaPack(md, torch.zeros((n, Lx), dtype=torch.int32, device='cuda'))
+    plan = pack.plan
+    assert plan.len.cpu().tolist() == lens
+    rows = R.packed_rows(plan.off, plan.rank, Lx)
+    live = torch.arange(Lx)[None, :] < torch.tensor(lens)[:, None]
+    xp = R.pack(x, rows, live, plan.cap).cuda().requires_grad_(True)          # NaN in the rows at and beyond the plan's total
+    out = Fn.PackedAttentionFn.apply(xp, mod, md, pack)
+    _close(out, want, what='packed attention')
+    _close(out[0], x[0].double().mean(0), what='packed attention over a fully masked title')
+    out.backward(dout.cuda())
+    torch.cuda.synchronize()
+    assert float(xr.grad[~live].abs().max()) == 0.0                           # nothing reaches a position the cover drops
+    _close(R.unpack(xp.grad, rows, live, F), xr.grad, tol=5e-5, what='d feature')
+    _additive_param_grads(mod, ref)
