@@ -457,6 +457,56 @@ int nnr_window_max_bwd(const float* g, const uint8_t* arg, int n, int C, int L, 
                        hipStream_t stream);
 int nnr_kcnn_repack(const float* in, float* out, int C, int E, int w, int mode, hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------------ HDC (csrc/hdc.hip)
+ * The kernels around the dilated convolutions of the HDC news encoder (newsEncoders.py:244-278), which run as accumulating products of
+ * nnr_gemm_f32.  Activations are position-major: n news of S = L + 2 rows (category row, subCategory row, L title word rows) of C floats,
+ * compact [n][S][C] or padded [n][S + 2 pad][C] with `pad` zero halo rows on both sides of every news.  All fp32, no float atomics.
+ * nnr_hdc_seq_fwd: d0 [n][S][E] and d0p [n][S + 2 pad][E] from the three tables (text int32 [n, L], category / subCategory int32 [n]; an id
+ *   outside its table: a zero row); tok_word / tok_cat / tok_sub int32 [n S]: the id at the rows that came from that table, -1 elsewhere
+ *   (sorted by nnr_token_sort they are the occurrence lists of the three table gradients).
+ * nnr_hdc_ln_relu_fwd: LayerNorm([F, S]) + ReLU per news.  z: z_rows >= S rows of F floats per news, rows [0, S) are read; mean and
+ *   variance over all S F values (two passes), gamma / beta [F][S] read in place; y [n][S][F]; y_padded (optional) [n][S + 2 pad][F] with
+ *   zero halo rows; stats [n][2] = mean, 1 / sqrt(var + eps).
+ * nnr_hdc_ln_relu_bwd: IN PLACE on z: rows [0, S) of every news become the gradient of the LayerNorm input, rows [S, z_rows) zero;
+ *   dgamma / dbeta [F][S] += sums over the news in a fixed order (partials of 32 news in ws, nnr_hdc_ln_bwd_ws_floats floats).
+ * nnr_hdc_unpad_add: out [n][S][C] = a [n][S][C] (may be NULL) + rows [pad, pad + S) of b_padded [n][S + 2 pad][C].
+ * nnr_hdc_repack, of a Conv1d weight W [F][C][w] and its tap-major form P [w][F] with rows of ldp >= C floats (C used):  mode 0: out = P;
+ *   mode 1: out [F][C][w] += in = P. */
+int nnr_hdc_seq_fwd(const float* word_table, int V, const float* cat_table, int ncat, const float* sub_table, int nsub, const int* text,
+                    const int* category, const int* subCategory, int n, int L, int E, int pad, float* d0, float* d0p, int* tok_word,
+                    int* tok_cat, int* tok_sub, hipStream_t stream);
+int nnr_hdc_ln_relu_fwd(const float* z, int z_rows, const float* gamma, const float* beta, int n, int S, int F, float eps, float* y,
+                        float* y_padded, int pad, float* stats, hipStream_t stream);
+size_t nnr_hdc_ln_bwd_ws_floats(int n, int S, int F);
+int nnr_hdc_ln_relu_bwd(const float* dy, const float* y, float* z, int z_rows, const float* stats, const float* gamma, int n, int S, int F,
+                        float* dgamma_accum, float* dbeta_accum, float* ws, hipStream_t stream);
+int nnr_hdc_unpad_add(const float* a, const float* b_padded, int n, int S, int pad, int C, float* out, hipStream_t stream);
+int nnr_hdc_repack(const float* in, float* out, int F, int C, int w, int ldp, int mode, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------ FIM (csrc/fim.hip)
+ * Conv3d(Cin -> Cout, kernel K^3) + bias + ELU + MaxPool3d(size P, stride St) in one launch (userEncoders.py:257-260); the dense
+ * convolution output is never stored.  The input is addressed through strides in floats: element (image, channel, depth, row, column) at
+ * image sxi + channel sxc + depth sxd + row sxh + column sxw.  Pooled sizes per axis: (in - K + 1 - P) / St + 1; convolution positions
+ * that no pool cell reads are not computed.  y / arg: [imgs][PD][PH][PW][Cout] (cf_out == 0) or [imgs][Cout][PD][PH][PW] (cf_out == 1);
+ * y = elu(maximum of the cell), arg (uint8) = (depth offset P + row offset) P + column offset of the LOWEST position in that scan order
+ * that attains it (positions with equal windows give equal bits).
+ * nnr_conv3d_repack of W [Cout][Cin][K][K][K]: mode 0 -> [Cin][K^3][Cout rounded up to 4] (the forward operand), mode 1 ->
+ *   [Cout][K^3][Cin rounded up to 4] (the input-gradient operand); pad entries zero.
+ * nnr_conv3d_pool_bwd: g = dy (1 if y > 0 else y + 1) reaches the one position arg names.  dw_accum [Cout][Cin][K^3] and db_accum [Cout]
+ *   += per-workgroup partials (ws, nnr_conv3d_pool_bwd_ws_floats floats) added in workgroup order; dx (same strides as x; may be NULL)
+ *   is written once per element by a gather.  No float atomics: the same bits on every run.
+ * NNR_ERR_UNSUPPORTED (nothing written) when K > 4, P > 4, St < P (overlapping windows), an axis is left without a pool cell, or the
+ * staged slab (Cin K^3 Cout weights + one row of cells) exceeds 160 KB of LDS. */
+int nnr_conv3d_pool_dims(int Cin, int D, int H, int W, int Cout, int K, int P, int St, int* PD, int* PH, int* PW);
+int nnr_conv3d_repack(const float* w, float* out, int Cout, int Cin, int K, int mode, hipStream_t stream);
+int nnr_conv3d_pool_fwd(const float* x, long sxi, long sxc, long sxd, long sxh, long sxw, const float* wp, const float* bias, int imgs,
+                        int Cin, int D, int H, int W, int Cout, int K, int P, int St, int cf_out, float* y, uint8_t* arg,
+                        hipStream_t stream);
+size_t nnr_conv3d_pool_bwd_ws_floats(int imgs, int Cin, int D, int H, int W, int Cout, int K, int P, int St);
+int nnr_conv3d_pool_bwd(const float* dy, const float* y, const uint8_t* arg, const float* x, long sxi, long sxc, long sxd, long sxh,
+                        long sxw, const float* wq, int imgs, int Cin, int D, int H, int W, int Cout, int K, int P, int St, int cf_out,
+                        float* dx, float* dw_accum, float* db_accum, float* ws, hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------ device-resident corpus
  * (SURVEY.md section 8 f-1 / f-2).  The corpus tables MIND_Corpus builds (MIND_corpus.py:261-268, 336-353) live in HBM;
  * a training batch is described by behaviour indices + the (1 + K) sampled news ids of each behaviour.

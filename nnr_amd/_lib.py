@@ -141,6 +141,17 @@ SIGNATURES = {
     'nnr_window_max_bwd_ws_floats': 'u64 i32 i32',
     'nnr_window_max_bwd': 'i32 ptr ptr i32 i32 i32 i32 i32 ptr ptr ptr stream',
     'nnr_kcnn_repack': 'i32 ptr ptr i32 i32 i32 i32 stream',
+    'nnr_hdc_seq_fwd': 'i32 ptr i32 ptr i32 ptr i32 ptr ptr ptr i32 i32 i32 i32 ptr ptr ptr ptr ptr stream',
+    'nnr_hdc_ln_relu_fwd': 'i32 ptr i32 ptr ptr i32 i32 i32 f32 ptr ptr i32 ptr stream',
+    'nnr_hdc_ln_bwd_ws_floats': 'u64 i32 i32 i32',
+    'nnr_hdc_ln_relu_bwd': 'i32 ptr ptr ptr i32 ptr ptr i32 i32 i32 ptr ptr ptr stream',
+    'nnr_hdc_unpad_add': 'i32 ptr ptr i32 i32 i32 i32 ptr stream',
+    'nnr_hdc_repack': 'i32 ptr ptr i32 i32 i32 i32 i32 stream',
+    'nnr_conv3d_pool_dims': 'i32 i32 i32 i32 i32 i32 i32 i32 i32 ptr ptr ptr',
+    'nnr_conv3d_repack': 'i32 ptr ptr i32 i32 i32 i32 stream',
+    'nnr_conv3d_pool_fwd': 'i32 ptr i64 i64 i64 i64 i64 ptr ptr i32 i32 i32 i32 i32 i32 i32 i32 i32 i32 ptr ptr stream',
+    'nnr_conv3d_pool_bwd_ws_floats': 'u64 i32 i32 i32 i32 i32 i32 i32 i32 i32',
+    'nnr_conv3d_pool_bwd': 'i32 ptr ptr ptr ptr i64 i64 i64 i64 i64 ptr i32 i32 i32 i32 i32 i32 i32 i32 i32 i32 ptr ptr ptr ptr stream',
     'nnr_corpus_batch': 'i32 CorpusTables BatchOut ptr ptr i32 i32 i32 stream',
     'nnr_history_graph': 'i32 ptr ptr i32 i32 i32 i32 ptr ptr ptr stream',
     'nnr_rank_metrics': 'i32 ptr ptr ptr i32 ptr ptr stream',

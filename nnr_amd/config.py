@@ -17,11 +17,13 @@ _FLAGS = [
     ('subCategory_embedding_dim', int, 50), ('dropout_rate', float, 0.2), ('gcn_normalization_type', str, 'symmetric'), ('gcn_layer_num', int, 4), ('hidden_dim', int, 200),
     ('click_predictor', str, 'dot_product'), ('OMAP_head_num', int, 3), ('HiFi_Ark_regularizer_coefficient', float, 0.1),
     ('Alpha', float, 0.1),
+    ('HDC_window_size', int, 3), ('HDC_filter_num', int, 150), ('conv3D_filter_num_first', int, 32), ('conv3D_kernel_size_first', int, 3),
+    ('conv3D_filter_num_second', int, 16), ('conv3D_kernel_size_second', int, 3), ('maxpooling3D_size', int, 3), ('maxpooling3D_stride', int, 3),
 ]
 _BOOL_FLAGS = ['no_self_connection', 'no_adjacent_normalization', 'no_gcn_residual', 'gcn_layer_norm']
 
-NEWS_ENCODERS = ['CNE', 'CNN', 'MHSA', 'PNE', 'DAE', 'Inception', 'KCNN']       # in scope; the reference lists 15
-USER_ENCODERS = ['SUE', 'MHSA', 'ATT', 'CATT', 'OMAP', 'PUE']  # in scope; the reference lists 11
+NEWS_ENCODERS = ['CNE', 'CNN', 'MHSA', 'PNE', 'DAE', 'Inception', 'HDC', 'KCNN']    # in scope; the reference lists 15
+USER_ENCODERS = ['SUE', 'MHSA', 'ATT', 'CATT', 'OMAP', 'PUE', 'FIM']  # in scope; the reference lists 11
 
 
 def build_parser():

@@ -55,6 +55,8 @@ const Entry REGISTRY[] = {
   R(nnr_user_rows_fwd), R(nnr_user_rows_bwd), R(nnr_pers_attn_fwd), R(nnr_pers_attn_bwd),
   R(nnr_bag_mean_fwd), R(nnr_bag_mean_bwd), R(nnr_row_dist_fwd), R(nnr_row_dist_bwd), R(nnr_sigmoid_drop_bwd),
   R(nnr_kcnn_image_fwd), R(nnr_kcnn_image_bwd), R(nnr_window_max_fwd), R(nnr_window_max_bwd), R(nnr_kcnn_repack),
+  R(nnr_hdc_seq_fwd), R(nnr_hdc_ln_relu_fwd), R(nnr_hdc_ln_relu_bwd), R(nnr_hdc_unpad_add), R(nnr_hdc_repack),
+  R(nnr_conv3d_repack), R(nnr_conv3d_pool_fwd), R(nnr_conv3d_pool_bwd),
 };
 #undef R
 constexpr int NREG = (int)(sizeof(REGISTRY) / sizeof(REGISTRY[0]));

@@ -564,3 +564,166 @@ class ExpandFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         return ops.expand_rows_bwd(dout.contiguous()), None
+
+
+class HdcFn(torch.autograd.Function):
+    """The HDC news encoder (newsEncoders.py:262-278) on position-major activations (csrc/hdc.hip): returns
+    d0 [n, S, E] and dL [3, n, S, F] with S = max_title_length + 2.  Layer l (dilation d = l + 1, window 3, padding d) reads its input with d
+    zero halo rows around every news, so its convolution is three accumulating products of the GEMM family on row pointers shifted by d rows;
+    LayerNorm([F, S]) + ReLU writes the layer's output compact (what the matching images read) and halo-padded (what the next layer reads).
+    Backward: per layer the gradient from the images and the one from the next layer are summed (images first), LayerNorm + ReLU backward
+    runs in place on the saved convolution output, whose zeroed halo rows make the data gradient three accumulating products again; the three
+    table gradients go through the sorted scatter.  Parameter gradients go straight into .grad."""
+
+    @staticmethod
+    def forward(ctx, anchor, enc, text, cat, sub, n, Lx, need_grad):
+        word, cat_t, sub_t = enc.word_embedding.weight, enc.category_embedding.weight, enc.subCategory_embedding.weight
+        convs, norms = enc.dilated_convs(), enc.layer_norms()
+        E, Fn_, S = word.shape[1], enc.HDC_filter_num, Lx + 2
+        dev = word.device
+        f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+        def padded(rows, C_):        # [rows, C]; one spare zero row behind it: the weight gradient reads rows of C rounded up to 4 columns
+            buf = torch.empty((rows + 1, C_), **f32)
+            ops.fill_zero(buf[rows:])
+            return buf[:rows]
+        d0, xp = torch.empty((n, S, E), **f32), padded(n * (S + 2), E)
+        toks = torch.empty((3, n * S), **i32)
+        ops.hdc_seq_fwd(word, cat_t, sub_t, text, cat, sub, n, Lx, 1, d0, xp, toks[0], toks[1], toks[2])
+        sorts = None
+        if need_grad:             # the sorts need nothing but the ids: on the leaf stream, under the forward pass
+            sorts = tuple(ops.TokenSort(toks[j], None, t.shape[0]) for j, t in enumerate((word, cat_t, sub_t)))
+        dL = torch.empty((3, n, S, Fn_), **f32)
+        saved = []
+        for l in range(3):
+            d, Cin = l + 1, xp.shape[1]
+            Sp = S + 2 * d
+            M = n * Sp - 2 * d
+            P = ops.hdc_weight(convs[l].weight)
+            z = torch.empty((n * Sp, Fn_), **f32)
+            for k in range(3):
+                ops.gemm(xp[k * d:], P[k], z, M=M, N=Fn_, K=Cin, lda=Cin, ldb=Cin, ldc=Fn_, bias=convs[l].bias if k == 0 else None, accumulate=k > 0)
+            stats = torch.empty((n, 2), **f32)
+            nxt = padded(n * (S + 2 * (d + 1)), Fn_) if l < 2 else None
+            ops.hdc_ln_relu_fwd(z, Sp, norms[l].weight, norms[l].bias, n, S, Fn_, norms[l].eps, dL[l], nxt, d + 1, stats)
+            saved.append((xp, z, stats) if need_grad else None)
+            xp = nxt
+        ctx.enc, ctx.saved, ctx.dims = enc, (saved, sorts), (n, S, E, Fn_)
+        ctx.save_for_backward(dL)          # (an output: held through autograd, not as an attribute, which would be a reference cycle)
+        return d0, dL
+
+    @staticmethod
+    def backward(ctx, dd0, ddL):
+        enc = ctx.enc
+        saved, sorts = ctx.saved
+        (dL,) = ctx.saved_tensors
+        ctx.saved = None
+        n, S, E, Fn_ = ctx.dims
+        convs, norms = enc.dilated_convs(), enc.layer_norms()
+        dev = ddL.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        ddL = ddL.contiguous()
+        dxp = None                                                    # gradient of layer l + 1's padded input
+        for l in (2, 1, 0):
+            d = l + 1
+            Sp = S + 2 * d
+            M = n * Sp - 2 * d
+            xp, z, stats = saved[l]
+            saved[l] = None
+            Cin = xp.shape[1]
+            dy = ddL[l]
+            if dxp is not None:
+                dy = torch.empty((n, S, Fn_), **f32)
+                ops.hdc_unpad_add(ddL[l], dxp, n, S, d + 1, Fn_, dy)
+            # the affine gradients of this call into a zeroed pair; added to .grad on the leaf stream (a plain read-modify-write: the candidate
+            # call's backward runs on the side stream, the history call's on the main one, and the one leaf stream orders the two adds)
+            dgb = ops.fill_zero(torch.empty((2,) + tuple(norms[l].weight.shape), **f32))
+            ops.hdc_ln_relu_bwd(dy, dL[l], z, Sp, stats, norms[l].weight, n, S, Fn_, dgb[0], dgb[1])
+            gg, gbeta = grad_of(norms[l].weight), grad_of(norms[l].bias)
+            ops.leaf_deferred(dev, n * S, lambda dgb=dgb, gg=gg, gbeta=gbeta: (ops.add_(gg, dgb[0]), ops.add_(gbeta, dgb[1])), dgb, force=True)
+            P = ops.hdc_weight(convs[l].weight)
+            gw, gb = grad_of(convs[l].weight), grad_of(convs[l].bias)
+
+            def weight_grad(xp=xp, z=z, d=d, M=M, Cin=Cin, gw=gw, gb=gb):
+                # rows of Cin rounded up to 4 columns (the extra ones read the next row's head and are dropped): a column count that is a
+                # multiple of 4 takes the split-K products through slabs and a fixed-order reduction, not through float atomics
+                Cp = (Cin + 3) & ~3
+                dP = torch.zeros((3, Fn_, Cp), **f32)
+                for k in range(3):
+                    ops.linear_bwd_weight(z[:M], xp[k * d:].as_strided((M, Cp), (Cin, 1)), dP[k], db=gb if k == 0 else None)
+                ops.hdc_repack(dP, gw, Fn_, Cin, 3, 1, ldp=Cp)
+            ops.leaf_deferred(dev, n * S, weight_grad, z, xp, force=True)
+            dxp = ops.fill_zero(torch.empty((n * Sp, Cin), **f32))
+            for k in range(3):
+                ops.gemm(z, P[k], dxp[k * d:], M=M, N=Cin, K=Fn_, lda=Fn_, ldb=Cin, ldc=Cin, trans_b=True, accumulate=True)
+        dx = torch.empty((n * S, E), **f32)
+        ops.hdc_unpad_add(dd0.contiguous() if dd0 is not None else None, dxp, n, S, 1, E, dx)
+        for ts, tab in zip(sorts, (enc.word_embedding.weight, enc.category_embedding.weight, enc.subCategory_embedding.weight)):
+            ops.embed_scatter_sorted(dx, ts, grad_of(tab), 0.0, 0)
+        return (None,) * 8
+
+
+class FimFn(torch.autograd.Function):
+    """The FIM user encoder (userEncoders.py:244-262): matching images -> two fused Conv3d + ELU + MaxPool3d layers (csrc/fim.hip) ->
+    [B, N, feature_size] in the reference's flatten order.  cand_d0 [B N, S, E], cand_dL [3, B N, S, F], hist_d0 [B H, S, E], hist_dL
+    [3, B H, S, F] (functional.HdcFn's layout).  The images are four batched products of the GEMM family (alpha = 1 / sqrt(F) for level 0
+    too), one plane [B][N S][H S] per level: the first convolution layer reads them through its input strides, channel = level, depth =
+    history slot, row = candidate position, column = history position.  Backward: the two layers' sparse backward passes, then eight
+    batched products for the candidate- and history-side gradients of the four levels."""
+
+    @staticmethod
+    def forward(ctx, cand_d0, cand_dL, hist_d0, hist_dL, enc, B, N, H):
+        S, Fn_ = cand_d0.shape[1], cand_dL.shape[3]
+        cand_d0, cand_dL, hist_d0, hist_dL = cand_d0.contiguous(), cand_dL.contiguous(), hist_d0.contiguous(), hist_dL.contiguous()
+        dev = cand_d0.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        alpha = 1.0 / enc.scalar
+        plane = B * N * S * H * S
+        img = torch.empty((4, plane), **f32)
+        levels = [(cand_d0, hist_d0)] + [(cand_dL[l], hist_dL[l]) for l in range(3)]
+        for l, (c, h) in enumerate(levels):
+            ops.match_images_fwd(c, h, B, N, H, S, alpha, img[l])
+        ca, cb = enc.conv_3D_a, enc.conv_3D_b
+        Ka, Kb, P, St = ca.kernel_size[0], cb.kernel_size[0], enc.pool_size, enc.pool_stride
+        F1, F2, imgs = ca.out_channels, cb.out_channels, B * N
+        strides_a = (S * H * S, plane, S, H * S, 1)
+        da = ops.conv3d_pool_dims(4, H, S, S, F1, Ka, P, St)
+        db = ops.conv3d_pool_dims(F1, da[0], da[1], da[2], F2, Kb, P, St)
+        cells_a, cells_b = da[0] * da[1] * da[2], db[0] * db[1] * db[2]
+        y1 = torch.empty((imgs, cells_a, F1), **f32)
+        a1 = torch.empty((imgs, cells_a, F1), device=dev, dtype=torch.uint8)
+        ops.conv3d_pool_fwd(img, strides_a, ops.conv3d_weight(ca.weight, 0), ca.bias, imgs, 4, H, S, S, F1, Ka, P, St, False, y1, a1)
+        strides_b = (cells_a * F1, 1, da[1] * da[2] * F1, da[2] * F1, F1)
+        y2 = torch.empty((imgs, F2 * cells_b), **f32)
+        a2 = torch.empty((imgs, F2 * cells_b), device=dev, dtype=torch.uint8)
+        ops.conv3d_pool_fwd(y1, strides_b, ops.conv3d_weight(cb.weight, 0), cb.bias, imgs, F1, da[0], da[1], da[2], F2, Kb, P, St, True, y2, a2)
+        ctx.enc, ctx.saved = enc, (levels, img, y1, a1, y2, a2)
+        ctx.dims = (B, N, H, S, Fn_, da, strides_a, strides_b)
+        return y2.view(B, N, F2 * cells_b)
+
+    @staticmethod
+    def backward(ctx, dout):
+        enc = ctx.enc
+        levels, img, y1, a1, y2, a2 = ctx.saved
+        ctx.saved = None
+        B, N, H, S, Fn_, da, strides_a, strides_b = ctx.dims
+        dev = dout.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        ca, cb = enc.conv_3D_a, enc.conv_3D_b
+        Ka, Kb, P, St = ca.kernel_size[0], cb.kernel_size[0], enc.pool_size, enc.pool_stride
+        F1, F2, imgs = ca.out_channels, cb.out_channels, B * N
+        dout = dout.contiguous()
+        dy1 = torch.empty_like(y1)
+        ops.conv3d_pool_bwd(dout, y2, a2, y1, strides_b, ops.conv3d_weight(cb.weight, 1), imgs, F1, da[0], da[1], da[2], F2, Kb, P, St, True, dy1,
+                            grad_of(cb.weight), grad_of(cb.bias))
+        dimg = torch.empty_like(img)
+        ops.conv3d_pool_bwd(dy1, y1, a1, img, strides_a, ops.conv3d_weight(ca.weight, 1), imgs, 4, H, S, S, F1, Ka, P, St, False, dimg,
+                            grad_of(ca.weight), grad_of(ca.bias))
+        del img, dy1
+        alpha = 1.0 / enc.scalar
+        E = levels[0][0].shape[2]
+        dc0, dh0 = torch.empty((B * N, S, E), **f32), torch.empty((B * H, S, E), **f32)
+        dcL, dhL = torch.empty((3, B * N, S, Fn_), **f32), torch.empty((3, B * H, S, Fn_), **f32)
+        for l, (c, h) in enumerate(levels):
+            dc, dh = (dc0, dh0) if l == 0 else (dcL[l - 1], dhL[l - 1])
+            ops.match_images_bwd(dimg[l], c, h, B, N, H, S, alpha, dc, dh)
+        return dc0, dcL, dh0, dhL, None, None, None, None

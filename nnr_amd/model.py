@@ -56,17 +56,21 @@ class _JoinSideFn(torch.autograd.Function):
     stream back, because those nodes write parameter gradients out of autograd's sight."""
 
     @staticmethod
-    def forward(ctx, x, side):
-        ctx.side, ctx.main = side, torch.cuda.current_stream(x.device)
+    def forward(ctx, side, *xs):
+        ctx.side, ctx.main = side, torch.cuda.current_stream(xs[0].device)
         ctx.main.wait_stream(side)
-        return x.view_as(x)
+        out = tuple(x.view_as(x) for x in xs)        # (a pair for the HDC representation (d0, dL))
+        return out[0] if len(out) == 1 else out
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, *gs):
         side = ctx.side
-        g.record_stream(side)                        # consumed by side-stream kernels after this node's buffer is released
-        torch.autograd.Variable._execution_engine.queue_callback(lambda: ops.join_extra_streams(g.device))
-        return g, None
+        for g in gs:
+            if g is not None:
+                g.record_stream(side)                # consumed by side-stream kernels after this node's buffer is released
+        dev = next(g.device for g in gs if g is not None)
+        torch.autograd.Variable._execution_engine.queue_callback(lambda: ops.join_extra_streams(dev))
+        return (None,) + tuple(gs)
 
 
 def negative_log_softmax(logits):
@@ -76,6 +80,10 @@ def negative_log_softmax(logits):
 class Model(nn.Module):
     def __init__(self, config, word_table=None, entity_table=None, context_table=None):
         super().__init__()
+        if config.news_encoder == 'HDC' or config.user_encoder == 'FIM':
+            # model.py:86-88, ahead of the encoders: there the other user encoders fail on HDC's news_embedding_dim = None before these are reached
+            assert config.news_encoder == 'HDC' and config.user_encoder == 'FIM', 'HDC and FIM must be paired and can not be used alone'
+            assert config.click_predictor == 'FIM', 'For the model FIM, the click predictor must be specially set as \'FIM\''
         if config.news_encoder == 'CNE':
             self.news_encoder = newsEncoders.CNE(config, word_table)
         elif config.news_encoder == 'CNN':
@@ -90,8 +98,10 @@ class Model(nn.Module):
             self.news_encoder = newsEncoders.Inception(config, word_table)
         elif config.news_encoder == 'KCNN':
             self.news_encoder = newsEncoders.KCNN(config, word_table, entity_table, context_table)
+        elif config.news_encoder == 'HDC':
+            self.news_encoder = newsEncoders.HDC(config, word_table)
         else:
-            raise Exception(config.news_encoder + ' is not on the MI355X hot path (in scope: CNE, CNN, MHSA, PNE, DAE, Inception, KCNN; SURVEY.md section 8a)')
+            raise Exception(config.news_encoder + ' is not on the MI355X hot path (in scope: CNE, CNN, MHSA, HDC, PNE, DAE, Inception, KCNN; SURVEY.md section 8a)')
         if config.user_encoder == 'SUE':
             self.user_encoder = userEncoders.SUE(self.news_encoder, config)
         elif config.user_encoder == 'MHSA':
@@ -104,8 +114,10 @@ class Model(nn.Module):
             self.user_encoder = userEncoders.OMAP(self.news_encoder, config)
         elif config.user_encoder == 'PUE':
             self.user_encoder = userEncoders.PUE(self.news_encoder, config)
+        elif config.user_encoder == 'FIM':
+            self.user_encoder = userEncoders.FIM(self.news_encoder, config)
         else:
-            raise Exception(config.user_encoder + ' is not on the MI355X hot path (in scope: SUE, MHSA, ATT, CATT, OMAP, PUE; SURVEY.md section 8a)')
+            raise Exception(config.user_encoder + ' is not on the MI355X hot path (in scope: SUE, MHSA, ATT, CATT, FIM, OMAP, PUE; SURVEY.md section 8a)')
         self.model_name = config.news_encoder + '-' + config.user_encoder
         self.news_embedding_dim = self.news_encoder.news_embedding_dim
         self.dropout = nn.Dropout(p=config.dropout_rate)                    # (model.py:77: part of the attribute surface; the user rows'
@@ -118,9 +130,26 @@ class Model(nn.Module):
             self.user_embedding = nn.Embedding(num_embeddings=config.user_num, embedding_dim=config.user_embedding_dim)
             self._user_seed_base = int(getattr(config, 'seed', 0)) * 6151 + 43
             self._user_calls = 0
-        if config.click_predictor != 'dot_product':
-            raise Exception('click_predictor=%s is out of scope (dot_product only, model.py:126-127)' % config.click_predictor)
+        if config.click_predictor != ('FIM' if config.user_encoder == 'FIM' else 'dot_product'):
+            raise Exception('click_predictor=%s is out of scope (dot_product, and FIM with the HDC / FIM pair; model.py:126-132)' % config.click_predictor)
         self.click_predictor = config.click_predictor
+        if self.click_predictor == 'FIM':                                                 # model.py:93-105
+            ue = self.user_encoder
+            S, H = self.news_encoder.HDC_sequence_length, config.max_history_num
+            first = (ue.conv_3D_a.out_channels, ue.conv_3D_a.kernel_size[0])
+            second = (ue.conv_3D_b.out_channels, ue.conv_3D_b.kernel_size[0])
+
+            def pooled(size):
+                conv1 = size - first[1] + 1
+                pool1 = (conv1 - ue.pool_size) // ue.pool_stride + 1
+                conv2 = pool1 - second[1] + 1
+                return (conv2 - ue.pool_size) // ue.pool_stride + 1
+            feature_size = pooled(S) * pooled(S) * pooled(H) * second[0]
+            # every limit of the fused layers (csrc/fim.hip), LDS footprint included, here and not at the first forward
+            da = ops.conv3d_pool_plan(4, H, S, S, first[0], first[1], ue.pool_size, ue.pool_stride)
+            if da is None or ops.conv3d_pool_plan(first[0], da[0], da[1], da[2], second[0], second[1], ue.pool_size, ue.pool_stride) is None:
+                raise Exception('HDC-FIM: ' + ops.FIM_UNSUPPORTED)
+            self.fc = nn.Linear(in_features=feature_size, out_features=1, bias=True)
 
     def initialize(self):
         self.news_encoder.initialize()
@@ -129,6 +158,9 @@ class Model(nn.Module):
             nn.init.uniform_(self.user_embedding.weight, -0.1, 0.1)
             with torch.no_grad():
                 self.user_embedding.weight[0].zero_()
+        if self.click_predictor == 'FIM':                                   # model.py:116-118
+            nn.init.xavier_uniform_(self.fc.weight)
+            nn.init.zeros_(self.fc.bias)
 
     def user_rows(self, user_ID):
         """dropout(user_embedding(user_ID)) (model.py:122), computed once per forward and handed to both news-encoder calls and to the user
@@ -188,7 +220,10 @@ class Model(nn.Module):
                     news_representation = self.news_encoder(*cand)
                 history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text,
                                                       user_content_mask, user_content_entity, user_category, user_subCategory, user_embedding)
-                news_representation = _JoinSideFn.apply(news_representation, side)
+                if isinstance(news_representation, tuple):
+                    news_representation = _JoinSideFn.apply(side, *news_representation)
+                else:
+                    news_representation = _JoinSideFn.apply(side, news_representation)
                 user_representation = self._encode_user(user_embedding, history_embedding, user_history_mask, user_history_graph,
                                                         user_history_category_mask, user_history_category_indices, news_representation)
             else:
@@ -197,4 +232,8 @@ class Model(nn.Module):
                                                         user_content_mask, user_content_entity, user_category, user_subCategory,
                                                         user_history_mask, user_history_graph, user_history_category_mask,
                                                         user_history_category_indices, user_embedding, news_representation)
+        if self.click_predictor == 'FIM':                                   # model.py:131-132
+            from .functional import LinearFn
+            B, N, D = user_representation.shape
+            return LinearFn.apply(user_representation.reshape(B * N, D), self.fc.weight, self.fc.bias, ops.ACT_NONE, 0.0, 0).view(B, N)
         return _DotProductFn.apply(user_representation, news_representation)

@@ -962,3 +962,49 @@ class KCNN(NewsEncoder):
         text, entity = _i32(title_text).reshape(n * Lx).contiguous(), _i32(title_entity).reshape(n * Lx).contiguous()
         rep = Fn.KcnnFn.apply(table, self, text, entity, n, Lx, torch.is_grad_enabled() and table.requires_grad)        # [n, C]
         return Fn.FuseFn.apply(rep, self, category, subCategory, p, seed).view(B, N, self.news_embedding_dim)
+
+
+class HDC(NewsEncoder):
+    """newsEncoders.py:244-278, the hierarchical dilated convolution of the FIM baseline: d0 = [category row | subCategory row | title word
+    rows] (both category tables at width word_embedding_dim), three dilated Conv1d (dilations 1, 2, 3) each followed by LayerNorm([F, S]) and
+    ReLU (functional.HdcFn, csrc/hdc.hip).  Only valid with the FIM user encoder and click predictor.
+
+    The representation is the reference's pair (d0, dL), held position-major: d0 [B, N, S, E] and dL [3, B, N, S, F] where the reference has
+    [B, N, E, S] and [B, N, 3, F, S] (S = max_title_length + 2); user_encoders.FIM reads this layout.  Observable quirks kept: no dropout and
+    no mask -- PAD positions take part with row 0 of the word table, which is trainable like any other row; `news_embedding_dim` is None;
+    the masks, the entity and content arguments and `user_embedding` are accepted and ignored.  The reference's padding (window - 1) // 2 +
+    dilation - 1 keeps the sequence length only for HDC_window_size == 3 (its LayerNorm fails otherwise): other windows are refused."""
+
+    def __init__(self, config, word_table=None):
+        super().__init__(config, word_table)
+        E, F, w = config.word_embedding_dim, config.HDC_filter_num, config.HDC_window_size
+        if w != 3:
+            raise Exception('HDC_window_size=%d: only 3 keeps the sequence length LayerNorm([HDC_filter_num, max_title_length + 2]) needs' % w)
+        self.category_embedding = nn.Embedding(num_embeddings=config.category_num, embedding_dim=E)
+        self.subCategory_embedding = nn.Embedding(num_embeddings=config.subCategory_num, embedding_dim=E)
+        self.max_title_length = config.max_title_length
+        self.HDC_sequence_length = config.max_title_length + 2
+        self.HDC_filter_num = F
+        self.dilated_conv1 = nn.Conv1d(in_channels=E, out_channels=F, kernel_size=w, padding=(w - 1) // 2, dilation=1)
+        self.dilated_conv2 = nn.Conv1d(in_channels=F, out_channels=F, kernel_size=w, padding=(w - 1) // 2 + 1, dilation=2)
+        self.dilated_conv3 = nn.Conv1d(in_channels=F, out_channels=F, kernel_size=w, padding=(w - 1) // 2 + 2, dilation=3)
+        self.layer_norm1 = nn.LayerNorm([F, self.HDC_sequence_length])
+        self.layer_norm2 = nn.LayerNorm([F, self.HDC_sequence_length])
+        self.layer_norm3 = nn.LayerNorm([F, self.HDC_sequence_length])
+        self.news_embedding_dim = None
+
+    def dilated_convs(self):
+        return (self.dilated_conv1, self.dilated_conv2, self.dilated_conv3)
+
+    def layer_norms(self):
+        return (self.layer_norm1, self.layer_norm2, self.layer_norm3)
+
+    def forward(self, title_text, title_mask, title_entity, content_text, content_mask, content_entity, category, subCategory, user_embedding):
+        from . import functional as Fn
+        B, N = title_text.shape[:2]
+        n, Lx, S = B * N, self.max_title_length, self.HDC_sequence_length
+        table = self.word_embedding.weight
+        text = _i32(title_text).reshape(n * Lx).contiguous()
+        cat, sub = _i32(category).reshape(n).contiguous(), _i32(subCategory).reshape(n).contiguous()
+        d0, dL = Fn.HdcFn.apply(table, self, text, cat, sub, n, Lx, torch.is_grad_enabled() and table.requires_grad)
+        return d0.view(B, N, S, self.word_embedding_dim), dL.view(3, B, N, S, self.HDC_filter_num)

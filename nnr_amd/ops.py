@@ -1595,6 +1595,163 @@ def kcnn_weight(weight, mode):
     return e.out
 
 
+# ---------------------------------------------------------------------------------------------- HDC / FIM (csrc/hdc.hip, csrc/fim.hip)
+FIM_UNSUPPORTED = ('unsupported size (conv3D kernel size > 4, maxpooling3D_size > 4 or > maxpooling3D_stride, an axis left without a pool cell, '
+                   'or weights + one row of pool cells beyond 160 KB of LDS)')
+
+
+def _fim_check(rc, what):
+    if rc == -3:
+        raise L.NnrHipError('%s: %s' % (what, FIM_UNSUPPORTED))
+    L.check(rc, what)
+
+
+def hdc_seq_fwd(word, cat_t, sub_t, text, cat, sub, n, Lx, pad, d0, d0p, tok_w, tok_c, tok_s):
+    """d0 [n, Lx + 2, E] and its halo-padded copy d0p [n, Lx + 2 + 2 pad, E] from the three tables; the three occurrence lists (include/nnr_hip.h)."""
+    E = word.shape[1]
+    # per padded row E floats written; per live row a table row read, a compact row written, an id read and three list entries written
+    with _hbm_span('hdc_seq_fwd', 4.0 * E, n * (Lx + 2 + 2 * pad), fixed=(2 * 4.0 * E + 16.0) * n * (Lx + 2)):
+        L.check(L.lib().nnr_hdc_seq_fwd(_p(word), word.shape[0], _p(cat_t), cat_t.shape[0], _p(sub_t), sub_t.shape[0], _p(text), _p(cat), _p(sub),
+                                        n, Lx, E, pad, _p(d0), _p(d0p), _p(tok_w), _p(tok_c), _p(tok_s), _s()), 'nnr_hdc_seq_fwd')
+
+
+def hdc_ln_relu_fwd(z, z_rows, gamma, beta, n, S, F, eps, y, yp, pad, stats):
+    """y [n, S, F] = relu(LayerNorm([F, S])(z rows [0, S) of every news)); yp (optional): the same with `pad` zero halo rows per side."""
+    with _hbm_span('hdc_ln_relu_fwd', 4.0 * F * (S + S + (S + 2 * pad if yp is not None else 0)) + 8.0, n, fixed=8.0 * F * S):
+        L.check(L.lib().nnr_hdc_ln_relu_fwd(_p(z), z_rows, _p(gamma), _p(beta), n, S, F, eps, _p(y), _p(yp), pad, _p(stats), _s()), 'nnr_hdc_ln_relu_fwd')
+
+
+def hdc_ln_relu_bwd(dy, y, z, z_rows, stats, gamma, n, S, F, dgamma, dbeta):
+    """In place: z becomes the gradient of the LayerNorm input (rows [S, z_rows) of every news zero); dgamma / dbeta [F, S] accumulate."""
+    ws = torch.empty(max(1, L.lib().nnr_hdc_ln_bwd_ws_floats(n, S, F)), device=dy.device, dtype=torch.float32)
+    tape_keep(ws)
+    with _hbm_span('hdc_ln_relu_bwd', 4.0 * F * (2 * 3 * S + z_rows), n, fixed=16.0 * F * S):
+        L.check(L.lib().nnr_hdc_ln_relu_bwd(_p(dy), _p(y), _p(z), z_rows, _p(stats), _p(gamma), n, S, F, _p(dgamma), _p(dbeta), _p(ws), _s()),
+                'nnr_hdc_ln_relu_bwd')
+
+
+def hdc_unpad_add(a, bp, n, S, pad, C_, out):
+    """out [n, S, C] = a (compact, may be None) + the live rows of bp [n, S + 2 pad, C]."""
+    with _hbm_span('hdc_unpad_add', 4.0 * C_ * S * (3 if a is not None else 2), n):
+        L.check(L.lib().nnr_hdc_unpad_add(_p(a), _p(bp), n, S, pad, C_, _p(out), _s()), 'nnr_hdc_unpad_add')
+
+
+def hdc_repack(src, out, F, C_, w, mode, ldp=None):
+    """mode 0: W [F, C, w] -> P [w, F, ldp];  mode 1: W [F, C, w] += P [w, F, ldp] (rows of ldp >= C floats, C of them used)."""
+    ldp = C_ if ldp is None else ldp
+    assert src.is_contiguous() and out.is_contiguous() and (out if mode else src).numel() == F * C_ * w and (src if mode else out).numel() == F * ldp * w
+    L.check(L.lib().nnr_hdc_repack(_p(src), _p(out), F, C_, w, ldp, mode, _s()), 'nnr_hdc_repack')
+
+
+def hdc_weight(weight):
+    """P [w, F, C] of a Conv1d weight [F, C, w]: tap k's [F, C] matrix is the B operand of the k-th accumulating product (an entry of the
+    derived-weight cache: repacked once per parameter version)."""
+    F, C_, w = weight.shape
+    e = _derived('hdc_p', weight, (F, C_, w), lambda: torch.empty((w, F, C_), device=weight.device, dtype=torch.float32), False)
+    _serve(e, (weight,), lambda: hdc_repack(weight, e.out, F, C_, w, 0))
+    return e.out
+
+
+def match_images_fwd(cand, hist, B, N, H, S, alpha, plane):
+    """One level's matching images (userEncoders.py:252-253): plane [B][N S][H S] = alpha cand[b] . hist[b]^T for cand [B N, S, C] and hist
+    [B H, S, C] -- one batched product, written in the layout the first convolution layer reads through its strides."""
+    C_ = cand.shape[2]
+    gemm(cand, hist, plane, M=N * S, N=H * S, K=C_, lda=C_, ldb=C_, ldc=H * S, alpha=alpha, batch=B, strideA=N * S * C_, strideB=H * S * C_,
+         strideC=N * S * H * S)
+
+
+def match_images_bwd(dplane, cand, hist, B, N, H, S, alpha, dcand, dhist):
+    """dcand [B N, S, C] = alpha dplane[b] . hist[b], dhist [B H, S, C] = alpha dplane[b]^T . cand[b] (both written)."""
+    C_ = cand.shape[2]
+    gemm(dplane, hist, dcand, M=N * S, N=C_, K=H * S, lda=H * S, ldb=C_, ldc=C_, trans_b=True, alpha=alpha, batch=B, strideA=N * S * H * S,
+         strideB=H * S * C_, strideC=N * S * C_)
+    gemm(dplane, cand, dhist, M=H * S, N=C_, K=N * S, lda=H * S, ldb=C_, ldc=C_, trans_a=True, trans_b=True, alpha=alpha, batch=B,
+         strideA=N * S * H * S, strideB=N * S * C_, strideC=H * S * C_)
+
+
+def conv3d_pool_plan(Cin, D, H, W, Cout, K, P, St):
+    """Host mirror of the library's shape rules (csrc/fim.hip:c3_shape), for constructors that run without a device: (PD, PH, PW), or
+    None where nnr_conv3d_pool_dims returns NNR_ERR_UNSUPPORTED (tests/test_hip_fim_gpu.py compares the two)."""
+    if not (1 <= K <= 4 and 1 <= P <= 4 and St >= P):
+        return None
+    pooled = lambda n: 0 if n - K + 1 < P else (n - K + 1 - P) // St + 1
+    PD, PH, PW = pooled(D), pooled(H), pooled(W)
+    if min(PD, PH, PW) <= 0:
+        return None
+    DD, Cp = P + K - 1, (Cout + 3) & ~3
+    WW = (PW - 1) * St + DD
+
+    def lds(phb):
+        xs = (Cin * DD * ((phb - 1) * St + DD) * WW + 3) & ~3
+        return 4 * (xs + Cin * K ** 3 * Cp + phb * PW * P ** 3 * Cp)
+    phb = 1
+    while phb < PH and phb * PW * P * P * (Cp // 4) < 256 and lds(phb + 1) <= 64 * 1024:
+        phb += 1
+    return (PD, PH, PW) if lds(phb) <= 160 * 1024 else None
+
+
+def conv3d_pool_dims(Cin, D, H, W, Cout, K, P, St):
+    """(PD, PH, PW) of the fused layer, or NnrHipError('... unsupported size ...')."""
+    out = [C.c_int(0) for _ in range(3)]
+    rc = L.lib().nnr_conv3d_pool_dims(Cin, D, H, W, Cout, K, P, St, *[C.addressof(o) for o in out])
+    if rc == -3:
+        raise L.NnrHipError('nnr_conv3d_pool_dims: %s' % FIM_UNSUPPORTED)
+    if rc != 0:
+        raise L.NnrHipError('nnr_conv3d_pool_dims failed with code %d' % rc)
+    return tuple(o.value for o in out)
+
+
+def conv3d_weight(weight, mode):
+    """The Conv3d weight [Cout, Cin, K, K, K] as the forward operand [Cin, K^3, Cout4] (mode 0) or the input-gradient operand
+    [Cout, K^3, Cin4] (mode 1); entries of the derived-weight cache."""
+    Cout, Cin, K = weight.shape[:3]
+    shape = (Cin, K ** 3, (Cout + 3) & ~3) if mode == 0 else (Cout, K ** 3, (Cin + 3) & ~3)
+    e = _derived('c3_q' if mode else 'c3_p', weight, (Cout, Cin, K), lambda: torch.empty(shape, device=weight.device, dtype=torch.float32), False)
+    _serve(e, (weight,), lambda: _fim_check(L.lib().nnr_conv3d_repack(_p(weight), _p(e.out), Cout, Cin, K, mode, _s()), 'nnr_conv3d_repack'))
+    return e.out
+
+
+def conv3d_pool_fwd(x, strides, wp, bias, imgs, Cin, D, H, W, Cout, K, P, St, cf_out, y, arg):
+    """y / arg = elu(max over each pool cell of conv3d(x) + bias) and the cell's one-byte argmax (include/nnr_hip.h); strides = (image,
+    channel, depth, row, column) of x in floats.  2 Cin K^3 flops per computed position and filter."""
+    PD, PH, PW = conv3d_pool_dims(Cin, D, H, W, Cout, K, P, St)
+    if not _prof.active():
+        _fim_check(L.lib().nnr_conv3d_pool_fwd(_p(x), *strides, _p(wp), _p(bias), imgs, Cin, D, H, W, Cout, K, P, St, int(cf_out), _p(y), _p(arg), _s()),
+                   'nnr_conv3d_pool_fwd')
+        return
+
+    def flops(vals=None):
+        return 2.0 * imgs * PD * PH * PW * P ** 3 * Cout * Cin * K ** 3
+    flops.dyn = []
+    flops.tag = 'imgs%d %dx%dx%dx%d->%d k%d p%d/%d' % (imgs, Cin, D, H, W, Cout, K, P, St)
+    with _prof.span('conv3d_pool_fwd', flops):
+        _fim_check(L.lib().nnr_conv3d_pool_fwd(_p(x), *strides, _p(wp), _p(bias), imgs, Cin, D, H, W, Cout, K, P, St, int(cf_out), _p(y), _p(arg), _s()),
+                   'nnr_conv3d_pool_fwd')
+
+
+def conv3d_pool_bwd(dy, y, arg, x, strides, wq, imgs, Cin, D, H, W, Cout, K, P, St, cf_out, dx, dw, db):
+    """dw [Cout, Cin, K, K, K] and db [Cout] accumulate, dx (same strides as x, or None) is written; reproducible (include/nnr_hip.h)."""
+    nws = L.lib().nnr_conv3d_pool_bwd_ws_floats(imgs, Cin, D, H, W, Cout, K, P, St)
+    if nws == 0 and imgs > 0:
+        raise L.NnrHipError('nnr_conv3d_pool_bwd: %s' % FIM_UNSUPPORTED)
+    ws = torch.empty(max(1, nws), device=dy.device, dtype=torch.float32)
+    tape_keep(ws)
+
+    def launch():
+        _fim_check(L.lib().nnr_conv3d_pool_bwd(_p(dy), _p(y), _p(arg), _p(x), *strides, _p(wq), imgs, Cin, D, H, W, Cout, K, P, St, int(cf_out), _p(dx),
+                                               _p(dw), _p(db), _p(ws), _s()), 'nnr_conv3d_pool_bwd')
+    if not _prof.active():
+        return launch()
+    PD, PH, PW = conv3d_pool_dims(Cin, D, H, W, Cout, K, P, St)
+
+    def flops(vals=None):           # one position per (cell, filter): the weight gradient's taps, and as many again for the input gradient
+        return 2.0 * imgs * PD * PH * PW * Cout * Cin * K ** 3 * (2 if dx is not None else 1)
+    flops.dyn = []
+    flops.tag = 'imgs%d %dx%dx%dx%d->%d k%d p%d/%d%s' % (imgs, Cin, D, H, W, Cout, K, P, St, '' if dx is not None else ' dw only')
+    with _prof.span('conv3d_pool_bwd', flops):
+        launch()
+
+
 def fill_zero(t):
     """t.zero_() as an entry point of the library (hipMemsetAsync on the current stream): part of the launch tape."""
     assert t.is_contiguous()

@@ -587,3 +587,43 @@ class PUE(UserEncoder):
         q_d = Fn.LinearFn.apply(user_embedding, self.dense.weight, self.dense.bias, ops.ACT_RELU, 0.0, 0)     # [B, personalized_embedding_dim]
         user = self.personalizedAttention(history_embedding, q_d, user_history_mask)                          # [B, news_embedding_dim]
         return Fn.ExpandFn.apply(user, candidate_news_representation.size(1))
+
+
+class FIM(UserEncoder):
+    """userEncoders.py:224-262, fine-grained interest matching: for every candidate, history slot and level of the HDC pair an S x S image
+    cand_level^T . hist_level / sqrt(HDC_filter_num) (level 0 too, although it contracts over word_embedding_dim), the four levels as the
+    channels of Conv3d over (history, candidate position, history position), elu -> maxpool -> elu -> maxpool -> [B, N, feature_size]
+    (functional.FimFn, csrc/fim.hip: each Conv3d + ELU + MaxPool3d is one launch, the dense convolution output never exists).
+    `user_history_mask` is not read: padded history slots take part."""
+
+    def __init__(self, news_encoder: NewsEncoder, config):
+        super().__init__(news_encoder, config)
+        from .news_encoders import HDC
+        assert type(self.news_encoder) == HDC, 'For FIM, the news encoder must be HDC'
+        self.HDC_sequence_length = news_encoder.HDC_sequence_length
+        self.max_history_num = config.max_history_num
+        self.scalar = math.sqrt(float(config.HDC_filter_num))
+        self.conv_3D_a = nn.Conv3d(in_channels=4, out_channels=config.conv3D_filter_num_first, kernel_size=config.conv3D_kernel_size_first)
+        self.conv_3D_b = nn.Conv3d(in_channels=config.conv3D_filter_num_first, out_channels=config.conv3D_filter_num_second,
+                                   kernel_size=config.conv3D_kernel_size_second)
+        self.maxpool_3D = nn.MaxPool3d(kernel_size=config.maxpooling3D_size, stride=config.maxpooling3D_stride)
+        self.pool_size, self.pool_stride = int(config.maxpooling3D_size), int(config.maxpooling3D_stride)
+
+    def initialize(self):
+        pass
+
+    def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask, user_content_entity,
+                user_category, user_subCategory, user_history_mask, user_history_graph, user_history_category_mask,
+                user_history_category_indices, user_embedding, candidate_news_representation):
+        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
+                                              user_content_entity, user_category, user_subCategory, user_embedding)
+        return self.encode_user(history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
+                                user_history_category_indices, candidate_news_representation)
+
+    def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
+                    user_history_category_indices, candidate_news_representation):
+        from . import functional as Fn
+        (h0, hL), (c0, cL) = history_embedding, candidate_news_representation
+        B, H, S, E = h0.shape
+        N, F = c0.shape[1], hL.shape[4]
+        return Fn.FimFn.apply(c0.reshape(B * N, S, E), cL.reshape(3, B * N, S, F), h0.reshape(B * H, S, E), hL.reshape(3, B * H, S, F), self, B, N, H)

@@ -163,8 +163,19 @@ def run_kcnn():
     run('tiny_KCNN_CATT', 'KCNN', 'CATT', False, min_gap=1e-3)
 
 
+def run_fim():
+    """`python tools/make_eval_goldens.py fim`: the HDC / FIM pair with its own click head, at the tiny FIM sizes of tools/make_goldens.py
+    (history 11 so that both pooled layers keep a cell; S = 10 -> 8 -> 4 -> 2 -> 1)."""
+    run('tiny_HDC_FIM', 'HDC', 'FIM', False, min_gap=1e-3, click_predictor='FIM', max_history_num=11, HDC_window_size=3, HDC_filter_num=6,
+        conv3D_filter_num_first=3, conv3D_kernel_size_first=3, conv3D_filter_num_second=2, conv3D_kernel_size_second=3, maxpooling3D_size=2,
+        maxpooling3D_stride=2)
+
+
 if __name__ == '__main__':
     torch.set_num_threads(4)
+    if len(sys.argv) > 1 and sys.argv[1] == 'fim':
+        run_fim()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'kcnn':
         run_kcnn()
         sys.exit(0)
@@ -189,3 +200,4 @@ if __name__ == '__main__':
     run_npa()
     run_bow()
     run_kcnn()
+    run_fim()
