@@ -186,6 +186,32 @@ int nnr_lstm_set_timeout_counter(unsigned* dev_counter);
 int nnr_lstm_fwd(const nnr_lstm_problem* probs, int nprob, int H, hipStream_t stream);
 int nnr_lstm_bwd(const nnr_lstm_problem* probs, int nprob, int H, hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------------ GRU
+ * Replaces nn.GRU on a PackedSequence (userEncoders.py:287-332) and its backward, csrc/gru.hip.  Every unit has four slots
+ * [r, z, n_x, n_h] in p-order: p = (unit/16)*64 + (unit%16)*4 + slot, padded to NP = ceil(H/16)*64.
+ * Supported: 1 <= H <= 256 and 1 <= T <= 255, anything else is NNR_ERR_UNSUPPORTED. */
+int nnr_gru_dims(int H, int T, int* UB, int* HP, int* NP);
+/* w_ih [3H, D], w_hh [3H, H], b_ih [3H], b_hh [3H] (gate order r | z | n) -> w_ihp [NP, D] (slot 3 rows zero),
+ * b_p [NP] = (b_ir + b_hr, b_iz + b_hz, b_in, b_hn), wf [UB*3*UB*256] (forward fragments), wb [UB*(NP/16)*256] (backward fragments) */
+int nnr_gru_pack_weights(const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int H, int D, float* w_ihp,
+                         float* b_p, float* wf, float* wb, hipStream_t stream);
+/* dw_ihp [NP, D], db_p [NP], dw_hhp [NP, H] (products / column sums over the buffer nnr_gru_bwd leaves) are ADDED to the gradients in
+ * nn.GRU's parameter layout, one writer per element (no atomics) */
+int nnr_gru_unpack_grads(const float* dw_ihp, const float* db_p, const float* dw_hhp, int H, int D, float* dw_ih, float* dw_hh,
+                         float* db_ih, float* db_hh, hipStream_t stream);
+/* gates [B*T, NP]: in = x . w_ihp^T + b_p for every history slot, out = (r, z, n, W_hn h + b_hn) at the live ones.  mask uint8 [B, T]:
+ * len[b] = number of non-zero entries (written to len [B]); user b runs slots 0 .. len[b]-1 and keeps h afterwards.  h0 [B, H] or NULL
+ * (zeros).  hout / hprev [B*T, H]: h_t / h_{t-1} at the live slots (the rest is left untouched), hfinal [B, H]. */
+int nnr_gru_fwd(float* gates, const unsigned char* mask, const float* h0, const float* wf, int B, int T, int H, float* hout,
+                float* hprev, float* hfinal, int* len, hipStream_t stream);
+/* gates: in = what nnr_gru_fwd left, out = d(pre-activations) (dr, dz, dn, dn r), ZERO at every dead slot; dhfinal [B, H];
+ * dh0 [B, H] or NULL receives dL/dh0 (= dhfinal for a user without history) */
+int nnr_gru_bwd(float* gates, const int* len, const float* hprev, const float* wb, const float* dhfinal, int B, int T, int H,
+                float* dh0, hipStream_t stream);
+/* the decoder's tail: rows of users without history are exactly zero (not tanh(bias)); dz = dy (1 - y^2), zero for those rows */
+int nnr_gru_zero_empty(float* y, const int* len, int B, int D, hipStream_t stream);
+int nnr_gru_tanh_bwd(const float* dy, const float* y, const int* len, int B, int D, float* dz, hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------ attention pooling
  * softmax(mask(score)) . x : the tails of `Attention` (layers.py:169-175) and `ScaledDotProduct_CandidateAttention`
  * (layers.py:197-203), forward and backward; see pool.hip for the layouts.  D <= 1280, L <= 128; D, ldx, ldth and the leading

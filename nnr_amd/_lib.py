@@ -74,6 +74,13 @@ SIGNATURES = {
     'nnr_lstm_set_timeout_counter': 'i32 ptr',
     'nnr_lstm_fwd': 'i32 LstmProblem i32 i32 stream',
     'nnr_lstm_bwd': 'i32 LstmProblem i32 i32 stream',
+    'nnr_gru_dims': 'i32 i32 i32 ptr ptr ptr',
+    'nnr_gru_pack_weights': 'i32 ptr ptr ptr ptr i32 i32 ptr ptr ptr ptr stream',
+    'nnr_gru_unpack_grads': 'i32 ptr ptr ptr i32 i32 ptr ptr ptr ptr stream',
+    'nnr_gru_fwd': 'i32 ptr ptr ptr ptr i32 i32 i32 ptr ptr ptr ptr stream',
+    'nnr_gru_bwd': 'i32 ptr ptr ptr ptr ptr i32 i32 i32 ptr stream',
+    'nnr_gru_zero_empty': 'i32 ptr ptr i32 i32 stream',
+    'nnr_gru_tanh_bwd': 'i32 ptr ptr ptr i32 i32 ptr stream',
     'nnr_attn_pool_fwd': 'i32 PoolArgs stream',
     'nnr_attn_pool_bwd': 'i32 PoolArgs stream',
     'nnr_gate_bwd': 'i32 ptr ptr ptr ptr ptr ptr i32 i32 stream',

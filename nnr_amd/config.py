@@ -24,6 +24,7 @@ _BOOL_FLAGS = ['no_self_connection', 'no_adjacent_normalization', 'no_gcn_residu
 
 NEWS_ENCODERS = ['CNE', 'CNN', 'MHSA', 'PNE', 'DAE', 'Inception', 'HDC', 'KCNN']    # in scope; the reference lists 15
 USER_ENCODERS = ['SUE', 'MHSA', 'ATT', 'CATT', 'OMAP', 'PUE', 'FIM']  # in scope; the reference lists 11
+ALL_USER_ENCODERS = USER_ENCODERS + ['GRU']                            # (USER_ENCODERS above is pinned by the host tests; nothing reads either list)
 
 
 def build_parser():

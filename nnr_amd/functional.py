@@ -566,6 +566,72 @@ class ExpandFn(torch.autograd.Function):
         return ops.expand_rows_bwd(dout.contiguous()), None
 
 
+class GruFn(torch.autograd.Function):
+    """h_final [B, H] of nn.GRU over the first len[b] = mask[b].sum() slots of x [B, T, D] (csrc/gru.hip): the projection of every slot is one
+    GEMM with the biases in its epilogue, the recurrence one launch.  h0 [B, H] or None (zeros); a user with len 0 returns h0[b] (or zero).
+    Also returns len (int32 [B]) and hs [B, T, H] = h_t at every live slot, zero elsewhere (both not differentiable).  Backward: one recurrence
+    launch that leaves the pre-activation gradients (zero at dead slots), then dX, the packed weight gradients and the bias sums as products /
+    fixed-order column sums -- no float atomics."""
+
+    @staticmethod
+    def forward(ctx, x, mask, gru, h0):
+        B, T, D = x.shape
+        H = gru.hidden_dim
+        x2 = x.contiguous().view(B * T, D)
+        m8 = (mask.view(torch.uint8) if mask.dtype == torch.bool else (mask if mask.dtype == torch.uint8 else (mask != 0).view(torch.uint8))).contiguous()
+        w = ops.gru_pack(gru, H, D)
+        f32 = dict(device=x.device, dtype=torch.float32)
+        gates = ops.linear_fwd(x2, w.w_ihp, w.b_p)                                               # [B*T, NP]
+        hout, hprev = torch.zeros((B * T, H), **f32), torch.zeros((B * T, H), **f32)             # (dead slots stay zero)
+        hfinal = torch.empty((B, H), **f32)
+        length = torch.empty(B, device=x.device, dtype=torch.int32)
+        h0c = h0.contiguous() if h0 is not None else None
+        ops.gru_fwd(gates, m8, h0c, w, B, T, H, hout, hprev, hfinal, length)
+        ctx.gru, ctx.saved, ctx.has_h0 = gru, (x2, gates, hprev, length, w, (B, T, D, H)), h0 is not None
+        hs = hout.view(B, T, H)
+        ctx.mark_non_differentiable(length, hs)
+        return hfinal, length, hs
+
+    @staticmethod
+    def backward(ctx, dhfinal, _dlen, _dhs):
+        gru = ctx.gru
+        x2, gates, hprev, length, w, (B, T, D, H) = ctx.saved
+        ctx.saved = None
+        f32 = dict(device=x2.device, dtype=torch.float32)
+        dh0 = torch.empty((B, H), **f32) if ctx.has_h0 else None
+        ops.gru_bwd(gates, length, hprev, w, dhfinal.contiguous(), B, T, H, dh0)
+        NP = w.NP
+        dw_ihp, dw_hhp, db_p = torch.zeros((NP, D), **f32), torch.zeros((NP, H), **f32), torch.zeros(NP, **f32)
+        for dw, act, K in ((dw_ihp, x2, D), (dw_hhp, hprev, H)):
+            # reproducible: split-K only through the slab + fixed-order reduction (needs K % 4 == 0), never through float atomics
+            split = ops.split_for(NP, K, B * T) if (K & 3) == 0 else 1
+            ops.gemm(gates, act, dw, M=NP, N=K, K=B * T, lda=NP, ldb=K, ldc=K, trans_a=True, trans_b=True, atomic=split > 1, split_k=split)
+        ops.bias_grad(gates, db_p)
+        ops.gru_unpack_grads(dw_ihp, db_p, dw_hhp, H, D, [grad_of(t) for t in gru.param_list()])
+        dx = ops.linear_bwd_data(gates, w.w_ihp)                                                  # zero at dead slots (slot 3 rows of w_ihp are zero)
+        return dx.view(B, T, D), None, None, dh0
+
+
+class GruDecFn(torch.autograd.Function):
+    """tanh(h W^T + b) [B, D] with the rows of users without history (len[b] == 0) exactly zero, forward and backward (userEncoders.py:316-329:
+    the reference concatenates zero rows, it does not decode a zero state)."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, length):
+        h = h.contiguous()
+        y = ops.linear_fwd(h, weight, bias, act=ops.ACT_TANH)
+        ops.gru_zero_empty(y, length)
+        ctx.h, ctx.weight, ctx.bias, ctx.length, ctx.y = h, weight, bias, length, y.detach()
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dz = torch.empty_like(ctx.y)
+        ops.gru_tanh_bwd(dy.contiguous(), ctx.y, ctx.length, dz)
+        ops.linear_bwd_weight(dz, ctx.h, grad_of(ctx.weight), db=grad_of(ctx.bias))
+        return ops.linear_bwd_data(dz, ctx.weight), None, None, None
+
+
 class HdcFn(torch.autograd.Function):
     """The HDC news encoder (newsEncoders.py:262-278) on position-major activations (csrc/hdc.hip): returns
     d0 [n, S, E] and dL [3, n, S, F] with S = max_title_length + 2.  Layer l (dilation d = l + 1, window 3, padding d) reads its input with d

@@ -52,6 +52,21 @@ class LSTMParams(nn.Module):
                 self.weight_ih_l0_reverse, self.weight_hh_l0_reverse, self.bias_ih_l0_reverse, self.bias_hh_l0_reverse]
 
 
+class GRUParams(nn.Module):
+    """Parameter holder with nn.GRU(num_layers=1, batch_first=True) names/shapes/default init (userEncoders.py:290); gate order r | z | n."""
+
+    def __init__(self, input_dim, hidden_dim):
+        super().__init__()
+        self.input_dim, self.hidden_dim = input_dim, hidden_dim
+        k = 1.0 / math.sqrt(hidden_dim)
+        for name, shape in (('weight_ih_l0', (3 * hidden_dim, input_dim)), ('weight_hh_l0', (3 * hidden_dim, hidden_dim)),
+                            ('bias_ih_l0', (3 * hidden_dim,)), ('bias_hh_l0', (3 * hidden_dim,))):
+            self.register_parameter(name, nn.Parameter(torch.empty(shape).uniform_(-k, k)))
+
+    def param_list(self):
+        return [self.weight_ih_l0, self.weight_hh_l0, self.bias_ih_l0, self.bias_hh_l0]
+
+
 # ------------------------------------------------------------------------------------------------ additive attention
 class _AttentionFn(torch.autograd.Function):
     """layers.py:167-175 on a dense [n, L, F] feature: tanh GEMM, w2 row-dot, then the softmax pool."""

@@ -116,8 +116,10 @@ class Model(nn.Module):
             self.user_encoder = userEncoders.PUE(self.news_encoder, config)
         elif config.user_encoder == 'FIM':
             self.user_encoder = userEncoders.FIM(self.news_encoder, config)
+        elif config.user_encoder == 'GRU':
+            self.user_encoder = userEncoders.GRU(self.news_encoder, config)
         else:
-            raise Exception(config.user_encoder + ' is not on the MI355X hot path (in scope: SUE, MHSA, ATT, CATT, FIM, OMAP, PUE; SURVEY.md section 8a)')
+            raise Exception(config.user_encoder + ' is not on the MI355X hot path (in scope: SUE, MHSA, ATT, CATT, FIM, OMAP, PUE, GRU; SURVEY.md section 8a)')
         self.model_name = config.news_encoder + '-' + config.user_encoder
         self.news_embedding_dim = self.news_encoder.news_embedding_dim
         self.dropout = nn.Dropout(p=config.dropout_rate)                    # (model.py:77: part of the attribute surface; the user rows'

@@ -915,6 +915,116 @@ def lstm_bwd(items, H):
         L.check(L.lib().nnr_lstm_bwd(arr, len(items), H, _s()), 'nnr_lstm_bwd')
 
 
+# ---------------------------------------------------------------------------------------------- GRU
+GRU_UNSUPPORTED = 'unsupported size (hidden_dim must be in 1 .. 256 and max_history_num in 1 .. 255)'
+
+
+def gru_supported(H, T):
+    """Host mirror of nnr_gru_dims' rule (csrc/gru.hip), for the constructors: no library call, no device."""
+    return 1 <= int(H) <= 256 and 1 <= int(T) <= 255
+
+
+def gru_dims(H, T=1):
+    """(UB, HP, NP) of hidden size H: unit blocks, padded units, padded slot columns (four per unit)."""
+    ub, hp, np_ = C.c_int(), C.c_int(), C.c_int()
+    rc = L.lib().nnr_gru_dims(H, T, C.byref(ub), C.byref(hp), C.byref(np_))
+    if rc != 0:
+        raise L.NnrHipError('nnr_gru_dims(H=%d, T=%d): %s' % (H, T, GRU_UNSUPPORTED))
+    return ub.value, hp.value, np_.value
+
+
+def gru_pack_host(w_ih, w_hh, b_ih, b_hh):
+    """Host mirror of nnr_gru_pack_weights on CPU tensors: (w_ihp [NP, D], b_p [NP], wf, wb), element for element what the kernel writes."""
+    H, D = w_hh.shape[1], w_ih.shape[1]
+    UB = (H + 15) // 16
+    NP, HP = UB * 64, UB * 16
+    unit = torch.arange(HP)
+    live = unit < H
+    u = unit.clamp(max=H - 1)
+    w_ihp = torch.zeros((UB, 16, 4, D), dtype=w_ih.dtype)
+    b_p = torch.zeros((UB, 16, 4), dtype=w_ih.dtype)
+    whh_p = torch.zeros((UB, 16, 4, HP), dtype=w_ih.dtype)              # W_hh rows in p-order (slot 2 zero), columns padded
+    for slot, gx, gh in ((0, 0, 0), (1, 1, 1), (2, 2, None), (3, None, 2)):
+        if gx is not None:
+            w_ihp[:, :, slot] = (w_ih[gx * H + u] * live[:, None]).view(UB, 16, D)
+        if gh is not None:
+            whh_p[:, :, slot, :H] = (w_hh[gh * H + u] * live[:, None]).view(UB, 16, H)
+        bias = (b_ih[gx * H + u] if gx is not None else 0) + (b_hh[gh * H + u] if gh is not None else 0)
+        b_p[:, :, slot] = (bias * live).view(UB, 16)
+    # wf[ub][g][kg][lane][ii] = w_hh[g*H + ub*16 + (lane & 15)][16 kg + 4 (lane >> 4) + ii]
+    whh = torch.zeros((3, HP, HP), dtype=w_ih.dtype)
+    whh[:, :H, :H] = w_hh.view(3, H, H)
+    wf = whh.view(3, UB, 16, UB, 4, 4).permute(1, 0, 3, 4, 2, 5).contiguous().view(-1)        # [ub][g][kg][lane >> 4][lane & 15][ii]
+    # wb[ubn][kg][lane][ii] = whh_p[p = 16 kg + 4 (lane >> 4) + ii][ubn*16 + (lane & 15)]
+    wb = whh_p.view(NP // 16, 4, 4, UB, 16).permute(3, 0, 1, 4, 2).contiguous().view(-1)      # [ubn][kg][lane >> 4][lane & 15][ii]
+    return w_ihp.view(NP, D), b_p.view(NP), wf, wb
+
+
+class GruPacked:
+    """nn.GRU parameters `p` = (w_ih, w_hh, b_ih, b_hh) re-laid out for the recurrent kernels (csrc/gru.hip); pack(p) refills the buffers
+    in place (fill=False: allocate only)."""
+
+    def __init__(self, p, H, D, fill=True):
+        ub, hp, np_ = gru_dims(H)
+        f = dict(device=p[0].device, dtype=torch.float32)
+        self.UB, self.HP, self.NP, self.H, self.D = ub, hp, np_, H, D
+        self.w_ihp = torch.empty((np_, D), **f)
+        self.b_p = torch.empty(np_, **f)
+        self.wf = torch.empty(ub * 3 * ub * 256, **f)
+        self.wb = torch.empty(ub * (np_ // 16) * 256, **f)
+        self.bufs = (self.w_ihp, self.b_p, self.wf, self.wb)
+        if fill:
+            self.pack(p)
+
+    def pack(self, p):
+        L.check(L.lib().nnr_gru_pack_weights(*[_p(t) for t in p], self.H, self.D, _p(self.w_ihp), _p(self.b_p), _p(self.wf), _p(self.wb), _s()),
+                'nnr_gru_pack_weights')
+
+
+def gru_pack(gru, H, D):
+    """The parameters of `gru` (layers.GRUParams) in the recurrent kernels' layouts (GruPacked), behind the derived-weight cache with the
+    freshness rule of the LSTM packs: refilled in place when a parameter changed."""
+    p = gru.param_list()
+    e = _derived('gru', gru, (H, D), lambda: GruPacked(p, H, D, fill=False), False)
+    _serve(e, p, lambda: e.out.pack(p))
+    return e.out
+
+
+def gru_unpack_grads(dw_ihp, db_p, dw_hhp, H, D, grads):
+    """grads: (w_ih, w_hh, b_ih, b_hh) gradients in nn.GRU's layout, added into without atomics."""
+    L.check(L.lib().nnr_gru_unpack_grads(_p(dw_ihp), _p(db_p), _p(dw_hhp), H, D, *[_p(t) for t in grads], _s()), 'nnr_gru_unpack_grads')
+
+
+def _gru_flops(B, T, H, cols):
+    def flops(vals=None):
+        return 2.0 * B * T * H * cols * H        # upper bound: every slot live
+    flops.dyn = []
+    flops.tag = 'B%d T%d H%d' % (B, T, H)
+    return flops
+
+
+def gru_fwd(gates, mask, h0, w, B, T, H, hout, hprev, hfinal, length):
+    """rc of nnr_gru_fwd is checked; mask uint8 [B, T] contiguous."""
+    assert mask.dtype == torch.uint8 and mask.is_contiguous()
+    with _prof.span('gru_fwd', _gru_flops(B, T, H, 3)):
+        L.check(L.lib().nnr_gru_fwd(_p(gates), _p(mask), _p(h0), _p(w.wf), B, T, H, _p(hout), _p(hprev), _p(hfinal), _p(length), _s()), 'nnr_gru_fwd')
+
+
+def gru_bwd(gates, length, hprev, w, dhfinal, B, T, H, dh0=None):
+    with _prof.span('gru_bwd', _gru_flops(B, T, H, 4)):
+        L.check(L.lib().nnr_gru_bwd(_p(gates), _p(length), _p(hprev), _p(w.wb), _p(dhfinal), B, T, H, _p(dh0), _s()), 'nnr_gru_bwd')
+
+
+def gru_zero_empty(y, length):
+    B, D = y.shape
+    L.check(L.lib().nnr_gru_zero_empty(_p(y), _p(length), B, D, _s()), 'nnr_gru_zero_empty')
+
+
+def gru_tanh_bwd(dy, y, length, dz):
+    B, D = y.shape
+    L.check(L.lib().nnr_gru_tanh_bwd(_p(dy), _p(y), _p(length), B, D, _p(dz), _s()), 'nnr_gru_tanh_bwd')
+
+
 # ---------------------------------------------------------------------------------------------- pooling
 def _pool_args(x, ldx, D, n, Lx, plan=None, mask=None, mask_div=1, score=None, v=None, ldv=0, scale=1.0, alpha=None, out=None,
                ldo=0, add_in=None, ldadd=0, dout=None, lddo=0, dout2=None, lddo2=0, dx=None, lddx=0, dx_accumulate=False,

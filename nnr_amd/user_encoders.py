@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .layers import Attention, CandidateAttention, ScaledDotProduct_CandidateAttention, MultiHeadAttention, GCN, grad_of, _CandAttnFn
+from .layers import Attention, CandidateAttention, ScaledDotProduct_CandidateAttention, MultiHeadAttention, GCN, GRUParams, grad_of, _CandAttnFn
 from .news_encoders import NewsEncoder
 
 
@@ -425,6 +425,41 @@ class ATT(UserEncoder):
                     user_history_category_indices, candidate_news_representation):
         from . import functional as Fn
         return Fn.ExpandFn.apply(self.attention(history_embedding), candidate_news_representation.size(1))
+
+
+class GRU(UserEncoder):
+    """userEncoders.py:287-332 (the user encoder of the DAE-GRU baseline): nn.GRU over the first user_history_mask.sum() history slots from
+    h = 0, user vector tanh(dec(h_final)), exactly zero for a user without history.  The sort / pack / de-sort of the reference is replaced by
+    running every user for t < len and freezing h afterwards (csrc/gru.hip): same values, no planner, no host sync."""
+
+    def __init__(self, news_encoder: NewsEncoder, config):
+        super().__init__(news_encoder, config)
+        if not ops.gru_supported(config.hidden_dim, config.max_history_num):
+            raise Exception('GRU: ' + ops.GRU_UNSUPPORTED)
+        self.gru = GRUParams(self.news_embedding_dim, config.hidden_dim)
+        self.dec = nn.Linear(config.hidden_dim, self.news_embedding_dim, bias=True)
+
+    def initialize(self):
+        """userEncoders.py:293-300: orthogonal_ on each whole [3H, .] matrix, zero GRU biases, xavier_uniform_ (tanh gain) / zeros on dec."""
+        for p in self.gru.param_list():
+            (nn.init.orthogonal_ if p.dim() >= 2 else nn.init.zeros_)(p.data)
+        nn.init.xavier_uniform_(self.dec.weight, gain=nn.init.calculate_gain('tanh'))
+        nn.init.zeros_(self.dec.bias)
+
+    def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask, user_content_entity,
+                user_category, user_subCategory, user_history_mask, user_history_graph, user_history_category_mask,
+                user_history_category_indices, user_embedding, candidate_news_representation):
+        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
+                                              user_content_entity, user_category, user_subCategory, user_embedding)
+        return self.encode_user(history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
+                                user_history_category_indices, candidate_news_representation)
+
+    def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
+                    user_history_category_indices, candidate_news_representation):
+        from . import functional as Fn
+        h, length, _ = Fn.GruFn.apply(history_embedding, user_history_mask, self.gru, None)
+        user = Fn.GruDecFn.apply(h, self.dec.weight, self.dec.bias, length)
+        return Fn.ExpandFn.apply(user, candidate_news_representation.size(1))
 
 
 class CATT(UserEncoder):

@@ -30,10 +30,11 @@ from make_goldens import stable_sort_patch          # noqa: E402
 from oracle.nnr_oracle import default_config        # noqa: E402  (attribute bag only)
 
 
-def run(tag, news, user, stable, min_gap=None, batch_size=8, **cfg_over):
+def run(tag, news, user, stable, min_gap=None, batch_size=8, zero_ties=False, **cfg_over):
     """`cfg_over`: flags default_config lacks (OMAP_head_num, HiFi_Ark_regularizer_coefficient: config.py:74-75; user_embedding_dim,
     personalized_embedding_dim: config.py:64-65).  `batch_size` is stored: PNE's scores depend on it (newsEncoders.py:359 pairs title row r
-    of a batch with user r % batch)."""
+    of a batch with user r % batch).  `zero_ties`: impressions whose scores are ALL exactly zero (GRU: a user without history has a zero user
+    vector) are left out of the gap check: their ties are exact on both sides, not rounding noise."""
     rng = np.random.default_rng(21)
     cwd = os.getcwd()
     with tempfile.TemporaryDirectory() as tmp:
@@ -58,6 +59,13 @@ def run(tag, news, user, stable, min_gap=None, batch_size=8, **cfg_over):
             corpus = MIND_corpus.MIND_Corpus(cfg)
             m = ref_model.Model(cfg)
             m.initialize()
+            if user == 'GRU':
+                m.user_encoder.device = torch.device('cpu')     # userEncoders.py:310,327: the empty users' zero rows go to self.device ('cuda')
+                with torch.no_grad():                           # initialize() zeroes the biases: tanh(dec.bias) would hide the zero-row rule
+                    gb = torch.Generator().manual_seed(77)
+                    for k, p in m.user_encoder.named_parameters():
+                        if not k.startswith('news_encoder.') and p.dim() == 1:
+                            p.copy_(0.1 * torch.randn(p.shape, generator=gb))
             with torch.no_grad():                               # larger weights: scores spread out (ranks are then robust to fp32 noise)
                 for k, p in m.named_parameters():
                     if 'word_embedding' not in k:
@@ -112,7 +120,7 @@ def run(tag, news, user, stable, min_gap=None, batch_size=8, **cfg_over):
     if min_gap is not None:                             # the fixture must decide the ranks: no two scores of an impression closer than this
         o, gaps = 0, []
         for n in out['sizes']:
-            if n > 1:
+            if n > 1 and not (zero_ties and not out['scores'][o:o + n].any()):
                 gaps.append(float(np.diff(np.sort(out['scores'][o:o + n])).min()))
             o += n
         assert min(gaps) > min_gap, (tag, min(gaps))
@@ -163,6 +171,11 @@ def run_kcnn():
     run('tiny_KCNN_CATT', 'KCNN', 'CATT', False, min_gap=1e-3)
 
 
+def run_gru():
+    """`python tools/make_eval_goldens.py gru`: DAE + GRU (random biases: see run())."""
+    run('tiny_DAE_GRU', 'DAE', 'GRU', False, min_gap=1e-4, zero_ties=True, Alpha=0.1)
+
+
 def run_fim():
     """`python tools/make_eval_goldens.py fim`: the HDC / FIM pair with its own click head, at the tiny FIM sizes of tools/make_goldens.py
     (history 11 so that both pooled layers keep a cell; S = 10 -> 8 -> 4 -> 2 -> 1)."""
@@ -175,6 +188,9 @@ if __name__ == '__main__':
     torch.set_num_threads(4)
     if len(sys.argv) > 1 and sys.argv[1] == 'fim':
         run_fim()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'gru':
+        run_gru()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'kcnn':
         run_kcnn()
@@ -201,3 +217,4 @@ if __name__ == '__main__':
     run_bow()
     run_kcnn()
     run_fim()
+    run_gru()

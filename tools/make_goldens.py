@@ -20,6 +20,7 @@ Usage:  python tools/make_goldens.py            (rewrites every fixture)
         python tools/make_goldens.py bow        (the DAE and Inception bag-of-words news encoders)
         python tools/make_goldens.py kcnn       (the KCNN news encoder of DKN, with entity ids written into the batches)
         python tools/make_goldens.py fim        (the HDC news encoder, the FIM user encoder and the FIM click head)
+        python tools/make_goldens.py gru        (the GRU user encoder of DAE-GRU)
 """
 import os
 import pickle
@@ -62,6 +63,8 @@ def build_reference_model(cfg, word_table):
         finally:
             os.chdir(cwd)
     m.initialize()
+    if cfg.user_encoder == 'GRU':               # userEncoders.py:310,327 allocate the empty users' zero rows on self.device ('cuda')
+        m.user_encoder.device = torch.device('cpu')
     return m
 
 
@@ -578,6 +581,44 @@ FIM_MARGIN_FACTOR = 20.0
 FIM_SEEDS = {'tiny_HDC_FIM': 61, 'tiny_HDC_FIM_p3': 65}       # (p3: 61, 62 and 64 miss the margin; 63 draws a batch whose every cell ties)
 
 
+def gru_cases():
+    """The GRU user encoder (`python tools/make_goldens.py gru`; userEncoders.py:287-332) under the DAE, CNN and CNE news encoders, make_state
+    weights (gain 2.0 tiny, 1.0 full: matrices AND biases are drawn at random -- with initialize()'s zero biases an empty user's tanh(dec.bias)
+    would be zero like the reference's zero rows), three Adam steps.  Every tiny batch holds a user without history and one with a full history:
+    the batch seed is the first from the starting value for which it does.  Asserted below: those two users, max|tanh(dec.bias)| > 1e-2, and that
+    the encoder's own parameters carry at least 1 % of the total gradient norm."""
+    def pick(cfg, sseed, bs, seed):
+        while True:
+            lens = SynthCorpus(tiny_spec(cfg, sseed)).batch(bs, np.random.default_rng(seed + 100))['user_history_mask'].sum(axis=1)
+            if (lens == 0).any() and (lens == cfg.max_history_num).any():
+                return seed
+            seed += 1
+
+    def check(tag, tiny):
+        z = np.load(os.path.join(OUT, tag + '.npz'))
+        lens = z['in/user_history_mask'].astype(bool).sum(axis=1)
+        total = float(z['grad_total_norm'])
+        share = {k: float(z['gradnorm/user_encoder.' + k]) / total for k in ('gru.weight_ih_l0', 'gru.weight_hh_l0', 'dec.weight')}
+        print('  %s: history lengths %s, |g| / |g_total| %s, %d bytes' % (tag, lens.tolist(), {k: round(v, 4) for k, v in share.items()},
+                                                                       os.path.getsize(os.path.join(OUT, tag + '.npz'))))
+        if tiny:
+            assert (lens == 0).any() and (lens == z['in/user_history_mask'].shape[1]).any(), lens
+            assert float(np.abs(np.tanh(z['param1/user_encoder.dec.bias'])).max()) > 1e-2
+            assert min(share.values()) >= 0.01, share
+
+    for tag, news, kw, bs, seed, sseed in (('tiny_DAE_GRU', 'DAE', dict(Alpha=0.1), 8, 43, 4), ('tiny_CNN_GRU', 'CNN', {}, 8, 11, 3),
+                                           ('tiny_CNE_GRU_h48', 'CNE', dict(hidden_dim=48, category_embedding_dim=50, subCategory_embedding_dim=50), 8, 31, 5)):
+        cfg = tiny_cfg(news, 'GRU', **{k: v for k, v in kw.items() if k == 'Alpha'})
+        vars(cfg).update(kw)
+        seed = pick(cfg, sseed, bs, seed)
+        # (CNE at hidden_dim 48: the word table's gradient alone is 1.6 MB -- 64-element slices there, as for tiny_CNE_SUE_h48_stable)
+        run_case(tag, cfg, tiny_spec(cfg, sseed), batch_size=bs, seed=seed, mode='train', gain=1.5 if news == 'CNE' else 2.0, full_arrays=news != 'CNE')
+        check(tag, True)
+    cfg = full_cfg('DAE', 'GRU', V=400, Alpha=0.1)
+    run_case('full_DAE_GRU_g1p0', cfg, full_spec(cfg, 9), batch_size=2, seed=17, mode='train', gain=1.0, full_arrays=False)
+    check('full_DAE_GRU_g1p0', False)
+
+
 def fim_margin(z):
     """(M, smallest margin, tied cells, cells) of a tiny FIM fixture: M = FIM_MARGIN_FACTOR x the largest deviation of the reference's own
     fp32 convolution outputs from its float64 run; the margin is the smallest gap, over both layers' pool cells, between a cell's maximum
@@ -635,6 +676,9 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == 'fim':
         torch.set_num_threads(8)
         return fim_cases(search=len(sys.argv) > 2 and sys.argv[2] == 'search')
+    if len(sys.argv) > 1 and sys.argv[1] == 'gru':
+        torch.set_num_threads(8)
+        return gru_cases()
     if len(sys.argv) > 1 and sys.argv[1] == 'kcnn':
         torch.set_num_threads(8)
         return kcnn_cases()
