@@ -296,6 +296,14 @@ int nnr_transpose2d(const float* in, float* out, long rows, int cols, int accumu
  * them for the W^T copies of the weights that the data-gradient GEMMs multiply by: refreshed once per optimizer step). */
 typedef struct nnr_transpose_desc { const float* in; float* out; int rows, cols; } nnr_transpose_desc;
 int nnr_transpose_batch(const nnr_transpose_desc* descs_dev, int count, hipStream_t stream);
+/* Strided permute of at most four axes: out[i0 so0 + i1 so1 + i2 so2 + i3 so3] (+)= in[i0 si0 + i1 si1 + i2 si2 + i3 si3] for 0 <= id < nd
+ * (accumulate != 0: added to what is there, one plain writer per element).  Strides are in floats; unused leading axes have extent 1.
+ * Source strides may be negative: the caller passes `in` offset so that every address lies inside the source.  Threads walk the index
+ * space row-major, i3 fastest, so the caller makes i3 the destination's unit-stride axis (coalesced writes, strided reads).  Elements of
+ * `out` that no index reaches are not touched.  This is how every weight takes the layout its product reads, once per parameter version
+ * (KCNN, HDC, FIM below).  NNR_ERR_ARG: a null pointer or an extent < 1; NNR_ERR_UNSUPPORTED: n0 n1 n2 n3 >= 2^31. */
+int nnr_permute(const float* in, float* out, int n0, int n1, int n2, int n3, long si0, long si1, long si2, long si3, long so0, long so1,
+                long so2, long so3, int accumulate, hipStream_t stream);
 int nnr_add(float* y, const float* x, long n, float alpha, hipStream_t stream);
 int nnr_add_atomic(float* y, const float* x, long n, float alpha, hipStream_t stream);   /* y += alpha*x with f32 atomics */
 int nnr_add2d(float* y, int ldy, const float* x, int ldx, int rows, int cols, float alpha, int accumulate, hipStream_t stream);
@@ -467,10 +475,9 @@ int nnr_row_dist_bwd(const float* a, int lda, const float* b, int ldb, const flo
  *   product reads w - 1 of them), g[i, c] at row lead_rows + i * Lp + arg[i, c], zero elsewhere (also in the rows the maximum never sees).
  *   db [C] is WRITTEN (not added to): the sum of g[i, c] over the titles with arg != 255 in a fixed order (groups of 8 titles, then the
  *   groups in order): same inputs, same bits.  ws: nnr_window_max_bwd_ws_floats(n, C) floats owned by the calling stream.
- * nnr_kcnn_repack, of the Conv2d weight W [C][E][w][3]:  mode 0: out [C][w][3][E] = the B operand of the convolution;  mode 1: out
- *   [3][E][w][C] with the window reversed, out[j][e][k][c] = W[c][e][w-1-k][j] = the B operand of the data gradient dXp = dz . W (A = dz with
- *   lda = C < K = w C);  mode 2: the inverse of mode 0 with accumulation, out [C][E][w][3] += in [C][w][3][E] (one plain writer per
- *   element: concurrent calls must not share `out`).
+ * The operand layouts of the Conv2d weight W [C][E][w][3] are nnr_permute calls: P [C][w][3][E] = the B operand of the convolution,
+ *   Q [3][E][w][C] with the window reversed (Q[j][e][k][c] = W[c][e][w-1-k][j]) = the B operand of the data gradient dXp = dz . W (A = dz
+ *   with lda = C < K = w C), and W.grad += the gradient of P.
  * NNR_ERR_UNSUPPORTED when L + w - 1 > 255, w > 8, E > 1024 or L < w (the reference's slice is empty there). */
 int nnr_kcnn_image_fwd(const float* word_table, int V, const int* text, const float* pre1, const float* pre2, int n, int L, int E, int w,
                        float* Xp, hipStream_t stream);
@@ -481,7 +488,6 @@ int nnr_window_max_fwd(const float* z, int ldz, const float* bias, int n, int C,
 size_t nnr_window_max_bwd_ws_floats(int n, int C);
 int nnr_window_max_bwd(const float* g, const uint8_t* arg, int n, int C, int L, int w, int lead_rows, float* dz, float* db, float* ws,
                        hipStream_t stream);
-int nnr_kcnn_repack(const float* in, float* out, int C, int E, int w, int mode, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------ HDC (csrc/hdc.hip)
  * The kernels around the dilated convolutions of the HDC news encoder (newsEncoders.py:244-278), which run as accumulating products of
@@ -496,8 +502,8 @@ int nnr_kcnn_repack(const float* in, float* out, int C, int E, int w, int mode, 
  * nnr_hdc_ln_relu_bwd: IN PLACE on z: rows [0, S) of every news become the gradient of the LayerNorm input, rows [S, z_rows) zero;
  *   dgamma / dbeta [F][S] += sums over the news in a fixed order (partials of 32 news in ws, nnr_hdc_ln_bwd_ws_floats floats).
  * nnr_hdc_unpad_add: out [n][S][C] = a [n][S][C] (may be NULL) + rows [pad, pad + S) of b_padded [n][S + 2 pad][C].
- * nnr_hdc_repack, of a Conv1d weight W [F][C][w] and its tap-major form P [w][F] with rows of ldp >= C floats (C used):  mode 0: out = P;
- *   mode 1: out [F][C][w] += in = P. */
+ * The tap-major form P [w][F] (rows of ldp >= C floats, C used) of a Conv1d weight W [F][C][w], and W.grad += the gradient of P, are
+ *   nnr_permute calls. */
 int nnr_hdc_seq_fwd(const float* word_table, int V, const float* cat_table, int ncat, const float* sub_table, int nsub, const int* text,
                     const int* category, const int* subCategory, int n, int L, int E, int pad, float* d0, float* d0p, int* tok_word,
                     int* tok_cat, int* tok_sub, hipStream_t stream);
@@ -507,7 +513,6 @@ size_t nnr_hdc_ln_bwd_ws_floats(int n, int S, int F);
 int nnr_hdc_ln_relu_bwd(const float* dy, const float* y, float* z, int z_rows, const float* stats, const float* gamma, int n, int S, int F,
                         float* dgamma_accum, float* dbeta_accum, float* ws, hipStream_t stream);
 int nnr_hdc_unpad_add(const float* a, const float* b_padded, int n, int S, int pad, int C, float* out, hipStream_t stream);
-int nnr_hdc_repack(const float* in, float* out, int F, int C, int w, int ldp, int mode, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------ FIM (csrc/fim.hip)
  * Conv3d(Cin -> Cout, kernel K^3) + bias + ELU + MaxPool3d(size P, stride St) in one launch (userEncoders.py:257-260); the dense
@@ -516,15 +521,14 @@ int nnr_hdc_repack(const float* in, float* out, int F, int C, int w, int ldp, in
  * that no pool cell reads are not computed.  y / arg: [imgs][PD][PH][PW][Cout] (cf_out == 0) or [imgs][Cout][PD][PH][PW] (cf_out == 1);
  * y = elu(maximum of the cell), arg (uint8) = (depth offset P + row offset) P + column offset of the LOWEST position in that scan order
  * that attains it (positions with equal windows give equal bits).
- * nnr_conv3d_repack of W [Cout][Cin][K][K][K]: mode 0 -> [Cin][K^3][Cout rounded up to 4] (the forward operand), mode 1 ->
- *   [Cout][K^3][Cin rounded up to 4] (the input-gradient operand); pad entries zero.
+ * wp / wq, of W [Cout][Cin][K][K][K]: [Cin][K^3][Cout rounded up to 4] (the forward operand) / [Cout][K^3][Cin rounded up to 4] (the
+ *   input-gradient operand), 16-byte aligned, pad entries zero (nnr_permute into a zeroed buffer).
  * nnr_conv3d_pool_bwd: g = dy (1 if y > 0 else y + 1) reaches the one position arg names.  dw_accum [Cout][Cin][K^3] and db_accum [Cout]
  *   += per-workgroup partials (ws, nnr_conv3d_pool_bwd_ws_floats floats) added in workgroup order; dx (same strides as x; may be NULL)
  *   is written once per element by a gather.  No float atomics: the same bits on every run.
  * NNR_ERR_UNSUPPORTED (nothing written) when K > 4, P > 4, St < P (overlapping windows), an axis is left without a pool cell, or the
  * staged slab (Cin K^3 Cout weights + one row of cells) exceeds 160 KB of LDS. */
 int nnr_conv3d_pool_dims(int Cin, int D, int H, int W, int Cout, int K, int P, int St, int* PD, int* PH, int* PW);
-int nnr_conv3d_repack(const float* w, float* out, int Cout, int Cin, int K, int mode, hipStream_t stream);
 int nnr_conv3d_pool_fwd(const float* x, long sxi, long sxc, long sxd, long sxh, long sxw, const float* wp, const float* bias, int imgs,
                         int Cin, int D, int H, int W, int Cout, int K, int P, int St, int cf_out, float* y, uint8_t* arg,
                         hipStream_t stream);

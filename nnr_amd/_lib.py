@@ -102,6 +102,7 @@ SIGNATURES = {
     'nnr_embed_scatter_sorted': 'i32 ptr ptr ptr i64 i32 i32 ptr f32 seed ptr stream',
     'nnr_transpose2d': 'i32 ptr ptr i64 i32 i32 stream',
     'nnr_transpose_batch': 'i32 TransposeDesc i32 stream',
+    'nnr_permute': 'i32 ptr ptr i32 i32 i32 i32 i64 i64 i64 i64 i64 i64 i64 i64 i32 stream',
     'nnr_add': 'i32 ptr ptr i64 f32 stream',
     'nnr_add_atomic': 'i32 ptr ptr i64 f32 stream',
     'nnr_add2d': 'i32 ptr i32 ptr i32 i32 i32 f32 i32 stream',
@@ -147,15 +148,12 @@ SIGNATURES = {
     'nnr_window_max_fwd': 'i32 ptr i32 ptr i32 i32 i32 i32 ptr ptr stream',
     'nnr_window_max_bwd_ws_floats': 'u64 i32 i32',
     'nnr_window_max_bwd': 'i32 ptr ptr i32 i32 i32 i32 i32 ptr ptr ptr stream',
-    'nnr_kcnn_repack': 'i32 ptr ptr i32 i32 i32 i32 stream',
     'nnr_hdc_seq_fwd': 'i32 ptr i32 ptr i32 ptr i32 ptr ptr ptr i32 i32 i32 i32 ptr ptr ptr ptr ptr stream',
     'nnr_hdc_ln_relu_fwd': 'i32 ptr i32 ptr ptr i32 i32 i32 f32 ptr ptr i32 ptr stream',
     'nnr_hdc_ln_bwd_ws_floats': 'u64 i32 i32 i32',
     'nnr_hdc_ln_relu_bwd': 'i32 ptr ptr ptr i32 ptr ptr i32 i32 i32 ptr ptr ptr stream',
     'nnr_hdc_unpad_add': 'i32 ptr ptr i32 i32 i32 i32 ptr stream',
-    'nnr_hdc_repack': 'i32 ptr ptr i32 i32 i32 i32 i32 stream',
     'nnr_conv3d_pool_dims': 'i32 i32 i32 i32 i32 i32 i32 i32 i32 ptr ptr ptr',
-    'nnr_conv3d_repack': 'i32 ptr ptr i32 i32 i32 i32 stream',
     'nnr_conv3d_pool_fwd': 'i32 ptr i64 i64 i64 i64 i64 ptr ptr i32 i32 i32 i32 i32 i32 i32 i32 i32 i32 ptr ptr stream',
     'nnr_conv3d_pool_bwd_ws_floats': 'u64 i32 i32 i32 i32 i32 i32 i32 i32 i32',
     'nnr_conv3d_pool_bwd': 'i32 ptr ptr ptr ptr i64 i64 i64 i64 i64 ptr i32 i32 i32 i32 i32 i32 i32 i32 i32 i32 ptr ptr ptr ptr stream',
@@ -272,10 +270,15 @@ def build_id():
     return {'src_sha256': h.hexdigest()[:16], 'lib_sha256': lib_hash}
 
 
+NNR_ERR_UNSUPPORTED = -3
 CALLS = [0]          # C-ABI calls checked so far (bench.py reports calls per step; each is one or a few kernel launches)
 
 
-def check(rc, what):
-    CALLS[0] += 1
+def check(rc, what, unsupported=None, counted=True):
+    """unsupported: the sentence to raise with when the entry point answers NNR_ERR_UNSUPPORTED (sizes beyond a kernel family's limits).
+    counted=False: a size query that launches nothing and is not one of a step's calls."""
+    CALLS[0] += counted
+    if rc == NNR_ERR_UNSUPPORTED and unsupported is not None:
+        raise NnrHipError('%s: %s' % (what, unsupported))
     if rc != 0:
         raise NnrHipError('%s failed with code %d' % (what, rc))

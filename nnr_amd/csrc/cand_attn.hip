@@ -26,14 +26,6 @@ constexpr int CA_RELU = 1, CA_TANH = 2;          // nnr_gemm_args.act numbering
 constexpr int CA_NQ = 8;                         // queries per register chunk
 constexpr int CA_LDS_BYTES = 64 * 1024;          // dynamic LDS a launch may ask for without an attribute
 
-template <int V> struct ca_vec;
-template <> struct ca_vec<4> { typedef f32x4 type; };
-template <> struct ca_vec<1> { typedef float type; };
-template <int V> __device__ __forceinline__ typename ca_vec<V>::type ca_zero();
-template <> __device__ __forceinline__ f32x4 ca_zero<4>() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-template <> __device__ __forceinline__ float ca_zero<1>() { return 0.f; }
-__device__ __forceinline__ float ca_dot(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
-__device__ __forceinline__ float ca_dot(float a, float b) { return a * b; }
 
 // activation and its derivative at z
 __device__ __forceinline__ void ca_act_grad(float z, int act, float* a, float* d) {
@@ -57,7 +49,7 @@ __global__ __launch_bounds__(256) void cand_attn_fwd_kernel(const float* __restr
                                                             const float* __restrict__ w2, const float* __restrict__ feat, int ldf,
                                                             const uint8_t* __restrict__ mask, int N, int H, int A, int D, int act, int S,
                                                             float* __restrict__ alpha, float* __restrict__ out) {
-  typedef typename ca_vec<V>::type vec;
+  typedef typename vec_t<V>::type vec;
   extern __shared__ __align__(16) float ca_smem[];
   const int b = blockIdx.x / S, slice = blockIdx.x - b * S;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -117,11 +109,11 @@ __global__ __launch_bounds__(256) void cand_attn_fwd_kernel(const float* __restr
   for (int n0 = 0; n0 < N; n0 += CA_NQ) {
     vec acc[CA_NQ];
 #pragma unroll
-    for (int j = 0; j < CA_NQ; ++j) acc[j] = ca_zero<V>();
+    for (int j = 0; j < CA_NQ; ++j) acc[j] = vzero<V>();
     for (int h0 = w; h0 < H; h0 += 16) {
       vec f[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) f[u] = (live && h0 + 4 * u < H) ? *reinterpret_cast<const vec*>(fb + (long)(h0 + 4 * u) * ldf) : ca_zero<V>();
+      for (int u = 0; u < 4; ++u) f[u] = (live && h0 + 4 * u < H) ? *reinterpret_cast<const vec*>(fb + (long)(h0 + 4 * u) * ldf) : vzero<V>();
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (h0 + 4 * u < H) {
@@ -166,7 +158,7 @@ __global__ __launch_bounds__(256) void cand_attn_bwd_da_kernel(const float* __re
                                                                const uint8_t* __restrict__ mask, const float* __restrict__ alpha,
                                                                const float* __restrict__ dout, int B, int N, int H, int A, int D, int act,
                                                                float* __restrict__ da_ws, float* __restrict__ dP, float* __restrict__ dw2_rows) {
-  typedef typename ca_vec<V>::type vec;
+  typedef typename vec_t<V>::type vec;
   extern __shared__ __align__(16) float ca_smem[];
   float* sal = ca_smem;
   float* sdl = sal + H;
@@ -190,7 +182,7 @@ __global__ __launch_bounds__(256) void cand_attn_bwd_da_kernel(const float* __re
 #pragma unroll
       for (int u = 0; u < 4; ++u) f[u] = *reinterpret_cast<const vec*>(fr[u] + (long)x * V);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) p[u] += ca_dot(d, f[u]);
+      for (int u = 0; u < 4; ++u) p[u] += vdot(d, f[u]);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -243,7 +235,7 @@ __global__ __launch_bounds__(256) void cand_attn_bwd_dx_kernel(const float* __re
                                                                const float* __restrict__ da_ws, const float* __restrict__ dout, int N, int H,
                                                                int A, int D, int act, int S, float* __restrict__ dQ, float* __restrict__ dfeat,
                                                                int accumulate) {
-  typedef typename ca_vec<V>::type vec;
+  typedef typename vec_t<V>::type vec;
   extern __shared__ __align__(16) float ca_smem[];
   const int b = blockIdx.x / (S + CA_ZQ), y = blockIdx.x - b * (S + CA_ZQ);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -285,9 +277,9 @@ __global__ __launch_bounds__(256) void cand_attn_bwd_dx_kernel(const float* __re
   for (int n0 = 0; n0 < N; n0 += CA_NQ) {
     vec dv[CA_NQ];
 #pragma unroll
-    for (int j = 0; j < CA_NQ; ++j) dv[j] = n0 + j < N ? *reinterpret_cast<const vec*>(dout + ((long)b * N + n0 + j) * D + (long)c * V) : ca_zero<V>();
+    for (int j = 0; j < CA_NQ; ++j) dv[j] = n0 + j < N ? *reinterpret_cast<const vec*>(dout + ((long)b * N + n0 + j) * D + (long)c * V) : vzero<V>();
     for (int h = w; h < H; h += 4) {
-      vec acc = ca_zero<V>();
+      vec acc = vzero<V>();
 #pragma unroll
       for (int j = 0; j < CA_NQ; ++j)
         if (n0 + j < N) acc += ca_smem[(n0 + j) * H + h] * dv[j];
@@ -298,7 +290,6 @@ __global__ __launch_bounds__(256) void cand_attn_bwd_dx_kernel(const float* __re
   }
 }
 
-inline bool ca_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -312,7 +303,7 @@ extern "C" int nnr_cand_attn_fwd(const float* P, const float* Q, const float* w2
                                  int H, int A, int D, int act, float* alpha, float* out, hipStream_t stream) {
   if (!P || !Q || !w2 || !feat || !alpha || !out || B < 1 || N < 1 || H < 1 || A < 1 || D < 1 || ldf < D || (act != CA_RELU && act != CA_TANH))
     return NNR_ERR_ARG;
-  const int V = (!(D & 3) && !(ldf & 3) && ca_al16(feat) && ca_al16(out)) ? 4 : 1;
+  const int V = (!(D & 3) && !(ldf & 3) && al16(feat) && al16(out)) ? 4 : 1;
   const int S = (D / V + 63) / 64;
   const long small = (long)N * A + A + (long)N * H;
   if (small * 4 > CA_LDS_BYTES) return NNR_ERR_UNSUPPORTED;
@@ -342,7 +333,7 @@ extern "C" int nnr_cand_attn_bwd(const float* P, const float* Q, const float* w2
       ldf < D || (act != CA_RELU && act != CA_TANH))
     return NNR_ERR_ARG;
   if (nnr_cand_attn_ws_floats(B, N, H, A) < 0) return NNR_ERR_UNSUPPORTED;
-  const int V = (!(D & 3) && !(ldf & 3) && ca_al16(feat) && ca_al16(dout) && ca_al16(dfeat)) ? 4 : 1;
+  const int V = (!(D & 3) && !(ldf & 3) && al16(feat) && al16(dout) && al16(dfeat)) ? 4 : 1;
   const int S = (D / V + 63) / 64;
   const long lds2 = ((long)N * H + (long)N * A) * 4;
   if (3L * H * 4 > CA_LDS_BYTES || lds2 > CA_LDS_BYTES || (long)H * A > 0x7fffffffL) return NNR_ERR_UNSUPPORTED;

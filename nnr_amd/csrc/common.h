@@ -5,6 +5,7 @@
 #include "../../include/nnr_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define NNR_CHECK_LAUNCH()                                   \
   do {                                                       \
@@ -65,3 +66,47 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-
 // Absolute error ~2e-7 (1-2 ulp of the result), far inside the 1e-4 parity bar (tests/test_hip_ops_gpu.py: 2e-5).
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
 __device__ __forceinline__ float fast_tanh(float x) { return 2.f * fast_sigmoid(2.f * x) - 1.f; }
+
+// ---------------------------------------------------------------- V = 4 (float4) / V = 1 (scalar) variants of one kernel body
+template <int V> struct vec_t;
+template <> struct vec_t<4> { typedef f32x4 type; };
+template <> struct vec_t<1> { typedef float type; };
+template <int V> __device__ __forceinline__ typename vec_t<V>::type vzero();
+template <> __device__ __forceinline__ f32x4 vzero<4>() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
+template <> __device__ __forceinline__ float vzero<1>() { return 0.f; }
+__device__ __forceinline__ float vdot(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
+__device__ __forceinline__ float vdot(float a, float b) { return a * b; }
+__device__ __forceinline__ f32x4 vtanh(f32x4 z) { return f32x4{tanhf(z[0]), tanhf(z[1]), tanhf(z[2]), tanhf(z[3])}; }
+__device__ __forceinline__ float vtanh(float z) { return tanhf(z); }
+
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// blocks of 256 threads for an element-wise kernel with a grid-stride loop over `total` elements, capped
+static inline unsigned grid_for(long total, long cap = 8192) {
+  const long b = (total + 255) / 256;
+  return (unsigned)(b > cap ? cap : (b < 1 ? 1 : b));
+}
+
+// ---------------------------------------------------------------- fixed-order sum of partial rows
+// sum over q = 0 .. rows - 1, ascending, of ws[q * stride + p]: strictly sequential adds (same inputs -> same bits), four loads in flight
+__device__ __forceinline__ float partial_rows_sum(const float* __restrict__ ws, int rows, long stride, long p) {
+  float t = 0.f;
+  int q = 0;
+  for (; q + 4 <= rows; q += 4) {
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = ws[(long)(q + u) * stride + p];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) t += v[u];
+  }
+  for (; q < rows; ++q) t += ws[(long)q * stride + p];
+  return t;
+}
+// out[p] (+)= the partial rows ws[rows][n] in row order, one thread per element
+template <bool ACCUMULATE>
+__global__ __launch_bounds__(256) void partial_rows_sum_kernel(const float* __restrict__ ws, int rows, long n, float* __restrict__ out) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n) return;
+  const float t = partial_rows_sum(ws, rows, n, p);
+  out[p] = ACCUMULATE ? out[p] + t : t;
+}

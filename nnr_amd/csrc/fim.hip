@@ -198,16 +198,7 @@ __global__ __launch_bounds__(256) void conv3d_pool_dw_reduce_kernel(const float*
   const int o = blockIdx.x * 256 + threadIdx.x;
   const int T1 = T + 1;
   if (o >= Cout * T1) return;
-  float s = 0.f;
-  int q = 0;
-  for (; q + 4 <= blocks; q += 4) {
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = ws[(long)(q + u) * Cout * T1 + o];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) s += v[u];
-  }
-  for (; q < blocks; ++q) s += ws[(long)q * Cout * T1 + o];
+  const float s = partial_rows_sum(ws, blocks, (long)Cout * T1, o);
   const int f = o / T1, t = o - f * T1;
   if (t < T) dw[f * T + t] += s;
   else db[f] += s;
@@ -260,18 +251,6 @@ __global__ __launch_bounds__(256) void conv3d_pool_dx_kernel(const c3_args a, lo
     if (cg * 4 + u < a.Cin) dst[(cg * 4 + u) * a.sxc] = acc[u];
 }
 
-// mode 0: W [Cout][Cin][K^3] -> [Cin][K^3][CoutPad]; mode 1: W -> [Cout][K^3][CinPad]; pad entries are zero
-__global__ __launch_bounds__(256) void conv3d_repack_kernel(const float* __restrict__ w, float* __restrict__ out, int Cout, int Cin, int taps, int mode) {
-  const int CoutPad = (Cout + 3) & ~3, CinPad = (Cin + 3) & ~3;
-  const long total = mode == 0 ? (long)Cin * taps * CoutPad : (long)Cout * taps * CinPad;
-  for (long o = blockIdx.x * 256L + threadIdx.x; o < total; o += (long)gridDim.x * 256) {
-    int f, ci, kk;
-    if (mode == 0) { f = (int)(o % CoutPad); kk = (int)((o / CoutPad) % taps); ci = (int)(o / ((long)CoutPad * taps)); }
-    else { ci = (int)(o % CinPad); kk = (int)((o / CinPad) % taps); f = (int)(o / ((long)CinPad * taps)); }
-    out[o] = (f < Cout && ci < Cin) ? w[((long)f * Cin + ci) * taps + kk] : 0.f;
-  }
-}
-
 struct c3_plan { int PD, PH, PW, PHB, nchunk; size_t lds; };
 
 static bool c3_shape(int Cin, int D, int H, int W, int Cout, int K, int P, int St, c3_plan* pl) {
@@ -318,8 +297,6 @@ static int c3_fwd_launch(const c3_args& a, long blocks, size_t lds, hipStream_t 
     default: return NNR_ERR_UNSUPPORTED;                                                                           \
   }
 
-static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int nnr_conv3d_pool_dims(int Cin, int D, int H, int W, int Cout, int K, int P, int St, int* PD, int* PH, int* PW) {
@@ -329,16 +306,6 @@ extern "C" int nnr_conv3d_pool_dims(int Cin, int D, int H, int W, int Cout, int 
   if (PD) *PD = pl.PD;
   if (PH) *PH = pl.PH;
   if (PW) *PW = pl.PW;
-  return NNR_OK;
-}
-
-extern "C" int nnr_conv3d_repack(const float* w, float* out, int Cout, int Cin, int K, int mode, hipStream_t stream) {
-  if (!w || !out || Cout <= 0 || Cin <= 0 || K <= 0 || mode < 0 || mode > 1) return NNR_ERR_ARG;
-  if (K > C3_MAX_K) return NNR_ERR_UNSUPPORTED;
-  const long total = mode == 0 ? (long)Cin * K * K * K * ((Cout + 3) & ~3) : (long)Cout * K * K * K * ((Cin + 3) & ~3);
-  const long blocks = (total + 255) / 256;
-  hipLaunchKernelGGL(conv3d_repack_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, stream, w, out, Cout, Cin, K * K * K, mode);
-  NNR_CHECK_LAUNCH();
   return NNR_OK;
 }
 

@@ -103,8 +103,7 @@ __global__ __launch_bounds__(256) void hdc_ln_param_reduce_kernel(const float* _
   const int e = blockIdx.x * 256 + threadIdx.x;
   const int n = S * F;
   if (e >= n) return;
-  float g = 0.f, b = 0.f;
-  for (int c = 0; c < chunks; ++c) { g += ws[((long)c * 2) * n + e]; b += ws[((long)c * 2 + 1) * n + e]; }
+  const float g = partial_rows_sum(ws, chunks, 2L * n, e), b = partial_rows_sum(ws + n, chunks, 2L * n, e);
   const int sp = e / F, f = e - sp * F;
   dgamma[f * S + sp] += g;
   dbeta[f * S + sp] += b;
@@ -147,27 +146,6 @@ __global__ __launch_bounds__(256) void hdc_unpad_add_kernel(const float* __restr
     const float v = bp[i * (long)Sp * C + (long)pad * C + (o - i * SC)];
     out[o] = a ? a[o] + v : v;
   }
-}
-
-// mode 0: W [F][C][w] -> P [w][F][ldp] (C of ldp floats per row written);  mode 1: W[f][c][k] += P[k][f][c], rows of ldp floats
-__global__ __launch_bounds__(256) void hdc_repack_kernel(const float* __restrict__ in, float* __restrict__ out, int F, int C, int w, int ldp, int mode) {
-  const long total = (long)F * C * w;
-  for (long o = blockIdx.x * 256L + threadIdx.x; o < total; o += (long)gridDim.x * 256) {
-    if (mode == 0) {
-      const int c = (int)(o % C); const long r = o / C;
-      const int f = (int)(r % F), k = (int)(r / F);
-      out[r * ldp + c] = in[((long)f * C + c) * w + k];
-    } else {
-      const int k = (int)(o % w); const long r = o / w;
-      const int c = (int)(r % C), f = (int)(r / C);
-      out[o] += in[((long)k * F + f) * ldp + c];
-    }
-  }
-}
-
-static inline unsigned grid_for(long total) {
-  const long b = (total + 255) / 256;
-  return (unsigned)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
 }
 
 }  // namespace
@@ -220,13 +198,6 @@ extern "C" int nnr_hdc_unpad_add(const float* a, const float* b_padded, int n, i
   if (n == 0) return NNR_OK;
   const long total = (long)n * S * C;
   hipLaunchKernelGGL(hdc_unpad_add_kernel, dim3(grid_for(total)), dim3(256), 0, stream, a, b_padded, total, S, S + 2 * pad, pad, C, out);
-  NNR_CHECK_LAUNCH();
-  return NNR_OK;
-}
-
-extern "C" int nnr_hdc_repack(const float* in, float* out, int F, int C, int w, int ldp, int mode, hipStream_t stream) {
-  if (!in || !out || F <= 0 || C <= 0 || w <= 0 || ldp < C || mode < 0 || mode > 1) return NNR_ERR_ARG;
-  hipLaunchKernelGGL(hdc_repack_kernel, dim3(grid_for((long)F * C * w)), dim3(256), 0, stream, in, out, F, C, w, ldp, mode);
   NNR_CHECK_LAUNCH();
   return NNR_OK;
 }

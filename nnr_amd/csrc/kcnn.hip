@@ -5,7 +5,8 @@
 // a row, p = (w - 1) / 2 leading and w - 1 - p trailing zero rows per title): the window of output position t is the contiguous 3 w E
 // floats that start at padded row t, i.e. a row-major A with lda = 3 E < K = 3 w E.  The kernels here build that image (word rows gathered
 // straight from the table, tanh of the two projected knowledge channels, halo rows), take it apart again for the backward pass, do the
-// relu + max over the first L - w + 1 positions with its dense gradient, and repack the Conv2d weight.  They move bytes: no MFMA, no LDS.
+// relu + max over the first L - w + 1 positions with its dense gradient.  (The Conv2d weight's operand layouts: nnr_permute, csrc/misc.hip.)
+// They move bytes: no MFMA, no LDS.
 #include "common.h"
 
 namespace {
@@ -16,7 +17,6 @@ constexpr int KCNN_MAX_E = 1024;
 constexpr int WM_TITLES = 8;         // titles per thread of window_max_bwd_kernel (one partial bias-gradient row per group)
 
 static inline bool kcnn_dims_ok(int L, int E, int w) { return L + w - 1 <= KCNN_MAX_ROWS && w <= KCNN_MAX_W && E <= KCNN_MAX_E && L >= w; }
-static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // one wave per padded row (i, s); VEC = 4: float4 accesses (E % 4 == 0, 16-byte aligned bases), VEC = 1: scalar
 template <int VEC>
@@ -139,53 +139,6 @@ __global__ __launch_bounds__(256) void window_max_bwd_kernel(const float* __rest
   ws[(long)grp * C + c] = part;
 }
 
-// db[c] = the groups' partials in group order (plain store: the caller owns db)
-__global__ __launch_bounds__(256) void window_max_db_kernel(const float* __restrict__ ws, int groups, int C, float* __restrict__ db) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
-  float t = 0.f;
-  int q = 0;
-  for (; q + 4 <= groups; q += 4) {                            // four loads in flight, added in group order
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = ws[(long)(q + u) * C + c];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) t += v[u];
-  }
-  for (; q < groups; ++q) t += ws[(long)q * C + c];
-  db[c] = t;
-}
-
-// mode 0: W [C][E][w][3] -> P [C][w][3][E];  mode 1: W -> Q [3][E][w][C] with the window reversed (Q[j][e][k][c] = W[c][e][w-1-k][j]);
-// mode 2: W[c][e][dt][j] += P[c][dt][j][e].  One thread per element of the written array, its index fastest along the written rows.
-__global__ __launch_bounds__(256) void kcnn_repack_kernel(const float* __restrict__ in, float* __restrict__ out, int C, int E, int w, int mode) {
-  const long total = (long)C * E * w * 3;
-  for (long o = blockIdx.x * 256L + threadIdx.x; o < total; o += (long)gridDim.x * 256) {
-    if (mode == 0) {
-      const int e = (int)(o % E);
-      long r = o / E;
-      const int j = (int)(r % 3); r /= 3;
-      const int dt = (int)(r % w);
-      const long c = r / w;
-      out[o] = in[((c * E + e) * w + dt) * 3 + j];
-    } else if (mode == 1) {
-      const long c = o % C;
-      long r = o / C;
-      const int k = (int)(r % w); r /= w;
-      const int e = (int)(r % E);
-      const int j = (int)(r / E);
-      out[o] = in[((c * E + e) * w + (w - 1 - k)) * 3 + j];
-    } else {
-      const int j = (int)(o % 3);
-      long r = o / 3;
-      const int dt = (int)(r % w); r /= w;
-      const int e = (int)(r % E);
-      const long c = r / E;
-      out[o] += in[((c * w + dt) * 3 + j) * E + e];
-    }
-  }
-}
-
 }  // namespace
 
 extern "C" int nnr_kcnn_image_fwd(const float* word_table, int V, const int* text, const float* pre1, const float* pre2, int n, int L, int E, int w,
@@ -244,17 +197,7 @@ extern "C" int nnr_window_max_bwd(const float* g, const uint8_t* arg, int n, int
     hipLaunchKernelGGL(window_max_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, g, arg, n, C, L + w - 1, lead_rows, dz, ws);
     NNR_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(window_max_db_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, ws, groups, C, db);
-  NNR_CHECK_LAUNCH();
-  return NNR_OK;
-}
-
-extern "C" int nnr_kcnn_repack(const float* in, float* out, int C, int E, int w, int mode, hipStream_t stream) {
-  if (!in || !out || C <= 0 || E <= 0 || w <= 0 || mode < 0 || mode > 2) return NNR_ERR_ARG;
-  if (w > KCNN_MAX_W || E > KCNN_MAX_E) return NNR_ERR_UNSUPPORTED;
-  const long total = (long)C * E * w * 3;
-  const long blocks = (total + 255) / 256;
-  hipLaunchKernelGGL(kcnn_repack_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, stream, in, out, C, E, w, mode);
+  hipLaunchKernelGGL(partial_rows_sum_kernel<false>, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, (const float*)ws, groups, (long)C, db);   // plain store: the caller owns db
   NNR_CHECK_LAUNCH();
   return NNR_OK;
 }

@@ -976,6 +976,20 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
   }
 }
 
+// one thread per element of the index space, i3 fastest (a 32-bit index: the entry point bounds the element count)
+__global__ __launch_bounds__(256) void permute_kernel(const float* __restrict__ in, float* __restrict__ out, unsigned total, unsigned n1, unsigned n2,
+                                                      unsigned n3, long si0, long si1, long si2, long si3, long so0, long so1, long so2, long so3,
+                                                      int accumulate) {
+  for (unsigned o = blockIdx.x * 256u + threadIdx.x; o < total; o += gridDim.x * 256u) {
+    const unsigned r3 = o / n3, i3 = o - r3 * n3;
+    const unsigned r2 = r3 / n2, i2 = r3 - r2 * n2;
+    const unsigned i0 = r2 / n1, i1 = r2 - i0 * n1;
+    const float v = in[i0 * si0 + i1 * si1 + i2 * si2 + i3 * si3];
+    float* __restrict__ d = out + (i0 * so0 + i1 * so1 + i2 * so2 + i3 * so3);
+    *d = accumulate ? *d + v : v;
+  }
+}
+
 }  // namespace
 
 #define EW_LAUNCH(kern, n, ...)                                                             \
@@ -1106,6 +1120,17 @@ extern "C" int nnr_transpose_batch(const nnr_transpose_desc* descs_dev, int coun
   if (count <= 0) return NNR_OK;
   if (!descs_dev) return NNR_ERR_ARG;
   hipLaunchKernelGGL(transpose_batch_kernel, dim3(64, count), dim3(256), 0, stream, descs_dev);
+  NNR_CHECK_LAUNCH();
+  return NNR_OK;
+}
+
+extern "C" int nnr_permute(const float* in, float* out, int n0, int n1, int n2, int n3, long si0, long si1, long si2, long si3, long so0, long so1,
+                           long so2, long so3, int accumulate, hipStream_t stream) {
+  if (!in || !out || n0 < 1 || n1 < 1 || n2 < 1 || n3 < 1) return NNR_ERR_ARG;
+  const long total = (long)n0 * n1;
+  if (total > 0x7fffffffL || total * n2 > 0x7fffffffL || total * n2 * n3 > 0x7fffffffL) return NNR_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(permute_kernel, dim3(grid_for(total * n2 * n3, 4096)), dim3(256), 0, stream, in, out, (unsigned)(total * n2 * n3), (unsigned)n1,
+                     (unsigned)n2, (unsigned)n3, si0, si1, si2, si3, so0, so1, so2, so3, accumulate);
   NNR_CHECK_LAUNCH();
   return NNR_OK;
 }

@@ -22,7 +22,7 @@
 //                                      whose alpha is 1/H), G = (dS + dS^T) / s -> workspace.
 //   backward 3 omap_bwd_dx_kernel      per (user, slice): dY again (K FMAs per element, cheaper than a [B, H, D] round trip), dX = dY + alpha^T dY
 //                                      + G X on the MFMA, and the user's rows of dW = Y^T db / s -> workspace.
-//   backward 4 omap_dw_reduce_kernel   dW += the per-user rows added in user order by one thread per element: no float atomics into shared
+//   backward 4 partial_rows_sum_kernel dW += the per-user rows added in user order by one thread per element: no float atomics into shared
 //                                      destinations, same inputs -> same bits (nnr_colsum would do the same in two launches).
 // The regulariser coef * ||(W^T W) o (J - I)||_F is one workgroup forward (Off and Omega stay on the device for the backward pass) and one
 // elementwise launch backward, scaled by the device-side upstream gradient; an exactly zero Omega gives an exactly zero gradient, as torch.
@@ -31,8 +31,6 @@
 #include "common.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int OM_KC = 64;                    // columns of a streamed chunk / of a slice
 constexpr int OM_LD = OM_KC + 1;             // LDS row stride of a chunk (odd: a thread per row walks it conflict-free)
@@ -537,16 +535,6 @@ __global__ __launch_bounds__(256) void omap_bwd_dx_kernel(const float* __restric
   }
 }
 
-// backward 4: dW[p] += sum_b rows[b, p], b ascending
-__global__ __launch_bounds__(256) void omap_dw_reduce_kernel(const float* __restrict__ rows, int B, long n, float* __restrict__ dW) {
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= n) return;
-  float a = 0.f;
-#pragma unroll 8
-  for (int b = 0; b < B; ++b) a += rows[(long)b * n + p];
-  dW[p] += a;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- regulariser
 // one workgroup: off[k1 * K + k2] = (W^T W)[k1, k2] off the diagonal, 0 on it; off[K * K] = Omega = ||Off||_F; loss = coef * Omega
 __global__ __launch_bounds__(256) void omap_reg_fwd_kernel(const float* __restrict__ W, int D, int K, float coef, float* __restrict__ off,
@@ -665,7 +653,7 @@ extern "C" int nnr_omap_bwd(const float* hist, int ldf, const float* cand, const
 #undef OM_L2
 #undef OM_L3
   const long n = (long)D * K;
-  hipLaunchKernelGGL(omap_dw_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)rows, B, n, dW_accum);
+  hipLaunchKernelGGL(partial_rows_sum_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)rows, B, n, dW_accum);   // backward 4
   NNR_CHECK_LAUNCH();
   return NNR_OK;
 }

@@ -23,16 +23,6 @@ namespace {
 constexpr int PA_NA = 4;                          // 64-lane chunks of the A axis held in registers
 constexpr int PA_UR = 4;                          // positions in flight per trip
 
-template <int V> struct pa_vec;
-template <> struct pa_vec<4> { typedef f32x4 type; };
-template <> struct pa_vec<1> { typedef float type; };
-template <int V> __device__ __forceinline__ typename pa_vec<V>::type pa_zero();
-template <> __device__ __forceinline__ f32x4 pa_zero<4>() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-template <> __device__ __forceinline__ float pa_zero<1>() { return 0.f; }
-__device__ __forceinline__ float pa_dot(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
-__device__ __forceinline__ float pa_dot(float a, float b) { return a * b; }
-__device__ __forceinline__ f32x4 pa_tanh(f32x4 z) { return f32x4{tanhf(z[0]), tanhf(z[1]), tanhf(z[2]), tanhf(z[3])}; }
-__device__ __forceinline__ float pa_tanh(float z) { return tanhf(z); }
 
 // the next (up to) PA_UR set bits of `bits`, lowest first; t[u] = -1 when there are fewer
 __device__ __forceinline__ void pa_take(unsigned long long& bits, int (&t)[PA_UR]) {
@@ -57,7 +47,7 @@ __global__ __launch_bounds__(256) void pers_attn_fwd_kernel(const float* __restr
                                                             int U, const float* __restrict__ w2, const float* __restrict__ feat, int ldf,
                                                             const uint8_t* __restrict__ mask, int n, int L, int A, int F,
                                                             float* __restrict__ alpha, float* __restrict__ out) {
-  typedef typename pa_vec<V>::type vec;
+  typedef typename vec_t<V>::type vec;
   const int lane = threadIdx.x & 63;
   const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= n) return;                                                      // (wave-uniform; the kernel has no barrier)
@@ -75,8 +65,8 @@ __global__ __launch_bounds__(256) void pers_attn_fwd_kernel(const float* __restr
     for (int c = 0; c < PA_NA; ++c) {
       const int col = c * 64 + lane;
       const bool in = col < ncA;
-      p[c] = (in && has_q) ? *reinterpret_cast<const vec*>(P + (long)u * A + (long)col * V) : pa_zero<V>();
-      w[c] = in ? *reinterpret_cast<const vec*>(w2 + (long)col * V) : pa_zero<V>();
+      p[c] = (in && has_q) ? *reinterpret_cast<const vec*>(P + (long)u * A + (long)col * V) : vzero<V>();
+      w[c] = in ? *reinterpret_cast<const vec*>(w2 + (long)col * V) : vzero<V>();
     }
     float s = -INFINITY;
     const float* qb = Qf + i * L * A;
@@ -94,9 +84,9 @@ __global__ __launch_bounds__(256) void pers_attn_fwd_kernel(const float* __restr
         vec q[PA_UR];
 #pragma unroll
         for (int r = 0; r < PA_UR; ++r)
-          q[r] = (col < ncA && t[r] >= 0) ? *reinterpret_cast<const vec*>(qb + (long)t[r] * A + (long)col * V) : pa_zero<V>();
+          q[r] = (col < ncA && t[r] >= 0) ? *reinterpret_cast<const vec*>(qb + (long)t[r] * A + (long)col * V) : vzero<V>();
 #pragma unroll
-        for (int r = 0; r < PA_UR; ++r) part[r] += pa_dot(w[c], pa_tanh(q[r] + p[c]));      // (w = 0 beyond A)
+        for (int r = 0; r < PA_UR; ++r) part[r] += vdot(w[c], vtanh(q[r] + p[c]));      // (w = 0 beyond A)
       }
 #pragma unroll
       for (int r = 0; r < PA_UR; ++r) {
@@ -115,14 +105,14 @@ __global__ __launch_bounds__(256) void pers_attn_fwd_kernel(const float* __restr
   for (int c0 = 0; c0 < ncF; c0 += 64) {
     const int col = c0 + lane;
     const bool in = col < ncF;
-    vec acc = pa_zero<V>();
+    vec acc = vzero<V>();
     unsigned long long bits = used;
     while (bits) {
       int t[PA_UR];
       pa_take(bits, t);
       vec f[PA_UR];
 #pragma unroll
-      for (int r = 0; r < PA_UR; ++r) f[r] = (in && t[r] >= 0) ? *reinterpret_cast<const vec*>(fb + (long)t[r] * ldf + (long)col * V) : pa_zero<V>();
+      for (int r = 0; r < PA_UR; ++r) f[r] = (in && t[r] >= 0) ? *reinterpret_cast<const vec*>(fb + (long)t[r] * ldf + (long)col * V) : vzero<V>();
 #pragma unroll
       for (int r = 0; r < PA_UR; ++r) acc += __shfl(a, t[r] < 0 ? 0 : t[r], 64) * f[r];
     }
@@ -138,7 +128,7 @@ __global__ __launch_bounds__(256) void pers_attn_bwd_kernel(const float* __restr
                                                             const float* __restrict__ dout, int n, int L, int A, int F,
                                                             float* __restrict__ dQf, float* __restrict__ dfeat, float* __restrict__ rows_p,
                                                             float* __restrict__ rows_w) {
-  typedef typename pa_vec<V>::type vec;
+  typedef typename vec_t<V>::type vec;
   const int lane = threadIdx.x & 63;
   const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= n) return;
@@ -163,13 +153,13 @@ __global__ __launch_bounds__(256) void pers_attn_bwd_kernel(const float* __restr
     for (int c0 = 0; c0 < ncF; c0 += 64) {
       const int col = c0 + lane;
       const bool in = col < ncF;
-      const vec d = in ? *reinterpret_cast<const vec*>(dr + (long)col * V) : pa_zero<V>();
+      const vec d = in ? *reinterpret_cast<const vec*>(dr + (long)col * V) : vzero<V>();
       vec f[PA_UR];
 #pragma unroll
-      for (int r = 0; r < PA_UR; ++r) f[r] = (in && lv[r]) ? *reinterpret_cast<const vec*>(fb + (long)(t0 + r) * ldf + (long)col * V) : pa_zero<V>();
+      for (int r = 0; r < PA_UR; ++r) f[r] = (in && lv[r]) ? *reinterpret_cast<const vec*>(fb + (long)(t0 + r) * ldf + (long)col * V) : vzero<V>();
 #pragma unroll
       for (int r = 0; r < PA_UR; ++r) {
-        part[r] += pa_dot(d, f[r]);
+        part[r] += vdot(d, f[r]);
         if (in && t0 + r < L) *reinterpret_cast<vec*>(dfb + (long)(t0 + r) * F + (long)col * V) = at[r] * d;
       }
     }
@@ -191,10 +181,10 @@ __global__ __launch_bounds__(256) void pers_attn_bwd_kernel(const float* __restr
   for (int c = 0; c < PA_NA; ++c) {
     const int col = c * 64 + lane;
     const bool in = col < ncA;
-    p[c] = (in && has_q) ? *reinterpret_cast<const vec*>(P + (long)u * A + (long)col * V) : pa_zero<V>();
-    w[c] = in ? *reinterpret_cast<const vec*>(w2 + (long)col * V) : pa_zero<V>();
-    accP[c] = pa_zero<V>();
-    accW[c] = pa_zero<V>();
+    p[c] = (in && has_q) ? *reinterpret_cast<const vec*>(P + (long)u * A + (long)col * V) : vzero<V>();
+    w[c] = in ? *reinterpret_cast<const vec*>(w2 + (long)col * V) : vzero<V>();
+    accP[c] = vzero<V>();
+    accW[c] = vzero<V>();
   }
   const float* qb = Qf + i * L * A;
   float* dqb = dQf + i * L * A;
@@ -213,12 +203,12 @@ __global__ __launch_bounds__(256) void pers_attn_bwd_kernel(const float* __restr
       const bool in = col < ncA;
       vec q[PA_UR];
 #pragma unroll
-      for (int r = 0; r < PA_UR; ++r) q[r] = (in && lv[r]) ? *reinterpret_cast<const vec*>(qb + (long)(t0 + r) * A + (long)col * V) : pa_zero<V>();
+      for (int r = 0; r < PA_UR; ++r) q[r] = (in && lv[r]) ? *reinterpret_cast<const vec*>(qb + (long)(t0 + r) * A + (long)col * V) : vzero<V>();
 #pragma unroll
       for (int r = 0; r < PA_UR; ++r) {
-        vec g = pa_zero<V>();
+        vec g = vzero<V>();
         if (lv[r]) {
-          const vec th = pa_tanh(q[r] + p[c]);
+          const vec th = vtanh(q[r] + p[c]);
           g = dt[r] * w[c] * (1.f - th * th);
           accP[c] += g;
           accW[c] += dt[r] * th;
@@ -256,7 +246,6 @@ __global__ __launch_bounds__(256) void pers_attn_user_sum_kernel(const float* __
   if (k < A) dP[(long)u * A + k] = acc;
 }
 
-inline bool pa_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -269,7 +258,7 @@ extern "C" int nnr_pers_attn_ws_floats(int n, int L, int A) {
 extern "C" int nnr_pers_attn_fwd(const float* Qf, const float* P, const int* uidx, int U, const float* w2, const float* feat, int ldf,
                                  const uint8_t* mask, int n, int L, int A, int F, float* alpha, float* out, hipStream_t stream) {
   if (!Qf || !P || !uidx || !w2 || !feat || !alpha || !out || U < 1 || n < 1 || L < 1 || A < 1 || F < 1 || ldf < F) return NNR_ERR_ARG;
-  const int V = (!(A & 3) && !(F & 3) && !(ldf & 3) && pa_al16(Qf) && pa_al16(P) && pa_al16(w2) && pa_al16(feat) && pa_al16(out)) ? 4 : 1;
+  const int V = (!(A & 3) && !(F & 3) && !(ldf & 3) && al16(Qf) && al16(P) && al16(w2) && al16(feat) && al16(out)) ? 4 : 1;
   if (L > 64 || A > 64 * PA_NA * V) return NNR_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)((n + 3) / 4)), block(256);
   if (V == 4)
@@ -290,8 +279,8 @@ extern "C" int nnr_pers_attn_bwd(const float* Qf, const float* P, const int* uid
   float* rows_p = ws;
   float* rows_w = ws + (long)n * A;
   float* slots = rows_w + (long)n * A;
-  const int V = (!(A & 3) && !(F & 3) && !(ldf & 3) && pa_al16(Qf) && pa_al16(P) && pa_al16(w2) && pa_al16(feat) && pa_al16(dout) &&
-                 pa_al16(dQf) && pa_al16(dfeat) && pa_al16(ws)) ? 4 : 1;
+  const int V = (!(A & 3) && !(F & 3) && !(ldf & 3) && al16(Qf) && al16(P) && al16(w2) && al16(feat) && al16(dout) &&
+                 al16(dQf) && al16(dfeat) && al16(ws)) ? 4 : 1;
   const int SA = (A + 63) / 64;
   if (L > 64 || A > 64 * PA_NA * V || (long)U * SA > 0x7fffffffL) return NNR_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)((n + 3) / 4)), block(256);

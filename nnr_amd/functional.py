@@ -375,8 +375,7 @@ class BagMeanFn(torch.autograd.Function):
         out = torch.empty((n, E), device=dev, dtype=torch.float32)
         count = torch.empty(n, device=dev, dtype=torch.float32)
         plan = ops.BagPlan(n, ids_a.shape[1], ids_b.shape[1], table.shape[0], dev) if need_grad else None
-        if ops.bag_mean_fwd(table, ids_a, mask_a, ids_b, mask_b, False, act, out, E, 0, 0, count, plan) != 0:
-            raise ops.L.NnrHipError('nnr_bag_mean_fwd: unsupported size (a stream of more than 128 positions or word_embedding_dim > 320)')
+        ops.bag_mean_fwd(table, ids_a, mask_a, ids_b, mask_b, False, act, out, E, 0, 0, count, plan)
         if plan is not None:
             plan.sort()
         ctx.table, ctx.saved, ctx.act = table, (out.detach(), count, plan), act
@@ -426,8 +425,7 @@ class InceptionFn(torch.autograd.Function):
         f32 = dict(device=dev, dtype=torch.float32)
         emb, count = torch.empty((n, 4 * E), **f32), torch.empty(2 * n, **f32)
         plan = ops.BagPlan(n, tt.shape[1], ct.shape[1], table.shape[0], dev) if need_grad else None
-        if ops.bag_mean_fwd(table, tt, tm, ct, cm, True, ops.ACT_NONE, emb, 4 * E, 0, E, count, plan) != 0:
-            raise ops.L.NnrHipError('nnr_bag_mean_fwd: unsupported size (a stream of more than 128 positions or word_embedding_dim > 320)')
+        ops.bag_mean_fwd(table, tt, tm, ct, cm, True, ops.ACT_NONE, emb, 4 * E, 0, E, count, plan)
         if plan is not None:
             plan.sort()
         ops.small_embed_fwd(enc.category_embedding.weight, cat, emb[:, 2 * E:], 4 * E, 0.0, 0)
@@ -480,7 +478,7 @@ class KcnnFn(torch.autograd.Function):
     around ONE convolution product (csrc/kcnn.hip):
       pre_j = table_j[entity] M_j^T + b_j (entity / context rows gathered in the GEMM's A loader);  Xp = the padded image [n, L + w - 1, 3 E]
       (word rows gathered straight from the table, tanh(pre_j), zero halo rows);  z = Xp' . P^T with Xp' the overlapping-row view of Xp
-      (lda = 3 E < K = 3 w E) and P the repacked Conv2d weight;  out = relu-then-max over the first L - w + 1 positions of z + bias.
+      (lda = 3 E < K = 3 w E) and P the permuted Conv2d weight;  out = relu-then-max over the first L - w + 1 positions of z + bias.
     No dropout and no mask: PAD positions take part with row 0 of each table.  Backward: dense dz (every element written once), dXp = dz' . Q^T
     (dz' the overlapping-row view with lda = C < K = w C, Q the transposed, window-reversed weight), dP = dz^T . Xp' (split-K through
     slabs), then the image apart again, the two projections' gradients with the table rows gathered in the B loader, and the three table
@@ -535,7 +533,7 @@ class KcnnFn(torch.autograd.Function):
         def weight_grad():
             dP = torch.zeros((Cn, 3 * w * E), **f32)
             ops.linear_bwd_weight(dz[:R], Xp.as_strided((R, 3 * w * E), (3 * E, 1)), dP)
-            ops.kcnn_repack(dP, gw, Cn, E, w, 2)
+            ops.permute(dP, gw, 'kcnn_dw', (Cn, E, w), accumulate=True)
         ops.leaf_deferred(dev, rows, weight_grad, dzp, Xp, force=True)
         dXp = torch.empty((n * Lp, 3 * E), **f32)
         ops.gemm(dzp, ops.kcnn_weight(conv.weight, 1), dXp, M=n * Lp, N=3 * E, K=w * Cn, lda=Cn, ldb=w * Cn, ldc=3 * E)
@@ -716,7 +714,7 @@ class HdcFn(torch.autograd.Function):
                 dP = torch.zeros((3, Fn_, Cp), **f32)
                 for k in range(3):
                     ops.linear_bwd_weight(z[:M], xp[k * d:].as_strided((M, Cp), (Cin, 1)), dP[k], db=gb if k == 0 else None)
-                ops.hdc_repack(dP, gw, Fn_, Cin, 3, 1, ldp=Cp)
+                ops.permute(dP, gw, 'hdc_dw', (Fn_, Cin, 3, Cp), accumulate=True)
             ops.leaf_deferred(dev, n * S, weight_grad, z, xp, force=True)
             dxp = ops.fill_zero(torch.empty((n * Sp, Cin), **f32))
             for k in range(3):

@@ -927,9 +927,7 @@ def gru_supported(H, T):
 def gru_dims(H, T=1):
     """(UB, HP, NP) of hidden size H: unit blocks, padded units, padded slot columns (four per unit)."""
     ub, hp, np_ = C.c_int(), C.c_int(), C.c_int()
-    rc = L.lib().nnr_gru_dims(H, T, C.byref(ub), C.byref(hp), C.byref(np_))
-    if rc != 0:
-        raise L.NnrHipError('nnr_gru_dims(H=%d, T=%d): %s' % (H, T, GRU_UNSUPPORTED))
+    L.check(L.lib().nnr_gru_dims(H, T, C.byref(ub), C.byref(hp), C.byref(np_)), 'nnr_gru_dims(H=%d, T=%d)' % (H, T), GRU_UNSUPPORTED, counted=False)
     return ub.value, hp.value, np_.value
 
 
@@ -1539,27 +1537,34 @@ def _embed_scatter(dout, idx, dtable, p, seed, dyn, n, dim):
     L.check(L.lib().nnr_embed_scatter(_p(dout), _p(idx), n, dim, _p(dtable), p, seed, _s()), 'nnr_embed_scatter')
 
 
+def _sort_on_leaf(tok, total, vocab):
+    """`tok` (int32 keys; total: device count of the live ones, or None for all) sorted by key on the LEAF stream behind the current stream's
+    work (csrc/sort.hip; stable) -> (sorted keys, their positions in `tok`, the event its consumers wait for)."""
+    dev, cap = tok.device, tok.numel()
+    buf = torch.empty(4 * cap, device=dev, dtype=torch.int32)    # keys_tmp | pos_tmp | keys_sorted | pos_sorted
+    temp = torch.empty(max(L.lib().nnr_token_sort_workspace_bytes(cap, vocab), 256), device=dev, dtype=torch.uint8)
+    leaf = leaf_stream(dev)
+    leaf.wait_stream(torch.cuda.current_stream(dev))              # behind the launch that wrote `tok` / `total`
+    with torch.cuda.stream(leaf):
+        L.check(L.lib().nnr_token_sort(_p(tok), cap, _p(total), vocab, _p(buf[:cap]), _p(buf[cap:2 * cap]), _p(buf[2 * cap:3 * cap]), _p(buf[3 * cap:]),
+                                       _p(temp), temp.numel(), _s()), 'nnr_token_sort')
+        event = torch.cuda.Event()
+        event.record()
+    # a graph that is dropped without a backward pass frees these while the sort may still run: the allocator must wait for the leaf
+    # stream before it hands them out again (a few MB, unlike the GB-sized buffers leaf_scope holds by reference instead)
+    for t in (tok, buf, temp):
+        t.record_stream(leaf)
+    return buf[2 * cap:3 * cap], buf[3 * cap:], event
+
+
 class TokenSort:
     """The live rows of a packed token stream sorted by word id (csrc/sort.hip), issued on the LEAF stream behind the planner: it
     needs nothing but the planned ids, so it runs under the forward pass; the backward's nnr_embed_scatter_sorted waits for `event`."""
 
     def __init__(self, tok, total, vocab):
-        dev, cap = tok.device, tok.numel()
-        self.cap, self.vocab, self.total = cap, int(vocab), total
-        i32 = dict(device=dev, dtype=torch.int32)
-        buf = torch.empty(4 * cap, **i32)                        # keys_tmp | rows_tmp | keys_sorted | rows_sorted
-        self.keys, self.rows = buf[2 * cap:3 * cap], buf[3 * cap:]
-        nb = L.lib().nnr_token_sort_workspace_bytes(cap, self.vocab)
-        temp = torch.empty(max(nb, 256), device=dev, dtype=torch.uint8)
-        self.partial = torch.empty(L.lib().nnr_embed_scatter_sorted_workspace_floats(cap), device=dev, dtype=torch.float32)
-        leaf = leaf_stream(dev)
-        leaf.wait_stream(torch.cuda.current_stream(dev))          # behind the planner that wrote `tok` / `total`
-        with torch.cuda.stream(leaf):
-            L.check(L.lib().nnr_token_sort(_p(tok), cap, _p(total), self.vocab, _p(buf[:cap]), _p(buf[cap:2 * cap]), _p(self.keys), _p(self.rows),
-                                           _p(temp), temp.numel(), _s()), 'nnr_token_sort')
-            self.event = torch.cuda.Event()
-            self.event.record()
-        self._keep = (buf, temp)
+        self.cap, self.vocab, self.total = tok.numel(), int(vocab), total
+        self.partial = torch.empty(L.lib().nnr_embed_scatter_sorted_workspace_floats(self.cap), device=tok.device, dtype=torch.float32)
+        self.keys, self.rows, self.event = _sort_on_leaf(tok, total, self.vocab)
 
 
 def embed_scatter_sorted(dout, ts, dtable, p, seed):
@@ -1572,6 +1577,9 @@ def embed_scatter_sorted(dout, ts, dtable, p, seed):
 
 
 # ---------------------------------------------------------------------------------------------- bag of words (csrc/bag.hip)
+BAG_UNSUPPORTED = 'unsupported size (a stream of more than 128 positions or word_embedding_dim > 320)'
+
+
 class BagPlan:
     """Occurrence list of one bag_mean_fwd call for its backward pass: `tok` [n, La + Lb] (written by the forward launch: word id of a live
     position, -1 elsewhere) sorted by word id on the LEAF stream behind the forward launch (csrc/sort.hip; stable, so a word's
@@ -1580,33 +1588,18 @@ class BagPlan:
     def __init__(self, n, La, Lb, vocab, dev):
         self.n, self.La, self.Lb, self.vocab = n, La, Lb, int(vocab)
         self.cap = cap = n * (La + Lb)
-        i32 = dict(device=dev, dtype=torch.int32)
-        self.tok = torch.empty(cap, **i32)
-        self._buf = torch.empty(4 * cap, **i32)                  # keys_tmp | pos_tmp | keys_sorted | pos_sorted
-        self.keys, self.pos = self._buf[2 * cap:3 * cap], self._buf[3 * cap:]
-        self._temp = torch.empty(max(L.lib().nnr_token_sort_workspace_bytes(cap, self.vocab), 256), device=dev, dtype=torch.uint8)
+        self.tok = torch.empty(cap, device=dev, dtype=torch.int32)
         self.partial = torch.empty(L.lib().nnr_bag_mean_bwd_ws_floats(cap), device=dev, dtype=torch.float32)
         self.event = None
 
     def sort(self):
-        dev, cap, buf = self.tok.device, self.cap, self._buf
-        leaf = leaf_stream(dev)
-        leaf.wait_stream(torch.cuda.current_stream(dev))          # behind the forward launch that wrote `tok`
-        with torch.cuda.stream(leaf):
-            L.check(L.lib().nnr_token_sort(_p(self.tok), cap, None, self.vocab, _p(buf[:cap]), _p(buf[cap:2 * cap]), _p(self.keys), _p(self.pos),
-                                           _p(self._temp), self._temp.numel(), _s()), 'nnr_token_sort')
-            self.event = torch.cuda.Event()
-            self.event.record()
-        # a graph that is dropped without a backward pass frees these while the sort may still run: the allocator must wait for the leaf
-        # stream before it hands them out again (a few MB, unlike the GB-sized buffers leaf_scope holds by reference instead)
-        for t in (self.tok, self._buf, self._temp):
-            t.record_stream(leaf)
+        self.keys, self.pos, self.event = _sort_on_leaf(self.tok, None, self.vocab)
 
 
 def bag_mean_fwd(table, ids_a, mask_a, ids_b, mask_b, separate, act, out, ldo, off_a, off_b, count, plan=None, live=None):
     """Masked mean of table rows over the live positions of ids_a [n, La] (+ ids_b [n, Lb], optional); see include/nnr_hip.h.  Masks are
     bool / uint8 [n, L], written in place (column 0) when `separate`.  plan: a BagPlan whose `tok` the launch fills.  live (profiling
-    only): live positions of the call, for the byte count.  Returns the entry point's code for NNR_ERR_UNSUPPORTED (-3) instead of raising."""
+    only): live positions of the call, for the byte count.  Returns 0; every failure raises (sizes beyond the limits: BAG_UNSUPPORTED)."""
     n, La = ids_a.shape
     Lb = ids_b.shape[1] if ids_b is not None else 0
     V, E = table.shape
@@ -1615,9 +1608,7 @@ def bag_mean_fwd(table, ids_a, mask_a, ids_b, mask_b, separate, act, out, ldo, o
     with _hbm_span('bag_mean_fwd', per_row, n, fixed=4.0 * E * (live if live is not None else n * (La + Lb))):
         rc = L.lib().nnr_bag_mean_fwd(_p(table), V, E, _p(ids_a), _p(_u8(mask_a)), La, _p(ids_b), _p(_u8(mask_b)), Lb, n, int(bool(separate)), act,
                                       _p(out), ldo, off_a, off_b, _p(count), _p(plan.tok) if plan is not None else None, _s())
-    if rc == -3:
-        return rc
-    L.check(rc, 'nnr_bag_mean_fwd')
+    L.check(rc, 'nnr_bag_mean_fwd', BAG_UNSUPPORTED)
     return 0
 
 
@@ -1650,14 +1641,50 @@ def row_dist_bwd(a, b, dist, gup, coef, da, db):
                                          db.stride(0), _s()), 'nnr_row_dist_bwd')
 
 
+# ---------------------------------------------------------------------------------------------- weight layouts (nnr_permute, csrc/misc.hip)
+def _pad4(n):
+    return (n + 3) & ~3
+
+
+# kind -> dims -> (extents n0..n3, source strides, destination strides, source offset, destination shape), strides and offset in floats, the
+# destination's unit-stride axis last.  Source: the weight as torch holds it (or, for the *_dw kinds, the gradient of its permuted form).
+LAYOUTS = {
+    # Conv2d weight W [C, E, w, 3]: P[c][dt][j][e] | Q[j][e][k][c] = W[c][e][w-1-k][j] | W.grad[c][e][dt][j] += dP[c][dt][j][e]
+    'kcnn_p': lambda C_, E, w: ((C_, w, 3, E), (E * w * 3, 3, 1, w * 3), (w * 3 * E, 3 * E, E, 1), 0, (C_, 3 * w * E)),
+    'kcnn_q': lambda C_, E, w: ((3, E, w, C_), (1, w * 3, -3, E * w * 3), (E * w * C_, w * C_, C_, 1), (w - 1) * 3, (3 * E, w * C_)),
+    'kcnn_dw': lambda C_, E, w: ((C_, E, w, 3), (w * 3 * E, 1, 3 * E, E), (E * w * 3, w * 3, 3, 1), 0, (C_, E, w, 3)),
+    # Conv1d weight W [F, C, w]: P[k][f][c] in rows of ldp >= C floats | W.grad[f][c][k] += dP[k][f][c]
+    'hdc_p': lambda F, C_, w, ldp: ((1, w, F, C_), (0, 1, C_ * w, w), (0, F * ldp, ldp, 1), 0, (w, F, ldp)),
+    'hdc_dw': lambda F, C_, w, ldp: ((1, F, C_, w), (0, ldp, 1, F * ldp), (0, C_ * w, w, 1), 0, (F, C_, w)),
+    # Conv3d weight W [Cout, Cin, K^3]: [ci][t][f] in rows of Cout rounded up to 4 | [f][t][ci] in rows of Cin rounded up to 4
+    'c3_p': lambda Co, Ci, K: ((1, Ci, K ** 3, Co), (0, K ** 3, 1, Ci * K ** 3), (0, K ** 3 * _pad4(Co), _pad4(Co), 1), 0, (Ci, K ** 3, _pad4(Co))),
+    'c3_q': lambda Co, Ci, K: ((1, Co, K ** 3, Ci), (0, Ci * K ** 3, 1, K ** 3), (0, K ** 3 * _pad4(Ci), _pad4(Ci), 1), 0, (Co, K ** 3, _pad4(Ci))),
+}
+
+
+def permute(src, out, kind, dims, accumulate=False):
+    """out (+)= src in the layout LAYOUTS[kind](*dims), both contiguous; every address is checked against the two sizes here."""
+    n, si, so, off, _ = LAYOUTS[kind](*dims)
+    assert src.is_contiguous() and out.is_contiguous()
+    for t, strides, base in ((src, si, off), (out, so, 0)):
+        lo = base + sum((m - 1) * st for m, st in zip(n, strides) if st < 0)
+        hi = base + sum((m - 1) * st for m, st in zip(n, strides) if st > 0)
+        assert 0 <= lo and hi < t.numel(), (kind, dims, tuple(t.shape))
+    L.check(L.lib().nnr_permute(_p(src) + 4 * off, _p(out), *n, *si, *so, int(accumulate), _s()), 'nnr_permute')
+
+
+def _permuted_weight(kind, weight, dims):
+    """`weight` in the layout `kind`, an entry of the derived-weight cache.  Elements of the layout that the permute does not reach (the pad
+    columns of a row) are zeroed once, when the entry's buffer is made: nothing else ever writes it."""
+    n, _, _, _, shape = LAYOUTS[kind](*dims)
+    padded = math.prod(shape) != math.prod(n)
+    e = _derived(kind, weight, dims, lambda: (torch.zeros if padded else torch.empty)(shape, device=weight.device, dtype=torch.float32), False)
+    _serve(e, (weight,), lambda: permute(weight, e.out, kind, dims))
+    return e.out
+
+
 # ---------------------------------------------------------------------------------------------- KCNN / DKN (csrc/kcnn.hip)
 KCNN_UNSUPPORTED = 'unsupported size (max_title_length + cnn_window_size - 1 > 255, cnn_window_size > 8 or > max_title_length, or word_embedding_dim > 1024)'
-
-
-def _kcnn_check(rc, what):
-    if rc == -3:
-        raise L.NnrHipError('%s: %s' % (what, KCNN_UNSUPPORTED))
-    L.check(rc, what)
 
 
 def kcnn_image_fwd(table, text, pre1, pre2, n, Lx, w, Xp):
@@ -1665,19 +1692,19 @@ def kcnn_image_fwd(table, text, pre1, pre2, n, Lx, w, Xp):
     V, E = table.shape
     # per padded row 3 E floats written; per title position an id, a table row and two pre-activation rows read
     with _hbm_span('kcnn_image_fwd', 3 * 4.0 * E, n * (Lx + w - 1), fixed=(3 * 4.0 * E + 4.0) * n * Lx):
-        _kcnn_check(L.lib().nnr_kcnn_image_fwd(_p(table), V, _p(text), _p(pre1), _p(pre2), n, Lx, E, w, _p(Xp), _s()), 'nnr_kcnn_image_fwd')
+        L.check(L.lib().nnr_kcnn_image_fwd(_p(table), V, _p(text), _p(pre1), _p(pre2), n, Lx, E, w, _p(Xp), _s()), 'nnr_kcnn_image_fwd', KCNN_UNSUPPORTED)
 
 
 def kcnn_image_bwd(dXp, Xp, n, Lx, E, w, dx0, dpre1, dpre2):
     """dx0 / dpre1 / dpre2 [n * Lx, E] from the padded gradient image (the tanh derivative from the forward image's channels 1 and 2)."""
     with _hbm_span('kcnn_image_bwd', (3 + 2 + 3) * 4.0 * E, n * Lx):
-        _kcnn_check(L.lib().nnr_kcnn_image_bwd(_p(dXp), _p(Xp), n, Lx, E, w, _p(dx0), _p(dpre1), _p(dpre2), _s()), 'nnr_kcnn_image_bwd')
+        L.check(L.lib().nnr_kcnn_image_bwd(_p(dXp), _p(Xp), n, Lx, E, w, _p(dx0), _p(dpre1), _p(dpre2), _s()), 'nnr_kcnn_image_bwd', KCNN_UNSUPPORTED)
 
 
 def window_max_fwd(z, ldz, bias, n, C, Lx, w, out, arg):
     """out [n, C] = relu-then-max over the first Lx - w + 1 positions of z + bias, arg [n, C] uint8 (255: no positive maximum)."""
     with _hbm_span('window_max_fwd', 4.0 * C * (Lx - w + 1) + 5.0 * C, n):
-        _kcnn_check(L.lib().nnr_window_max_fwd(_p(z), ldz, _p(bias), n, C, Lx, w, _p(out), _p(arg), _s()), 'nnr_window_max_fwd')
+        L.check(L.lib().nnr_window_max_fwd(_p(z), ldz, _p(bias), n, C, Lx, w, _p(out), _p(arg), _s()), 'nnr_window_max_fwd', KCNN_UNSUPPORTED)
 
 
 def window_max_bwd(g, arg, n, C, Lx, w, lead, dz, db):
@@ -1685,35 +1712,22 @@ def window_max_bwd(g, arg, n, C, Lx, w, lead, dz, db):
     ws = torch.empty(max(1, L.lib().nnr_window_max_bwd_ws_floats(n, C)), device=g.device, dtype=torch.float32)
     tape_keep(ws)
     with _hbm_span('window_max_bwd', 4.0 * C * (Lx + w - 1) + 5.0 * C, n):
-        _kcnn_check(L.lib().nnr_window_max_bwd(_p(g), _p(arg), n, C, Lx, w, lead, _p(dz), _p(db), _p(ws), _s()), 'nnr_window_max_bwd')
-
-
-def kcnn_repack(src, out, C, E, w, mode):
-    """The Conv2d weight [C, E, w, 3] -> mode 0: [C, w, 3, E] | mode 1: [3, E, w (reversed), C]; mode 2: out [C, E, w, 3] += src [C, w, 3, E]."""
-    assert src.is_contiguous() and out.is_contiguous() and src.numel() == out.numel() == C * E * w * 3
-    _kcnn_check(L.lib().nnr_kcnn_repack(_p(src), _p(out), C, E, w, mode, _s()), 'nnr_kcnn_repack')
+        L.check(L.lib().nnr_window_max_bwd(_p(g), _p(arg), n, C, Lx, w, lead, _p(dz), _p(db), _p(ws), _s()), 'nnr_window_max_bwd', KCNN_UNSUPPORTED)
 
 
 def kcnn_weight(weight, mode):
     """P [C, 3 w E] (mode 0) or Q [3 E, w C] (mode 1) of the Conv2d weight [C, E, w, 3]: the B operand of the convolution product or of its
-    data gradient, an entry of the derived-weight cache (repacked once per parameter version, by the first of the two encoder calls that
+    data gradient, an entry of the derived-weight cache (permuted once per parameter version, by the first of the two encoder calls that
     asks; its bf16x3 images follow it)."""
     C_, E, w, _ = weight.shape
-    shape = (C_, 3 * w * E) if mode == 0 else (3 * E, w * C_)
-    e = _derived('kcnn_q' if mode else 'kcnn_p', weight, (C_, E, w), lambda: torch.empty(shape, device=weight.device, dtype=torch.float32), False)
-    _serve(e, (weight,), lambda: kcnn_repack(weight, e.out, C_, E, w, mode))
-    return e.out
+    if w > 8 or E > 1024:
+        raise L.NnrHipError('kcnn_weight: %s' % KCNN_UNSUPPORTED)
+    return _permuted_weight('kcnn_q' if mode else 'kcnn_p', weight, (C_, E, w))
 
 
 # ---------------------------------------------------------------------------------------------- HDC / FIM (csrc/hdc.hip, csrc/fim.hip)
 FIM_UNSUPPORTED = ('unsupported size (conv3D kernel size > 4, maxpooling3D_size > 4 or > maxpooling3D_stride, an axis left without a pool cell, '
                    'or weights + one row of pool cells beyond 160 KB of LDS)')
-
-
-def _fim_check(rc, what):
-    if rc == -3:
-        raise L.NnrHipError('%s: %s' % (what, FIM_UNSUPPORTED))
-    L.check(rc, what)
 
 
 def hdc_seq_fwd(word, cat_t, sub_t, text, cat, sub, n, Lx, pad, d0, d0p, tok_w, tok_c, tok_s):
@@ -1746,20 +1760,11 @@ def hdc_unpad_add(a, bp, n, S, pad, C_, out):
         L.check(L.lib().nnr_hdc_unpad_add(_p(a), _p(bp), n, S, pad, C_, _p(out), _s()), 'nnr_hdc_unpad_add')
 
 
-def hdc_repack(src, out, F, C_, w, mode, ldp=None):
-    """mode 0: W [F, C, w] -> P [w, F, ldp];  mode 1: W [F, C, w] += P [w, F, ldp] (rows of ldp >= C floats, C of them used)."""
-    ldp = C_ if ldp is None else ldp
-    assert src.is_contiguous() and out.is_contiguous() and (out if mode else src).numel() == F * C_ * w and (src if mode else out).numel() == F * ldp * w
-    L.check(L.lib().nnr_hdc_repack(_p(src), _p(out), F, C_, w, ldp, mode, _s()), 'nnr_hdc_repack')
-
-
 def hdc_weight(weight):
     """P [w, F, C] of a Conv1d weight [F, C, w]: tap k's [F, C] matrix is the B operand of the k-th accumulating product (an entry of the
-    derived-weight cache: repacked once per parameter version)."""
+    derived-weight cache: permuted once per parameter version)."""
     F, C_, w = weight.shape
-    e = _derived('hdc_p', weight, (F, C_, w), lambda: torch.empty((w, F, C_), device=weight.device, dtype=torch.float32), False)
-    _serve(e, (weight,), lambda: hdc_repack(weight, e.out, F, C_, w, 0))
-    return e.out
+    return _permuted_weight('hdc_p', weight, (F, C_, w, C_))
 
 
 def match_images_fwd(cand, hist, B, N, H, S, alpha, plane):
@@ -1803,22 +1808,16 @@ def conv3d_pool_plan(Cin, D, H, W, Cout, K, P, St):
 def conv3d_pool_dims(Cin, D, H, W, Cout, K, P, St):
     """(PD, PH, PW) of the fused layer, or NnrHipError('... unsupported size ...')."""
     out = [C.c_int(0) for _ in range(3)]
-    rc = L.lib().nnr_conv3d_pool_dims(Cin, D, H, W, Cout, K, P, St, *[C.addressof(o) for o in out])
-    if rc == -3:
-        raise L.NnrHipError('nnr_conv3d_pool_dims: %s' % FIM_UNSUPPORTED)
-    if rc != 0:
-        raise L.NnrHipError('nnr_conv3d_pool_dims failed with code %d' % rc)
+    L.check(L.lib().nnr_conv3d_pool_dims(Cin, D, H, W, Cout, K, P, St, *[C.addressof(o) for o in out]), 'nnr_conv3d_pool_dims', FIM_UNSUPPORTED,
+            counted=False)
     return tuple(o.value for o in out)
 
 
 def conv3d_weight(weight, mode):
     """The Conv3d weight [Cout, Cin, K, K, K] as the forward operand [Cin, K^3, Cout4] (mode 0) or the input-gradient operand
-    [Cout, K^3, Cin4] (mode 1); entries of the derived-weight cache."""
+    [Cout, K^3, Cin4] (mode 1); entries of the derived-weight cache, their pad columns zero."""
     Cout, Cin, K = weight.shape[:3]
-    shape = (Cin, K ** 3, (Cout + 3) & ~3) if mode == 0 else (Cout, K ** 3, (Cin + 3) & ~3)
-    e = _derived('c3_q' if mode else 'c3_p', weight, (Cout, Cin, K), lambda: torch.empty(shape, device=weight.device, dtype=torch.float32), False)
-    _serve(e, (weight,), lambda: _fim_check(L.lib().nnr_conv3d_repack(_p(weight), _p(e.out), Cout, Cin, K, mode, _s()), 'nnr_conv3d_repack'))
-    return e.out
+    return _permuted_weight('c3_q' if mode else 'c3_p', weight, (Cout, Cin, K))
 
 
 def conv3d_pool_fwd(x, strides, wp, bias, imgs, Cin, D, H, W, Cout, K, P, St, cf_out, y, arg):
@@ -1826,8 +1825,8 @@ def conv3d_pool_fwd(x, strides, wp, bias, imgs, Cin, D, H, W, Cout, K, P, St, cf
     channel, depth, row, column) of x in floats.  2 Cin K^3 flops per computed position and filter."""
     PD, PH, PW = conv3d_pool_dims(Cin, D, H, W, Cout, K, P, St)
     if not _prof.active():
-        _fim_check(L.lib().nnr_conv3d_pool_fwd(_p(x), *strides, _p(wp), _p(bias), imgs, Cin, D, H, W, Cout, K, P, St, int(cf_out), _p(y), _p(arg), _s()),
-                   'nnr_conv3d_pool_fwd')
+        L.check(L.lib().nnr_conv3d_pool_fwd(_p(x), *strides, _p(wp), _p(bias), imgs, Cin, D, H, W, Cout, K, P, St, int(cf_out), _p(y), _p(arg), _s()),
+                   'nnr_conv3d_pool_fwd', FIM_UNSUPPORTED)
         return
 
     def flops(vals=None):
@@ -1835,8 +1834,8 @@ def conv3d_pool_fwd(x, strides, wp, bias, imgs, Cin, D, H, W, Cout, K, P, St, cf
     flops.dyn = []
     flops.tag = 'imgs%d %dx%dx%dx%d->%d k%d p%d/%d' % (imgs, Cin, D, H, W, Cout, K, P, St)
     with _prof.span('conv3d_pool_fwd', flops):
-        _fim_check(L.lib().nnr_conv3d_pool_fwd(_p(x), *strides, _p(wp), _p(bias), imgs, Cin, D, H, W, Cout, K, P, St, int(cf_out), _p(y), _p(arg), _s()),
-                   'nnr_conv3d_pool_fwd')
+        L.check(L.lib().nnr_conv3d_pool_fwd(_p(x), *strides, _p(wp), _p(bias), imgs, Cin, D, H, W, Cout, K, P, St, int(cf_out), _p(y), _p(arg), _s()),
+                   'nnr_conv3d_pool_fwd', FIM_UNSUPPORTED)
 
 
 def conv3d_pool_bwd(dy, y, arg, x, strides, wq, imgs, Cin, D, H, W, Cout, K, P, St, cf_out, dx, dw, db):
@@ -1848,8 +1847,8 @@ def conv3d_pool_bwd(dy, y, arg, x, strides, wq, imgs, Cin, D, H, W, Cout, K, P, 
     tape_keep(ws)
 
     def launch():
-        _fim_check(L.lib().nnr_conv3d_pool_bwd(_p(dy), _p(y), _p(arg), _p(x), *strides, _p(wq), imgs, Cin, D, H, W, Cout, K, P, St, int(cf_out), _p(dx),
-                                               _p(dw), _p(db), _p(ws), _s()), 'nnr_conv3d_pool_bwd')
+        L.check(L.lib().nnr_conv3d_pool_bwd(_p(dy), _p(y), _p(arg), _p(x), *strides, _p(wq), imgs, Cin, D, H, W, Cout, K, P, St, int(cf_out), _p(dx),
+                                               _p(dw), _p(db), _p(ws), _s()), 'nnr_conv3d_pool_bwd', FIM_UNSUPPORTED)
     if not _prof.active():
         return launch()
     PD, PH, PW = conv3d_pool_dims(Cin, D, H, W, Cout, K, P, St)

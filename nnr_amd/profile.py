@@ -149,12 +149,12 @@ HBM_KERNELS_OTHER = {
     'bag_mean_fwd': (('bag_mean_fwd_kernel',), 1), 'bag_mean_bwd': (('bag_mean_bwd_kernel', 'bag_mean_bwd_fix_kernel'), 2),
     'row_dist_fwd': (('row_dist_fwd_kernel',), 1), 'row_dist_bwd': (('row_dist_bwd_kernel',), 1),
     'kcnn_image_fwd': (('kcnn_image_fwd_kernel',), 1), 'kcnn_image_bwd': (('kcnn_image_bwd_kernel',), 1),
-    'window_max_fwd': (('window_max_fwd_kernel',), 1), 'window_max_bwd': (('window_max_bwd_kernel', 'window_max_db_kernel'), 2),
+    'window_max_fwd': (('window_max_fwd_kernel',), 1), 'window_max_bwd': (('window_max_bwd_kernel', 'partial_rows_sum_kernel<false'), 2),
     'hdc_seq_fwd': (('hdc_seq_fwd_kernel',), 1), 'hdc_ln_relu_fwd': (('hdc_ln_relu_fwd_kernel',), 1),
     'hdc_ln_relu_bwd': (('hdc_ln_param_kernel', 'hdc_ln_param_reduce_kernel', 'hdc_ln_relu_bwd_kernel'), 3),
     'hdc_unpad_add': (('hdc_unpad_add_kernel',), 1),
     'omap_fwd': (('omap_alpha_kernel', 'omap_mix_kernel', 'omap_pool_kernel'), 3),
-    'omap_bwd': (('omap_bwd_pool_kernel', 'omap_bwd_dalpha_kernel', 'omap_bwd_dx_kernel', 'omap_dw_reduce_kernel'), 4),
+    'omap_bwd': (('omap_bwd_pool_kernel', 'omap_bwd_dalpha_kernel', 'omap_bwd_dx_kernel', 'partial_rows_sum_kernel<true'), 4),
 }
 PEAK_HBM_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 TB/s achievable by a float4 copy)
 

@@ -21,6 +21,7 @@ from .news_encoders import NewsEncoder
 
 class UserEncoder(nn.Module):
     """userEncoders.py:12-39: holds a reference to the SAME news-encoder instance (:16)."""
+    needs_user_embedding = False         # True: encode_user takes the user embedding rows as a seventh argument (model.Model passes them)
 
     def __init__(self, news_encoder: NewsEncoder, config):
         super().__init__()
@@ -37,7 +38,11 @@ class UserEncoder(nn.Module):
     def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask, user_content_entity,
                 user_category, user_subCategory, user_history_mask, user_history_graph, user_history_category_mask,
                 user_history_category_indices, user_embedding, candidate_news_representation):
-        raise Exception('Function forward must be implemented at sub-class')
+        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
+                                              user_content_entity, user_category, user_subCategory, user_embedding)
+        extra = (user_embedding,) if self.needs_user_embedding else ()
+        return self.encode_user(history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
+                                user_history_category_indices, candidate_news_representation, *extra)
 
 
 class _SUEFunction(torch.autograd.Function):
@@ -349,14 +354,6 @@ class SUE(UserEncoder):
         nn.init.zeros_(self.clusterFeatureAffine.bias)
         self.interClusterAttention.initialize()
 
-    def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask, user_content_entity,
-                user_category, user_subCategory, user_history_mask, user_history_graph, user_history_category_mask,
-                user_history_category_indices, user_embedding, candidate_news_representation):
-        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
-                                              user_content_entity, user_category, user_subCategory, user_embedding)
-        return self.encode_user(history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
-                                user_history_category_indices, candidate_news_representation)
-
     def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
                     user_history_category_indices, candidate_news_representation):
         """Everything of forward() after the history news have been encoded (userEncoders.py:73-75, 79-98)."""
@@ -383,14 +380,6 @@ class MHSA(UserEncoder):
         nn.init.zeros_(self.affine.bias)
         self.attention.initialize()
 
-    def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask, user_content_entity,
-                user_category, user_subCategory, user_history_mask, user_history_graph, user_history_category_mask,
-                user_history_category_indices, user_embedding, candidate_news_representation):
-        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
-                                              user_content_entity, user_category, user_subCategory, user_embedding)
-        return self.encode_user(history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
-                                user_history_category_indices, candidate_news_representation)
-
     def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
                     user_history_category_indices, candidate_news_representation):
         from . import functional as Fn
@@ -412,14 +401,6 @@ class ATT(UserEncoder):
 
     def initialize(self):
         self.attention.initialize()
-
-    def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask, user_content_entity,
-                user_category, user_subCategory, user_history_mask, user_history_graph, user_history_category_mask,
-                user_history_category_indices, user_embedding, candidate_news_representation):
-        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
-                                              user_content_entity, user_category, user_subCategory, user_embedding)
-        return self.encode_user(history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
-                                user_history_category_indices, candidate_news_representation)
 
     def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
                     user_history_category_indices, candidate_news_representation):
@@ -445,14 +426,6 @@ class GRU(UserEncoder):
             (nn.init.orthogonal_ if p.dim() >= 2 else nn.init.zeros_)(p.data)
         nn.init.xavier_uniform_(self.dec.weight, gain=nn.init.calculate_gain('tanh'))
         nn.init.zeros_(self.dec.bias)
-
-    def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask, user_content_entity,
-                user_category, user_subCategory, user_history_mask, user_history_graph, user_history_category_mask,
-                user_history_category_indices, user_embedding, candidate_news_representation):
-        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
-                                              user_content_entity, user_category, user_subCategory, user_embedding)
-        return self.encode_user(history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
-                                user_history_category_indices, candidate_news_representation)
 
     def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
                     user_history_category_indices, candidate_news_representation):
@@ -488,14 +461,6 @@ class CATT(UserEncoder):
         D, g = self.news_embedding_dim, grad_of(self.affine1.weight)
         grad_of(self.affine2.bias)                              # (stays zero)
         return g[:, :D], grad_of(self.affine1.bias), g[:, D:], grad_of(self.affine2.weight).view(-1)
-
-    def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask, user_content_entity,
-                user_category, user_subCategory, user_history_mask, user_history_graph, user_history_category_mask,
-                user_history_category_indices, user_embedding, candidate_news_representation):
-        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
-                                              user_content_entity, user_category, user_subCategory, user_embedding)
-        return self.encode_user(history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
-                                user_history_category_indices, candidate_news_representation)
 
     def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
                     user_history_category_indices, candidate_news_representation):
@@ -573,14 +538,6 @@ class OMAP(UserEncoder):
     def initialize(self):
         nn.init.orthogonal_(self.W.data)
 
-    def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask, user_content_entity,
-                user_category, user_subCategory, user_history_mask, user_history_graph, user_history_category_mask,
-                user_history_category_indices, user_embedding, candidate_news_representation):
-        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
-                                              user_content_entity, user_category, user_subCategory, user_embedding)
-        return self.encode_user(history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
-                                user_history_category_indices, candidate_news_representation)
-
     def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
                     user_history_category_indices, candidate_news_representation):
         user_representation = _OmapFn.apply(history_embedding, candidate_news_representation, self, user_history_mask)
@@ -605,14 +562,6 @@ class PUE(UserEncoder):
         nn.init.xavier_uniform_(self.dense.weight, gain=nn.init.calculate_gain('relu'))
         nn.init.zeros_(self.dense.bias)
         self.personalizedAttention.initialize()
-
-    def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask, user_content_entity,
-                user_category, user_subCategory, user_history_mask, user_history_graph, user_history_category_mask,
-                user_history_category_indices, user_embedding, candidate_news_representation):
-        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
-                                              user_content_entity, user_category, user_subCategory, user_embedding)
-        return self.encode_user(history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
-                                user_history_category_indices, candidate_news_representation, user_embedding)
 
     def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
                     user_history_category_indices, candidate_news_representation, user_embedding=None):
@@ -646,14 +595,6 @@ class FIM(UserEncoder):
 
     def initialize(self):
         pass
-
-    def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask, user_content_entity,
-                user_category, user_subCategory, user_history_mask, user_history_graph, user_history_category_mask,
-                user_history_category_indices, user_embedding, candidate_news_representation):
-        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
-                                              user_content_entity, user_category, user_subCategory, user_embedding)
-        return self.encode_user(history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
-                                user_history_category_indices, candidate_news_representation)
 
     def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
                     user_history_category_indices, candidate_news_representation):

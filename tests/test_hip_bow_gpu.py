@@ -22,7 +22,6 @@ LOGIT_TOL = 1e-4
 TIGHT = 2e-5
 TINY = ['tiny_DAE_ATT', 'tiny_DAE_CATT', 'tiny_Inception_ATT', 'tiny_Inception_CATT']
 CASES = TINY + ['full_DAE_ATT_g1p0', 'full_Inception_ATT_g1p0']
-UNSUPPORTED = -3
 # (n, La, Lb, E, V): the smallest case | E % 4 != 0 with one stream | MIND widths, n no multiple of the 4 waves of a workgroup, two ballots,
 # heavy duplication | three words: segments of thousands of occurrences that span several workgroups' partial rows | beyond the issue's four:
 # odd E (the scalar-lane forward instantiation) | ONE word: a segment of ~4 300 occurrences = ~135 chunks, more than the 64 one window of the
@@ -155,7 +154,7 @@ def test_bag_kernels_match_the_float64_restatement(shape, mode):
 
 def test_bag_sizes_beyond_the_limits_are_unsupported():
     """More than 128 positions in a stream (two ballots) or more than 320 columns (five per lane in the backward pass): NNR_ERR_UNSUPPORTED
-    before any launch; the autograd function turns it into an error (there is no fallback)."""
+    before any launch, which ops.bag_mean_fwd turns into an error (there is no fallback); the autograd function passes it on."""
     from nnr_amd import ops, _lib
     from nnr_amd import functional as Fn
     dev = dict(device='cuda')
@@ -164,7 +163,8 @@ def test_bag_sizes_beyond_the_limits_are_unsupported():
         ia, ib = torch.zeros(2, La, dtype=torch.int32, **dev), torch.zeros(2, Lb, dtype=torch.int32, **dev)
         ma, mb = torch.ones(2, La, dtype=torch.bool, **dev), torch.ones(2, Lb, dtype=torch.bool, **dev)
         out, count = torch.empty(2, E, **dev), torch.empty(2, **dev)
-        assert ops.bag_mean_fwd(table, ia, ma, ib, mb, False, ops.ACT_NONE, out, E, 0, 0, count) == UNSUPPORTED
+        with pytest.raises(_lib.NnrHipError, match='unsupported size'):
+            ops.bag_mean_fwd(table, ia, ma, ib, mb, False, ops.ACT_NONE, out, E, 0, 0, count)
         with pytest.raises(_lib.NnrHipError, match='unsupported size'):
             Fn.BagMeanFn.apply(table, ia, ma, ib, mb, ops.ACT_NONE, False)
 

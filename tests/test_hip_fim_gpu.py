@@ -52,6 +52,10 @@ CONV_CASES = {
     'one_image': dict(imgs=1, Cin=4, dims=(9, 12, 12), Cout=8, K=3, P=3, St=3),
     'seven_images': dict(imgs=7, Cin=4, dims=(8, 8, 8), Cout=8, K=3, P=3, St=3, cf=True),
     'many_rows': dict(imgs=2, Cin=4, dims=(5, 34, 34), Cout=32, K=3, P=3, St=3),
+    # one pool cell per image: the weight gradient sums one partial row per image -- 1, 4 and 5 rows, around its groups of four loads
+    'one_partial_row': dict(imgs=1, Cin=4, dims=(5, 5, 5), Cout=8, K=3, P=3, St=3),
+    'four_partial_rows': dict(imgs=4, Cin=4, dims=(5, 5, 5), Cout=8, K=3, P=3, St=3),
+    'five_partial_rows': dict(imgs=5, Cin=3, dims=(5, 5, 5), Cout=5, K=3, P=3, St=3),
 }
 
 
@@ -237,9 +241,18 @@ def test_matching_images_forward_and_backward():
 def test_layernorm_relu_forward_and_backward(FS):
     """Three news; news 1 has a constant input, so its pre-activation is beta, negative everywhere: output and input gradient zero.  The
     rows behind a news' S live rows hold NaN going in and zero coming out of the backward call."""
+    _layernorm_relu_case(FS[0], FS[1], 3)
+
+
+@pytest.mark.parametrize('n', [100, 130])
+def test_layernorm_relu_backward_over_several_chunks_of_news(n):
+    """The affine gradients are summed from one partial row per 32 news: 4 and 5 rows (the three news of the test above: one)."""
+    _layernorm_relu_case(6, 7, n)
+
+
+def _layernorm_relu_case(Fn, S, n):
     from nnr_amd import ops
-    Fn, S = FS
-    n, pad, d = 3, 2, dev()
+    pad, d = 2, dev()
     Sp = S + 2 * pad
     g = torch.Generator().manual_seed(13 + Fn)
     z = torch.full((n, Sp, Fn), float('nan'))

@@ -104,11 +104,12 @@ def _window_case(n, C, L, w, seed, ldz):
     return z, bias, full
 
 
-@pytest.mark.parametrize('shape', [(19, 400, 7, 3, 400), (5, 6, 32, 3, 9), (9, 130, 6, 4, 130), (3, 6, 5, 1, 6), (8, 130, 9, 5, 132)], ids=_ids)
+@pytest.mark.parametrize('shape', [(19, 400, 7, 3, 400), (5, 6, 32, 3, 9), (9, 130, 6, 4, 130), (3, 6, 5, 1, 6), (8, 130, 9, 5, 132),
+                                   (30, 6, 7, 3, 6), (33, 70, 5, 3, 70)], ids=_ids)
 def test_window_max_forward_and_backward_are_exact(shape):
     """out, arg, dz and db equal torch's fp32 relu-then-max over the first L - w + 1 positions EXACTLY (grid values: every sum is exact, every
     maximum unique); arg = 255 and a zero gradient where nothing is positive; dz and db are prefilled with NaN: every element is written,
-    the leading rows included."""
+    the leading rows included.  db sums one partial row per 8 titles: the title counts cover 1, 2, 3, 4 and 5 rows."""
     from nnr_amd import ops
     n, C, L, w, ldz = shape
     Lp, T = L + w - 1, L - w + 1
@@ -137,21 +138,43 @@ def test_window_max_forward_and_backward_are_exact(shape):
 
 
 def test_repack_round_trip_is_exact():
+    """ops.permute (nnr_permute) over the seven layouts of ops.LAYOUTS at the host test's sizes, plus the default KCNN weight (1.08 M elements:
+    past one pass of the 4096-block grid): the destination, prefilled with NaN, equals the CPU permutation bit for bit -- its pad columns
+    still NaN --, the source is unchanged, and a gradient kind added twice into a zeroed buffer gives W, then 2 W (its source is W's
+    permuted form with NaN in the pad columns: they are never read)."""
     from nnr_amd import ops
+    import layout_ref
     d = dev()
-    for C, E, w in ((12, 16, 3), (5, 10, 4), (400, 300, 3), (3, 7, 1)):
-        W = torch.randn(C, E, w, 3, generator=torch.Generator().manual_seed(C))
-        Wd = W.to(d)
-        P, Q, back = (torch.full((C * E * w * 3,), float('nan'), device=d) for _ in range(3))
-        ops.kcnn_repack(Wd, P, C, E, w, 0)
-        ops.kcnn_repack(Wd, Q, C, E, w, 1)
-        assert torch.equal(P.cpu().view(C, w, 3, E), W.permute(0, 2, 3, 1))
-        assert torch.equal(Q.cpu().view(3, E, w, C), W.flip(2).permute(3, 1, 2, 0))
-        back.zero_()
-        ops.kcnn_repack(P, back, C, E, w, 2)
-        assert torch.equal(back.cpu().view(C, E, w, 3), W)
-        ops.kcnn_repack(P, back, C, E, w, 2)
-        assert torch.equal(back.cpu().view(C, E, w, 3), 2 * W)
+    for kind, dims in layout_ref.CASES + [(k, (400, 300, 3)) for k in ('kcnn_p', 'kcnn_q', 'kcnn_dw')]:
+        shape = ops.LAYOUTS[kind](*dims)[4]
+        nan = torch.full(shape, float('nan'))
+        if kind.endswith('_dw'):
+            fwd = kind[:-2] + 'p'
+            W = layout_ref.source(fwd, dims)
+            src = layout_ref.expected(fwd, W, dims, torch.full(ops.LAYOUTS[fwd](*dims)[4], float('nan')))
+            sd, out = src.to(d), torch.zeros(shape, device=d)
+            for times in (1, 2):
+                ops.permute(sd, out, kind, dims, accumulate=True)
+                assert torch.equal(out.cpu(), times * W), (kind, dims, times)
+        else:
+            src = layout_ref.source(kind, dims)
+            sd, out = src.to(d), nan.to(d)
+            ops.permute(sd, out, kind, dims)
+            exp, got = layout_ref.expected(kind, src, dims, nan), out.cpu()
+            pad = torch.isnan(exp)
+            assert torch.equal(torch.isnan(got), pad) and torch.equal(got[~pad], exp[~pad]), (kind, dims)
+            assert bool(pad.any()) == (exp.numel() != src.numel())          # rows of ldp > C floats, of Cout / Cin rounded up to 4
+        assert torch.equal(sd.cpu().nan_to_num(nan=7.0), src.nan_to_num(nan=7.0))
+    # served through the derived-weight cache, the Conv3d operands' pad columns are zero: after the first serve and after the weight changed
+    for Cout, Cin, K in layout_ref.C3_DIMS:
+        w = torch.nn.Parameter(layout_ref.source('c3_p', (Cout, Cin, K)).view(Cout, Cin, K, K, K).to(d))
+        for step in range(2):
+            for mode, kind in enumerate(('c3_p', 'c3_q')):
+                got = ops.conv3d_weight(w, mode)
+                exp = layout_ref.expected(kind, w.detach().cpu().view(Cout, Cin, K ** 3), (Cout, Cin, K), torch.zeros(got.shape))
+                assert torch.equal(got.cpu(), exp), (kind, Cout, Cin, K, step)
+            with torch.no_grad():
+                w.mul_(-1.5)
 
 
 @pytest.mark.parametrize('dims', [(254, 8, 3), (16, 8, 9), (5, 1028, 3), (3, 8, 4)], ids=_ids)
@@ -176,7 +199,7 @@ def test_sizes_beyond_the_limits_are_unsupported(dims):
             ops.window_max_bwd(torch.zeros(n, C, device=d), torch.zeros(n, C, device=d, dtype=torch.uint8), n, C, L, w, 0, z, torch.zeros(C, device=d))
     if w > 8 or E > 1024:
         with pytest.raises(_lib.NnrHipError, match='unsupported size'):
-            ops.kcnn_repack(torch.zeros(C * E * w * 3, device=d), torch.zeros(C * E * w * 3, device=d), C, E, w, 0)
+            ops.kcnn_weight(torch.zeros(C, E, w, 3, device=d), 0)
 
 
 # ------------------------------------------------------------------------------------------------ the encoder at odd sizes

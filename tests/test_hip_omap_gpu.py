@@ -20,7 +20,7 @@ TIGHT = 2e-5
 OMAP_CASES = ['tiny_CNE_OMAP_stable', 'tiny_CNN_OMAP', 'full_CNE_OMAP_g0p35_stable']
 #         B, N, H, D, K
 SHAPES = [(64, 5, 50, 900, 3), (2, 5, 50, 900, 3), (5, 1, 50, 500, 3), (1, 1, 1, 4, 1), (7, 4, 33, 30, 5), (3, 3, 6, 40, 3),
-          (2, 3, 70, 130, 16)]
+          (2, 3, 70, 130, 16), (4, 3, 6, 40, 3)]      # (B = 1, 4, 5: the weight gradient sums one partial row per user, four loads at a time)
 SCALE = {900: 0.3, 500: 0.4, 130: 0.5, 40: 0.5, 30: 0.6, 24: 0.6, 13: 0.6, 4: 0.6}      # keeps the three softmaxes off saturation (see _expected's assertion)
 
 

@@ -15,7 +15,7 @@ import kcnn_ref
 
 TINY = ['tiny_KCNN_CATT', 'tiny_KCNN_ATT']
 FULL = ['full_KCNN_CATT_g1p0']
-ENTRY_POINTS = ('nnr_kcnn_image_fwd', 'nnr_kcnn_image_bwd', 'nnr_window_max_fwd', 'nnr_window_max_bwd', 'nnr_window_max_bwd_ws_floats', 'nnr_kcnn_repack')
+ENTRY_POINTS = ('nnr_kcnn_image_fwd', 'nnr_kcnn_image_bwd', 'nnr_window_max_fwd', 'nnr_window_max_bwd', 'nnr_window_max_bwd_ws_floats', 'nnr_permute')
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MARGIN = 1e-3
 
@@ -195,5 +195,5 @@ def test_entry_points_are_declared_listed_and_exported():
         assert (L.nnr_tape_fn_id(name.encode()) >= 0) == (name != 'nnr_window_max_bwd_ws_floats'), name
     assert L.nnr_window_max_bwd_ws_floats(0, 400) == 0 and L.nnr_window_max_bwd_ws_floats(17, 400) == 3 * 400
     assert profile.HBM_KERNELS_OTHER['kcnn_image_fwd'] == (('kcnn_image_fwd_kernel',), 1)
-    assert profile.HBM_KERNELS_OTHER['window_max_bwd'] == (('window_max_bwd_kernel', 'window_max_db_kernel'), 2)
+    assert profile.HBM_KERNELS_OTHER['window_max_bwd'] == (('window_max_bwd_kernel', 'partial_rows_sum_kernel<false'), 2)
     assert open(os.path.join(ROOT, 'nnr_amd', 'csrc', 'build.sh')).read().count(' kcnn ') == 1

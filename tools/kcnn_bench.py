@@ -88,12 +88,12 @@ def mode_kernel(a):
              'kcnn_image_bwd': lambda i: ops.kcnn_image_bwd(dXp, Xp, n, L, E, w, *outs),
              'window_max_fwd': lambda i: ops.window_max_fwd(z, C, bias, n, C, L, w, out, arg),
              'window_max_bwd': lambda i: ops.window_max_bwd(gup, arg, n, C, L, w, w - 1, dz, db),
-             'kcnn_repack': lambda i: ops.kcnn_repack(W, P, C, E, w, 0)}
+             'kcnn_permute': lambda i: ops.permute(W, P, 'kcnn_p', (C, E, w))}
         t = alternate(v, a.steps, a.warmup, a.rounds)
         med = {k: float(np.median(x)) for k, x in t.items()}
         nbytes = {'kcnn_image_fwd': 4.0 * (3 * E * n * Lp + 3 * E * n * L) + 4.0 * n * L, 'kcnn_image_bwd': 4.0 * E * n * L * (3 + 2 + 3),
                   'window_max_fwd': 4.0 * n * (L - w + 1) * C + 5.0 * n * C, 'window_max_bwd': 4.0 * ((w - 1) + n * Lp) * C + 5.0 * n * C,
-                  'kcnn_repack': 2 * 4.0 * C * E * w * 3}
+                  'kcnn_permute': 2 * 4.0 * C * E * w * 3}
         res['batch%d' % B] = {'shape': dict(n=n, L=L, E=E, C=C, w=w), 'ms': t, 'median_ms': med, 'MB': {k: round(x / 1e6, 1) for k, x in nbytes.items()},
                               'GBps': {k: round(nbytes[k] / med[k] / 1e6, 1) for k in med},
                               'share_of_hbm_peak': {k: round(nbytes[k] / med[k] / 1e6 / prof.PEAK_HBM_GBS, 4) for k in med}}
