@@ -489,6 +489,39 @@ size_t nnr_window_max_bwd_ws_floats(int n, int C);
 int nnr_window_max_bwd(const float* g, const uint8_t* arg, int n, int C, int L, int w, int lead_rows, float* dz, float* db, float* ws,
                        hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------------ NAML view attention (csrc/naml.hip)
+ * The multi-view attention of the NAML family (variantEncoders.py:139-142): out[i] = sum over the V = Vt + 2 views of softmax_v(score_v[i]) *
+ * row_v[i] for n news of C floats.  Views in order: Vt text views (t0, and t1 when Vt == 2: rows [n, C], scores [n]), then two TABLE views
+ * A and B given as (rows [R, C], score [R], ids int32 [n]) -- news i takes row ids[i]; an id outside [0, R) reads row 0 and sends no
+ * gradient.  All fp32, no float atomics.
+ * nnr_view_pool_fwd: alpha [n, V] (the softmax weights, the maximum subtracted) and out [n, C] are written.  t1 / ts1 are ignored for Vt == 1.
+ * nnr_view_pool_bwd: from dout [n, C]: dt_v [n, C] = alpha_v dout and dts_v [n] = ds_v = alpha_v (<dout, row_v> - sum_u alpha_u <dout, row_u>)
+ *   for the text views; for a table view drows [R, C] = the sum of alpha_v dout, and dscore [R] the sum of ds_v, over the news with that id
+ *   in ascending news order inside four fixed quarters of the news list (same inputs, same bits); a table row without news gets zeros.
+ *   All eight outputs are WRITTEN.  ws: 2 n floats owned by the calling stream.
+ * NNR_ERR_UNSUPPORTED for a non-positive n, C, Ra or Rb and for Vt outside 1..2. */
+int nnr_view_pool_fwd(const float* t0, const float* ts0, const float* t1, const float* ts1, int Vt, const float* rowsA, const float* scoreA,
+                      const int* idsA, int Ra, const float* rowsB, const float* scoreB, const int* idsB, int Rb, int n, int C, float* alpha,
+                      float* out, hipStream_t stream);
+int nnr_view_pool_bwd(const float* dout, const float* t0, const float* t1, int Vt, const float* rowsA, const int* idsA, int Ra,
+                      const float* rowsB, const int* idsB, int Rb, const float* alpha, int n, int C, float* dt0, float* dts0, float* dt1,
+                      float* dts1, float* drowsA, float* dscoreA, float* drowsB, float* dscoreB, float* ws, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------ padded-row Conv1d image (csrc/naml.hip)
+ * The kernels around the ONE product of Conv1d(E -> C, window k, padding (k - 1) / 2) over n news of L positions (Lp = L + k - 1):
+ * nnr_conv1d_image_fwd: Xp [n][Lp][E], every element written by this launch: rows [0, (k - 1) / 2) and [(k - 1) / 2 + L, Lp) of a news are
+ *   zero, row (k - 1) / 2 + t holds dropout(word_table[text[i, t]]) (text int32 [n, L]; an id outside [0, V): a zero row).  The keep-mask is
+ *   keyed on the compact index (i L + t) E + e: bit for bit nnr_embed_gather's for the same p and seed on the un-padded [n L, E] rows.
+ *   The window of output position t is the k E floats from padded row t on: a product with lda = E < K = k E over M = n Lp - (k - 1) rows.
+ * nnr_conv1d_dz_pad: dz [(k - 1) + n Lp][C], every element written: row (k - 1) + i Lp + t = (y > 0 ? dy : 0) of the compact row i L + t for
+ *   t < L (y: the compact relu output or anything with its sign, e.g. its dropped copy), zero in the k - 1 leading rows and at t >= L.
+ * nnr_conv1d_image_bwd: dx [n L, E] = the keep-mask (same key, p, seed as forward) times row i Lp + (k - 1) / 2 + t of dXp [n Lp, E].
+ * NNR_ERR_UNSUPPORTED for a non-positive dimension, an even k and k > 8. */
+int nnr_conv1d_image_fwd(const float* word_table, int V, const int* text, int n, int L, int E, int k, float p, uint32_t seed, float* Xp,
+                         hipStream_t stream);
+int nnr_conv1d_dz_pad(const float* dy, const float* y, int n, int L, int C, int k, float* dz, hipStream_t stream);
+int nnr_conv1d_image_bwd(const float* dXp, int n, int L, int E, int k, float p, uint32_t seed, float* dx, hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------ HDC (csrc/hdc.hip)
  * The kernels around the dilated convolutions of the HDC news encoder (newsEncoders.py:244-278), which run as accumulating products of
  * nnr_gemm_f32.  Activations are position-major: n news of S = L + 2 rows (category row, subCategory row, L title word rows) of C floats,

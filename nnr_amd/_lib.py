@@ -148,6 +148,11 @@ SIGNATURES = {
     'nnr_window_max_fwd': 'i32 ptr i32 ptr i32 i32 i32 i32 ptr ptr stream',
     'nnr_window_max_bwd_ws_floats': 'u64 i32 i32',
     'nnr_window_max_bwd': 'i32 ptr ptr i32 i32 i32 i32 i32 ptr ptr ptr stream',
+    'nnr_view_pool_fwd': 'i32 ptr ptr ptr ptr i32 ptr ptr ptr i32 ptr ptr ptr i32 i32 i32 ptr ptr stream',
+    'nnr_view_pool_bwd': 'i32 ptr ptr ptr i32 ptr ptr i32 ptr ptr i32 ptr i32 i32 ptr ptr ptr ptr ptr ptr ptr ptr ptr stream',
+    'nnr_conv1d_image_fwd': 'i32 ptr i32 ptr i32 i32 i32 i32 f32 seed ptr stream',
+    'nnr_conv1d_dz_pad': 'i32 ptr ptr i32 i32 i32 i32 ptr stream',
+    'nnr_conv1d_image_bwd': 'i32 ptr i32 i32 i32 i32 f32 seed ptr stream',
     'nnr_hdc_seq_fwd': 'i32 ptr i32 ptr i32 ptr i32 ptr ptr ptr i32 i32 i32 i32 ptr ptr ptr ptr ptr stream',
     'nnr_hdc_ln_relu_fwd': 'i32 ptr i32 ptr ptr i32 i32 i32 f32 ptr ptr i32 ptr stream',
     'nnr_hdc_ln_bwd_ws_floats': 'u64 i32 i32 i32',

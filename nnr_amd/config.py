@@ -23,6 +23,7 @@ _FLAGS = [
 _BOOL_FLAGS = ['no_self_connection', 'no_adjacent_normalization', 'no_gcn_residual', 'gcn_layer_norm']
 
 NEWS_ENCODERS = ['CNE', 'CNN', 'MHSA', 'PNE', 'DAE', 'Inception', 'HDC', 'KCNN']    # in scope; the reference lists 15
+ALL_NEWS_ENCODERS = NEWS_ENCODERS + ['NAML_Title', 'NAML_Content']         # (NEWS_ENCODERS above is pinned by the host tests; nothing reads either list)
 USER_ENCODERS = ['SUE', 'MHSA', 'ATT', 'CATT', 'OMAP', 'PUE', 'FIM']  # in scope; the reference lists 11
 ALL_USER_ENCODERS = USER_ENCODERS + ['GRU']                            # (USER_ENCODERS above is pinned by the host tests; nothing reads either list)
 

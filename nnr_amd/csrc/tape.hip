@@ -55,6 +55,7 @@ const Entry REGISTRY[] = {
   R(nnr_user_rows_fwd), R(nnr_user_rows_bwd), R(nnr_pers_attn_fwd), R(nnr_pers_attn_bwd),
   R(nnr_bag_mean_fwd), R(nnr_bag_mean_bwd), R(nnr_row_dist_fwd), R(nnr_row_dist_bwd), R(nnr_sigmoid_drop_bwd),
   R(nnr_kcnn_image_fwd), R(nnr_kcnn_image_bwd), R(nnr_window_max_fwd), R(nnr_window_max_bwd),
+  R(nnr_view_pool_fwd), R(nnr_view_pool_bwd), R(nnr_conv1d_image_fwd), R(nnr_conv1d_dz_pad), R(nnr_conv1d_image_bwd),
   R(nnr_hdc_seq_fwd), R(nnr_hdc_ln_relu_fwd), R(nnr_hdc_ln_relu_bwd), R(nnr_hdc_unpad_add),
   R(nnr_permute), R(nnr_conv3d_pool_fwd), R(nnr_conv3d_pool_bwd),
   R(nnr_gru_pack_weights), R(nnr_gru_unpack_grads), R(nnr_gru_fwd), R(nnr_gru_bwd), R(nnr_gru_zero_empty), R(nnr_gru_tanh_bwd),

@@ -551,6 +551,128 @@ class KcnnFn(torch.autograd.Function):
         return (None,) * 7
 
 
+class Conv1dImageFn(torch.autograd.Function):
+    """relu(Conv1d(E -> C, window k odd, 'same' padding)) over dropout(word_table[text]) as ONE product (csrc/naml.hip): the launch that
+    gathers and drops the word rows writes them as a halo-padded image Xp [n, L + k - 1, E], whose windows are contiguous (lda = E < K = k E);
+    bias and relu sit in the product's epilogue, which writes the live rows compact through a row map: y [n L, C], as Conv1dReluFn's.  The
+    word rows' keep-mask is nnr_embed_gather's for the same seed.  Backward: relu backward and the zero rows of the padded gradient in one
+    launch, the data gradient one product against the transposed, window-reversed weight, the weight gradient one TN product over the
+    overlapping rows (the bias gradient its column sums), and the word rows' gradient through the mask into the sorted scatter."""
+
+    @staticmethod
+    def forward(ctx, table, text, conv, n, Lx, p, seed, need_grad):
+        E = table.shape[1]
+        Cn, _, k = conv.weight.shape
+        Lp, dev = Lx + k - 1, table.device
+        idx = text.reshape(-1)
+        idx = (idx if idx.dtype == torch.int32 else idx.to(torch.int32)).contiguous()
+        # the sort needs nothing but the ids: on the leaf stream, under the forward pass (the sorted scatter carries rows of <= 320 floats)
+        ts = ops.TokenSort(idx, None, table.shape[0]) if need_grad and E <= 320 else None
+        f32 = dict(device=dev, dtype=torch.float32)
+        Xp = torch.empty((n * Lp, E), **f32)
+        ops.conv1d_image_fwd(table, idx, n, Lx, k, p, seed, Xp)
+        y = torch.empty((n * Lx, Cn), **f32)
+        ops.gemm(Xp, ops.conv1d_weight(conv.weight, 0), y, M=n * Lp - (k - 1), N=Cn, K=k * E, lda=E, ldb=k * E, ldc=Cn, bias=conv.bias,
+                 act=ops.ACT_RELU, c_idx=ops.conv1d_rowmap(n, Lx, k, dev))
+        ctx.table, ctx.conv, ctx.saved, ctx.dims = table, conv, (Xp if need_grad else None, idx, ts, y), (n, Lx, E, Cn, k, p, seed)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        table, conv = ctx.table, ctx.conv
+        Xp, idx, ts, y = ctx.saved
+        ctx.saved = None
+        n, Lx, E, Cn, k, p, seed = ctx.dims
+        dev, Lp, lead = dy.device, Lx + k - 1, k - 1
+        f32 = dict(device=dev, dtype=torch.float32)
+        dzp = torch.empty((lead + n * Lp, Cn), **f32)                 # k - 1 leading zero rows: row r of the view starts at dz row r - (k - 1)
+        ops.conv1d_dz_pad(dy.contiguous(), y, n, Lx, k, dzp)
+        M = n * Lp - lead
+        gw, gb = grad_of(conv.weight), grad_of(conv.bias)
+
+        def weight_grad():
+            dP = torch.zeros((Cn, k * E), **f32)
+            ops.linear_bwd_weight(dzp[lead:lead + M], Xp.as_strided((M, k * E), (E, 1)), dP, db=gb)
+            ops.permute(dP, gw, 'c1_dw', (Cn, E, k), accumulate=True)
+        ops.leaf_deferred(dev, n * Lx, weight_grad, dzp, Xp, force=True)      # (the permute is a plain read-modify-write: one stream for both calls)
+        dXp = torch.empty((n * Lp, E), **f32)
+        ops.gemm(dzp, ops.conv1d_weight(conv.weight, 1), dXp, M=n * Lp, N=E, K=k * Cn, lda=Cn, ldb=k * Cn, ldc=E)
+        dx = torch.empty((n * Lx, E), **f32)
+        ops.conv1d_image_bwd(dXp, n, Lx, k, p, seed, dx)
+        if ts is not None:
+            ops.embed_scatter_sorted(dx, ts, grad_of(table), 0.0, 0)
+        else:
+            ops.embed_scatter(dx, idx, grad_of(table), 0.0, 0)
+        return (None,) * 8
+
+
+class ViewPoolFn(torch.autograd.Function):
+    """The multi-view attention of the NAML family (variantEncoders.py:137-142) over 1 or 2 text views [n, C] and the category and
+    subCategory views (csrc/naml.hip): rep = sum_v softmax_v(affine2 . tanh(affine1(F_v))) * F_v.  The two table views are pure functions of
+    an id (no dropout on them in the reference), so relu(affine(table)), its tanh projection and its score are computed once per TABLE row
+    -- the text rows and the table rows go through affine1 as one [n Vt + Ra + Rb, C] operand -- and the kernel only indexes them; the
+    [n, V, C] stack never exists.  Backward: the kernel sums the table rows' gradients over the news that name them in a fixed order, the
+    rest are dense products over those n Vt + Ra + Rb rows; the embedding tables'
+    gradients are [rows, dim] products, no scatter.  Parameter gradients go straight into .grad."""
+
+    @staticmethod
+    def forward(ctx, enc, category, subCategory, *texts):
+        Vt, (n, Cn) = len(texts), texts[0].shape
+        cat_t, sub_t = enc.category_embedding.weight, enc.subCategory_embedding.weight
+        Ra, Rb = cat_t.shape[0], sub_t.shape[0]
+        dev = texts[0].device
+        f32 = dict(device=dev, dtype=torch.float32)
+        cat = category.reshape(n).to(torch.int32).contiguous()
+        sub = subCategory.reshape(n).to(torch.int32).contiguous()
+        rows = n * Vt + Ra + Rb
+        stack = torch.empty((rows, Cn), **f32)                      # [text view 0 | text view 1 | category rows | subCategory rows]
+        for v, t in enumerate(texts):
+            ops.add2d(stack[v * n:], Cn, t.contiguous(), Cn, n, Cn)
+        rowsA, rowsB = stack[n * Vt:n * Vt + Ra], stack[n * Vt + Ra:]
+        ops.linear_fwd(cat_t, enc.category_affine.weight, enc.category_affine.bias, out=rowsA, act=ops.ACT_RELU)
+        ops.linear_fwd(sub_t, enc.subCategory_affine.weight, enc.subCategory_affine.bias, out=rowsB, act=ops.ACT_RELU)
+        th = ops.linear_fwd(stack, enc.affine1.weight, enc.affine1.bias, act=ops.ACT_TANH)
+        score = torch.empty(rows, **f32)
+        ops.rowdot(th, enc.affine2.weight, score)
+        alpha, out = torch.empty((n, Vt + 2), **f32), torch.empty((n, Cn), **f32)
+        ops.view_pool_fwd([stack[v * n:(v + 1) * n] for v in range(Vt)], [score[v * n:(v + 1) * n] for v in range(Vt)], rowsA,
+                          score[n * Vt:n * Vt + Ra], cat, rowsB, score[n * Vt + Ra:], sub, alpha, out)
+        ctx.enc, ctx.saved, ctx.dims = enc, (stack, th, alpha, cat, sub), (Vt, n, Cn, Ra, Rb)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        enc = ctx.enc
+        stack, th, alpha, cat, sub = ctx.saved
+        ctx.saved = None
+        Vt, n, Cn, Ra, Rb = ctx.dims
+        dev = dout.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        dout = dout.contiguous()
+        rows, A = n * Vt + Ra + Rb, th.shape[1]
+        a0, b0 = n * Vt, n * Vt + Ra
+        dstack, dscore = torch.empty((rows, Cn), **f32), torch.empty(rows, **f32)
+        sl = lambda x: [x[v * n:(v + 1) * n] for v in range(Vt)]
+        ops.view_pool_bwd(dout, sl(stack), stack[a0:b0], cat, stack[b0:], sub, alpha, sl(dstack), sl(dscore), dstack[a0:b0],
+                          dscore[a0:b0], dstack[b0:], dscore[b0:])
+        ops.tanh_score_bwd(th, dscore, enc.affine2.weight, grad_of(enc.affine2.weight), None, A)          # th := d(pre-activation)
+        gw, gb = grad_of(enc.affine1.weight), grad_of(enc.affine1.bias)
+        ops.leaf_deferred(dev, rows, lambda: ops.linear_bwd_weight(th, stack, gw, db=gb), th, stack)
+        if rows >= 1024 and (A & 3) == 0:
+            ops.gemm(th, ops.wt(enc.affine1.weight), dstack, M=rows, N=Cn, K=A, lda=A, ldb=A, ldc=Cn, accumulate=True)      # NT on W1^T
+        else:
+            ops.gemm(th, enc.affine1.weight, dstack, M=rows, N=Cn, K=A, lda=A, ldb=Cn, ldc=Cn, trans_b=True, accumulate=True)
+        dz_all = ops.relu_bwd(dstack[a0:], stack[a0:])                  # both tables' rows lie back to back: one launch
+        for lo, hi, table, lin in ((0, Ra, enc.category_embedding.weight, enc.category_affine),
+                                   (Ra, Ra + Rb, enc.subCategory_embedding.weight, enc.subCategory_affine)):
+            dz, dim = dz_all[lo:hi], table.shape[1]
+            ops.linear_bwd_weight(dz, table, grad_of(lin.weight), db=grad_of(lin.bias))
+            # the table's gradient is a dense [rows, dim] product, added atomically: the candidate call's backward (side stream) and the
+            # history call's (main stream) may overlap, and two addends into a zeroed buffer commute -- the same bits on every run
+            ops.gemm(dz, lin.weight, grad_of(table), M=hi - lo, N=dim, K=Cn, lda=Cn, ldb=dim, ldc=dim, trans_b=True, atomic=True)
+        return (None, None, None) + tuple(sl(dstack))
+
+
 class ExpandFn(torch.autograd.Function):
     """[B, D] -> [B, N, D] (repeat / expand over the candidates, userEncoders.py:172,190); backward sums over N."""
 

@@ -100,8 +100,13 @@ class Model(nn.Module):
             self.news_encoder = newsEncoders.KCNN(config, word_table, entity_table, context_table)
         elif config.news_encoder == 'HDC':
             self.news_encoder = newsEncoders.HDC(config, word_table)
+        elif config.news_encoder == 'NAML_Title':
+            self.news_encoder = newsEncoders.NAML_Title(config, word_table)
+        elif config.news_encoder == 'NAML_Content':
+            self.news_encoder = newsEncoders.NAML_Content(config, word_table)
         else:
-            raise Exception(config.news_encoder + ' is not on the MI355X hot path (in scope: CNE, CNN, MHSA, HDC, PNE, DAE, Inception, KCNN; SURVEY.md section 8a)')
+            raise Exception(config.news_encoder + ' is not on the MI355X hot path (in scope: CNE, CNN, MHSA, HDC, PNE, DAE, Inception, KCNN, NAML_Title, '
+                            'NAML_Content; SURVEY.md section 8a)')
         if config.user_encoder == 'SUE':
             self.user_encoder = userEncoders.SUE(self.news_encoder, config)
         elif config.user_encoder == 'MHSA':

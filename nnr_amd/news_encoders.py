@@ -826,6 +826,91 @@ class PNE(NewsEncoder):
         return Fn.FuseFn.apply(rep, self, category, subCategory, p, seed).view(B, N, self.news_embedding_dim)
 
 
+CONV1D_IMAGE = True         # the text stream's convolution as one padded-row product (functional.Conv1dImageFn); False (tools/naml_bench.py): CNN's shifted products
+
+
+class _NAMLSingle(NewsEncoder):
+    """variantEncoders.py:102-187, the single-view members of the NAML family over ONE text stream (`stream`: 'title' or 'content'):
+    dropout(word rows) -> Conv1d + ReLU -> dropout_ -> additive attention pool over ALL positions -> multi-view attention with
+    relu(category_affine(category row)) and relu(subCategory_affine(subCategory row)) (functional.ViewPoolFn, csrc/naml.hip).
+
+    Observable quirks kept: no feature fusion (news_embedding_dim = cnn_kernel_num) and no mask -- PAD positions take part with row 0 of the
+    word table, which is trainable like any other row; no dropout on the two category views; the masks, the entity arguments, the other
+    text stream and `user_embedding` are accepted and ignored.  initialize() draws the three view-attention matrices with gain 1 and leaves
+    the convolution as torch made it.  An even cnn_window_size gives the reference max_length - 1 convolution outputs: refused.
+    Dropout seeds as CNN's: seed + 1 the word rows, seed + 2 the convolution output, both keyed on the compact (news, position, column)."""
+    batch_independent = True
+
+    def __init__(self, config, stream, word_table=None):
+        super().__init__(config, word_table)
+        if config.cnn_window_size % 2 == 0:
+            raise Exception('cnn_window_size=%d: unsupported size (an even window leaves the reference one convolution output short of the '
+                            'sequence length)' % config.cnn_window_size)
+        self.text_stream = stream
+        self.max_length = config.max_title_length if stream == 'title' else config.max_abstract_length
+        setattr(self, 'max_%s_length' % stream, self.max_length)
+        self.cnn_kernel_num = config.cnn_kernel_num
+        self.news_embedding_dim = config.cnn_kernel_num
+        setattr(self, stream + '_conv', Conv1D(config.cnn_method, config.word_embedding_dim, config.cnn_kernel_num, config.cnn_window_size))
+        setattr(self, stream + '_attention', Attention(config.cnn_kernel_num, config.attention_dim))
+        self.category_affine = nn.Linear(config.category_embedding_dim, config.cnn_kernel_num, bias=True)
+        self.subCategory_affine = nn.Linear(config.subCategory_embedding_dim, config.cnn_kernel_num, bias=True)
+        self.affine1 = nn.Linear(config.cnn_kernel_num, config.attention_dim, bias=True)
+        self.affine2 = nn.Linear(config.attention_dim, 1, bias=False)
+
+    def text_conv(self):
+        return getattr(self, self.text_stream + '_conv')
+
+    def text_attention(self):
+        return getattr(self, self.text_stream + '_attention')
+
+    def initialize(self):
+        super().initialize()
+        self.text_attention().initialize()
+        for lin in (self.category_affine, self.subCategory_affine, self.affine1):
+            nn.init.xavier_uniform_(lin.weight)
+            nn.init.zeros_(lin.bias)
+        nn.init.xavier_uniform_(self.affine2.weight)
+
+    def text_view(self, text, n, p, seed):
+        """One text stream's view [n, C]: the stages in front of the multi-view attention (a second stream is a second call of this)."""
+        from . import functional as Fn
+        Lx = self.max_length
+        table = self.word_embedding.weight
+        if CONV1D_IMAGE:
+            c = Fn.Conv1dImageFn.apply(table, text, self.text_conv().conv, n, Lx, p, seed + 1, torch.is_grad_enabled() and table.requires_grad)
+        else:
+            w = Fn.EmbedDropFn.apply(table, text, p, seed + 1)
+            c = Fn.Conv1dReluFn.apply(w, self.text_conv().conv, n, Lx)                                      # [n*L, C]
+        c = Fn.DropoutFn.apply(c, p, seed + 2)
+        return self.text_attention()(c.view(n, Lx, self.cnn_kernel_num))                                   # no mask
+
+    def forward(self, title_text, title_mask, title_entity, content_text, content_mask, content_entity, category, subCategory, user_embedding):
+        from . import functional as Fn
+        text = title_text if self.text_stream == 'title' else content_text
+        B, N = text.shape[:2]
+        n = B * N
+        p = self.dropout_rate if self.training else 0.0
+        seed = self._next_seed()
+        view = self.text_view(text, n, p, seed)
+        rep = Fn.ViewPoolFn.apply(self, category, subCategory, view)
+        return rep.view(B, N, self.news_embedding_dim)
+
+
+class NAML_Title(_NAMLSingle):
+    """variantEncoders.py:102-143: the title stream (title_conv.*, title_attention.*)."""
+
+    def __init__(self, config, word_table=None):
+        super().__init__(config, 'title', word_table)
+
+
+class NAML_Content(_NAMLSingle):
+    """variantEncoders.py:146-187: the abstract stream, max_abstract_length positions (content_conv.*, content_attention.*)."""
+
+    def __init__(self, config, word_table=None):
+        super().__init__(config, 'content', word_table)
+
+
 def _bow_streams(title_text, title_mask, content_text, content_mask):
     """ids [n, L] int32 and mask VIEWS [n, L] of both token streams of a call (views: an in-place mask fix must reach the caller's tensors)."""
     B, N, La = title_text.shape

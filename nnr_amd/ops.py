@@ -1656,6 +1656,10 @@ LAYOUTS = {
     # Conv1d weight W [F, C, w]: P[k][f][c] in rows of ldp >= C floats | W.grad[f][c][k] += dP[k][f][c]
     'hdc_p': lambda F, C_, w, ldp: ((1, w, F, C_), (0, 1, C_ * w, w), (0, F * ldp, ldp, 1), 0, (w, F, ldp)),
     'hdc_dw': lambda F, C_, w, ldp: ((1, F, C_, w), (0, ldp, 1, F * ldp), (0, C_ * w, w, 1), 0, (F, C_, w)),
+    # Conv1d weight W [C, E, k] of the padded-row convolution: P[c][dt][e] | Q[e][j][c] = W[c][e][k-1-j] | W.grad[c][e][dt] += dP[c][dt][e]
+    'c1_p': lambda C_, E, k: ((1, C_, k, E), (0, E * k, 1, k), (0, k * E, E, 1), 0, (C_, k * E)),
+    'c1_q': lambda C_, E, k: ((1, E, k, C_), (0, k, -1, E * k), (0, k * C_, C_, 1), k - 1, (E, k * C_)),
+    'c1_dw': lambda C_, E, k: ((1, C_, E, k), (0, k * E, 1, E), (0, E * k, k, 1), 0, (C_, E, k)),
     # Conv3d weight W [Cout, Cin, K^3]: [ci][t][f] in rows of Cout rounded up to 4 | [f][t][ci] in rows of Cin rounded up to 4
     'c3_p': lambda Co, Ci, K: ((1, Ci, K ** 3, Co), (0, K ** 3, 1, Ci * K ** 3), (0, K ** 3 * _pad4(Co), _pad4(Co), 1), 0, (Ci, K ** 3, _pad4(Co))),
     'c3_q': lambda Co, Ci, K: ((1, Co, K ** 3, Ci), (0, Ci * K ** 3, 1, K ** 3), (0, K ** 3 * _pad4(Ci), _pad4(Ci), 1), 0, (Co, K ** 3, _pad4(Ci))),
@@ -1723,6 +1727,87 @@ def kcnn_weight(weight, mode):
     if w > 8 or E > 1024:
         raise L.NnrHipError('kcnn_weight: %s' % KCNN_UNSUPPORTED)
     return _permuted_weight('kcnn_q' if mode else 'kcnn_p', weight, (C_, E, w))
+
+
+# ---------------------------------------------------------------------------------------------- NAML view attention (csrc/naml.hip)
+VIEW_POOL_UNSUPPORTED = 'unsupported size (a non-positive dimension, or text views outside 1..2)'
+
+
+def view_pool_fwd(texts, scores, rowsA, scoreA, idsA, rowsB, scoreB, idsB, alpha, out):
+    """out [n, C] = sum over the views of softmax_v(score_v) * row_v; alpha [n, V] (include/nnr_hip.h).  texts / scores: 1 or 2 text views."""
+    Vt, (n, Cn) = len(texts), out.shape
+    t1, s1 = (texts[1], scores[1]) if Vt == 2 else (None, None)
+    # per news: V rows read (the table rows mostly from cache), one row + V weights written, V scores + 2 ids read
+    with _hbm_span('view_pool_fwd', 4.0 * Cn * (Vt + 3) + 8.0 * (Vt + 2) + 8.0, n):
+        L.check(L.lib().nnr_view_pool_fwd(_p(texts[0]), _p(scores[0]), _p(t1), _p(s1), Vt, _p(rowsA), _p(scoreA), _p(idsA), rowsA.shape[0],
+                                          _p(rowsB), _p(scoreB), _p(idsB), rowsB.shape[0], n, Cn, _p(alpha), _p(out), _s()),
+                'nnr_view_pool_fwd', VIEW_POOL_UNSUPPORTED)
+
+
+def view_pool_bwd(dout, texts, rowsA, idsA, rowsB, idsB, alpha, dtexts, dtscores, drowsA, dscoreA, drowsB, dscoreB):
+    """The eight gradients of view_pool_fwd, all written (include/nnr_hip.h)."""
+    Vt, (n, Cn) = len(texts), dout.shape
+    t1, d1, ds1 = (texts[1], dtexts[1], dtscores[1]) if Vt == 2 else (None, None, None)
+    ws = torch.empty(2 * n, device=dout.device, dtype=torch.float32)
+    # per news: dout read twice (per news, per table view), V rows read, Vt rows written; per table row one row written
+    with _hbm_span('view_pool_bwd', 4.0 * Cn * (2 * Vt + 5) + 4.0 * (3 * Vt + 10), n, fixed=4.0 * (Cn + 1) * (rowsA.shape[0] + rowsB.shape[0])):
+        L.check(L.lib().nnr_view_pool_bwd(_p(dout), _p(texts[0]), _p(t1), Vt, _p(rowsA), _p(idsA), rowsA.shape[0],
+                                          _p(rowsB), _p(idsB), rowsB.shape[0], _p(alpha), n, Cn, _p(dtexts[0]),
+                                          _p(dtscores[0]), _p(d1), _p(ds1), _p(drowsA), _p(dscoreA), _p(drowsB), _p(dscoreB), _p(ws), _s()),
+                'nnr_view_pool_bwd', VIEW_POOL_UNSUPPORTED)
+
+
+CONV1D_UNSUPPORTED = 'unsupported size (a non-positive dimension, an even cnn_window_size, or cnn_window_size > 8)'
+_C1_ROWMAP = {}
+
+
+def conv1d_image_fwd(table, text, n, Lx, k, p, seed, Xp):
+    """Xp [n, Lx + k - 1, E]: zero halo rows and dropout(table[text]) rows, the mask keyed on the compact rows (include/nnr_hip.h)."""
+    V, E = table.shape
+    with _hbm_span('conv1d_image_fwd', 4.0 * E, n * (Lx + k - 1), fixed=(4.0 * E + 4.0) * n * Lx):
+        L.check(L.lib().nnr_conv1d_image_fwd(_p(table), V, _p(text), n, Lx, E, k, p, seed, _p(Xp), _s()), 'nnr_conv1d_image_fwd', CONV1D_UNSUPPORTED)
+
+
+def conv1d_dz_pad(dy, y, n, Lx, k, dz):
+    """dz [(k - 1) + n (Lx + k - 1), C] written densely: relu backward of the compact dy at the live rows, zero elsewhere."""
+    Cn = dy.shape[1]
+    with _hbm_span('conv1d_dz_pad', 4.0 * Cn, k - 1 + n * (Lx + k - 1), fixed=8.0 * Cn * n * Lx):
+        L.check(L.lib().nnr_conv1d_dz_pad(_p(dy), _p(y), n, Lx, Cn, k, _p(dz), _s()), 'nnr_conv1d_dz_pad', CONV1D_UNSUPPORTED)
+
+
+def conv1d_image_bwd(dXp, n, Lx, k, p, seed, dx):
+    """dx [n Lx, E] = keep-mask * the word rows of dXp [n (Lx + k - 1), E]."""
+    E = dx.shape[1]
+    with _hbm_span('conv1d_image_bwd', 8.0 * E, n * Lx):
+        L.check(L.lib().nnr_conv1d_image_bwd(_p(dXp), n, Lx, E, k, p, seed, _p(dx), _s()), 'nnr_conv1d_image_bwd', CONV1D_UNSUPPORTED)
+
+
+def conv1d_weight(weight, mode):
+    """P [C, k E] (mode 0) or Q [E, k C] (mode 1) of the Conv1d weight [C, E, k]: the B operand of the padded-row convolution product or of
+    its data gradient, an entry of the derived-weight cache (as kcnn_weight)."""
+    C_, E, k = weight.shape
+    if k > 8 or k % 2 == 0:
+        raise L.NnrHipError('conv1d_weight: %s' % CONV1D_UNSUPPORTED)
+    return _permuted_weight('c1_q' if mode else 'c1_p', weight, (C_, E, k))
+
+
+def conv1d_rowmap(n, Lx, k, dev):
+    """int32 [n Lp - (k - 1)]: the compact row i Lx + t of image row i Lp + t, -1 for the rows t >= Lx that straddle two news (the
+    product's epilogue drops them); None for k == 1 (no junk rows).  Depends on the shape alone: kept per (n, Lx, k, device)."""
+    if k == 1:
+        return None
+    key = (n, Lx, k, dev.type, dev.index)
+    m = _C1_ROWMAP.get(key)
+    if m is None:
+        if len(_C1_ROWMAP) >= 16:
+            _C1_ROWMAP.clear()
+        Lp = Lx + k - 1
+        t = torch.arange(Lp, device=dev, dtype=torch.int32)[None, :]
+        base = (torch.arange(n, device=dev, dtype=torch.int32) * Lx)[:, None]
+        m = torch.where(t < Lx, base + t, torch.full_like(base + t, -1)).reshape(-1)[:n * Lp - (k - 1)].contiguous()
+        _C1_ROWMAP[key] = m
+    tape_keep(m)
+    return m
 
 
 # ---------------------------------------------------------------------------------------------- HDC / FIM (csrc/hdc.hip, csrc/fim.hip)

@@ -150,6 +150,9 @@ HBM_KERNELS_OTHER = {
     'row_dist_fwd': (('row_dist_fwd_kernel',), 1), 'row_dist_bwd': (('row_dist_bwd_kernel',), 1),
     'kcnn_image_fwd': (('kcnn_image_fwd_kernel',), 1), 'kcnn_image_bwd': (('kcnn_image_bwd_kernel',), 1),
     'window_max_fwd': (('window_max_fwd_kernel',), 1), 'window_max_bwd': (('window_max_bwd_kernel', 'partial_rows_sum_kernel<false'), 2),
+    'view_pool_fwd': (('view_pool_fwd_kernel',), 1), 'view_pool_bwd': (('view_pool_bwd_news_kernel', 'view_pool_bwd_table_kernel'), 2),
+    'conv1d_image_fwd': (('conv1d_image_fwd_kernel',), 1), 'conv1d_dz_pad': (('conv1d_dz_pad_kernel',), 1),
+    'conv1d_image_bwd': (('conv1d_image_bwd_kernel',), 1),
     'hdc_seq_fwd': (('hdc_seq_fwd_kernel',), 1), 'hdc_ln_relu_fwd': (('hdc_ln_relu_fwd_kernel',), 1),
     'hdc_ln_relu_bwd': (('hdc_ln_param_kernel', 'hdc_ln_param_reduce_kernel', 'hdc_ln_relu_bwd_kernel'), 3),
     'hdc_unpad_add': (('hdc_unpad_add_kernel',), 1),

@@ -176,6 +176,12 @@ def run_gru():
     run('tiny_DAE_GRU', 'DAE', 'GRU', False, min_gap=1e-4, zero_ties=True, Alpha=0.1)
 
 
+def run_naml():
+    """`python tools/make_eval_goldens.py naml`: NAML_Title under ATT.  (The view softmax averages three rows: the scores lie closer together
+    than the concatenating encoders'; the smallest gap inside an impression is 8.3e-5, forty times the fp32 error of a score.)"""
+    run('tiny_NAML_Title_ATT', 'NAML_Title', 'ATT', False, min_gap=5e-5)
+
+
 def run_fim():
     """`python tools/make_eval_goldens.py fim`: the HDC / FIM pair with its own click head, at the tiny FIM sizes of tools/make_goldens.py
     (history 11 so that both pooled layers keep a cell; S = 10 -> 8 -> 4 -> 2 -> 1)."""
@@ -191,6 +197,9 @@ if __name__ == '__main__':
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'gru':
         run_gru()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'naml':
+        run_naml()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'kcnn':
         run_kcnn()
@@ -218,3 +227,4 @@ if __name__ == '__main__':
     run_kcnn()
     run_fim()
     run_gru()
+    run_naml()
