@@ -7,7 +7,7 @@ import os
 import torch
 
 from . import ops
-from .layers import grad_of
+from .layers import attention_bwd, attention_fwd, grad_of
 
 
 class EmbedDropFn(torch.autograd.Function):
@@ -15,8 +15,7 @@ class EmbedDropFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, ids, p, seed):
-        idx = ids.reshape(-1)
-        idx = (idx if idx.dtype == torch.int32 else idx.to(torch.int32)).contiguous()
+        idx = ops.ids32(ids, -1)
         out = ops.embed_gather(table, idx, p, seed)
         ctx.table, ctx.idx, ctx.p, ctx.seed = table, idx, p, seed
         return out
@@ -116,36 +115,23 @@ class PackedAttentionFn(torch.autograd.Function):
         cap, F = feature.shape
         A = mod.affine1.weight.shape[0]
         x = feature.contiguous()
+        fused = A <= 256 and A % 4 == 0                               # the pool takes the w2 . th row-dot in its own pass
+        th, score = attention_fwd(mod, x, dyn=plan.total, score=not fused)
         f32 = dict(device=x.device, dtype=torch.float32)
-        th = torch.empty((cap, A), **f32)
-        ops.gemm(x, mod.affine1.weight, th, M=cap, N=A, K=F, lda=F, ldb=F, ldc=A, bias=mod.affine1.bias, act=ops.ACT_TANH, dyn=plan.total, dyn_dim=1)
-        alpha = torch.empty(cap, **f32)
-        out = torch.empty((plan.n, F), **f32)
-        if A <= 256 and A % 4 == 0:
-            ops.pool_fwd(x=x, ldx=F, D=F, n=plan.n, Lx=plan.L, plan=plan, mask=mask, th=th, w2=mod.affine2.weight, alpha=alpha, out=out, ldo=F)
-        else:
-            score = torch.empty(cap, **f32)
-            ops.rowdot(th, mod.affine2.weight, score, dyn=plan.total)
-            ops.pool_fwd(x=x, ldx=F, D=F, n=plan.n, Lx=plan.L, plan=plan, mask=mask, score=score, alpha=alpha, out=out, ldo=F)
-        ctx.mod, ctx.mask, ctx.plan, ctx.saved = mod, mask, plan, (x, th, alpha, F, A)
+        alpha, out = torch.empty(cap, **f32), torch.empty((plan.n, F), **f32)
+        sc = dict(th=th, w2=mod.affine2.weight) if fused else dict(score=score)
+        ops.pool_fwd(x=x, ldx=F, D=F, n=plan.n, Lx=plan.L, plan=plan, mask=mask, alpha=alpha, out=out, ldo=F, **sc)
+        ctx.mod, ctx.mask, ctx.plan, ctx.saved = mod, mask, plan, (x, th, alpha, F)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         mod, plan = ctx.mod, ctx.plan
-        x, th, alpha, F, A = ctx.saved
-        cap = plan.cap
+        x, th, alpha, F = ctx.saved
         f32 = dict(device=x.device, dtype=torch.float32)
-        dx = torch.empty((cap, F), **f32)
-        ds = torch.empty(cap, **f32)
+        dx, ds = torch.empty((plan.cap, F), **f32), torch.empty(plan.cap, **f32)
         ops.pool_bwd(x=x, ldx=F, D=F, n=plan.n, Lx=plan.L, plan=plan, mask=ctx.mask, alpha=alpha, dout=dout.contiguous(), lddo=F, dx=dx, lddx=F, dscore=ds)
-        ops.tanh_score_bwd(th, ds, mod.affine2.weight, grad_of(mod.affine2.weight), plan, A)          # th := d(pre-activation)
-        gw, gb = grad_of(mod.affine1.weight), grad_of(mod.affine1.bias)
-        ops.leaf_deferred(x.device, cap, lambda: ops.linear_bwd_weight(th, x, gw, db=gb, dyn=plan.total), th, x)
-        if cap >= 1024 and (A & 3) == 0:
-            ops.gemm(th, ops.wt(mod.affine1.weight), dx, M=cap, N=F, K=A, lda=A, ldb=A, ldc=F, accumulate=True, dyn=plan.total, dyn_dim=1)
-        else:
-            ops.gemm(th, mod.affine1.weight, dx, M=cap, N=F, K=A, lda=A, ldb=F, ldc=F, trans_b=True, accumulate=True, dyn=plan.total, dyn_dim=1)
+        attention_bwd(mod, x, th, ds, dx, plan)
         return dx, None, None, None
 
 
@@ -343,8 +329,7 @@ class FuseFn(torch.autograd.Function):
         D = F + cd + sd
         out = torch.empty((n, D), device=rep.device, dtype=torch.float32)
         ops.add2d(out, D, rep.contiguous(), F, n, F)
-        cat = category.reshape(n).to(torch.int32).contiguous()
-        sub = subCategory.reshape(n).to(torch.int32).contiguous()
+        cat, sub = ops.ids32(category, n), ops.ids32(subCategory, n)
         # (both tables in one launch, the kernel of the CNE step; same per-element masks as two nnr_small_embed_fwd calls)
         ops.fusion_rows_fwd(enc.category_embedding.weight, enc.subCategory_embedding.weight, cat, sub, None, None, out[:, F:], D, p, seed + 3, seed + 4)
         ctx.enc, ctx.cat, ctx.sub, ctx.dims, ctx.p, ctx.seed = enc, cat, sub, (n, F, cd, sd, D), p, seed
@@ -473,16 +458,44 @@ class InceptionFn(torch.autograd.Function):
         return (None,) * 9
 
 
+def rowconv_fwd(Xp, weight, out, **epilogue):
+    """The convolution over a halo-padded row image as ONE product.  Xp [n (L + w - 1), Cin] has w - 1 zero halo rows
+    per news, so row r of its overlapping-row view Xp' (lda = Cin < K = w Cin) is the window that starts at image row r:
+    out[r] = epilogue(Xp'[r] . P^T) for every window inside the image, P the permuted weight; bias / act / c_idx go to the epilogue."""
+    rows, Cin = Xp.shape
+    Cn, w = weight.shape[0], weight.shape[2]
+    ops.gemm(Xp, ops.rowconv_weight(weight, 0), out, M=rows - (w - 1), N=Cn, K=w * Cin, lda=Cin, ldb=w * Cin, ldc=Cn, **epilogue)
+
+
+def rowconv_bwd(dzp, Xp, weight, leaf_rows, db=None):
+    """Both gradients of rowconv_fwd from dzp [(w - 1) + n (L + w - 1), C]: the dense output gradient behind w - 1 leading zero rows, so row r
+    of ITS overlapping-row view starts at dz row r - (w - 1).  Returns dXp = dz' . Q^T (Q: the transposed, window-reversed weight).  The
+    weight gradient is one TN product over Xp' into a zeroed dP (db: the bias gradient, its column sums) that nnr_permute adds into
+    weight.grad: a plain read-modify-write, so always on the ONE leaf stream, for both encoder calls."""
+    rows, Cin = Xp.shape
+    Cn, w = weight.shape[0], weight.shape[2]
+    lead, R, gw = w - 1, rows - (w - 1), grad_of(weight)
+    f32 = dict(device=Xp.device, dtype=torch.float32)
+
+    def weight_grad():
+        dP = torch.zeros((Cn, w * Cin), **f32)
+        ops.linear_bwd_weight(dzp[lead:lead + R], Xp.as_strided((R, w * Cin), (Cin, 1)), dP, db=db)
+        ops.permute(dP, gw, 'kcnn_dw', ops.rowconv_dims(weight), accumulate=True)
+    ops.leaf_deferred(Xp.device, leaf_rows, weight_grad, dzp, Xp, force=True)
+    dXp = torch.empty((rows, Cin), **f32)
+    ops.gemm(dzp, ops.rowconv_weight(weight, 1), dXp, M=rows, N=Cin, K=w * Cn, lda=Cn, ldb=w * Cn, ldc=Cin)
+    return dXp
+
+
 class KcnnFn(torch.autograd.Function):
     """The KCNN news encoder up to its pooled [n, C] representation (newsEncoders.py:233-238, layers.py:77-78), forward and backward by hand
-    around ONE convolution product (csrc/kcnn.hip):
+    around ONE convolution product (rowconv_fwd / rowconv_bwd; csrc/kcnn.hip):
       pre_j = table_j[entity] M_j^T + b_j (entity / context rows gathered in the GEMM's A loader);  Xp = the padded image [n, L + w - 1, 3 E]
-      (word rows gathered straight from the table, tanh(pre_j), zero halo rows);  z = Xp' . P^T with Xp' the overlapping-row view of Xp
-      (lda = 3 E < K = 3 w E) and P the permuted Conv2d weight;  out = relu-then-max over the first L - w + 1 positions of z + bias.
-    No dropout and no mask: PAD positions take part with row 0 of each table.  Backward: dense dz (every element written once), dXp = dz' . Q^T
-    (dz' the overlapping-row view with lda = C < K = w C, Q the transposed, window-reversed weight), dP = dz^T . Xp' (split-K through
-    slabs), then the image apart again, the two projections' gradients with the table rows gathered in the B loader, and the three table
-    gradients through the sorted scatter (reproducible, no pile-up of atomics on id 0).  Parameter gradients go straight into .grad."""
+      (word rows gathered straight from the table, tanh(pre_j), zero halo rows);  out = relu-then-max over the first L - w + 1 positions of
+      the product + bias.  No dropout and no mask: PAD positions take part with row 0 of each table.  Backward: dense dz (every element
+    written once), the two products, then the image apart again, the two projections' gradients with the table rows gathered in the B
+    loader, and the three table gradients through the sorted scatter (reproducible, no pile-up of atomics on id 0).  Parameter gradients go
+    straight into .grad."""
 
     @staticmethod
     def forward(ctx, anchor, enc, text, entity, n, Lx, need_grad):
@@ -503,9 +516,8 @@ class KcnnFn(torch.autograd.Function):
         Xp = torch.empty((n * Lp, 3 * E), **f32)
         ops.kcnn_image_fwd(word, text, pre[0], pre[1], n, Lx, w, Xp)
         del pre
-        R = n * Lp - (w - 1)                                          # the last window that lies inside the image starts at row R - 1
         z = torch.empty((n * Lp, Cn), **f32)                          # (its last w - 1 rows stay unwritten: no maximum reads them)
-        ops.gemm(Xp, ops.kcnn_weight(conv.weight, 0), z, M=R, N=Cn, K=3 * w * E, lda=3 * E, ldb=3 * w * E, ldc=Cn)
+        rowconv_fwd(Xp, conv.weight, z)
         out = torch.empty((n, Cn), **f32)
         arg = torch.empty((n, Cn), device=dev, dtype=torch.uint8)
         ops.window_max_fwd(z, Cn, conv.bias, n, Cn, Lx, w, out, arg)
@@ -525,18 +537,9 @@ class KcnnFn(torch.autograd.Function):
         dzp = torch.empty((lead + n * Lp, Cn), **f32)                 # w - 1 leading zero rows: row r of dz' starts at dz row r - (w - 1)
         db = torch.empty(Cn, **f32)
         ops.window_max_bwd(dout, arg, n, Cn, Lx, w, lead, dzp, db)
-        gb, gw = grad_of(conv.bias), grad_of(conv.weight)
+        gb = grad_of(conv.bias)
         ops.leaf_deferred(dev, rows, lambda: ops.add_(gb, db), db, force=True)        # (plain read-modify-write: one stream for both calls)
-        dz = dzp[lead:]
-        R = n * Lp - lead
-
-        def weight_grad():
-            dP = torch.zeros((Cn, 3 * w * E), **f32)
-            ops.linear_bwd_weight(dz[:R], Xp.as_strided((R, 3 * w * E), (3 * E, 1)), dP)
-            ops.permute(dP, gw, 'kcnn_dw', (Cn, E, w), accumulate=True)
-        ops.leaf_deferred(dev, rows, weight_grad, dzp, Xp, force=True)
-        dXp = torch.empty((n * Lp, 3 * E), **f32)
-        ops.gemm(dzp, ops.kcnn_weight(conv.weight, 1), dXp, M=n * Lp, N=3 * E, K=w * Cn, lda=Cn, ldb=w * Cn, ldc=3 * E)
+        dXp = rowconv_bwd(dzp, Xp, conv.weight, rows)
         dx0, dp1, dp2 = (torch.empty((rows, E), **f32) for _ in range(3))
         ops.kcnn_image_bwd(dXp, Xp, n, Lx, E, w, dx0, dp1, dp2)
         del dXp
@@ -552,28 +555,25 @@ class KcnnFn(torch.autograd.Function):
 
 
 class Conv1dImageFn(torch.autograd.Function):
-    """relu(Conv1d(E -> C, window k odd, 'same' padding)) over dropout(word_table[text]) as ONE product (csrc/naml.hip): the launch that
-    gathers and drops the word rows writes them as a halo-padded image Xp [n, L + k - 1, E], whose windows are contiguous (lda = E < K = k E);
-    bias and relu sit in the product's epilogue, which writes the live rows compact through a row map: y [n L, C], as Conv1dReluFn's.  The
-    word rows' keep-mask is nnr_embed_gather's for the same seed.  Backward: relu backward and the zero rows of the padded gradient in one
-    launch, the data gradient one product against the transposed, window-reversed weight, the weight gradient one TN product over the
-    overlapping rows (the bias gradient its column sums), and the word rows' gradient through the mask into the sorted scatter."""
+    """relu(Conv1d(E -> C, window k odd, 'same' padding)) over dropout(word_table[text]) as ONE product (rowconv_fwd; csrc/naml.hip): the launch
+    that gathers and drops the word rows writes them as the halo-padded image Xp [n, L + k - 1, E]; bias and relu sit in the product's
+    epilogue, which writes the live rows compact through a row map: y [n L, C], as Conv1dReluFn's.  The word rows' keep-mask is
+    nnr_embed_gather's for the same seed.  Backward: relu backward and the zero rows of the padded gradient in one launch, rowconv_bwd (the
+    bias gradient rides on the weight gradient), and the word rows' gradient through the mask into the sorted scatter."""
 
     @staticmethod
     def forward(ctx, table, text, conv, n, Lx, p, seed, need_grad):
         E = table.shape[1]
         Cn, _, k = conv.weight.shape
         Lp, dev = Lx + k - 1, table.device
-        idx = text.reshape(-1)
-        idx = (idx if idx.dtype == torch.int32 else idx.to(torch.int32)).contiguous()
+        idx = ops.ids32(text, -1)
         # the sort needs nothing but the ids: on the leaf stream, under the forward pass (the sorted scatter carries rows of <= 320 floats)
         ts = ops.TokenSort(idx, None, table.shape[0]) if need_grad and E <= 320 else None
         f32 = dict(device=dev, dtype=torch.float32)
         Xp = torch.empty((n * Lp, E), **f32)
         ops.conv1d_image_fwd(table, idx, n, Lx, k, p, seed, Xp)
         y = torch.empty((n * Lx, Cn), **f32)
-        ops.gemm(Xp, ops.conv1d_weight(conv.weight, 0), y, M=n * Lp - (k - 1), N=Cn, K=k * E, lda=E, ldb=k * E, ldc=Cn, bias=conv.bias,
-                 act=ops.ACT_RELU, c_idx=ops.conv1d_rowmap(n, Lx, k, dev))
+        rowconv_fwd(Xp, conv.weight, y, bias=conv.bias, act=ops.ACT_RELU, c_idx=ops.conv1d_rowmap(n, Lx, k, dev))
         ctx.table, ctx.conv, ctx.saved, ctx.dims = table, conv, (Xp if need_grad else None, idx, ts, y), (n, Lx, E, Cn, k, p, seed)
         return y
 
@@ -587,16 +587,7 @@ class Conv1dImageFn(torch.autograd.Function):
         f32 = dict(device=dev, dtype=torch.float32)
         dzp = torch.empty((lead + n * Lp, Cn), **f32)                 # k - 1 leading zero rows: row r of the view starts at dz row r - (k - 1)
         ops.conv1d_dz_pad(dy.contiguous(), y, n, Lx, k, dzp)
-        M = n * Lp - lead
-        gw, gb = grad_of(conv.weight), grad_of(conv.bias)
-
-        def weight_grad():
-            dP = torch.zeros((Cn, k * E), **f32)
-            ops.linear_bwd_weight(dzp[lead:lead + M], Xp.as_strided((M, k * E), (E, 1)), dP, db=gb)
-            ops.permute(dP, gw, 'c1_dw', (Cn, E, k), accumulate=True)
-        ops.leaf_deferred(dev, n * Lx, weight_grad, dzp, Xp, force=True)      # (the permute is a plain read-modify-write: one stream for both calls)
-        dXp = torch.empty((n * Lp, E), **f32)
-        ops.gemm(dzp, ops.conv1d_weight(conv.weight, 1), dXp, M=n * Lp, N=E, K=k * Cn, lda=Cn, ldb=k * Cn, ldc=E)
+        dXp = rowconv_bwd(dzp, Xp, conv.weight, n * Lx, db=grad_of(conv.bias))
         dx = torch.empty((n * Lx, E), **f32)
         ops.conv1d_image_bwd(dXp, n, Lx, k, p, seed, dx)
         if ts is not None:
@@ -622,8 +613,7 @@ class ViewPoolFn(torch.autograd.Function):
         Ra, Rb = cat_t.shape[0], sub_t.shape[0]
         dev = texts[0].device
         f32 = dict(device=dev, dtype=torch.float32)
-        cat = category.reshape(n).to(torch.int32).contiguous()
-        sub = subCategory.reshape(n).to(torch.int32).contiguous()
+        cat, sub = ops.ids32(category, n), ops.ids32(subCategory, n)
         rows = n * Vt + Ra + Rb
         stack = torch.empty((rows, Cn), **f32)                      # [text view 0 | text view 1 | category rows | subCategory rows]
         for v, t in enumerate(texts):
@@ -631,9 +621,7 @@ class ViewPoolFn(torch.autograd.Function):
         rowsA, rowsB = stack[n * Vt:n * Vt + Ra], stack[n * Vt + Ra:]
         ops.linear_fwd(cat_t, enc.category_affine.weight, enc.category_affine.bias, out=rowsA, act=ops.ACT_RELU)
         ops.linear_fwd(sub_t, enc.subCategory_affine.weight, enc.subCategory_affine.bias, out=rowsB, act=ops.ACT_RELU)
-        th = ops.linear_fwd(stack, enc.affine1.weight, enc.affine1.bias, act=ops.ACT_TANH)
-        score = torch.empty(rows, **f32)
-        ops.rowdot(th, enc.affine2.weight, score)
+        th, score = attention_fwd(enc, stack)
         alpha, out = torch.empty((n, Vt + 2), **f32), torch.empty((n, Cn), **f32)
         ops.view_pool_fwd([stack[v * n:(v + 1) * n] for v in range(Vt)], [score[v * n:(v + 1) * n] for v in range(Vt)], rowsA,
                           score[n * Vt:n * Vt + Ra], cat, rowsB, score[n * Vt + Ra:], sub, alpha, out)
@@ -649,19 +637,13 @@ class ViewPoolFn(torch.autograd.Function):
         dev = dout.device
         f32 = dict(device=dev, dtype=torch.float32)
         dout = dout.contiguous()
-        rows, A = n * Vt + Ra + Rb, th.shape[1]
+        rows = n * Vt + Ra + Rb
         a0, b0 = n * Vt, n * Vt + Ra
         dstack, dscore = torch.empty((rows, Cn), **f32), torch.empty(rows, **f32)
         sl = lambda x: [x[v * n:(v + 1) * n] for v in range(Vt)]
         ops.view_pool_bwd(dout, sl(stack), stack[a0:b0], cat, stack[b0:], sub, alpha, sl(dstack), sl(dscore), dstack[a0:b0],
                           dscore[a0:b0], dstack[b0:], dscore[b0:])
-        ops.tanh_score_bwd(th, dscore, enc.affine2.weight, grad_of(enc.affine2.weight), None, A)          # th := d(pre-activation)
-        gw, gb = grad_of(enc.affine1.weight), grad_of(enc.affine1.bias)
-        ops.leaf_deferred(dev, rows, lambda: ops.linear_bwd_weight(th, stack, gw, db=gb), th, stack)
-        if rows >= 1024 and (A & 3) == 0:
-            ops.gemm(th, ops.wt(enc.affine1.weight), dstack, M=rows, N=Cn, K=A, lda=A, ldb=A, ldc=Cn, accumulate=True)      # NT on W1^T
-        else:
-            ops.gemm(th, enc.affine1.weight, dstack, M=rows, N=Cn, K=A, lda=A, ldb=Cn, ldc=Cn, trans_b=True, accumulate=True)
+        attention_bwd(enc, stack, th, dscore, dstack)
         dz_all = ops.relu_bwd(dstack[a0:], stack[a0:])                  # both tables' rows lie back to back: one launch
         for lo, hi, table, lin in ((0, Ra, enc.category_embedding.weight, enc.category_affine),
                                    (Ra, Ra + Rb, enc.subCategory_embedding.weight, enc.subCategory_affine)):
@@ -698,7 +680,7 @@ class GruFn(torch.autograd.Function):
         B, T, D = x.shape
         H = gru.hidden_dim
         x2 = x.contiguous().view(B * T, D)
-        m8 = (mask.view(torch.uint8) if mask.dtype == torch.bool else (mask if mask.dtype == torch.uint8 else (mask != 0).view(torch.uint8))).contiguous()
+        m8 = ops.mask_u8(mask)
         w = ops.gru_pack(gru, H, D)
         f32 = dict(device=x.device, dtype=torch.float32)
         gates = ops.linear_fwd(x2, w.w_ihp, w.b_p)                                               # [B*T, NP]

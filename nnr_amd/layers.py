@@ -68,40 +68,54 @@ class GRUParams(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------ additive attention
+def attention_fwd(mod, x, dyn=None, score=True):
+    """th [rows, A] = tanh(affine1(x)) over a contiguous x [rows, F] and, with `score`, its row-dot with w2 [rows] (layers.py:167-169; without:
+    the caller's pool takes th . w2 in its own pass).  dyn: device int32, the number of LIVE rows (packed rows: the rest is undefined)."""
+    rows, F = x.shape
+    A = mod.affine1.weight.shape[0]
+    th = torch.empty((rows, A), device=x.device, dtype=torch.float32)
+    dk = dict(dyn=dyn, dyn_dim=1) if dyn is not None else {}
+    ops.gemm(x, mod.affine1.weight, th, M=rows, N=A, K=F, lda=F, ldb=F, ldc=A, bias=mod.affine1.bias, act=ops.ACT_TANH, **dk)
+    s = torch.empty(rows, device=x.device, dtype=torch.float32) if score else None
+    if score and A & 3:                  # nnr_rowdot reads a row four floats at a time: such an A as an N = 1 product
+        ops.gemm(th, mod.affine2.weight, s, M=rows, N=1, K=A, lda=A, ldb=A, ldc=1, **dk)
+    elif score:
+        ops.rowdot(th, mod.affine2.weight, s, dyn=dyn)
+    return th, s
+
+
+def attention_bwd(mod, x, th, dscore, dx, plan=None):
+    """The tail behind the pool's backward (which wrote dx and dscore): th := d(pre-activation) and dw2, the affine1 gradients as a leaf
+    (own stream, ops.leaf_deferred), dx += th . W1.  plan: the packed rows' plan (live rows: plan.total)."""
+    dyn = plan.total if plan is not None else None
+    dk = dict(dyn=dyn, dyn_dim=1) if dyn is not None else {}
+    ops.tanh_score_bwd(th, dscore, mod.affine2.weight, grad_of(mod.affine2.weight), plan, th.shape[1])
+    gw, gb = grad_of(mod.affine1.weight), grad_of(mod.affine1.bias)
+    ops.leaf_deferred(x.device, th.shape[0], lambda: ops.linear_bwd_weight(th, x, gw, db=gb, dyn=dyn), th, x)
+    ops.linear_bwd_data(th, mod.affine1.weight, out=dx, accumulate=True, **dk)
+
+
 class _AttentionFn(torch.autograd.Function):
     """layers.py:167-175 on a dense [n, L, F] feature: tanh GEMM, w2 row-dot, then the softmax pool."""
 
     @staticmethod
     def forward(ctx, feature, mod, mask):
         n, Lx, F = feature.shape
-        A = mod.affine1.weight.shape[0]
         x = feature.contiguous().view(n * Lx, F)
+        th, score = attention_fwd(mod, x)
         f32 = dict(device=x.device, dtype=torch.float32)
-        th = torch.empty((n * Lx, A), **f32)
-        score = torch.empty(n * Lx, **f32)
-        ops.gemm(x, mod.affine1.weight, th, M=n * Lx, N=A, K=F, lda=F, ldb=F, ldc=A, bias=mod.affine1.bias, act=ops.ACT_TANH)
-        ops.rowdot(th, mod.affine2.weight, score)
-        alpha = torch.empty(n * Lx, **f32)
-        out = torch.empty((n, F), **f32)
+        alpha, out = torch.empty(n * Lx, **f32), torch.empty((n, F), **f32)
         ops.pool_fwd(x=x, ldx=F, D=F, n=n, Lx=Lx, mask=mask, score=score, alpha=alpha, out=out, ldo=F)
-        ctx.mod, ctx.mask, ctx.saved = mod, mask, (x, th, alpha, n, Lx, F, A)
+        ctx.mod, ctx.mask, ctx.saved = mod, mask, (x, th, alpha, n, Lx, F)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        mod = ctx.mod
-        x, th, alpha, n, Lx, F, A = ctx.saved
+        x, th, alpha, n, Lx, F = ctx.saved
         f32 = dict(device=x.device, dtype=torch.float32)
-        dx = torch.empty((n * Lx, F), **f32)
-        ds = torch.empty(n * Lx, **f32)
+        dx, ds = torch.empty((n * Lx, F), **f32), torch.empty(n * Lx, **f32)
         ops.pool_bwd(x=x, ldx=F, D=F, n=n, Lx=Lx, mask=ctx.mask, alpha=alpha, dout=dout.contiguous(), lddo=F, dx=dx, lddx=F, dscore=ds)
-        ops.tanh_score_bwd(th, ds, mod.affine2.weight, grad_of(mod.affine2.weight), None, A)
-        gw, gb = grad_of(mod.affine1.weight), grad_of(mod.affine1.bias)
-        ops.leaf_deferred(x.device, n * Lx, lambda: ops.linear_bwd_weight(th, x, gw, db=gb), th, x)      # leaf: own stream (ops.leaf_deferred)
-        if n * Lx >= 1024 and (A & 3) == 0:
-            ops.gemm(th, ops.wt(mod.affine1.weight), dx, M=n * Lx, N=F, K=A, lda=A, ldb=A, ldc=F, accumulate=True)      # NT on W1^T
-        else:
-            ops.gemm(th, mod.affine1.weight, dx, M=n * Lx, N=F, K=A, lda=A, ldb=F, ldc=F, trans_b=True, accumulate=True)
+        attention_bwd(ctx.mod, x, th, ds, dx)
         return dx.view(n, Lx, F), None, None
 
 
@@ -193,8 +207,7 @@ class _CandAttnFn(torch.autograd.Function):
         A = w2.numel()
         x = feature.contiguous()
         q = query.contiguous().view(B * N, Qd)
-        if mask is not None:
-            mask = (mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0).contiguous()
+        mask = ops.mask_u8(mask)
         f32 = dict(device=x.device, dtype=torch.float32)
         P = ops.linear_fwd(q, wq, bq)                                                           # [B*N, A]
         Q = ops.linear_fwd(x.view(B * H, F), wf)                                                # [B*H, A]
@@ -244,9 +257,8 @@ class _PersAttnFn(torch.autograd.Function):
         A = w2.numel()
         x = feature.contiguous()
         q = query.contiguous()
-        uidx = (uidx if uidx.dtype == torch.int32 else uidx.to(torch.int32)).contiguous()
-        if mask is not None:
-            mask = (mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0).contiguous()
+        uidx = ops.ids32(uidx, -1)
+        mask = ops.mask_u8(mask)
         f32 = dict(device=x.device, dtype=torch.float32)
         P = ops.linear_fwd(q, wq, bq)                                                           # [U, A]
         Qf = ops.linear_fwd(x.view(n * Lx, F), wf)                                              # [n*L, A]

@@ -69,9 +69,16 @@ class NewsEncoder(nn.Module):
     def forward(self, title_text, title_mask, title_entity, content_text, content_mask, content_entity, category, subCategory, user_embedding):
         raise Exception('Function forward must be implemented at sub-class')
 
-
-def _i32(t):
-    return t if t.dtype == torch.int32 else t.to(torch.int32)
+    def conv_text(self, text, conv, n, Lx, p, seed, image=False):
+        """The CNN family's text front [n*L, C]: dropout(word rows, seed + 1) -> Conv1d + ReLU -> dropout_(seed + 2); the convolution as k
+        shifted GEMMs or, with `image`, as one padded-row product (functional.Conv1dImageFn)."""
+        from . import functional as Fn
+        table = self.word_embedding.weight
+        if image:
+            c = Fn.Conv1dImageFn.apply(table, text, conv, n, Lx, p, seed + 1, torch.is_grad_enabled() and table.requires_grad)
+        else:
+            c = Fn.Conv1dReluFn.apply(Fn.EmbedDropFn.apply(table, text, p, seed + 1), conv, n, Lx)
+        return Fn.DropoutFn.apply(c, p, seed + 2)
 
 
 # ================================================================================================== CNE
@@ -262,7 +269,7 @@ def _cne_fwd_pre(mod, title_text, title_mask, content_text, content_mask, catego
 
     def prepare(slot, name, ids, mask, Lx, lstm, Hlin, Mlin, satt, catt):
         parts = list(zip(ids, mask)) if union else [(ids, mask)]
-        ids2 = [_i32(i).reshape(-1, Lx).contiguous() for i, _ in parts]
+        ids2 = [ops.ids32(i, -1, Lx) for i, _ in parts]
         mask2 = [m.view(-1, Lx) for _, m in parts]      # views: the in-place mask[:,0]=1 must reach the caller's tensors
         perm = _torch_tie_perm(mask2).to(dev) if mod.tie_order == 'torch' else None
         plan = ops.SeqPlan(mask2[0], ids2[0], perm, *((mask2[1], ids2[1]) if union else ()))
@@ -374,11 +381,11 @@ def _cne_fwd_post(mod, sv, par=False):
     # feature fusion (newsEncoders.py:50-54): category + subCategory rows of both calls in ONE launch, the two calls' id tensors read
     # where they lie (round 2: torch.cat x 2 + two launches)
     if sv['union']:
-        cat0, cat1 = (_i32(x).reshape(-1).contiguous() for x in sv.pop('category'))
-        sub0, sub1 = (_i32(x).reshape(-1).contiguous() for x in sv.pop('subCategory'))
+        cat0, cat1 = (ops.ids32(x, -1) for x in sv.pop('category'))
+        sub0, sub1 = (ops.ids32(x, -1) for x in sv.pop('subCategory'))
     else:
-        cat0, cat1 = _i32(sv.pop('category')).reshape(n).contiguous(), None
-        sub0, sub1 = _i32(sv.pop('subCategory')).reshape(n).contiguous(), None
+        cat0, cat1 = ops.ids32(sv.pop('category'), n), None
+        sub0, sub1 = ops.ids32(sv.pop('subCategory'), n), None
     cd, sd = mod.category_embedding.weight.shape[1], mod.subCategory_embedding.weight.shape[1]
     ops.fusion_rows_fwd(mod.category_embedding.weight, mod.subCategory_embedding.weight, cat0, sub0, cat1, sub1, rep[:, 2 * H2:], D, p,
                         seed + _SITE['cat'], seed + _SITE['sub'])
@@ -609,7 +616,7 @@ def cne_history_dedup(mod, title_text, title_mask, content_text, content_mask, c
     tm, cm = title_mask.view(n, T), content_mask.view(n, Cx)
     tm[:, 0] = 1                                        # in place on the caller's tensors, as every CNE call does (newsEncoders.py:108-109)
     cm[:, 0] = 1
-    tt, ct = _i32(title_text).reshape(n, T), _i32(content_text).reshape(n, Cx)
+    tt, ct = ops.ids32(title_text, n, T), ops.ids32(content_text, n, Cx)
     tlen, clen = tm.sum(dim=1), cm.sum(dim=1)
     order_t = torch.sort(tlen, descending=True, stable=True)[1]
     order_c = torch.sort(clen, descending=True, stable=True)[1]
@@ -617,7 +624,7 @@ def cne_history_dedup(mod, title_text, title_mask, content_text, content_mask, c
     ar = torch.arange(n, device=dev)
     rank_t[order_t], rank_c[order_c] = ar, ar
     pc_t, pt_c = order_c[rank_t], order_t[rank_c]       # partner sequences under the call's own rank pairing
-    cat, sub = _i32(category).reshape(n), _i32(subCategory).reshape(n)
+    cat, sub = ops.ids32(category, n), ops.ids32(subCategory, n)
     padlike = (tlen == 1) & (tt[:, 0] == 0) & (clen == 1) & (ct[:, 0] == 0) & (cat == 0) & (sub == 0)
     drop = padlike & padlike[pc_t] & padlike[pt_c]
     nd = int(drop.sum())
@@ -736,7 +743,7 @@ class MHSA(NewsEncoder):
         mask = title_mask.view(n, Lx)
         if mhsa_packed(self, title_text):
             # only the token rows that can reach the result (functional.MhsaPack): ~36 % of n * L at MIND title lengths
-            pack = Fn.MhsaPack(mask, _i32(title_text).reshape(n, Lx))
+            pack = Fn.MhsaPack(mask, ops.ids32(title_text, n, Lx))
             w = Fn.PackedEmbedDropFn.apply(self.word_embedding.weight, pack, p, seed + 1)                   # [cap, E], live rows only
             qkv = Fn.QKVFn.apply(w, self.multiheadAttention, pack.plan.total)
             c = Fn.PackedMhsaCoreFn.apply(qkv, mask, pack, self.head_num, self.head_dim, p, seed + 2)       # [cap, h*d], dropout fused
@@ -773,9 +780,7 @@ class CNN(NewsEncoder):
         p = self.dropout_rate if self.training else 0.0
         seed = self._next_seed()
         mask = title_mask.view(n, Lx)
-        w = Fn.EmbedDropFn.apply(self.word_embedding.weight, title_text, p, seed + 1)
-        c = Fn.Conv1dReluFn.apply(w, self.conv.conv, n, Lx)                                                # [n*L, C]
-        c = Fn.DropoutFn.apply(c, p, seed + 2)
+        c = self.conv_text(title_text, self.conv.conv, n, Lx, p, seed)                                     # [n*L, C]
         rep = self.attention(c.view(n, Lx, self.cnn_kernel_num), mask)
         return Fn.FuseFn.apply(rep, self, category, subCategory, p, seed).view(B, N, self.news_embedding_dim)
 
@@ -817,9 +822,7 @@ class PNE(NewsEncoder):
         p = self.dropout_rate if self.training else 0.0
         seed = self._next_seed()
         mask = title_mask.view(n, Lx)
-        w = Fn.EmbedDropFn.apply(self.word_embedding.weight, title_text, p, seed + 1)
-        c = Fn.Conv1dReluFn.apply(w, self.conv.conv, n, Lx)                                                # [n*L, C]
-        c = Fn.DropoutFn.apply(c, p, seed + 2)
+        c = self.conv_text(title_text, self.conv.conv, n, Lx, p, seed)                                     # [n*L, C]
         q_w = Fn.LinearFn.apply(user_embedding, self.dense.weight, self.dense.bias, ops.ACT_RELU, 0.0, 0)    # [B, personalized_embedding_dim]
         uidx = torch.arange(n, device=title_text.device, dtype=torch.int32) % B                            # the `.repeat` pairing: row r <- user r % B
         rep = personalized_attention(self.personalizedAttention, c.view(n, Lx, self.cnn_kernel_num), q_w, uidx, mask)
@@ -874,16 +877,8 @@ class _NAMLSingle(NewsEncoder):
 
     def text_view(self, text, n, p, seed):
         """One text stream's view [n, C]: the stages in front of the multi-view attention (a second stream is a second call of this)."""
-        from . import functional as Fn
-        Lx = self.max_length
-        table = self.word_embedding.weight
-        if CONV1D_IMAGE:
-            c = Fn.Conv1dImageFn.apply(table, text, self.text_conv().conv, n, Lx, p, seed + 1, torch.is_grad_enabled() and table.requires_grad)
-        else:
-            w = Fn.EmbedDropFn.apply(table, text, p, seed + 1)
-            c = Fn.Conv1dReluFn.apply(w, self.text_conv().conv, n, Lx)                                      # [n*L, C]
-        c = Fn.DropoutFn.apply(c, p, seed + 2)
-        return self.text_attention()(c.view(n, Lx, self.cnn_kernel_num))                                   # no mask
+        c = self.conv_text(text, self.text_conv().conv, n, self.max_length, p, seed, image=CONV1D_IMAGE)
+        return self.text_attention()(c.view(n, self.max_length, self.cnn_kernel_num))                      # no mask
 
     def forward(self, title_text, title_mask, title_entity, content_text, content_mask, content_entity, category, subCategory, user_embedding):
         from . import functional as Fn
@@ -916,7 +911,7 @@ def _bow_streams(title_text, title_mask, content_text, content_mask):
     B, N, La = title_text.shape
     Lb = content_text.shape[2]
     n = B * N
-    return (_i32(title_text).reshape(n, La).contiguous(), title_mask.view(n, La), _i32(content_text).reshape(n, Lb).contiguous(),
+    return (ops.ids32(title_text, n, La), title_mask.view(n, La), ops.ids32(content_text, n, Lb),
             content_mask.view(n, Lb))
 
 
@@ -994,7 +989,7 @@ class Inception(NewsEncoder):
         n = B * N
         table = self.word_embedding.weight
         tt, tm, ct, cm = _bow_streams(title_text, title_mask, content_text, content_mask)
-        cat, sub = _i32(category).reshape(n).contiguous(), _i32(subCategory).reshape(n).contiguous()
+        cat, sub = ops.ids32(category, n), ops.ids32(subCategory, n)
         rep = Fn.InceptionFn.apply(table, self, tt, tm, ct, cm, cat, sub, torch.is_grad_enabled() and table.requires_grad)
         return rep.view(B, N, self.news_embedding_dim)
 
@@ -1044,7 +1039,7 @@ class KCNN(NewsEncoder):
         p = self.dropout_rate if self.training else 0.0
         seed = self._next_seed()
         table = self.word_embedding.weight
-        text, entity = _i32(title_text).reshape(n * Lx).contiguous(), _i32(title_entity).reshape(n * Lx).contiguous()
+        text, entity = ops.ids32(title_text, n * Lx), ops.ids32(title_entity, n * Lx)
         rep = Fn.KcnnFn.apply(table, self, text, entity, n, Lx, torch.is_grad_enabled() and table.requires_grad)        # [n, C]
         return Fn.FuseFn.apply(rep, self, category, subCategory, p, seed).view(B, N, self.news_embedding_dim)
 
@@ -1089,7 +1084,7 @@ class HDC(NewsEncoder):
         B, N = title_text.shape[:2]
         n, Lx, S = B * N, self.max_title_length, self.HDC_sequence_length
         table = self.word_embedding.weight
-        text = _i32(title_text).reshape(n * Lx).contiguous()
-        cat, sub = _i32(category).reshape(n).contiguous(), _i32(subCategory).reshape(n).contiguous()
+        text = ops.ids32(title_text, n * Lx)
+        cat, sub = ops.ids32(category, n), ops.ids32(subCategory, n)
         d0, dL = Fn.HdcFn.apply(table, self, text, cat, sub, n, Lx, torch.is_grad_enabled() and table.requires_grad)
         return d0.view(B, N, S, self.word_embedding_dim), dL.view(3, B, N, S, self.HDC_filter_num)

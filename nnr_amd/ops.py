@@ -1223,6 +1223,16 @@ def _u8(mask):
     return None if mask is None else (mask.view(torch.uint8) if mask.dtype == torch.bool else mask)
 
 
+def mask_u8(mask):
+    """`mask` as the contiguous uint8 tensor the kernels read: a bool or uint8 mask is viewed, any other dtype compared with 0; None stays."""
+    return None if mask is None else _u8(mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0).contiguous()
+
+
+def ids32(ids, *shape):
+    """`ids` as a contiguous int32 tensor of `shape` (int32 already: no conversion; contiguous already: no copy)."""
+    return (ids if ids.dtype == torch.int32 else ids.to(torch.int32)).reshape(shape).contiguous()
+
+
 def cand_attn_fwd(P, Q, w2, feat, mask, B, N, H, A, D, act, alpha, out):
     """Candidate-aware additive attention (csrc/cand_attn.hip): P [B*N, A], Q [B*H, A], w2 [A], feat [B, H, D], mask [B, H] bool / uint8 or
     None -> alpha [B, N, H], out [B, N, D]."""
@@ -1649,17 +1659,14 @@ def _pad4(n):
 # kind -> dims -> (extents n0..n3, source strides, destination strides, source offset, destination shape), strides and offset in floats, the
 # destination's unit-stride axis last.  Source: the weight as torch holds it (or, for the *_dw kinds, the gradient of its permuted form).
 LAYOUTS = {
-    # Conv2d weight W [C, E, w, 3]: P[c][dt][j][e] | Q[j][e][k][c] = W[c][e][w-1-k][j] | W.grad[c][e][dt][j] += dP[c][dt][j][e]
-    'kcnn_p': lambda C_, E, w: ((C_, w, 3, E), (E * w * 3, 3, 1, w * 3), (w * 3 * E, 3 * E, E, 1), 0, (C_, 3 * w * E)),
-    'kcnn_q': lambda C_, E, w: ((3, E, w, C_), (1, w * 3, -3, E * w * 3), (E * w * C_, w * C_, C_, 1), (w - 1) * 3, (3 * E, w * C_)),
-    'kcnn_dw': lambda C_, E, w: ((C_, E, w, 3), (w * 3 * E, 1, 3 * E, E), (E * w * 3, w * 3, 3, 1), 0, (C_, E, w, 3)),
+    # Conv weight W [C, E, w, J] of the padded-row convolution (KCNN's Conv2d, which the kinds are named after: J = 3; Conv1d [C, E, w]: J = 1):
+    # P[c][dt][j][e] | Q[j][e][k][c] = W[c][e][w-1-k][j] | W.grad[c][e][dt][j] += dP[c][dt][j][e]
+    'kcnn_p': lambda C_, E, w, J=3: ((C_, w, J, E), (E * w * J, J, 1, w * J), (w * J * E, J * E, E, 1), 0, (C_, J * w * E)),
+    'kcnn_q': lambda C_, E, w, J=3: ((J, E, w, C_), (1, w * J, -J, E * w * J), (E * w * C_, w * C_, C_, 1), (w - 1) * J, (J * E, w * C_)),
+    'kcnn_dw': lambda C_, E, w, J=3: ((C_, E, w, J), (w * J * E, 1, J * E, E), (E * w * J, w * J, J, 1), 0, (C_, E, w, J)),
     # Conv1d weight W [F, C, w]: P[k][f][c] in rows of ldp >= C floats | W.grad[f][c][k] += dP[k][f][c]
     'hdc_p': lambda F, C_, w, ldp: ((1, w, F, C_), (0, 1, C_ * w, w), (0, F * ldp, ldp, 1), 0, (w, F, ldp)),
     'hdc_dw': lambda F, C_, w, ldp: ((1, F, C_, w), (0, ldp, 1, F * ldp), (0, C_ * w, w, 1), 0, (F, C_, w)),
-    # Conv1d weight W [C, E, k] of the padded-row convolution: P[c][dt][e] | Q[e][j][c] = W[c][e][k-1-j] | W.grad[c][e][dt] += dP[c][dt][e]
-    'c1_p': lambda C_, E, k: ((1, C_, k, E), (0, E * k, 1, k), (0, k * E, E, 1), 0, (C_, k * E)),
-    'c1_q': lambda C_, E, k: ((1, E, k, C_), (0, k, -1, E * k), (0, k * C_, C_, 1), k - 1, (E, k * C_)),
-    'c1_dw': lambda C_, E, k: ((1, C_, E, k), (0, k * E, 1, E), (0, E * k, k, 1), 0, (C_, E, k)),
     # Conv3d weight W [Cout, Cin, K^3]: [ci][t][f] in rows of Cout rounded up to 4 | [f][t][ci] in rows of Cin rounded up to 4
     'c3_p': lambda Co, Ci, K: ((1, Ci, K ** 3, Co), (0, K ** 3, 1, Ci * K ** 3), (0, K ** 3 * _pad4(Co), _pad4(Co), 1), 0, (Ci, K ** 3, _pad4(Co))),
     'c3_q': lambda Co, Ci, K: ((1, Co, K ** 3, Ci), (0, Ci * K ** 3, 1, K ** 3), (0, K ** 3 * _pad4(Ci), _pad4(Ci), 1), 0, (Co, K ** 3, _pad4(Ci))),
@@ -1719,14 +1726,20 @@ def window_max_bwd(g, arg, n, C, Lx, w, lead, dz, db):
         L.check(L.lib().nnr_window_max_bwd(_p(g), _p(arg), n, C, Lx, w, lead, _p(dz), _p(db), _p(ws), _s()), 'nnr_window_max_bwd', KCNN_UNSUPPORTED)
 
 
-def kcnn_weight(weight, mode):
-    """P [C, 3 w E] (mode 0) or Q [3 E, w C] (mode 1) of the Conv2d weight [C, E, w, 3]: the B operand of the convolution product or of its
-    data gradient, an entry of the derived-weight cache (permuted once per parameter version, by the first of the two encoder calls that
-    asks; its bf16x3 images follow it)."""
-    C_, E, w, _ = weight.shape
-    if w > 8 or E > 1024:
-        raise L.NnrHipError('kcnn_weight: %s' % KCNN_UNSUPPORTED)
-    return _permuted_weight('kcnn_q' if mode else 'kcnn_p', weight, (C_, E, w))
+def rowconv_dims(weight):
+    return tuple(weight.shape) if weight.dim() == 4 else tuple(weight.shape) + (1,)          # (C, E, w, J); a Conv1d weight [C, E, w]: J = 1
+
+
+def rowconv_weight(weight, mode):
+    """P [C, J w E] (mode 0) or Q [J E, w C] (mode 1) of the Conv2d weight [C, E, w, J] or the Conv1d weight [C, E, w] (J = 1): the B operand
+    of the padded-row convolution product or of its data gradient, an entry of the derived-weight cache (permuted once per parameter
+    version, by the first of the two encoder calls that asks; its bf16x3 images follow it)."""
+    _, E, w, _ = dims = rowconv_dims(weight)
+    if weight.dim() == 4 and (w > 8 or E > 1024):
+        raise L.NnrHipError('rowconv_weight: %s' % KCNN_UNSUPPORTED)
+    if weight.dim() == 3 and (w > 8 or w % 2 == 0):
+        raise L.NnrHipError('rowconv_weight: %s' % CONV1D_UNSUPPORTED)
+    return _permuted_weight('kcnn_q' if mode else 'kcnn_p', weight, dims)
 
 
 # ---------------------------------------------------------------------------------------------- NAML view attention (csrc/naml.hip)
@@ -1780,15 +1793,6 @@ def conv1d_image_bwd(dXp, n, Lx, k, p, seed, dx):
     E = dx.shape[1]
     with _hbm_span('conv1d_image_bwd', 8.0 * E, n * Lx):
         L.check(L.lib().nnr_conv1d_image_bwd(_p(dXp), n, Lx, E, k, p, seed, _p(dx), _s()), 'nnr_conv1d_image_bwd', CONV1D_UNSUPPORTED)
-
-
-def conv1d_weight(weight, mode):
-    """P [C, k E] (mode 0) or Q [E, k C] (mode 1) of the Conv1d weight [C, E, k]: the B operand of the padded-row convolution product or of
-    its data gradient, an entry of the derived-weight cache (as kcnn_weight)."""
-    C_, E, k = weight.shape
-    if k > 8 or k % 2 == 0:
-        raise L.NnrHipError('conv1d_weight: %s' % CONV1D_UNSUPPORTED)
-    return _permuted_weight('c1_q' if mode else 'c1_p', weight, (C_, E, k))
 
 
 def conv1d_rowmap(n, Lx, k, dev):

@@ -85,7 +85,7 @@ _ID_INPUTS = (1, 2, 3, 6, 13, 14, 15, 18)       # category / subCategory / title
 
 def recordable(batch):
     """May a launch tape be recorded from a step on `batch`?  Every tensor must be used where it lies: a non-contiguous tensor or an
-    int64 id tensor would be converted by a torch op outside the library (news_encoders._i32 / .contiguous()) into a temporary the
+    int64 id tensor would be converted by a torch op outside the library (ops.ids32) into a temporary the
     tape knows nothing about.  Such batches (not what the reference's DataLoader or DeviceCorpus produce: SURVEY.md appendix C) run
     the native step call by call."""
     return (all(t.is_cuda and t.is_contiguous() for t in batch) and all(batch[i].dtype == torch.int32 for i in _ID_INPUTS)

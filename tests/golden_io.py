@@ -17,6 +17,31 @@ ALL_CASES = ['tiny_CNE_SUE', 'tiny_CNE_SUE_scaled', 'tiny_MHSA_MHSA', 'tiny_CNN_
              'tiny_CNE_SUE_ln_stable', 'tiny_CNE_SUE_ln_nores_stable', 'tiny_CNE_SUE_h48_stable', 'tiny_CNE_SUE_h112_stable']
 
 
+def build_model(case, mode=None, **over):
+    """(model, cfg): the package's Model on the GPU with the case's parameters, on a copy of its config with `over` applied; mode 'train' /
+    'eval' (default: the mode the reference ran the case in)."""
+    from nnr_amd.model import Model
+    cfg = SimpleNamespace(**vars(case.config))
+    vars(cfg).update(over)
+    model = Model(cfg, case.word_table())
+    case.load_into(model)
+    model = model.cuda()
+    return (model.train() if (mode or case.meta['mode']) == 'train' else model.eval()), cfg
+
+
+def eval_fixture(tag):
+    """(z, model): the arrays of golden/eval_<tag>.npz and, on the CPU, the Model of its config (cfg_keys / cfg_vals / cfg_types, tie_order)
+    holding the reference's own state_dict, loaded strictly (names and shapes unchanged)."""
+    from nnr_amd.model import Model
+    z = np.load(os.path.join(GOLDEN_DIR, 'eval_%s.npz' % tag))
+    cast = {'int': int, 'float': float, 'str': str, 'bool': lambda v: v == 'True'}
+    cfg = SimpleNamespace(**{k: cast[t](v) for k, v, t in zip(z['cfg_keys'], z['cfg_vals'], z['cfg_types'])})
+    cfg.tie_order = str(z['tie_order'])
+    model = Model(cfg, torch.zeros(cfg.vocabulary_size, cfg.word_embedding_dim))
+    model.load_state_dict({k[len('state/'):]: torch.from_numpy(z[k].copy()) for k in z.files if k.startswith('state/')}, strict=True)
+    return z, model
+
+
 def _parse(v):
     if v in ('True', 'False'):
         return v == 'True'

@@ -2,15 +2,13 @@
 the reference's own float64 run stored in the fixtures, the fixtures' margin condition, and the public surface -- flags, dispatch, the
 reference's assertions, refusals, parameter names and shapes, and the paths this pair does not take."""
 import functools
-import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
 import fim_ref
-from golden_io import GoldenCase, GOLDEN_DIR
+from golden_io import GoldenCase, eval_fixture
 from nnr_amd.synth import BATCH_FIELDS
 
 TINY = ['tiny_HDC_FIM', 'tiny_HDC_FIM_p3']
@@ -161,13 +159,7 @@ def test_state_dict_is_the_references():
     F, S, E = case.config.HDC_filter_num, case.config.max_title_length + 2, case.config.word_embedding_dim
     assert names['news_encoder.layer_norm2.weight'] == (F, S) and names['news_encoder.dilated_conv1.weight'] == (F, E, 3)
     assert names['news_encoder.subCategory_embedding.weight'][1] == E and names['user_encoder.conv_3D_a.weight'] == (3, 4, 3, 3, 3)
-    z = np.load(os.path.join(GOLDEN_DIR, 'eval_tiny_HDC_FIM.npz'))
-    cast = {'int': int, 'float': float, 'str': str, 'bool': lambda v: v == 'True'}
-    cfg = SimpleNamespace(**{k: cast[t](v) for k, v, t in zip(z['cfg_keys'], z['cfg_vals'], z['cfg_types'])})
-    ref_state = {k[len('state/'):]: torch.from_numpy(z[k].copy()) for k in z.files if k.startswith('state/')}
-    m = _model(cfg)
-    assert sorted(m.state_dict()) == sorted(ref_state)
-    m.load_state_dict(ref_state)                                     # strict: unchanged names and shapes
+    eval_fixture('tiny_HDC_FIM')                                      # strict: unchanged names and shapes
 
 
 def test_paths_not_taken():

@@ -5,14 +5,12 @@ Bars.  Op tests: for each op and shape the same formula is evaluated in fp32 by 
 tests/bow_ref.py (pinned to the reference by tests/test_bow_host.py); the kernel's bar is 4 x that error (the factor covers another
 summation order), never below 1e-6 x the expected tensor's max magnitude.  Every measured value is printed (profiles/bow_summary.md keeps
 them).  Model tests: the bars of tests/test_hip_npa_gpu.py's model test, unchanged."""
-import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from golden_io import GoldenCase, GOLDEN_DIR
+from golden_io import GoldenCase, build_model, eval_fixture
 import bow_ref
 from bow_ref import f64
 
@@ -267,18 +265,6 @@ def test_linear_fn_none_and_relu_are_the_same_gemm_call_as_before(act):
 
 
 # ------------------------------------------------------------------------------------------------ the model
-def _build(case, **over):
-    from nnr_amd.model import Model
-    cfg = SimpleNamespace(**vars(case.config))
-    for k, v in over.items():
-        setattr(cfg, k, v)
-    model = Model(cfg, case.word_table())
-    case.load_into(model)
-    model = model.cuda()
-    model.train() if case.meta['mode'] == 'train' else model.eval()
-    return model, cfg
-
-
 def _loss(model, logits):
     from nnr_amd.model import negative_log_softmax
     loss = negative_log_softmax(logits)
@@ -292,7 +278,7 @@ def test_model_matches_reference_golden(tag):
     """The body of tests/test_hip_npa_gpu.py::test_model_matches_reference_golden with the trainer's auxiliary term, bars unchanged."""
     from nnr_amd.trainer import Trainer
     case = GoldenCase(tag)
-    model, cfg = _build(case)
+    model, cfg = build_model(case)
     trainer = Trainer(model, cfg)
     steps = int(case.meta['adam_steps'])
     rec = {}
@@ -382,7 +368,7 @@ def test_trainer_step_reproduces_the_reference_losses(tag):
     """Trainer.train_step itself (its own zero_grad, auxiliary term, clip and Adam): the loss of each of the three steps is the reference's."""
     from nnr_amd.trainer import Trainer
     case = GoldenCase(tag)
-    model, cfg = _build(case)
+    model, cfg = build_model(case)
     trainer = Trainer(model, cfg)
     for s in range(int(case.meta['adam_steps'])):
         _, loss = trainer.train_step(case.batch('cuda'))
@@ -400,7 +386,7 @@ def test_the_history_call_wins_on_the_side_stream_branch_too(tag):
     runs = []
     old = ops.LEAF_MIN_ROWS
     for side in (False, True):
-        model, cfg = _build(case)
+        model, cfg = build_model(case)
         ops.LEAF_MIN_ROWS = 1 if side else 1 << 40
         try:
             batch = case.batch('cuda')
@@ -424,7 +410,7 @@ def test_the_history_call_wins_on_the_side_stream_branch_too(tag):
 @pytest.mark.parametrize('tag', TINY)
 def test_plugin_calls_equal_model_forward(tag):
     case = GoldenCase(tag)
-    model, cfg = _build(case)
+    model, cfg = build_model(case)
     logits = model(*case.batch('cuda')).detach()
     (uid, ucat, usub, utt, utm, ute, uct, ucm, uce, uhm, ug, ucmask, ucidx, ncat, nsub, ntt, ntm, nte, nct, ncm, nce) = case.batch('cuda')
     cand = model.news_encoder(ntt, ntm, nte, nct, ncm, nce, ncat, nsub, None)
@@ -446,13 +432,7 @@ def test_plugin_calls_equal_model_forward(tag):
 def test_compute_scores_and_metrics_match_reference(tag):
     """evaluate.py with its news cache on (both encoders are batch-independent): every distinct news encoded once."""
     from nnr_amd import evaluate as E
-    from nnr_amd.model import Model
-    z = np.load(os.path.join(GOLDEN_DIR, 'eval_%s.npz' % tag))
-    cast = {'int': int, 'float': float, 'str': str, 'bool': lambda v: v == 'True'}
-    cfg = SimpleNamespace(**{k: cast[t](v) for k, v, t in zip(z['cfg_keys'], z['cfg_vals'], z['cfg_types'])})
-    cfg.tie_order = str(z['tie_order'])
-    model = Model(cfg, torch.zeros(cfg.vocabulary_size, cfg.word_embedding_dim))
-    model.load_state_dict({k[len('state/'):]: torch.from_numpy(z[k].copy()) for k in z.files if k.startswith('state/')})
+    z, model = eval_fixture(tag)
     model = model.cuda().train()
     assert E.news_reps_cacheable(model)
     dc = E.dev_corpus({k: z[k] for k in z.files}, 'cuda', int(z['category_num']))
@@ -479,7 +459,7 @@ def test_dae_with_dropout_on_matches_the_restatement_fed_the_kernels_masks():
     from nnr_amd import ops
     case = GoldenCase('tiny_DAE_CATT')
     p = 0.2
-    model, cfg = _build(case, dropout_rate=p)
+    model, cfg = build_model(case, dropout_rate=p)
     ne = model.news_encoder
     assert ne.training and ne.dropout_rate == p
     (uid, ucat, usub, utt, utm, ute, uct, ucm, uce, uhm, ug, ucmask, ucidx, ncat, nsub, ntt, ntm, nte, nct, ncm, nce) = case.batch('cuda')

@@ -3,14 +3,13 @@ restatement of the reference's formulation (tests/cand_attn_ref.py, pinned to th
 reproducibility, and the model / plugin / layer / evaluation / dropout-on paths against golden vectors captured from the reference's
 own code (tests/golden/*CATT*.npz, layer_cand_attn.npz).  Bars as in tests/test_hip_model_gpu.py and tests/test_hip_eval_gpu.py."""
 import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
 from cand_attn_ref import pq_form, catt_user_rep, f64
-from golden_io import GoldenCase, GOLDEN_DIR
+from golden_io import GoldenCase, GOLDEN_DIR, build_model, eval_fixture
 
 pytestmark = pytest.mark.gpu
 
@@ -120,23 +119,13 @@ def test_kernels_are_bit_reproducible():
         assert torch.equal(a[k], b[k]), k
 
 
-def _build(case):
-    from nnr_amd.model import Model
-    cfg = case.config
-    model = Model(cfg, case.word_table())
-    case.load_into(model)
-    model = model.cuda()
-    model.train() if case.meta['mode'] == 'train' else model.eval()
-    return model, cfg
-
-
 @pytest.mark.parametrize('tag', CATT_CASES)
 def test_model_matches_reference_golden(tag):
     """The body of tests/test_hip_model_gpu.py::test_model_matches_reference_golden, bars unchanged."""
     from nnr_amd.trainer import Trainer
     from nnr_amd.model import negative_log_softmax
     case = GoldenCase(tag)
-    model, cfg = _build(case)
+    model, cfg = build_model(case)
     trainer = Trainer(model, cfg)
     steps = int(case.meta['adam_steps'])
     rec = {}
@@ -218,7 +207,7 @@ def test_model_matches_reference_golden(tag):
 @pytest.mark.parametrize('tag', ['tiny_CNE_CATT_stable', 'full_CNE_CATT_g1p0_stable'])
 def test_plugin_calls_equal_lockstep_path(tag):
     case = GoldenCase(tag)
-    model, cfg = _build(case)
+    model, cfg = build_model(case)
     b = case.batch('cuda')
     logits = model(*b).detach()
     b = case.batch('cuda')
@@ -258,13 +247,7 @@ def test_layers_match_the_reference(kind, mtag):
 
 
 def _eval_model(tag):
-    from nnr_amd.model import Model
-    z = np.load(os.path.join(GOLDEN_DIR, 'eval_%s.npz' % tag))
-    cast = {'int': int, 'float': float, 'str': str, 'bool': lambda v: v == 'True'}
-    cfg = SimpleNamespace(**{k: cast[t](v) for k, v, t in zip(z['cfg_keys'], z['cfg_vals'], z['cfg_types'])})
-    cfg.tie_order = str(z['tie_order'])
-    model = Model(cfg, torch.zeros(cfg.vocabulary_size, cfg.word_embedding_dim))
-    model.load_state_dict({k[len('state/'):]: torch.from_numpy(z[k].copy()) for k in z.files if k.startswith('state/')})
+    z, model = eval_fixture(tag)
     return z, model.cuda().train()
 
 

@@ -2,11 +2,12 @@
 util.compute_scores / evaluate.py produced (tests/golden/eval_*.npz).  Scores: fp32 within 1e-4 (north-star bar; 2e-5 expected);
 ranks: exact; metrics: float64 within 1e-12."""
 import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
+
+from golden_io import eval_fixture
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
@@ -38,14 +39,7 @@ def test_rank_metrics_ties_and_single_class():
 @pytest.mark.parametrize('graph', ['build', 'table'])
 def test_compute_scores_and_metrics_match_reference(tag, graph):
     from nnr_amd.evaluate import dev_corpus, compute_scores, rank_metrics
-    from nnr_amd.model import Model
-    z = np.load(os.path.join(GOLD, 'eval_%s.npz' % tag))
-    cast = {'int': int, 'float': float, 'str': str, 'bool': lambda v: v == 'True'}
-    cfg = SimpleNamespace(**{k: cast[t](v) for k, v, t in zip(z['cfg_keys'], z['cfg_vals'], z['cfg_types'])})
-    cfg.tie_order = str(z['tie_order'])
-    model = Model(cfg, torch.zeros(cfg.vocabulary_size, cfg.word_embedding_dim))
-    state = {k[len('state/'):]: torch.from_numpy(z[k].copy()) for k in z.files if k.startswith('state/')}
-    model.load_state_dict(state)                                                  # the reference's own state_dict, names unchanged
+    z, model = eval_fixture(tag)
     model = model.cuda()
     model.train()                                                                 # compute_scores must switch to eval itself (dropout 0.2)
     dc = dev_corpus({k: z[k] for k in z.files}, 'cuda', int(z['category_num']), graph=graph)
@@ -75,13 +69,7 @@ def test_cached_news_representations_give_the_reference_scores(tag):
     by id.  Same scores as the reference's per-sample util.compute_scores (goldens) and as this package's own per-sample form;
     the encoder processes several times fewer news rows.  CNE must refuse (rank-pairing quirk)."""
     from nnr_amd import evaluate as E
-    from nnr_amd.model import Model
-    z = np.load(os.path.join(GOLD, 'eval_%s.npz' % tag))
-    cast = {'int': int, 'float': float, 'str': str, 'bool': lambda v: v == 'True'}
-    cfg = SimpleNamespace(**{k: cast[t](v) for k, v, t in zip(z['cfg_keys'], z['cfg_vals'], z['cfg_types'])})
-    cfg.tie_order = str(z['tie_order'])
-    model = Model(cfg, torch.zeros(cfg.vocabulary_size, cfg.word_embedding_dim))
-    model.load_state_dict({k[len('state/'):]: torch.from_numpy(z[k].copy()) for k in z.files if k.startswith('state/')})
+    z, model = eval_fixture(tag)
     model = model.cuda().train()
     dc = E.dev_corpus({k: z[k] for k in z.files}, 'cuda', int(z['category_num']))
     assert E.news_reps_cacheable(model)
@@ -99,13 +87,7 @@ def test_cne_pad_slot_dedup_gives_the_reference_scores():
     """f-3, exact part for CNE: PAD history slots gated only by PAD-like partners are not encoded (one representative is); the scores
     are the reference's util.compute_scores goldens and equal the full per-sample form."""
     from nnr_amd import evaluate as E
-    from nnr_amd.model import Model
-    z = np.load(os.path.join(GOLD, 'eval_tiny_CNE_SUE_stable.npz'))
-    cast = {'int': int, 'float': float, 'str': str, 'bool': lambda v: v == 'True'}
-    cfg = SimpleNamespace(**{k: cast[t](v) for k, v, t in zip(z['cfg_keys'], z['cfg_vals'], z['cfg_types'])})
-    cfg.tie_order = str(z['tie_order'])
-    model = Model(cfg, torch.zeros(cfg.vocabulary_size, cfg.word_embedding_dim))
-    model.load_state_dict({k[len('state/'):]: torch.from_numpy(z[k].copy()) for k in z.files if k.startswith('state/')})
+    z, model = eval_fixture('tiny_CNE_SUE_stable')
     model = model.cuda().train()
     dc = E.dev_corpus({k: z[k] for k in z.files}, 'cuda', int(z['category_num']))
     dedup = E.compute_scores(model, dc, batch_size=8)

@@ -5,8 +5,6 @@ Pooled convolution, the active-set method: the forward argmax is checked first -
 of the float64 maximum of its cell, M = 20 x the deviation of torch's own fp32 convolution from float64 on the same data, relative to the
 largest absolute convolution output --, then the float64 backward pass runs WITH the kernel's indices and must agree."""
 import functools
-import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -15,7 +13,7 @@ import torch.nn.functional as F
 
 import fim_ref
 from fim_ref import t64
-from golden_io import GoldenCase, GOLDEN_DIR
+from golden_io import GoldenCase, build_model, eval_fixture
 from test_fim_host import restated, fixture_margin, TINY, FULL
 
 pytestmark = pytest.mark.gpu
@@ -333,14 +331,6 @@ CANCELLING = ('user_encoder.conv_3D_a.bias', 'user_encoder.conv_3D_b.bias')
 ZERO_GRADIENT = ('fc.bias', 'user_encoder.conv_3D_b.bias')     # tensors with an element whose gradient is zero on paper
 
 
-def _build(case):
-    from nnr_amd.model import Model
-    cfg = SimpleNamespace(**vars(case.config))
-    model = Model(cfg, case.word_table())
-    case.load_into(model)
-    return model.cuda().train(), cfg
-
-
 def _position_major(rep):
     """(d0 [B, N, S, E], dL [3, B, N, S, F]) -> the reference's ([B, N, E, S], [B, N, 3, F, S])."""
     d0, dL = rep
@@ -359,7 +349,7 @@ def test_model_matches_reference_golden(tag, bx3):
     before = ops.BX3[0]
     ops.BX3[0] = bx3
     try:
-        model, cfg = _build(case)
+        model, cfg = build_model(case, 'train')
         trainer = Trainer(model, cfg)
         reps = []
         model.news_encoder.register_forward_hook(lambda m, i, o: reps.append(_position_major(o)))
@@ -416,7 +406,7 @@ def test_model_argmax_is_within_the_fixture_margin(tag):
     from nnr_amd import ops
     case, st, out = restated(tag)
     M, _ = fixture_margin(case)
-    model, cfg = _build(case)
+    model, cfg = build_model(case, 'train')
     ue = model.user_encoder
     pm = lambda d0, dL: (d0.detach().permute(0, 1, 3, 2).float().contiguous().cuda(), dL.detach().permute(2, 0, 1, 4, 3).float().contiguous().cuda())
     cand, hist = pm(out['cand_d0'], out['cand_dL']), pm(out['hist_d0'], out['hist_dL'])
@@ -452,7 +442,7 @@ def test_model_at_the_default_shapes(bx3):
     before = ops.BX3[0]
     ops.BX3[0] = bx3
     try:
-        model, cfg = _build(case)
+        model, cfg = build_model(case, 'train')
         logits = model(*case.batch('cuda'))
         loss = negative_log_softmax(logits)
         loss.backward()
@@ -478,7 +468,7 @@ def test_user_encoder_never_holds_a_dense_convolution_output():
     the user encoder has no weight-operand product for ops.BX3 to move.)"""
     from nnr_amd import ops
     case = GoldenCase(FULL)
-    model, cfg = _build(case)
+    model, cfg = build_model(case, 'train')
     b = case.batch('cuda')
     with torch.no_grad():
         cand = model.news_encoder(b[15], b[16], b[17], b[18], b[19], b[20], b[13], b[14], None)
@@ -510,7 +500,7 @@ def test_backward_twice_gives_identical_bits(side):
     if side:
         ops.LEAF_MIN_ROWS = 1
     try:
-        model, cfg = _build(case)
+        model, cfg = build_model(case, 'train')
         runs = []
         for _ in range(3 if side else 2):
             for p in model.parameters():
@@ -547,7 +537,7 @@ def test_side_stream_branch_equals_the_sequential_one():
     try:
         for rows in (1, old):
             ops.LEAF_MIN_ROWS = rows
-            model, cfg = _build(case)
+            model, cfg = build_model(case, 'train')
             logits = model(*case.batch('cuda'))
             negative_log_softmax(logits).backward()
             ops.join_extra_streams()
@@ -565,13 +555,7 @@ def test_side_stream_branch_equals_the_sequential_one():
 def test_compute_scores_and_metrics_match_reference(bx3):
     """evaluate.py's per-batch form (the pair's representation is not cacheable) gives the reference's scores, ranks and metrics."""
     from nnr_amd import evaluate as E
-    from nnr_amd.model import Model
-    z = np.load(os.path.join(GOLDEN_DIR, 'eval_tiny_HDC_FIM.npz'))
-    cast = {'int': int, 'float': float, 'str': str, 'bool': lambda v: v == 'True'}
-    cfg = SimpleNamespace(**{k: cast[t](v) for k, v, t in zip(z['cfg_keys'], z['cfg_vals'], z['cfg_types'])})
-    cfg.tie_order = str(z['tie_order'])
-    model = Model(cfg, torch.zeros(cfg.vocabulary_size, cfg.word_embedding_dim))
-    model.load_state_dict({k[len('state/'):]: torch.from_numpy(z[k].copy()) for k in z.files if k.startswith('state/')})
+    z, model = eval_fixture('tiny_HDC_FIM')
     model = model.cuda().train()
     assert not E.news_reps_cacheable(model)
     dc = E.dev_corpus({k: z[k] for k in z.files}, 'cuda', int(z['category_num']))

@@ -4,15 +4,13 @@ plugin / evaluation paths against golden vectors captured from the reference's o
 absolute, every gradient within 5e-5 of its own largest magnitude (the house bars of tests/test_hip_catt_gpu.py; torch's own fp32 GRU stays
 within 7e-7 / 6e-7 of float64 at (64, 50, 300, 200)); model level as tests/test_hip_catt_gpu.py::test_model_matches_reference_golden."""
 import functools
-import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
 import gru_ref
-from golden_io import GoldenCase, GOLDEN_DIR
+from golden_io import GoldenCase, build_model, eval_fixture
 
 pytestmark = pytest.mark.gpu
 
@@ -170,16 +168,6 @@ def test_unsupported_sizes_return_the_error_code():
 
 
 # ---------------------------------------------------------------------------------------------- model level
-def _build(case):
-    from nnr_amd.model import Model
-    cfg = case.config
-    model = Model(cfg, case.word_table())
-    case.load_into(model)
-    model = model.cuda()
-    model.train() if case.meta['mode'] == 'train' else model.eval()
-    return model, cfg
-
-
 @pytest.mark.parametrize('tag', MODEL_CASES)
 def test_model_matches_reference_golden(tag):
     """The body of tests/test_hip_catt_gpu.py::test_model_matches_reference_golden, bars unchanged; plus: the user vectors of the users
@@ -187,7 +175,7 @@ def test_model_matches_reference_golden(tag):
     from nnr_amd.trainer import Trainer
     from nnr_amd.model import negative_log_softmax
     case = GoldenCase(tag)
-    model, cfg = _build(case)
+    model, cfg = build_model(case)
     trainer = Trainer(model, cfg)
     steps = int(case.meta['adam_steps'])
     rec = {}
@@ -275,7 +263,7 @@ def test_model_matches_reference_golden(tag):
 @pytest.mark.parametrize('tag', ['tiny_DAE_GRU', 'tiny_CNE_GRU_h48', 'full_DAE_GRU_g1p0'])
 def test_plugin_calls_equal_lockstep_path(tag):
     case = GoldenCase(tag)
-    model, cfg = _build(case)
+    model, cfg = build_model(case)
     b = case.batch('cuda')
     logits = model(*b).detach()
     b = case.batch('cuda')
@@ -288,13 +276,7 @@ def test_plugin_calls_equal_lockstep_path(tag):
 
 
 def _eval_model(tag):
-    from nnr_amd.model import Model
-    z = np.load(os.path.join(GOLDEN_DIR, 'eval_%s.npz' % tag))
-    cast = {'int': int, 'float': float, 'str': str, 'bool': lambda v: v == 'True'}
-    cfg = SimpleNamespace(**{k: cast[t](v) for k, v, t in zip(z['cfg_keys'], z['cfg_vals'], z['cfg_types'])})
-    cfg.tie_order = str(z['tie_order'])
-    model = Model(cfg, torch.zeros(cfg.vocabulary_size, cfg.word_embedding_dim))
-    model.load_state_dict({k[len('state/'):]: torch.from_numpy(z[k].copy()) for k in z.files if k.startswith('state/')}, strict=True)
+    z, model = eval_fixture(tag)
     return z, model.cuda().train()
 
 

@@ -1,14 +1,12 @@
 """GPU tests of the KCNN news encoder (DKN): the kernels of csrc/kcnn.hip op by op against float64 / exact fp32 expectations, the encoder at
 odd sizes against tests/kcnn_ref.py, and the model against the reference's own results (tests/golden/*KCNN*.npz) on both matrix paths."""
 import functools
-import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from golden_io import GoldenCase, GOLDEN_DIR
+from golden_io import GoldenCase, build_model, eval_fixture
 import kcnn_ref
 from kcnn_ref import f64
 
@@ -199,7 +197,7 @@ def test_sizes_beyond_the_limits_are_unsupported(dims):
             ops.window_max_bwd(torch.zeros(n, C, device=d), torch.zeros(n, C, device=d, dtype=torch.uint8), n, C, L, w, 0, z, torch.zeros(C, device=d))
     if w > 8 or E > 1024:
         with pytest.raises(_lib.NnrHipError, match='unsupported size'):
-            ops.kcnn_weight(torch.zeros(C, E, w, 3, device=d), 0)
+            ops.rowconv_weight(torch.zeros(C, E, w, 3, device=d), 0)
 
 
 # ------------------------------------------------------------------------------------------------ the encoder at odd sizes
@@ -256,14 +254,6 @@ def test_encoder_matches_the_float64_restatement_at_odd_sizes(c):
 
 
 # ------------------------------------------------------------------------------------------------ the model
-def _build(case):
-    from nnr_amd.model import Model
-    cfg = SimpleNamespace(**vars(case.config))
-    model = Model(cfg, case.word_table())
-    case.load_into(model)
-    return model.cuda().train(), cfg
-
-
 @functools.lru_cache(maxsize=None)
 def _full_size_scales(tag):
     """{parameter: max |gradient|} of a full-size fixture, from tests/kcnn_ref.py in float64 (computed once for both matrix paths)."""
@@ -318,7 +308,7 @@ def test_model_matches_reference_golden(tag, bx3):
     before = ops.BX3[0]
     ops.BX3[0] = bx3
     try:
-        model, cfg = _build(case)
+        model, cfg = build_model(case, 'train')
         assert model.news_encoder.auxiliary_loss is None
         batch = case.batch('cuda')
         logits = model(*batch)
@@ -341,7 +331,7 @@ def test_model_on_the_side_stream_branch_equals_the_sequential_one():
     old = ops.LEAF_MIN_ROWS
     ops.LEAF_MIN_ROWS = 1
     try:
-        model, cfg = _build(case)
+        model, cfg = build_model(case, 'train')
         logits = model(*case.batch('cuda'))
         loss = negative_log_softmax(logits)
         loss.backward()
@@ -357,7 +347,7 @@ def test_backward_twice_gives_identical_bits():
     enough for split-K: two passes from zeroed gradients, same bits."""
     from nnr_amd import ops
     case = GoldenCase(FULL)
-    model, cfg = _build(case)
+    model, cfg = build_model(case, 'train')
     enc = model.news_encoder
     b = case.batch('cuda')
     G = torch.randn(b[3].shape[0], b[3].shape[1], model.news_embedding_dim, generator=torch.Generator().manual_seed(1)).cuda()
@@ -381,7 +371,7 @@ def test_trainer_steps_move_the_tables_and_the_convolution():
     and the convolution move."""
     from nnr_amd.trainer import Trainer
     case = GoldenCase(TINY[0])
-    model, cfg = _build(case)
+    model, cfg = build_model(case, 'train')
     trainer = Trainer(model, cfg)
     watched = ['news_encoder.%s.weight' % k for k in ('word_embedding', 'entity_embedding', 'context_embedding', 'M_entity', 'M_context', 'knowledge_cnn.conv')]
     before = {k: p.detach().clone() for k, p in model.named_parameters() if k in watched}
@@ -401,13 +391,7 @@ def test_trainer_steps_move_the_tables_and_the_convolution():
 def test_compute_scores_and_metrics_match_reference():
     """evaluate.py with its news cache on (KCNN is batch-independent), to the bars of the other encoders' eval tests."""
     from nnr_amd import evaluate as E
-    from nnr_amd.model import Model
-    z = np.load(os.path.join(GOLDEN_DIR, 'eval_tiny_KCNN_CATT.npz'))
-    cast = {'int': int, 'float': float, 'str': str, 'bool': lambda v: v == 'True'}
-    cfg = SimpleNamespace(**{k: cast[t](v) for k, v, t in zip(z['cfg_keys'], z['cfg_vals'], z['cfg_types'])})
-    cfg.tie_order = str(z['tie_order'])
-    model = Model(cfg, torch.zeros(cfg.vocabulary_size, cfg.word_embedding_dim))
-    model.load_state_dict({k[len('state/'):]: torch.from_numpy(z[k].copy()) for k in z.files if k.startswith('state/')})
+    z, model = eval_fixture('tiny_KCNN_CATT')
     model = model.cuda().train()
     assert E.news_reps_cacheable(model)
     dc = E.dev_corpus({k: z[k] for k in z.files}, 'cuda', int(z['category_num']))

@@ -132,12 +132,16 @@ def _additive_param_grads(mod, ref):
         _close(p.grad, rp[k].grad, tol=5e-5, what='d ' + k)
 
 
-@pytest.mark.parametrize('masked', [False, True])
-def test_attention_standalone_forward_backward(masked):
+@pytest.mark.parametrize('masked,shape', [pytest.param(False, (9, 20, 260, 200), id='False'), pytest.param(True, (9, 20, 260, 200), id='True'),
+                                          pytest.param(True, (26, 40, 260, 200), id='1040rows-A200'),
+                                          pytest.param(True, (26, 40, 260, 198), id='1040rows-A198')])
+def test_attention_standalone_forward_backward(masked, shape):
     """`Attention` (layers.py:151-175) on a dense feature: tanh GEMM, w2 row-dot, the dense pool with mask_div = 1.  The mask has a fully
-    masked row (uniform alpha, no score gradient), a fully live one, one with only the last and one with only the first position live."""
+    masked row (uniform alpha, no score gradient), a fully live one, one with only the last and one with only the first position live.
+    180 rows: the data gradient through affine1 is the trans_b product; 1 040 rows: the NT product on W1^T (A = 200) or, with A % 4 != 0
+    (A = 198), the trans_b product again -- there the score is an N = 1 product (nnr_rowdot takes rows of a multiple of 4 floats)."""
     import pool_ref as R
-    n, Lx, F, A = 9, 20, 260, 200
+    n, Lx, F, A = shape
     ref, mod = _additive_pair(F, A, 7)
     x, dout = torch.randn(n, Lx, F), torch.randn(n, F)
     mask = R.hole_mask(n, Lx, 11) if masked else None
@@ -155,15 +159,16 @@ def test_attention_standalone_forward_backward(masked):
     _additive_param_grads(mod, ref)
 
 
-@pytest.mark.parametrize('A', [200, 264])
-def test_packed_attention_through_mhsa_pack(A):
+@pytest.mark.parametrize('A,n', [pytest.param(200, 11, id='200'), pytest.param(264, 11, id='264'), pytest.param(200, 30, id='200-cap1200')])
+def test_packed_attention_through_mhsa_pack(A, n):
     """functional.PackedAttentionFn over the rows functional.MhsaPack keeps (ops.mask_cover of the hole mask), against AdditivePool on the
     dense input with the original mask.  A = 200: the score is the pool's own th . w2 row-dot; A = 264 (> 256): nnr_rowdot, then the pool
-    with a given score.  Lengths on every body of the packed pool; row 0 is fully masked and keeps all L positions."""
+    with a given score.  Lengths on every body of the packed pool; row 0 is fully masked and keeps all L positions.  30 titles: the plan's
+    capacity (1 200 rows) is past the 1 024 rows from which the data gradient through affine1 is the NT product on W1^T."""
     import pool_ref as R
     from nnr_amd import functional as Fn
-    n, Lx, F = 11, 40, 260
-    lens = [40, 33, 32, 9, 20, 8, 5, 1, 8, 2, 3]
+    Lx, F = 40, 260
+    lens = [40, 33, 32, 9, 20, 8, 5, 1, 8, 2, 3] + [(7 * i) % Lx + 1 for i in range(n - 11)]
     g = torch.Generator().manual_seed(13)
     mask = (torch.rand(n, Lx, generator=g) < 0.6) & (torch.arange(Lx)[None, :] < torch.tensor(lens)[:, None])
     mask[torch.arange(n), torch.tensor(lens) - 1] = True

@@ -4,22 +4,12 @@ import numpy as np
 import pytest
 import torch
 
-from golden_io import GoldenCase, ALL_CASES
+from golden_io import GoldenCase, ALL_CASES, build_model
 
 pytestmark = pytest.mark.gpu
 
 LOGIT_TOL = 1e-4          # the north-star bar
 TIGHT = 2e-5              # what the fp32 kernels are expected to reach
-
-
-def _build(case):
-    from nnr_amd.model import Model
-    cfg = case.config
-    model = Model(cfg, case.word_table())
-    case.load_into(model)
-    model = model.cuda()
-    model.train() if case.meta['mode'] == 'train' else model.eval()
-    return model, cfg
 
 
 def _supported(tag):
@@ -38,7 +28,7 @@ def test_model_matches_reference_golden(tag):
     from nnr_amd.trainer import Trainer
     from nnr_amd.model import negative_log_softmax
     case = GoldenCase(tag)
-    model, cfg = _build(case)
+    model, cfg = build_model(case)
     trainer = Trainer(model, cfg)
     steps = int(case.meta['adam_steps'])
     rec = {}
@@ -128,7 +118,7 @@ def test_plugin_calls_equal_lockstep_path(tag):
     """The reference's plugin surface (news_encoder(...) then user_encoder(...), model.py:123-125) must give exactly what
     Model.forward's lock-step path gives (same kernels, only the recurrence launches are shared)."""
     case = GoldenCase(tag)
-    model, cfg = _build(case)
+    model, cfg = build_model(case)
     b = case.batch('cuda')
     logits = model(*b).detach()
     b = case.batch('cuda')

@@ -1,14 +1,12 @@
 """GPU tests of the single-view NAML news encoders: the view-pool kernels of csrc/naml.hip op by op against float64 (tests/naml_ref.py), and
 the model against the reference's own results (tests/golden/*NAML*.npz) on both matrix paths, with dropout on, through evaluation, and
 twice for bit equality.  Bars: those of tests/test_hip_kcnn_gpu.py -- 1e-4 of each tensor's scale (max |expected|), every element."""
-import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from golden_io import GoldenCase, GOLDEN_DIR
+from golden_io import GoldenCase, build_model, eval_fixture
 import naml_ref
 from naml_ref import f64
 
@@ -259,15 +257,6 @@ def test_conv_image_unsupported_sizes_are_refused(dims):
 
 
 # ------------------------------------------------------------------------------------------------ the model
-def _build(case, **over):
-    from nnr_amd.model import Model
-    cfg = SimpleNamespace(**vars(case.config))
-    vars(cfg).update(over)
-    model = Model(cfg, case.word_table())
-    case.load_into(model)
-    return model.cuda().train(), cfg
-
-
 _SCALES = {}
 
 
@@ -325,7 +314,7 @@ def test_model_matches_reference_golden(tag, bx3):
     before = ops.BX3[0]
     ops.BX3[0] = bx3
     try:
-        model, cfg = _build(case)
+        model, cfg = build_model(case, 'train')
         trainer = Trainer(model, cfg)
         for s in range(steps):
             batch = case.batch('cuda')
@@ -374,7 +363,7 @@ def test_dropout_on_matches_the_restatement_fed_the_kernels_masks():
     from nnr_amd.synth import BATCH_FIELDS
     case = GoldenCase('drop_tiny_NAML_Content_ATT')
     p = 0.25
-    model, cfg = _build(case)
+    model, cfg = build_model(case, 'train')
     ne = model.news_encoder
     assert ne.training and ne.dropout_rate == p
     batch = case.batch('cuda')
@@ -410,13 +399,7 @@ def test_compute_scores_and_metrics_match_reference():
     """evaluate.py with its news cache on (the encoders are batch-independent) and off: scores to the bars of the other encoders' eval
     tests, ranks equal."""
     from nnr_amd import evaluate as E
-    from nnr_amd.model import Model
-    z = np.load(os.path.join(GOLDEN_DIR, 'eval_tiny_NAML_Title_ATT.npz'))
-    cast = {'int': int, 'float': float, 'str': str, 'bool': lambda v: v == 'True'}
-    cfg = SimpleNamespace(**{k: cast[t](v) for k, v, t in zip(z['cfg_keys'], z['cfg_vals'], z['cfg_types'])})
-    cfg.tie_order = str(z['tie_order'])
-    model = Model(cfg, torch.zeros(cfg.vocabulary_size, cfg.word_embedding_dim))
-    model.load_state_dict({k[len('state/'):]: torch.from_numpy(z[k].copy()) for k in z.files if k.startswith('state/')}, strict=True)
+    z, model = eval_fixture('tiny_NAML_Title_ATT')
     model = model.cuda().train()
     assert E.news_reps_cacheable(model)
     dc = E.dev_corpus({k: z[k] for k in z.files}, 'cuda', int(z['category_num']))
@@ -442,7 +425,7 @@ def test_backward_twice_gives_identical_bits():
     fixture's shapes: two passes from zeroed gradients, same bits; the representation too."""
     from nnr_amd import ops
     case = GoldenCase(FULL)
-    model, cfg = _build(case)
+    model, cfg = build_model(case, 'train')
     enc = model.news_encoder
     b = case.batch('cuda')
     G = torch.randn(b[3].shape[0], b[3].shape[1], model.news_embedding_dim, generator=torch.Generator().manual_seed(1)).cuda()

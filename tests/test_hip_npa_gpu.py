@@ -2,14 +2,12 @@
 float64 restatements of tests/npa_ref.py (pinned to the reference by tests/test_npa_host.py), their guards and reproducibility, and the
 PNE / PUE model, plug-in, evaluation and dropout-on paths against golden vectors captured from the reference's own code
 (tests/golden/*PNE*.npz, *PUE*.npz).  Bars as in tests/test_hip_catt_gpu.py."""
-import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from golden_io import GoldenCase, GOLDEN_DIR
+from golden_io import GoldenCase, build_model, eval_fixture
 from npa_ref import pers_attn, pne_title_rep, pue_user_rep, f64
 
 pytestmark = pytest.mark.gpu
@@ -255,23 +253,13 @@ def test_user_rows_backward_applies_the_forward_mask_and_sums_duplicates_in_orde
 
 
 # ------------------------------------------------------------------------------------------------ the model
-def _build(case):
-    from nnr_amd.model import Model
-    cfg = case.config
-    model = Model(cfg, case.word_table())
-    case.load_into(model)
-    model = model.cuda()
-    model.train() if case.meta['mode'] == 'train' else model.eval()
-    return model, cfg
-
-
 @pytest.mark.parametrize('tag', NPA_CASES)
 def test_model_matches_reference_golden(tag):
     """The body of tests/test_hip_catt_gpu.py::test_model_matches_reference_golden, bars unchanged."""
     from nnr_amd.trainer import Trainer
     from nnr_amd.model import negative_log_softmax
     case = GoldenCase(tag)
-    model, cfg = _build(case)
+    model, cfg = build_model(case)
     trainer = Trainer(model, cfg)
     steps = int(case.meta['adam_steps'])
     rec = {}
@@ -345,7 +333,7 @@ def test_model_matches_reference_golden(tag):
 @pytest.mark.parametrize('tag', ['tiny_PNE_PUE', 'tiny_PNE_ATT', 'tiny_CNN_PUE'])
 def test_plugin_calls_equal_model_forward(tag):
     case = GoldenCase(tag)
-    model, cfg = _build(case)
+    model, cfg = build_model(case)
     logits = model(*case.batch('cuda')).detach()
     b = case.batch('cuda')
     (uid, ucat, usub, utt, utm, ute, uct, ucm, uce, uhm, ug, ucmask, ucidx, ncat, nsub, ntt, ntm, nte, nct, ncm, nce) = b
@@ -360,13 +348,7 @@ def test_plugin_calls_equal_model_forward(tag):
 
 def test_compute_scores_and_metrics_match_reference():
     from nnr_amd import evaluate as E
-    from nnr_amd.model import Model
-    z = np.load(os.path.join(GOLDEN_DIR, 'eval_tiny_PNE_PUE.npz'))
-    cast = {'int': int, 'float': float, 'str': str, 'bool': lambda v: v == 'True'}
-    cfg = SimpleNamespace(**{k: cast[t](v) for k, v, t in zip(z['cfg_keys'], z['cfg_vals'], z['cfg_types'])})
-    cfg.tie_order = str(z['tie_order'])
-    model = Model(cfg, torch.zeros(cfg.vocabulary_size, cfg.word_embedding_dim))
-    model.load_state_dict({k[len('state/'):]: torch.from_numpy(z[k].copy()) for k in z.files if k.startswith('state/')})
+    z, model = eval_fixture('tiny_PNE_PUE')
     model = model.cuda().train()
     assert not E.news_reps_cacheable(model)
     dc = E.dev_corpus({k: z[k] for k in z.files}, 'cuda', int(z['category_num']))

@@ -3,15 +3,13 @@ formulation (tests/omap_ref.py, pinned to the reference by tests/test_omap_host.
 (padded rows in the archives, users without history, masked_fill's blocked gradients), the regulariser, and the model / trainer /
 plugin / evaluation / dropout-on paths against golden vectors captured from the reference's own code (tests/golden/*OMAP*.npz).
 Bars as in tests/test_hip_catt_gpu.py, tests/test_hip_model_gpu.py and tests/test_hip_eval_gpu.py."""
-import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
 from omap_ref import omap_form, regularizer, omap_user_rep, f64
-from golden_io import GoldenCase, GOLDEN_DIR
+from golden_io import GoldenCase, build_model, eval_fixture
 
 pytestmark = pytest.mark.gpu
 
@@ -212,16 +210,6 @@ def test_regulariser_is_exactly_zero_at_orthogonal_columns():
 
 
 # ------------------------------------------------------------------------------------------------ the model
-def _build(case):
-    from nnr_amd.model import Model
-    cfg = case.config
-    model = Model(cfg, case.word_table())
-    case.load_into(model)
-    model = model.cuda()
-    model.train() if case.meta['mode'] == 'train' else model.eval()
-    return model, cfg
-
-
 def _trainer_loss(model, logits):
     """The loss as Trainer._train_step forms it (trainer.py:109-114 of the reference)."""
     from nnr_amd.model import negative_log_softmax
@@ -239,7 +227,7 @@ def test_model_matches_reference_golden(tag):
     from nnr_amd.trainer import Trainer
     from nnr_amd.model import negative_log_softmax
     case = GoldenCase(tag)
-    model, cfg = _build(case)
+    model, cfg = build_model(case)
     trainer = Trainer(model, cfg)
     steps = int(case.meta['adam_steps'])
     rec = {}
@@ -329,7 +317,7 @@ def test_model_matches_reference_golden(tag):
 @pytest.mark.parametrize('tag', ['tiny_CNE_OMAP_stable', 'full_CNE_OMAP_g0p35_stable'])
 def test_plugin_calls_equal_lockstep_path(tag):
     case = GoldenCase(tag)
-    model, cfg = _build(case)
+    model, cfg = build_model(case)
     b = case.batch('cuda')
     logits = model(*b).detach()
     b = case.batch('cuda')
@@ -343,7 +331,7 @@ def test_plugin_calls_equal_lockstep_path(tag):
 
 def test_eval_mode_leaves_the_auxiliary_loss_untouched():
     case = GoldenCase('tiny_CNN_OMAP')
-    model, cfg = _build(case)
+    model, cfg = build_model(case)
     ue = model.user_encoder
     model.eval()
     with torch.no_grad():
@@ -361,13 +349,7 @@ def test_eval_mode_leaves_the_auxiliary_loss_untouched():
 
 # ------------------------------------------------------------------------------------------------ evaluation
 def _eval_model(tag):
-    from nnr_amd.model import Model
-    z = np.load(os.path.join(GOLDEN_DIR, 'eval_%s.npz' % tag))
-    cast = {'int': int, 'float': float, 'str': str, 'bool': lambda v: v == 'True'}
-    cfg = SimpleNamespace(**{k: cast[t](v) for k, v, t in zip(z['cfg_keys'], z['cfg_vals'], z['cfg_types'])})
-    cfg.tie_order = str(z['tie_order'])
-    model = Model(cfg, torch.zeros(cfg.vocabulary_size, cfg.word_embedding_dim))
-    model.load_state_dict({k[len('state/'):]: torch.from_numpy(z[k].copy()) for k in z.files if k.startswith('state/')})
+    z, model = eval_fixture(tag)
     return z, model.cuda().train()
 
 

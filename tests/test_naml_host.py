@@ -260,35 +260,6 @@ def test_view_pool_restatement_for_two_text_views():
     assert float(al3[:, 1].max()) < 1e-60 and float((out3 - t0).abs().max()) < 1e-30
 
 
-@pytest.mark.parametrize('dims', [(12, 16, 3), (5, 10, 5), (3, 7, 1), (4, 6, 7)], ids=lambda d: 'C%d_E%d_k%d' % d)
-def test_conv1d_layouts_match_a_naive_index_loop(dims):
-    """ops.LAYOUTS 'c1_p', 'c1_q' and 'c1_dw' applied to a CPU array through their extents / strides / offset against the index loops
-    P[c][dt][e] = W[c][e][dt], Q[e][j][c] = W[c][e][k-1-j] and G[c][e][dt] = dP[c][dt][e]."""
-    from nnr_amd import ops
-    C, E, k = dims
-    W = torch.randn(C, E, k, generator=torch.Generator().manual_seed(C + E + k))
-
-    def apply(kind, src):
-        n, si, so, off, shape = ops.LAYOUTS[kind](*dims)
-        out = torch.full((int(np.prod(shape)),), float('nan'))
-        flat = src.reshape(-1)
-        for i0 in range(n[0]):
-            for i1 in range(n[1]):
-                for i2 in range(n[2]):
-                    for i3 in range(n[3]):
-                        out[i0 * so[0] + i1 * so[1] + i2 * so[2] + i3 * so[3]] = flat[off + i0 * si[0] + i1 * si[1] + i2 * si[2] + i3 * si[3]]
-        return out.view(shape)
-    P, Q = apply('c1_p', W), apply('c1_q', W)
-    assert tuple(P.shape) == (C, k * E) and tuple(Q.shape) == (E, k * C)
-    for c in range(C):
-        for e in range(E):
-            for dt in range(k):
-                assert float(P[c, dt * E + e]) == float(W[c, e, dt])
-                assert float(Q[e, dt * C + c]) == float(W[c, e, k - 1 - dt])
-    G = apply('c1_dw', P)
-    assert torch.equal(G, W)
-
-
 def test_entry_points_are_declared_listed_and_exported():
     from nnr_amd import _lib, profile
     header = open(os.path.join(ROOT, 'include', 'nnr_hip.h')).read()
