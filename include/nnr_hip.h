@@ -694,6 +694,44 @@ int nnr_fusion_rows_bwd_det(const int* cat0, const int* sub0, int n0, const int*
 int nnr_click_loss(const float* user, const float* cand, int B, int N, int D, float* logits, float* loss, float* dlogits, float* duser,
                    float* dcand, float* terms_ws, hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------------ DSSM (csrc/dssm.hip)
+ * The DSSM baseline of general_recommendation_methods/ (DSSM_model.py:29-36, DSSM_main.py:63).  All buffers fp32, no float atomics, same
+ * inputs -> same bits.
+ * Weighted bag: two streams in one launch, a (users: na rows of La positions) and b (news: nb rows of Lb positions; nb == 0: none), into
+ *   one stacked out [na + nb, E].  Per stream a term-vector table ids int32 [R, L] / w f32 [R, L] and an optional row selector sel int32
+ *   [n] (NULL: identity, then R >= n); a selector entry outside [0, R) selects an empty row.
+ *     out[r, e] = sum_j keep(seed, (r * L + j) * E + e) * scale * w[sel[r], j] * table[ids[sel[r], j], e],  scale = 1 / (1 - p)
+ *   (stream b: rows na + r, seed_b; r and j count inside the stream; keep is csrc/common.h:nnr_keep; p == 0 skips the hash).  A position
+ *   with w == 0 contributes nothing and its table row is not read: the reference's 0 * row differs only for a row holding a non-finite
+ *   value.  An id outside [0, V) contributes a zero row and receives no gradient.  Sum order: positions ascending inside a chunk of
+ *   `chunk` positions (compensated), then the chunks ascending.  tok (optional) int32 [na * La + nb * Lb] (stream a, then stream b)
+ *   receives the word id of every live position and -1 elsewhere: sorted by nnr_token_sort (n_dev = NULL) it is the backward's list.
+ *   ws: nnr_wbag_fwd_ws_floats(na, La, nb, Lb, E) floats (never NULL).
+ * nnr_wbag_dims (host only): the chunk length and the chunks per row of each stream; NNR_ERR_UNSUPPORTED (from the launches too, before
+ *   anything is written) unless 1 <= E <= 1024, 1 <= La <= 4096 and 0 <= Lb <= 4096 (chunk is written in either case).  Any E: rows move
+ *   as 16-byte vectors when E % 4 == 0, as 8-byte vectors when E % 2 == 0, as scalars otherwise.
+ * Backward: dtable[word, :] += sum over the word's live occurrences, in sorted-list order, of keep * scale * w * dout[row, :], dout
+ *   [na + nb, E] read through the occurrence's row: no [tokens, E] buffer.  cap = na * La + nb * Lb entries in keys_sorted / pos_sorted.
+ *   One writer per table row per launch (both streams share the one list); partial_ws: nnr_wbag_bwd_ws_floats(cap, E) floats.
+ * nnr_cosine_loss mirrors nnr_click_loss: user [B, F], news [B, N, F]; logits[b, n] = <u_b, v_bn> / (|u_b| |v_bn|), loss = mean_b of
+ *   -log_softmax(logits)[b, 0] (a fixed-order mean), dlogits [B, N], duser [B, F] (the sum over the N candidates in ascending order),
+ *   dnews [B, N, F] (duser and dnews: both or neither).  loss, dlogits, duser, dnews may all be NULL: the eval call, logits only (the
+ *   same bits).  ws: B floats, needed with loss.  N > 64: NNR_ERR_UNSUPPORTED.  A zero-norm row gives NaN logits (the reference's 0 / 0);
+ *   the gradients of such a sample are not specified.
+ * nnr_tanh_drop_bwd: dz = mask(dy) * (1 - t * t) behind y = dropout(tanh(z)), t = tanh(z); mask keyed by the flat element index. */
+int nnr_wbag_dims(int E, int La, int Lb, int* chunk, int* nchunk_a, int* nchunk_b);
+size_t nnr_wbag_fwd_ws_floats(int na, int La, int nb, int Lb, int E);
+int nnr_wbag_fwd(const float* table, int V, int E, const int* ids_a, const float* w_a, const int* sel_a, int Ra, int na, int La,
+                 const int* ids_b, const float* w_b, const int* sel_b, int Rb, int nb, int Lb, float p, uint32_t seed_a, uint32_t seed_b,
+                 float* out, int* tok, float* ws, hipStream_t stream);
+size_t nnr_wbag_bwd_ws_floats(long cap, int E);
+int nnr_wbag_bwd(const float* dout, const unsigned* keys_sorted, const int* pos_sorted, long cap, const float* w_a, const int* sel_a, int Ra,
+                 int na, int La, const float* w_b, const int* sel_b, int Rb, int nb, int Lb, int V, int E, float p, uint32_t seed_a,
+                 uint32_t seed_b, float* dtable_accum, float* partial_ws, hipStream_t stream);
+int nnr_cosine_loss(const float* user, const float* news, int B, int N, int F, float* logits, float* loss, float* dlogits, float* duser,
+                    float* dnews, float* ws, hipStream_t stream);
+int nnr_tanh_drop_bwd(const float* dy, const float* t, float* dz, long n, float p, uint32_t seed, hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------ fills / copies
  * What the host framework's fill / copy / index-put kernels did inside the step (optimizer.zero_grad() at trainer.py:116,
  * torch.cat of the two encoder calls' id tensors, `user_history_category_mask[:, -1] = 1` at userEncoders.py:73), as entry points,

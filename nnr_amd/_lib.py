@@ -191,6 +191,13 @@ SIGNATURES = {
     'nnr_fusion_rows_bwd': 'i32 ptr ptr i32 ptr ptr i32 i32 i32 ptr i32 ptr ptr f32 seed seed stream',
     'nnr_fusion_rows_bwd_det': 'i32 ptr ptr i32 ptr ptr i32 i32 i32 i32 i32 ptr i32 ptr ptr f32 seed seed stream',
     'nnr_click_loss': 'i32 ptr ptr i32 i32 i32 ptr ptr ptr ptr ptr ptr stream',
+    'nnr_wbag_dims': 'i32 i32 i32 i32 ptr ptr ptr',
+    'nnr_wbag_fwd_ws_floats': 'u64 i32 i32 i32 i32 i32',
+    'nnr_wbag_fwd': 'i32 ptr i32 i32 ptr ptr ptr i32 i32 i32 ptr ptr ptr i32 i32 i32 f32 seed seed ptr ptr ptr stream',
+    'nnr_wbag_bwd_ws_floats': 'u64 i64 i32',
+    'nnr_wbag_bwd': 'i32 ptr ptr ptr i64 ptr ptr i32 i32 i32 ptr ptr i32 i32 i32 i32 i32 f32 seed seed ptr ptr stream',
+    'nnr_cosine_loss': 'i32 ptr ptr i32 i32 i32 ptr ptr ptr ptr ptr ptr stream',
+    'nnr_tanh_drop_bwd': 'i32 ptr ptr ptr i64 f32 seed stream',
     'nnr_fill_zero': 'i32 ptr u64 stream',
     'nnr_copy_bytes': 'i32 ptr ptr u64 stream',
     'nnr_fill_column_u8': 'i32 ptr i32 i32 i32 i32 stream',

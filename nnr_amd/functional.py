@@ -139,22 +139,23 @@ CAPTURE_RELU = [None]      # diagnostics / parity tests: set CAPTURE_RELU[0] = [
 
 
 class LinearFn(torch.autograd.Function):
-    """y = dropout(act(x W^T + b)) for 2-D contiguous x;  act in {none, relu, sigmoid};  dropout mask keyed by the output element."""
+    """y = dropout(act(x W^T + b)) for 2-D contiguous x;  act in {none, relu, tanh, sigmoid};  dropout mask keyed by the output element."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, act, p, seed):
-        if act not in (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_SIGMOID):
-            raise ValueError('LinearFn: act must be none, relu or sigmoid')
+        if act not in (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_TANH, ops.ACT_SIGMOID):
+            raise ValueError('LinearFn: act must be none, relu, tanh or sigmoid')
         x = x.contiguous()
         M, K = x.shape
         N = weight.shape[0]
         y = torch.empty((M, N), device=x.device, dtype=torch.float32)
-        # r = act(.) before the dropout, what the backward mask needs; behind a sigmoid without dropout y itself is that value
-        r = torch.empty((M, N), device=x.device, dtype=torch.float32) if (act == ops.ACT_RELU or (act == ops.ACT_SIGMOID and p > 0)) else None
+        # r = act(.) before the dropout, what the backward mask needs; behind a sigmoid or tanh without dropout y itself is that value
+        smooth = act in (ops.ACT_SIGMOID, ops.ACT_TANH)
+        r = torch.empty((M, N), device=x.device, dtype=torch.float32) if (act == ops.ACT_RELU or (smooth and p > 0)) else None
         ops.gemm(x, weight, y, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, bias=bias, act=act, aux_out=r, ldaux=N, drop=(3, p, seed, N))
         if CAPTURE_RELU[0] is not None and r is not None and act == ops.ACT_RELU:
             CAPTURE_RELU[0].append(r)
-        if act == ops.ACT_SIGMOID and r is None:
+        if smooth and r is None:
             r = y.detach()               # (a second tensor object on y's storage: ctx must not hold its own output)
         ctx.x, ctx.weight, ctx.bias, ctx.r, ctx.act, ctx.p, ctx.seed = x, weight, bias, r, act, p, seed
         return y
@@ -165,6 +166,9 @@ class LinearFn(torch.autograd.Function):
         if ctx.act == ops.ACT_SIGMOID:
             dz = torch.empty_like(dy)
             ops.sigmoid_drop_bwd(dy, ctx.r, dz, ctx.p, ctx.seed)
+        elif ctx.act == ops.ACT_TANH:
+            dz = torch.empty_like(dy)
+            ops.tanh_drop_bwd(dy, ctx.r, dz, ctx.p, ctx.seed)
         elif ctx.act == ops.ACT_RELU or ctx.p > 0:
             dz = torch.empty_like(dy)
             r = ctx.r if ctx.r is not None else torch.ones_like(dy)
@@ -395,6 +399,59 @@ class RowDistFn(torch.autograd.Function):
         da, db = torch.zeros_like(a), torch.zeros_like(b)
         ops.row_dist_bwd(a, b, dist, gup.contiguous().float(), ctx.coef, da, db)
         return da, db, None
+
+
+class WbagFn(torch.autograd.Function):
+    """The two weighted bags of DSSM (DSSM_model.py:29-30, csrc/dssm.hip) as one stacked [na + nb, E]: dropout(word_embedding(ids) * w).sum
+    per row of the user stream `sa` and of the news stream `sb` (each (ids int32 [R, L], w f32 [R, L], sel int32 [n] or None)).  need_grad:
+    the launch also writes the occurrence keys, and their sort by word id runs on the leaf stream under the towers.  The table gradient is
+    a reduction with one plain writer per row over both streams' occurrences together (no float atomics)."""
+
+    @staticmethod
+    def forward(ctx, table, sa, sb, p, seed_a, seed_b, need_grad):
+        dev, E = table.device, table.shape[1]
+        na = sa[2].numel() if sa[2] is not None else sa[1].shape[0]
+        nb = 0 if sb is None else (sb[2].numel() if sb[2] is not None else sb[1].shape[0])
+        out = torch.empty((na + nb, E), device=dev, dtype=torch.float32)
+        cap = na * sa[1].shape[1] + (nb * sb[1].shape[1] if sb is not None else 0)
+        plan = ops.WbagPlan(cap, E, table.shape[0], dev) if need_grad else None
+        ops.wbag_fwd(table, sa, sb, p, seed_a, seed_b, out, plan)
+        if plan is not None:
+            plan.sort()
+        ctx.table, ctx.saved = table, (sa, sb, p, seed_a, seed_b, plan)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        sa, sb, p, seed_a, seed_b, plan = ctx.saved
+        ctx.saved = None
+        ops.wbag_bwd(dout.contiguous(), sa, sb, p, seed_a, seed_b, plan, grad_of(ctx.table))
+        return None, None, None, None, None, None, None
+
+
+class CosineLossFn(torch.autograd.Function):
+    """(logits [B, N], loss) of DSSM's cosine click head (DSSM_model.py:35-36, DSSM_main.py:63) from the stacked tower output y = [user rows
+    [B, F] ; news rows [B * N, F]]: one launch computes both and d loss / d y, which the backward pass scales by the incoming gradient of
+    the loss.  The logits are an output for the caller's eyes only (not differentiable on their own)."""
+
+    @staticmethod
+    def forward(ctx, y, B, N):
+        y = y.contiguous()
+        F, dev = y.shape[1], y.device
+        logits = torch.empty((B, N), device=dev, dtype=torch.float32)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        dlogits = torch.empty((B, N), device=dev, dtype=torch.float32)
+        dy = torch.empty_like(y)
+        ws = torch.empty(B, device=dev, dtype=torch.float32)
+        ops.cosine_loss(y[:B], y[B:], B, N, F, logits, loss, dlogits, dy[:B], dy[B:], ws)
+        ctx.saved = dy
+        ctx.mark_non_differentiable(logits)
+        return logits, loss
+
+    @staticmethod
+    def backward(ctx, _dlogits, dloss):
+        dy, ctx.saved = ctx.saved, None
+        return dy * dloss, None, None
 
 
 class InceptionFn(torch.autograd.Function):

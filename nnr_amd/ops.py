@@ -1651,6 +1651,87 @@ def row_dist_bwd(a, b, dist, gup, coef, da, db):
                                          db.stride(0), _s()), 'nnr_row_dist_bwd')
 
 
+# ---------------------------------------------------------------------------------------------- DSSM (csrc/dssm.hip)
+WBAG_MAXE, WBAG_MAXL = 1024, 4096      # nnr_wbag_dims' rule, restated so that a constructor can refuse a size without the library
+WBAG_UNSUPPORTED = 'unsupported size (a weighted bag takes 1 <= hidden dim <= 1024 and 1 <= positions per row <= 4096)'
+
+
+def wbag_supported(E, La, Lb=0):
+    """nnr_wbag_dims' rule without a library call."""
+    return 1 <= E <= WBAG_MAXE and 1 <= La <= WBAG_MAXL and 0 <= Lb <= WBAG_MAXL
+
+
+def wbag_dims(E, La, Lb=0):
+    """(chunk length, chunks per row of stream a, of stream b) of the weighted bag; sizes beyond the rule raise WBAG_UNSUPPORTED."""
+    chunk, ca, cb = C.c_int(), C.c_int(), C.c_int()
+    L.check(L.lib().nnr_wbag_dims(E, La, Lb, C.addressof(chunk), C.addressof(ca), C.addressof(cb)), 'nnr_wbag_dims', WBAG_UNSUPPORTED, counted=False)
+    return chunk.value, ca.value, cb.value
+
+
+def _wstream(s):
+    """A weighted-bag stream (ids int32 [R, L], w f32 [R, L], sel int32 [n] or None) -> (ids, w, sel, R, n, L); None: no stream."""
+    if s is None:
+        return None, None, None, 0, 0, 0
+    ids, w, sel = s
+    R, Lx = w.shape
+    assert ids.shape == w.shape and ids.dtype == torch.int32 and w.dtype == torch.float32 and ids.is_contiguous() and w.is_contiguous()
+    assert sel is None or (sel.dtype == torch.int32 and sel.is_contiguous())
+    return ids, w, sel, R, (sel.numel() if sel is not None else R), Lx
+
+
+class WbagPlan:
+    """Occurrence list of one wbag_fwd call for its backward pass: `tok` [na * La + nb * Lb] (written by the forward launch: word id of a
+    live position, -1 elsewhere) sorted by word id on the LEAF stream behind the forward launch (csrc/sort.hip; stable, so a word's
+    occurrences keep the order stream a, stream b, row, position).  Nothing is read on the host."""
+
+    def __init__(self, cap, E, vocab, dev):
+        self.cap, self.vocab = cap, int(vocab)
+        self.tok = torch.empty(max(cap, 1), device=dev, dtype=torch.int32)[:cap]
+        self.partial = torch.empty(max(L.lib().nnr_wbag_bwd_ws_floats(cap, E), 1), device=dev, dtype=torch.float32)
+        self.event = None
+
+    def sort(self):
+        self.keys, self.pos, self.event = _sort_on_leaf(self.tok, None, self.vocab)
+
+
+def wbag_fwd(table, sa, sb, p, seed_a, seed_b, out, plan=None):
+    """out [na + nb, E] = the weighted bags of both streams (see include/nnr_hip.h); sa / sb: (ids, w, sel) as _wstream takes them, sb may
+    be None.  plan: a WbagPlan whose `tok` the launch fills.  Sizes beyond the rule raise WBAG_UNSUPPORTED."""
+    V, E = table.shape
+    ia, wa, sla, Ra, na, La = _wstream(sa)
+    ib, wb, slb, Rb, nb, Lb = _wstream(sb)
+    assert out.shape == (na + nb, E) and out.is_contiguous() and table.is_contiguous()
+    if not wbag_supported(E, La, Lb):
+        raise L.NnrHipError('nnr_wbag_fwd: ' + WBAG_UNSUPPORTED)
+    ws = torch.empty(max(L.lib().nnr_wbag_fwd_ws_floats(na, La, nb, Lb, E), 1), device=table.device, dtype=torch.float32)
+    L.check(L.lib().nnr_wbag_fwd(_p(table), V, E, _p(ia), _p(wa), _p(sla), Ra, na, La, _p(ib), _p(wb), _p(slb), Rb, nb, Lb, p, seed_a, seed_b,
+                                 _p(out), _p(plan.tok) if plan is not None else None, _p(ws), _s()), 'nnr_wbag_fwd', WBAG_UNSUPPORTED)
+    return out
+
+
+def wbag_bwd(dout, sa, sb, p, seed_a, seed_b, plan, dtable):
+    """dtable[w] += sum over w's live occurrences of keep * scale * weight * dout[row] (reproducible, no float atomics); waits for the
+    plan's sort."""
+    V, E = dtable.shape
+    _, wa, sla, Ra, na, La = _wstream(sa)
+    _, wb, slb, Rb, nb, Lb = _wstream(sb)
+    assert dout.shape == (na + nb, E) and dout.is_contiguous() and plan.cap == na * La + nb * Lb
+    torch.cuda.current_stream(dout.device).wait_event(plan.event)
+    L.check(L.lib().nnr_wbag_bwd(_p(dout), _p(plan.keys), _p(plan.pos), plan.cap, _p(wa), _p(sla), Ra, na, La, _p(wb), _p(slb), Rb, nb, Lb, V, E,
+                                 p, seed_a, seed_b, _p(dtable), _p(plan.partial), _s()), 'nnr_wbag_bwd', WBAG_UNSUPPORTED)
+
+
+def cosine_loss(user, news, B, N, F, logits, loss=None, dlogits=None, duser=None, dnews=None, ws=None):
+    """Cosine click head (+ loss and every gradient, when their buffers are given) in one launch; loss .. dnews all None: logits only."""
+    L.check(L.lib().nnr_cosine_loss(_p(user), _p(news), B, N, F, _p(logits), _p(loss), _p(dlogits), _p(duser), _p(dnews), _p(ws), _s()),
+            'nnr_cosine_loss', 'unsupported size (more than 64 candidates per sample)')
+
+
+def tanh_drop_bwd(dy, t, dz, p, seed):
+    """dz = mask(dy) * (1 - t * t): backward of y = dropout(tanh(z)) given t = tanh(z)."""
+    L.check(L.lib().nnr_tanh_drop_bwd(_p(dy), _p(t), _p(dz), dy.numel(), p, seed, _s()), 'nnr_tanh_drop_bwd')
+
+
 # ---------------------------------------------------------------------------------------------- weight layouts (nnr_permute, csrc/misc.hip)
 def _pad4(n):
     return (n + 3) & ~3

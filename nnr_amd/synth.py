@@ -161,3 +161,25 @@ def to_torch(batch, device='cpu'):
     """dict of numpy arrays -> list of 21 contiguous torch tensors in Model.forward order."""
     import torch
     return [torch.from_numpy(np.array(batch[k], copy=True)).to(device) for k in BATCH_FIELDS]
+
+
+def tfidf_rows(rng, rows, length, vocabulary_size, zipf_s=1.1, mean_fill=0.6):
+    """Term vectors shaped like DSSM_util.py:12-27 builds them from tf-idf dictionaries: ids int32 [rows, length], weights float32 [rows,
+    length].  Per row the live ids are DISTINCT, Zipf(s)-distributed over [1, vocabulary_size), their weights positive and sorted
+    descending; the tail is zero (id 0, weight 0) and of random length; with more than one row, one row is fully empty."""
+    ids = np.zeros((rows, length), dtype=np.int32)
+    w = np.zeros((rows, length), dtype=np.float32)
+    live = np.clip(np.rint(rng.normal(mean_fill, 0.25, rows) * length), 1, length).astype(np.int64)
+    if rows > 1:
+        live[int(rng.integers(rows))] = 0
+    for r in range(rows):
+        want = int(min(live[r], vocabulary_size - 1))
+        got = np.zeros(0, dtype=np.int32)
+        while got.size < want:                        # top up until `want` distinct ids are there (first-seen order)
+            draw = _zipf_ids(rng, 2 * (want - got.size) + 8, 1, vocabulary_size, zipf_s)
+            both = np.concatenate([got, draw])
+            _, first = np.unique(both, return_index=True)
+            got = both[np.sort(first)]
+        ids[r, :want] = got[:want]
+        w[r, :want] = np.sort(rng.random(want).astype(np.float32) * 0.9 + 0.05)[::-1]
+    return ids, w
