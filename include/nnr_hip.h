@@ -374,6 +374,15 @@ int nnr_sue_intra_fwd(const float* kf, const float* qc, const float* g, const lo
 int nnr_sue_intra_bwd(const float* kf, const float* qc, const float* g, const long* cidx, const float* alpha, const float* dfeat, int B,
                       int N, int Hn, int C, int A, int D, float* dg, float* dkf, float* dqc, float* ds_ws /* [B*N*Hn] scratch */,
                       hipStream_t stream);
+/* The same segmented pool in GEMV form (SUE_wo_GCN, variantEncoders.py:377-381; the key projection's bias cancels in every segment softmax,
+ * so K(x_h) . q_n = x_h . u_n with u_n = W_K^T q_n):  x [B,Hn,D], u [B*N,D], cidx int64 [B,Hn] (clamped into [0, C)) -> alpha [B,N,Hn] =
+ * softmax of scale <x_h, u_n> within each cluster, feat [B*N*C, D] = sum of alpha_h x_h over a cluster's members in ascending h (an empty
+ * cluster's row is exactly 0).  Backward: dx [B,Hn,D] is written (not accumulated), du [B*N,D] = scale sum_h ds_h x_h; ds_ws [B*N*Hn] scratch.
+ * No atomics: same inputs, same bits.  NNR_ERR_UNSUPPORTED, before any launch, unless 1 <= Hn <= 64, 1 <= C <= 32, 1 <= N <= 8, B >= 1, D >= 1. */
+int nnr_sue_seg_pool_fwd(const float* x, const float* u, const long* cidx, int B, int N, int Hn, int C, int D, float scale, float* alpha,
+                         float* feat, hipStream_t stream);
+int nnr_sue_seg_pool_bwd(const float* x, const float* u, const long* cidx, const float* alpha, const float* dfeat, int B, int N, int Hn, int C,
+                         int D, float scale, float* dx, float* du, float* ds_ws, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------ candidate-aware additive attention
  * CATT (userEncoders.py:213-220, act = 1 relu) and layers.CandidateAttention / MultipleCandidateAttention (layers.py:225-232, 254-262,

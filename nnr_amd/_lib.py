@@ -127,6 +127,8 @@ SIGNATURES = {
     'nnr_sue_slice_bwd': 'i32 ptr ptr i32 i32 i32 i32 stream',
     'nnr_sue_intra_fwd': 'i32 ptr ptr ptr ptr i32 i32 i32 i32 i32 i32 ptr ptr stream',
     'nnr_sue_intra_bwd': 'i32 ptr ptr ptr ptr ptr ptr i32 i32 i32 i32 i32 i32 ptr ptr ptr ptr stream',
+    'nnr_sue_seg_pool_fwd': 'i32 ptr ptr ptr i32 i32 i32 i32 i32 f32 ptr ptr stream',
+    'nnr_sue_seg_pool_bwd': 'i32 ptr ptr ptr ptr ptr i32 i32 i32 i32 i32 f32 ptr ptr ptr stream',
     'nnr_cand_attn_ws_floats': 'i32 i32 i32 i32 i32',
     'nnr_cand_attn_fwd': 'i32 ptr ptr ptr ptr i32 ptr i32 i32 i32 i32 i32 i32 ptr ptr stream',
     'nnr_cand_attn_bwd': 'i32 ptr ptr ptr ptr i32 ptr ptr ptr i32 i32 i32 i32 i32 i32 ptr ptr ptr i32 ptr ptr stream',

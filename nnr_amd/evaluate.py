@@ -59,7 +59,7 @@ def compute_scores_cached(model, corpus, batch_size):
     scores = torch.zeros(corpus.num, device=dev, dtype=torch.float32)
     ue = model.user_encoder
     from .model import _DotProductFn
-    need_graph = type(ue).__name__ == 'SUE'
+    need_graph = getattr(ue, 'needs_history_graph', False)     # SUE and its ablations read the graph / cluster inputs
     for start in range(0, corpus.num, batch_size):
         idx = torch.arange(start, min(start + batch_size, corpus.num), device=dev)
         h = reps[slot_h[idx]]                                  # [B, H, D]

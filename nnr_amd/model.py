@@ -106,7 +106,7 @@ class Model(nn.Module):
             self.news_encoder = newsEncoders.NAML_Content(config, word_table)
         else:
             raise Exception(config.news_encoder + ' is not on the MI355X hot path (in scope: CNE, CNN, MHSA, HDC, PNE, DAE, Inception, KCNN, NAML_Title, '
-                            'NAML_Content; SURVEY.md section 8a)')
+                            'NAML_Content; SURVEY.md section 8a; of variantEncoders.py also the user encoders SUE_wo_GCN, SUE_wo_HCA)')
         if config.user_encoder == 'SUE':
             self.user_encoder = userEncoders.SUE(self.news_encoder, config)
         elif config.user_encoder == 'MHSA':
@@ -123,8 +123,13 @@ class Model(nn.Module):
             self.user_encoder = userEncoders.FIM(self.news_encoder, config)
         elif config.user_encoder == 'GRU':
             self.user_encoder = userEncoders.GRU(self.news_encoder, config)
+        elif config.user_encoder == 'SUE_wo_GCN':
+            self.user_encoder = userEncoders.SUE_wo_GCN(self.news_encoder, config)
+        elif config.user_encoder == 'SUE_wo_HCA':
+            self.user_encoder = userEncoders.SUE_wo_HCA(self.news_encoder, config)
         else:
-            raise Exception(config.user_encoder + ' is not on the MI355X hot path (in scope: SUE, MHSA, ATT, CATT, FIM, OMAP, PUE, GRU; SURVEY.md section 8a)')
+            raise Exception(config.user_encoder + ' is not on the MI355X hot path (in scope: SUE, MHSA, ATT, CATT, FIM, OMAP, PUE, GRU; SURVEY.md section 8a; '
+                            'of variantEncoders.py the ablations SUE_wo_GCN, SUE_wo_HCA)')
         self.model_name = config.news_encoder + '-' + config.user_encoder
         self.news_embedding_dim = self.news_encoder.news_embedding_dim
         self.dropout = nn.Dropout(p=config.dropout_rate)                    # (model.py:77: part of the attribute surface; the user rows'

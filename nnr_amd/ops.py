@@ -1219,6 +1219,31 @@ def _sue_intra_bwd(kf, qc, g, cidx, alpha, dfeat, B, N, Hn, Cn, A, D, dg, dkf, d
                                       _p(ws), _s()), 'nnr_sue_intra_bwd')
 
 
+SEG_POOL_MAXH, SEG_POOL_MAXC, SEG_POOL_MAXN = 64, 32, 8      # nnr_sue_seg_pool_*'s rule (the limits of sue_intra_*), restated for the constructors
+SEG_POOL_UNSUPPORTED = 'unsupported size (the segmented candidate pool takes 1 <= history slots <= 64, 1 <= clusters <= 32 and 1 <= candidates <= 8)'
+
+
+def seg_pool_supported(Hn, Cn, N=1, D=1, B=1):
+    """Host mirror of nnr_sue_seg_pool_*'s rule (csrc/seg_pool.hip), for the constructors: no library call, no device."""
+    return int(B) >= 1 and 1 <= int(N) <= SEG_POOL_MAXN and 1 <= int(Hn) <= SEG_POOL_MAXH and 1 <= int(Cn) <= SEG_POOL_MAXC and int(D) >= 1
+
+
+def sue_seg_pool_fwd(x, u, cidx, B, N, Hn, Cn, D, scale, alpha, feat):
+    """x [B, Hn, D], u [B*N, D], cidx int64 [B, Hn] -> alpha [B, N, Hn], feat [B*N*Cn, D]: the intra-cluster attention of SUE_wo_GCN with the
+    key projection folded into the query (u = q W_K)."""
+    L.check(L.lib().nnr_sue_seg_pool_fwd(_p(x), _p(u), _p(cidx), B, N, Hn, Cn, D, scale, _p(alpha), _p(feat), _s()), 'nnr_sue_seg_pool_fwd',
+            SEG_POOL_UNSUPPORTED)
+
+
+def sue_seg_pool_bwd(x, u, cidx, alpha, dfeat, B, N, Hn, Cn, D, scale, dx, du):
+    """dx [B, Hn, D] is written (not accumulated), du [B*N, D] too."""
+    if not seg_pool_supported(Hn, Cn, N, D, B):          # (before the scratch allocation, whose size the arguments give)
+        raise L.NnrHipError('nnr_sue_seg_pool_bwd: ' + SEG_POOL_UNSUPPORTED)
+    ws = torch.empty(B * N * Hn, device=x.device, dtype=torch.float32)
+    L.check(L.lib().nnr_sue_seg_pool_bwd(_p(x), _p(u), _p(cidx), _p(alpha), _p(dfeat), B, N, Hn, Cn, D, scale, _p(dx), _p(du), _p(ws), _s()),
+            'nnr_sue_seg_pool_bwd', SEG_POOL_UNSUPPORTED)
+
+
 def _u8(mask):
     return None if mask is None else (mask.view(torch.uint8) if mask.dtype == torch.bool else mask)
 

@@ -327,6 +327,7 @@ def _sue_backward_body(mod, sv, dout, leaf, B, Hn, D, N, Kc, G, Cn, A, p, seed, 
 
 class SUE(UserEncoder):
     """userEncoders.py:42-98."""
+    needs_history_graph = True           # evaluate.compute_scores_cached builds the graph / cluster inputs for such an encoder
 
     def __init__(self, news_encoder: NewsEncoder, config):
         super().__init__(news_encoder, config)
@@ -362,6 +363,200 @@ class SUE(UserEncoder):
         cidx = user_history_category_indices.contiguous()
         assert cidx.dtype == torch.int64 and graph.dtype == torch.float32
         return _SUEFunction.apply(history_embedding, candidate_news_representation, self, graph, user_history_category_mask, cidx)
+
+
+def _fix_cluster_mask(cmask):
+    """user_history_category_mask[:, -1] = 1, in place on the caller's tensor (userEncoders.py:73, variantEncoders.py:369)."""
+    if cmask.is_cuda and cmask.dim() == 2 and cmask.is_contiguous() and cmask.element_size() == 1:
+        ops.fill_column_u8(cmask, -1, 1)                # (a C-ABI call: recordable)
+    else:
+        cmask[:, -1] = 1
+
+
+class _SueWoGcnFn(torch.autograd.Function):
+    """SUE_wo_GCN after the news encoder (variantEncoders.py:369-390): SUE's pipeline from the intra-cluster attention on, straight on the
+    history representations.  The intra stage runs in GEMV form (ops.sue_seg_pool_*): intraCluster_K.bias shifts every score of a
+    (user, candidate) alike and cancels in each segment softmax, so the scores are x_h . u_n / sqrt(A) with u = Q(c) W_K -- one [B N, A] x
+    [A, D] product instead of the [B Hn, D] x [D, A] key projection and its two backward products.  Dropout site as SUE's: seed + 2, flat
+    over [B N C, D].  Parameter gradients accumulate into .grad (weight-gradient GEMMs on the leaf stream, joined before this returns);
+    the data-parallel early-bucket hook is SUE's alone and is not fired here."""
+
+    @staticmethod
+    def forward(ctx, hist, cand, mod, cmask, cidx):
+        hist, cand = hist.contiguous(), cand.contiguous()
+        B, Hn, D = hist.shape
+        N, Cn, A = cand.shape[1], mod.category_num, mod.attention_dim
+        f32 = dict(device=hist.device, dtype=torch.float32)
+        p = mod.dropout_rate if mod.training else 0.0
+        seed = mod._next_seed()
+        scale = 1.0 / math.sqrt(A)
+        _fix_cluster_mask(cmask)
+        cand2 = cand.view(B * N, D)
+        ia = mod.interClusterAttention
+        qc = ops.linear_fwd(cand2, mod.intraCluster_Q.weight, mod.intraCluster_Q.bias)                  # [B*N, A]
+        u = torch.empty((B * N, D), **f32)
+        ops.gemm(qc, mod.intraCluster_K.weight, u, M=B * N, N=D, K=A, lda=A, ldb=D, ldc=D, trans_b=True)   # W_K^T q
+        qv = ops.linear_fwd(cand2, ia.Q.weight, ia.Q.bias)                                               # [B*N, A]
+        v = torch.empty((B * N, D), **f32)
+        ops.gemm(qv, ia.K.weight, v, M=B * N, N=D, K=A, lda=A, ldb=D, ldc=D, trans_b=True)
+        # ---- intra-cluster attention
+        alpha_i = torch.empty((B, N, Hn), **f32)
+        feat = torch.empty((B * N * Cn, D), **f32)
+        ops.sue_seg_pool_fwd(hist, u, cidx, B, N, Hn, Cn, D, scale, alpha_i, feat)
+        # ---- cluster feature affine: dropout(relu(W F + b) + F)
+        rc = torch.empty((B * N * Cn, D), **f32)
+        f2 = torch.empty((B * N * Cn, D), **f32)
+        aff = mod.clusterFeatureAffine
+        ops.gemm(feat, aff.weight, f2, M=B * N * Cn, N=D, K=D, lda=D, ldb=D, ldc=D, bias=aff.bias, act=ops.ACT_RELU, aux_out=rc, ldaux=D,
+                 resid=feat, ldres=D, drop=(3, p, seed + 2, D))
+        # ---- inter-cluster attention (layers.py:196-203) in GEMV form
+        alpha_o = torch.empty(B * N * Cn, **f32)
+        out = torch.empty((B * N, D), **f32)
+        ops.pool_fwd(x=f2, ldx=D, D=D, n=B * N, Lx=Cn, mask=cmask, mask_div=N, v=v, ldv=D, scale=scale, alpha=alpha_o, out=out, ldo=D)
+        ctx.mod = mod
+        ctx.saved = dict(B=B, Hn=Hn, D=D, N=N, Cn=Cn, A=A, p=p, seed=seed, scale=scale, hist=hist, cand2=cand2, cmask=cmask, cidx=cidx, qc=qc,
+                         u=u, qv=qv, v=v, alpha_i=alpha_i, feat=feat, rc=rc, f2=f2, alpha_o=alpha_o)
+        return out.view(B, N, D)
+
+    @staticmethod
+    def backward(ctx, dout):
+        mod, sv = ctx.mod, ctx.saved
+        ctx.saved = None
+        B, Hn, D, N, Cn, A, p, seed, scale = (sv[k] for k in ('B', 'Hn', 'D', 'N', 'Cn', 'A', 'p', 'seed', 'scale'))
+        f32 = dict(device=dout.device, dtype=torch.float32)
+        dout = dout.contiguous().view(B * N, D)
+        cand2, ia, aff = sv['cand2'], mod.interClusterAttention, mod.clusterFeatureAffine
+        with ops.leaf_scope(dout.device) as leaf:
+            # ---- inter-cluster pool
+            df2 = torch.empty((B * N * Cn, D), **f32)
+            dv = torch.empty((B * N, D), **f32)
+            ops.pool_bwd(x=sv['f2'], ldx=D, D=D, n=B * N, Lx=Cn, mask=sv['cmask'], mask_div=N, v=sv['v'], ldv=D, scale=scale, alpha=sv['alpha_o'],
+                         dout=dout, lddo=D, dx=df2, lddx=D, dv=dv, lddv=D)
+            dqv = torch.empty((B * N, A), **f32)
+            ops.gemm(dv, ia.K.weight, dqv, M=B * N, N=A, K=D, lda=D, ldb=D, ldc=A)
+            leaf(lambda: (ops.linear_bwd_weight(sv['qv'], dv, grad_of(ia.K.weight)),
+                          ops.linear_bwd_weight(dqv, cand2, grad_of(ia.Q.weight), db=grad_of(ia.Q.bias))), dv, dqv)
+            dcand = ops.linear_bwd_data(dqv, ia.Q.weight)                                                # [B*N, D]
+            # ---- cluster affine
+            dS = torch.empty((B * N * Cn, D), **f32)
+            dfeat = torch.empty((B * N * Cn, D), **f32)
+            ops.relu_drop_bwd(df2, sv['rc'], dS, dfeat, p, seed + 2)
+            ops.linear_bwd_data(dS, aff.weight, out=dfeat, accumulate=True)
+            leaf(lambda: ops.linear_bwd_weight(dS, sv['feat'], grad_of(aff.weight), db=grad_of(aff.bias)), dS)
+            # ---- intra-cluster attention
+            dhist = torch.empty((B, Hn, D), **f32)
+            du = torch.empty((B * N, D), **f32)
+            ops.sue_seg_pool_bwd(sv['hist'], sv['u'], sv['cidx'], sv['alpha_i'], dfeat, B, N, Hn, Cn, D, scale, dhist, du)
+            dqc = torch.empty((B * N, A), **f32)
+            ops.gemm(du, mod.intraCluster_K.weight, dqc, M=B * N, N=A, K=D, lda=D, ldb=D, ldc=A)      # du W_K^T
+            grad_of(mod.intraCluster_K.bias)                                                            # (exactly zero: the bias cancels)
+            leaf(lambda: (ops.linear_bwd_weight(sv['qc'], du, grad_of(mod.intraCluster_K.weight)),
+                          ops.linear_bwd_weight(dqc, cand2, grad_of(mod.intraCluster_Q.weight), db=grad_of(mod.intraCluster_Q.bias))), du, dqc)
+            ops.linear_bwd_data(dqc, mod.intraCluster_Q.weight, out=dcand, accumulate=True)
+        return dhist, dcand.view(B, N, D), None, None, None
+
+
+class SUE_wo_GCN(UserEncoder):
+    """variantEncoders.py:342-390, the ablation of SUE without the GCN: hierarchical cluster attention on the news encoder's history output
+    (no proxy nodes, no graph, no slice).  intraCluster_K carries the reference's bias, which cannot change the output (see _SueWoGcnFn): it
+    stays a parameter so that a reference state_dict loads unchanged, and its gradient is exactly zero."""
+    needs_history_graph = True
+
+    def __init__(self, news_encoder: NewsEncoder, config):
+        super().__init__(news_encoder, config)
+        self.attention_dim = max(config.attention_dim, self.news_embedding_dim // 4)
+        self.intraCluster_K = nn.Linear(self.news_embedding_dim, self.attention_dim, bias=True)
+        self.intraCluster_Q = nn.Linear(self.news_embedding_dim, self.attention_dim, bias=True)
+        self.clusterFeatureAffine = nn.Linear(self.news_embedding_dim, self.news_embedding_dim, bias=True)
+        self.interClusterAttention = ScaledDotProduct_CandidateAttention(self.news_embedding_dim, self.news_embedding_dim, self.attention_dim)
+        self.dropout_rate = float(config.dropout_rate)
+        self.category_num = config.category_num + 1     # extra one category index for padding news
+        self.max_history_num = config.max_history_num
+        self.attention_scalar = math.sqrt(float(self.attention_dim))
+        if not ops.seg_pool_supported(self.max_history_num, self.category_num, config.negative_sample_num + 1):
+            raise Exception('SUE_wo_GCN: ' + ops.SEG_POOL_UNSUPPORTED)
+
+    def initialize(self):
+        nn.init.xavier_uniform_(self.intraCluster_K.weight)
+        nn.init.zeros_(self.intraCluster_K.bias)
+        nn.init.xavier_uniform_(self.intraCluster_Q.weight)
+        nn.init.zeros_(self.intraCluster_Q.bias)
+        nn.init.xavier_uniform_(self.clusterFeatureAffine.weight, gain=nn.init.calculate_gain('relu'))
+        nn.init.zeros_(self.clusterFeatureAffine.bias)
+        self.interClusterAttention.initialize()
+
+    def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
+                    user_history_category_indices, candidate_news_representation):
+        cidx = user_history_category_indices.contiguous()
+        assert cidx.dtype == torch.int64
+        return _SueWoGcnFn.apply(history_embedding, candidate_news_representation, self, user_history_category_mask, cidx)
+
+
+class _SueGcnFeatureFn(torch.autograd.Function):
+    """(gcn([history ; dropout_(proxy nodes)]) + X0)[:, :max_history_num] (variantEncoders.py:414-416) on SUE's own launches, with SUE's
+    dropout sites: the proxy nodes at seed + 1, GCN layer l at seed + 10 + l with p / 2.  The cluster mask is not touched."""
+
+    @staticmethod
+    def forward(ctx, hist, mod, graph):
+        hist = hist.contiguous()
+        B, Hn, D = hist.shape
+        Kc = mod.proxy_node_embedding.shape[0]
+        G = Hn + Kc
+        f32 = dict(device=hist.device, dtype=torch.float32)
+        p = mod.dropout_rate if mod.training else 0.0
+        seed = mod._next_seed()
+        x0 = torch.empty((B, G, D), **f32)
+        ops.sue_x0_fwd(hist, mod.proxy_node_embedding, x0, B, Hn, Kc, D, p, seed + 1)
+        x, gsv = gcn_forward(mod.gcn, x0, graph, seed + 10, mod.training)
+        gfeat = torch.empty((B, Hn, D), **f32)
+        ops.sue_slice_fwd(x, x0, gfeat, B, Hn, G, D)
+        ctx.mod, ctx.saved = mod, (gsv, graph, B, Hn, Kc, G, D, p, seed)
+        return gfeat
+
+    @staticmethod
+    def backward(ctx, dg):
+        mod = ctx.mod
+        gsv, graph, B, Hn, Kc, G, D, p, seed = ctx.saved
+        ctx.saved = None
+        f32 = dict(device=dg.device, dtype=torch.float32)
+        dpad = torch.empty((B, G, D), **f32)
+        ops.sue_slice_bwd(dg.contiguous(), dpad, B, Hn, G, D)
+        with ops.leaf_scope(dg.device) as leaf:
+            dy = gcn_backward(mod.gcn, gsv, dpad, graph, leaf)
+            dhist = torch.empty((B, Hn, D), **f32)
+            ops.sue_x0_bwd(dy, dhist, grad_of(mod.proxy_node_embedding), B, Hn, Kc, D, p, seed + 1, dx0_add=dpad)      # d(gcn(X0) + X0)
+        return dhist, None, None
+
+
+class SUE_wo_HCA(UserEncoder):
+    """variantEncoders.py:393-419, the ablation of SUE without the hierarchical cluster attention: the GCN over [history ; proxy nodes] with
+    its outer residual, the first max_history_num rows, one UNMASKED additive attention (padded history slots take part), the user vector
+    repeated over the candidates.  Reads neither the candidates nor any mask nor the cluster indices, and does not write the cluster mask."""
+    needs_history_graph = True
+
+    def __init__(self, news_encoder: NewsEncoder, config):
+        super().__init__(news_encoder, config)
+        self.max_history_num = config.max_history_num
+        self.proxy_node_embedding = nn.Parameter(torch.zeros([config.category_num, self.news_embedding_dim]))
+        self.gcn = GCN(in_dim=self.news_embedding_dim, out_dim=self.news_embedding_dim, hidden_dim=self.news_embedding_dim,
+                       num_layers=config.gcn_layer_num, dropout=config.dropout_rate / 2, residual=not config.no_gcn_residual,
+                       layer_norm=config.gcn_layer_norm)
+        self.attention = Attention(self.news_embedding_dim, config.attention_dim)
+        self.dropout_rate = float(config.dropout_rate)
+
+    def initialize(self):
+        nn.init.zeros_(self.proxy_node_embedding)
+        self.gcn.initialize()
+        self.attention.initialize()
+
+    def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
+                    user_history_category_indices, candidate_news_representation):
+        from . import functional as Fn
+        graph = user_history_graph.contiguous()
+        assert graph.dtype == torch.float32
+        gfeat = _SueGcnFeatureFn.apply(history_embedding, self, graph)
+        return Fn.ExpandFn.apply(self.attention(gfeat), candidate_news_representation.size(1))
+
 
 class MHSA(UserEncoder):
     """userEncoders.py:151-173.  Note F.dropout's default p = 0.5 (not dropout_rate) at :171 and the UNMASKED pool at :172."""

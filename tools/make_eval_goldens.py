@@ -190,8 +190,17 @@ def run_fim():
         maxpooling3D_stride=2)
 
 
+def run_sue_ablation():
+    """`python tools/make_eval_goldens.py sue_ablation`: the two user-encoder ablations of variantEncoders.py under CNN."""
+    run('tiny_CNN_SUE_wo_GCN', 'CNN', 'SUE_wo_GCN', False, min_gap=1e-4)
+    run('tiny_CNN_SUE_wo_HCA', 'CNN', 'SUE_wo_HCA', False, min_gap=1e-4)
+
+
 if __name__ == '__main__':
     torch.set_num_threads(4)
+    if len(sys.argv) > 1 and sys.argv[1] == 'sue_ablation':
+        run_sue_ablation()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'fim':
         run_fim()
         sys.exit(0)
@@ -228,3 +237,4 @@ if __name__ == '__main__':
     run_fim()
     run_gru()
     run_naml()
+    run_sue_ablation()

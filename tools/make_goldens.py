@@ -22,6 +22,7 @@ Usage:  python tools/make_goldens.py            (rewrites every fixture)
         python tools/make_goldens.py fim        (the HDC news encoder, the FIM user encoder and the FIM click head)
         python tools/make_goldens.py gru        (the GRU user encoder of DAE-GRU)
         python tools/make_goldens.py naml       (the single-view NAML news encoders NAML_Title / NAML_Content)
+        python tools/make_goldens.py sue_ablation   (the user-encoder ablations SUE_wo_GCN / SUE_wo_HCA)
 """
 import os
 import pickle
@@ -240,7 +241,9 @@ def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True
             getattr(ne64, stream + '_conv').conv.register_forward_hook(lambda mod, i, o: naml64.setdefault('z', []).append(o.detach().permute(0, 2, 1).clone().numpy()))
             ne64.category_affine.register_forward_hook(lambda mod, i, o: naml64.setdefault('za', []).append(o.detach().clone().numpy()))
             ne64.subCategory_affine.register_forward_hook(lambda mod, i, o: naml64.setdefault('zs', []).append(o.detach().clone().numpy()))
-        logits64 = m64(*to_torch(batch))
+        inp64 = to_torch(batch)
+        inp64[10] = inp64[10].double()          # user_history_graph: torch.bmm (layers.py:286) does not promote
+        logits64 = m64(*inp64)
         loss64 = (-torch.log_softmax(logits64, dim=1).select(dim=1, index=0)).mean()
         for e in (m64.news_encoder, m64.user_encoder):
             if e.auxiliary_loss is not None:
@@ -738,6 +741,75 @@ def naml_cases(search=False):
     check('full_NAML_Title_ATT_g1p0')
 
 
+def sue_ablation_conditions(z):
+    """The four conditions a tiny sue_ablation batch must meet (tests/test_sue_ablation_host.py asserts the same): a user without history and
+    one with a full history; a cluster with at least two members; a cluster that is empty but unmasked (the mask as SUE_wo_GCN reads it: last
+    column set); clusterFeatureAffine.bias / the proxy nodes visibly non-zero."""
+    hm = z['in/user_history_mask'].astype(bool)
+    cidx = z['in/user_history_category_indices']
+    cmask = z['in/user_history_category_mask'].astype(bool).copy()
+    cmask[:, -1] = True
+    lens = hm.sum(axis=1)
+    counts = np.stack([(cidx == c).sum(axis=1) for c in range(cmask.shape[1])], axis=1)          # [B, category_num + 1]
+    pre = 'param1/user_encoder.'
+    big = [float(np.abs(z[pre + k]).max()) for k in ('clusterFeatureAffine.bias', 'proxy_node_embedding') if pre + k in z.files]
+    return dict(empty_user=bool((lens == 0).any()), full_user=bool((lens == hm.shape[1]).any()), multi_member=bool((counts >= 2).any()),
+                empty_unmasked=bool(((counts == 0) & cmask).any()), visible=bool(big) and min(big) > 1e-2), lens
+
+
+def sue_ablation_cases():
+    """The user-encoder ablations of the paper's own model (`python tools/make_goldens.py sue_ablation`; variantEncoders.py:342-419):
+    SUE_wo_GCN and SUE_wo_HCA under the CNN and CNE news encoders, make_state weights (gain 2.0 tiny, 1.0 full: matrices AND biases drawn at
+    random, so clusterFeatureAffine.bias and the proxy nodes -- zero after initialize() -- take part), three Adam steps, the tiny cases with
+    step 0 of a float64 run of the same classes (`f64/...`).  tiny_CNN_SUE_wo_HCA_ln: --gcn_layer_norm, one Adam step (see extra_cases).
+    Every tiny batch meets sue_ablation_conditions: the batch seed is the first from the starting value for which it does (tiny_spec(cfg, 3)
+    at batch 8 from seed 19 gives history lengths [2,0,4,0,4,5,0,1]: no full user)."""
+    def pick(cfg, sseed, bs, seed):
+        while True:
+            b = SynthCorpus(tiny_spec(cfg, sseed)).batch(bs, np.random.default_rng(seed + 100))
+            ok, _ = sue_ablation_conditions(_NoFiles({'in/' + k: b[k] for k in ('user_history_mask', 'user_history_category_indices',
+                                                                                 'user_history_category_mask')}))
+            if all(v for k, v in ok.items() if k != 'visible'):
+                return seed
+            seed += 1
+
+    def check(tag, tiny):
+        z = np.load(os.path.join(OUT, tag + '.npz'))
+        ok, lens = sue_ablation_conditions(z)
+        total = float(z['grad_total_norm'])
+        share = {k[len('gradnorm/user_encoder.'):]: round(float(z[k]) / total, 4) for k in z.files
+                 if k.startswith('gradnorm/user_encoder.') and not k.startswith('gradnorm/user_encoder.news_encoder.')}
+        print('  %s: history lengths %s, %s, |g| / |g_total| %s, %d bytes' % (tag, lens.tolist(), ok, share, os.path.getsize(os.path.join(OUT, tag + '.npz'))))
+        assert os.path.getsize(os.path.join(OUT, tag + '.npz')) < 350000, tag
+        if tiny:
+            assert all(ok.values()), (tag, ok)
+        kb = 'grad/user_encoder.intraCluster_K.bias'
+        if kb in z.files:
+            qmax = float(np.abs(z['grad/user_encoder.intraCluster_Q.bias']).max())
+            print('  %s: max|d intraCluster_K.bias| %.2e, max|d intraCluster_Q.bias| %.2e' % (tag, float(np.abs(z[kb]).max()), qmax))
+            assert float(np.abs(z[kb]).max()) < 1e-5 * qmax, tag
+
+    for user in ('SUE_wo_GCN', 'SUE_wo_HCA'):
+        cfg = tiny_cfg('CNN', user)
+        run_case('tiny_CNN_%s' % user, cfg, tiny_spec(cfg, 3), batch_size=8, seed=pick(cfg, 3, 8, 19), mode='train', gain=2.0, f64_step=True)
+        check('tiny_CNN_%s' % user, True)
+        with stable_sort_patch():
+            cfg = tiny_cfg('CNE', user)
+            run_case('tiny_CNE_%s_stable' % user, cfg, tiny_spec(cfg, 3), batch_size=8, seed=pick(cfg, 3, 8, 19), mode='train', gain=2.0, f64_step=True)
+        check('tiny_CNE_%s_stable' % user, True)
+        cfg = full_cfg('CNN', user, V=400)
+        run_case('full_CNN_%s_g1p0' % user, cfg, full_spec(cfg, 9), batch_size=2, seed=17, mode='train', gain=1.0, full_arrays=False)
+        check('full_CNN_%s_g1p0' % user, False)
+    cfg = tiny_cfg('CNN', 'SUE_wo_HCA', gcn_layer_norm=True)
+    run_case('tiny_CNN_SUE_wo_HCA_ln', cfg, tiny_spec(cfg, 3), batch_size=8, seed=pick(cfg, 3, 8, 19), mode='train', gain=2.0, adam_steps=1, f64_step=True)
+    check('tiny_CNN_SUE_wo_HCA_ln', True)
+
+
+class _NoFiles(dict):
+    """A plain dict of batch arrays as sue_ablation_conditions' argument: no stored parameters."""
+    files = ()
+
+
 KCNN_SEEDS = {'tiny_KCNN_CATT': 55, 'tiny_KCNN_ATT': 54}      # (53, 54 and 53 miss the margin: 2.3e-4, 4.3e-4 and 1.8e-4 of the scale)
 
 
@@ -751,6 +823,9 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == 'gru':
         torch.set_num_threads(8)
         return gru_cases()
+    if len(sys.argv) > 1 and sys.argv[1] == 'sue_ablation':
+        torch.set_num_threads(8)
+        return sue_ablation_cases()
     if len(sys.argv) > 1 and sys.argv[1] == 'kcnn':
         torch.set_num_threads(8)
         return kcnn_cases()
