@@ -10,15 +10,12 @@
 //     of (word, position) pairs ordered by word for the backward pass, and the counts as floats.
 //   * bag_mean_bwd_kernel / bag_mean_bwd_fix_kernel: dtable[w] += sum over the live occurrences (r, pos) of w of g[r] / count[r], with
 //     g[r] = dout[r] (or dout[r] * out[r] * (1 - out[r]) behind the sigmoid) read from the owning news' row through the sorted position
-//     (r = pos / (La + Lb)): n rows that stay in L2, not one row per token.  One wave sums a chunk of 32 sorted occurrences in list
-//     order; a word whose occurrences lie inside one chunk is added to its table row by that wave alone with a plain read-add-write, a
-//     run that crosses a chunk boundary is stored as a partial row, and the workgroup whose chunk holds the START of such a word adds
-//     the partial rows in chunk order and writes the table row.  Every table row has exactly one writer: no float atomics, same bits
-//     every run.  (The chunk / partial geometry and the boundary rules are csrc/sort.hip's: keep the two copies in step.)
+//     (r = pos / (La + Lb)): n rows that stay in L2, not one row per token.  The reduction is csrc/sorted_rows.h's (chunks of 32, 8 rows
+//     in flight in both passes, plain adds: every table row has exactly one writer, no float atomics, same bits every run).
 //   * row_dist_fwd_kernel / row_dist_bwd_kernel: aux[r] = coef * ||a[r] - b[r]||_2 and its backward into both operands; one wave per row.
 // Row loads are 16-byte vectors when E % 4 == 0, 8-byte vectors when E % 2 == 0 (a row of E = 50 floats starts on an 8-byte boundary
 // only), scalars otherwise.
-#include "common.h"
+#include "sorted_rows.h"
 
 namespace {
 
@@ -26,18 +23,7 @@ constexpr int BAG_MAXL = 128;      // positions per stream: two ballots
 constexpr int BAG_MAXE = 320;      // floats per row: 5 columns per lane in the backward pass
 constexpr int BAG_CH = 32;         // sorted occurrences per wave
 constexpr int BAG_MAXJ = 5;
-constexpr int BAG_FL = 8;          // rows in flight per wave
-constexpr int BAG_PITCH = 64 * BAG_MAXJ;
-
-template <int VEC> struct VecT;
-template <> struct VecT<4> { typedef float4 type; };
-template <> struct VecT<2> { typedef float2 type; };
-template <> struct VecT<1> { typedef float type; };
-
-template <int VEC> __device__ __forceinline__ void vec_get(const typename VecT<VEC>::type& v, float (&f)[VEC]);
-template <> __device__ __forceinline__ void vec_get<4>(const float4& v, float (&f)[4]) { f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w; }
-template <> __device__ __forceinline__ void vec_get<2>(const float2& v, float (&f)[2]) { f[0] = v.x; f[1] = v.y; }
-template <> __device__ __forceinline__ void vec_get<1>(const float& v, float (&f)[1]) { f[0] = v; }
+constexpr int BAG_FL = 8;          // rows in flight per wave, both passes
 
 // ---- forward: one wave per news row
 template <int VEC>
@@ -154,168 +140,44 @@ __global__ __launch_bounds__(256) void bag_mean_fwd_kernel(const float* __restri
   }
 }
 
-// ---- backward, pass 1: one wave per chunk of BAG_CH sorted occurrences
+// ---- backward: csrc/sorted_rows.h over the sorted occurrences.  An entry is a position p of `tok`; it adds g[r] / count with r = p / (La + Lb)
+struct BagRows {
+  struct Rec { int r, off; float cnt; };
+  static constexpr int NV = 2;                                     // the gradient row, and the output row behind the sigmoid
+  const float *dout, *outp, *count;
+  const int* poss;
+  int lddo, ldo, off_a, off_b, La, Lb, n, separate;
+  __device__ Rec pad() const { return {0, off_a, 1.f}; }
+  __device__ Rec record(long i, bool live) const {
+    if (!live) return pad();
+    const int Lt = La + Lb;
+    const int p = poss[i];
+    const int r = min(max(p / Lt, 0), n - 1);
+    const bool isb = (p - r * Lt) >= La;
+    return {r, (separate && isb) ? off_b : off_a, count[(separate && isb) ? n + r : r]};
+  }
+  __device__ int nv() const { return outp ? 2 : 1; }
+  __device__ const Rec& prep(const Rec& e) const { return e; }
+  __device__ const float* row(const Rec& e, int k) const { return k ? outp + (long)e.r * ldo + e.off : dout + (long)e.r * lddo + e.off; }
+  __device__ float addend(const Rec& e, int, bool in, const float (&v)[2]) const {
+    float g = in ? v[0] : 0.f;
+    if (outp) g = in ? g * v[1] * (1.f - v[1]) : 0.f;
+    return g / e.cnt;
+  }
+};
+
 __global__ __launch_bounds__(256) void bag_mean_bwd_kernel(const float* __restrict__ dout, int lddo, const float* __restrict__ outp, int ldo,
                                                            int off_a, int off_b, const float* __restrict__ count,
                                                            const unsigned* __restrict__ keys, const int* __restrict__ poss, long cap, int La,
                                                            int Lb, int n, unsigned V, int E, int separate, float* __restrict__ dtable,
                                                            float* __restrict__ partial) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long c = blockIdx.x * 4L + wv;
-  const long p0 = c * BAG_CH;
-  if (p0 >= cap) return;
-  const long p1 = min(cap, p0 + BAG_CH);
-  const int cnt = (int)(p1 - p0);
-  const int Lt = La + Lb;
-  unsigned myk = V;
-  int myr = 0, myo = off_a;
-  float myc = 1.f;
-  if (lane < cnt) {
-    myk = keys[p0 + lane];
-    if (myk < V) {
-      const int p = poss[p0 + lane];
-      const int r = min(max(p / Lt, 0), n - 1);
-      const bool isb = (p - r * Lt) >= La;
-      myr = r;
-      myo = (separate && isb) ? off_b : off_a;
-      myc = count[(separate && isb) ? n + r : r];
-    }
-  }
-  const unsigned k0 = __shfl(myk, 0, 64);
-  if (k0 >= V) return;                                            // sorted: nothing but pad entries from here on
-  const unsigned prevK = p0 > 0 ? keys[p0 - 1] : 0xFFFFFFFFu;     // (0xFFFFFFFF equals no valid key)
-  const unsigned nextK = p1 < cap ? keys[p1] : 0xFFFFFFFFu;
-  float acc[BAG_MAXJ];
-#pragma unroll
-  for (int j = 0; j < BAG_MAXJ; ++j) acc[j] = 0.f;
-  unsigned run_key = k0;
-  bool first = true;
-  auto flush = [&](bool open_right) {
-    const bool open_left = first && prevK == run_key;
-    if (!open_left && !open_right) {                              // the whole segment of this word: this wave is the row's only writer
-#pragma unroll
-      for (int j = 0; j < BAG_MAXJ; ++j) {
-        const int col = lane + 64 * j;
-        if (col < E) dtable[(long)run_key * E + col] += acc[j];
-      }
-    } else {
-      float* dst = partial + (c * 2 + (first ? 0 : 1)) * (long)BAG_PITCH;
-#pragma unroll
-      for (int j = 0; j < BAG_MAXJ; ++j) dst[lane + 64 * j] = acc[j];
-    }
-  };
-  bool done = false;
-  const int elast = E - 1;
-  for (int i0 = 0; i0 < cnt && !done; i0 += BAG_FL) {
-    float v[BAG_FL][BAG_MAXJ], o[BAG_FL][BAG_MAXJ];
-    unsigned kk[BAG_FL];
-    int rr[BAG_FL], oo[BAG_FL];
-    float cc[BAG_FL];
-#pragma unroll
-    for (int u = 0; u < BAG_FL; ++u) {
-      const int i = i0 + u;                                       // (< 64: lanes >= cnt hold the pad key, row 0 and count 1)
-      kk[u] = __shfl(myk, i, 64);
-      rr[u] = __shfl(myr, i, 64);
-      oo[u] = __shfl(myo, i, 64);
-      cc[u] = __shfl(myc, i, 64);
-    }
-#pragma unroll
-    for (int u = 0; u < BAG_FL; ++u) {
-      const float* src = dout + (long)rr[u] * lddo + oo[u];
-#pragma unroll
-      for (int j = 0; j < BAG_MAXJ; ++j) v[u][j] = src[min(lane + 64 * j, elast)];
-      if (outp) {
-        const float* so = outp + (long)rr[u] * ldo + oo[u];
-#pragma unroll
-        for (int j = 0; j < BAG_MAXJ; ++j) o[u][j] = so[min(lane + 64 * j, elast)];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < BAG_FL; ++u) {
-      if (done) break;
-      if (kk[u] >= V) { done = true; break; }
-      if (kk[u] != run_key) {
-        flush(false);
-        run_key = kk[u];
-        first = false;
-#pragma unroll
-        for (int j = 0; j < BAG_MAXJ; ++j) acc[j] = 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < BAG_MAXJ; ++j) {
-        const int col = lane + 64 * j;
-        float g = col < E ? v[u][j] : 0.f;
-        if (outp) g = col < E ? g * o[u][j] * (1.f - o[u][j]) : 0.f;
-        acc[j] += g / cc[u];
-      }
-    }
-  }
-  flush(nextK == run_key);                                        // (a chunk that ran into pad entries has nextK = pad: closed)
+  sorted_rows::pass1<BAG_CH, BAG_MAXJ, BAG_FL, false, false>(BagRows{dout, outp, count, poss, lddo, ldo, off_a, off_b, La, Lb, n, separate}, keys, cap, V, E,
+                                                      dtable, partial);
 }
 
-// ---- backward, pass 2: the workgroup of the chunk in which a multi-chunk word STARTS adds its partial rows in chunk order
 __global__ __launch_bounds__(256) void bag_mean_bwd_fix_kernel(const unsigned* __restrict__ keys, long cap, unsigned V, int E,
                                                                float* __restrict__ dtable, const float* __restrict__ partial) {
-  __shared__ float red[4][BAG_PITCH];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long nchunks = (cap + BAG_CH - 1) / BAG_CH;
-  for (int ci = 0; ci < 4; ++ci) {
-    const long c = blockIdx.x * 4L + ci;
-    const long p0 = c * BAG_CH;
-    if (p0 >= cap) break;                                          // (uniform over the workgroup, like every branch below)
-    const long p1 = min(cap, p0 + BAG_CH);
-    const unsigned k0 = keys[p0];
-    if (k0 >= V) break;
-    const unsigned prevK = p0 > 0 ? keys[p0 - 1] : 0xFFFFFFFFu;
-    const unsigned kl = keys[p1 - 1];
-    const unsigned nextK = p1 < cap ? keys[p1] : 0xFFFFFFFFu;
-    for (int cand = 0; cand < 2; ++cand) {
-      // cand 0: the chunk's first run, if the word STARTS here and runs on into the next chunk; cand 1: its last run, likewise
-      const unsigned key = cand == 0 ? k0 : kl;
-      const bool own = cand == 0 ? (prevK != k0 && kl == k0 && nextK == k0) : (kl != k0 && kl < V && nextK == kl);
-      if (!own) continue;
-      float acc[BAG_MAXJ];
-#pragma unroll
-      for (int j = 0; j < BAG_MAXJ; ++j) acc[j] = 0.f;
-      long cc = c + 1;
-      while (true) {
-        const bool cont = (cc + lane < nchunks) && keys[(cc + lane) * BAG_CH] == key;
-        const unsigned long long m = __ballot(cont);
-        const int nc = (m == ~0ull) ? 64 : __builtin_ctzll(~m);   // chunks cc .. cc + nc - 1 begin with this word: their slot 0 is its partial
-        for (int q = wv; q < nc; q += 32) {                        // this wave: chunks q, q + 4, ..., q + 28 of the window, in order
-          float v[8][BAG_MAXJ];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            const float* sp = partial + ((cc + min(q + 4 * u, nc - 1)) * 2) * (long)BAG_PITCH;
-#pragma unroll
-            for (int j = 0; j < BAG_MAXJ; ++j) v[u][j] = sp[lane + 64 * j];
-          }
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            if (q + 4 * u < nc) {
-#pragma unroll
-              for (int j = 0; j < BAG_MAXJ; ++j) acc[j] += v[u][j];
-            }
-          }
-        }
-        cc += nc;
-        if (nc < 64) break;
-      }
-#pragma unroll
-      for (int j = 0; j < BAG_MAXJ; ++j) red[wv][lane + 64 * j] = acc[j];
-      __syncthreads();
-      if (wv == 0) {
-        const float* src = partial + (c * 2 + cand) * (long)BAG_PITCH;      // the run's own part in its first chunk
-#pragma unroll
-        for (int j = 0; j < BAG_MAXJ; ++j) {
-          const int col = lane + 64 * j;
-          const float t = (((src[col] + red[0][col]) + red[1][col]) + red[2][col]) + red[3][col];
-          if (col < E) dtable[(long)key * E + col] += t;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  sorted_rows::fix<BAG_CH, BAG_MAXJ, BAG_FL, false>(keys, cap, V, E, dtable, partial);
 }
 
 // ---- aux[r] = coef * ||a[r] - b[r]||_2 ; one wave per row, fixed-order butterfly sum
@@ -382,7 +244,7 @@ extern "C" int nnr_bag_mean_fwd(const float* table, int V, int E, const int* ids
 }
 
 extern "C" size_t nnr_bag_mean_bwd_ws_floats(long cap) {
-  return cap <= 0 ? 0 : (size_t)((cap + BAG_CH - 1) / BAG_CH) * 2 * BAG_PITCH;
+  return sorted_rows::ws_floats(cap, BAG_CH, BAG_MAXJ);
 }
 
 extern "C" int nnr_bag_mean_bwd(const float* dout, int lddo, const float* out, int ldo, int off_a, int off_b, const float* count,
@@ -394,8 +256,7 @@ extern "C" int nnr_bag_mean_bwd(const float* dout, int lddo, const float* out, i
     return NNR_ERR_ARG;
   if (La > BAG_MAXL || Lb > BAG_MAXL || E > BAG_MAXE) return NNR_ERR_UNSUPPORTED;
   if (cap == 0) return NNR_OK;
-  const long nchunks = (cap + BAG_CH - 1) / BAG_CH;
-  const unsigned blocks = (unsigned)((nchunks + 3) / 4);
+  const unsigned blocks = sorted_rows::blocks(cap, BAG_CH);
   hipLaunchKernelGGL(bag_mean_bwd_kernel, dim3(blocks), dim3(256), 0, stream, dout, lddo, act == 3 ? out : (const float*)nullptr, ldo, off_a, off_b,
                      count, keys_sorted, pos_sorted, cap, La, Lb, n, (unsigned)V, E, separate, dtable_accum, partial_ws);
   NNR_CHECK_LAUNCH();

@@ -8,11 +8,12 @@ mkdir -p build
 pids=()
 compiled=""
 kept=""
-# incremental: a source is recompiled when it, common.h or the public header is newer than its object (NNR_BUILD_FORCE=1: everything);
+# incremental: a source is recompiled when it, any header here or the public header is newer than its object (NNR_BUILD_FORCE=1: everything);
 # what was compiled and what was kept is printed, so a caller can see which it got
+newest_h=$(ls -t *.h ../../include/nnr_hip.h | head -1)
 for f in gemm seq_plan lstm pool misc mhsa corpus dp gcn tape fuse sort cand_attn omap pers_attn kcnn hdc fim gru naml dssm seg_pool bag; do
   [ -f $f.hip ] || continue
-  if [ "${NNR_BUILD_FORCE}" = "1" ] || [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || [ ../../include/nnr_hip.h -nt build/$f.o ]; then
+  if [ "${NNR_BUILD_FORCE}" = "1" ] || [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ $newest_h -nt build/$f.o ]; then
     hipcc $FLAGS -c $f.hip -o build/$f.o &
     pids+=($!)
     compiled="$compiled $f"

@@ -79,6 +79,20 @@ __device__ __forceinline__ float vdot(float a, float b) { return a * b; }
 __device__ __forceinline__ f32x4 vtanh(f32x4 z) { return f32x4{tanhf(z[0]), tanhf(z[1]), tanhf(z[2]), tanhf(z[3])}; }
 __device__ __forceinline__ float vtanh(float z) { return tanhf(z); }
 
+// ---------------------------------------------------------------- row loads of the width a row's alignment allows (float4 / float2 / float)
+template <int VEC> struct VecT;
+template <> struct VecT<4> { typedef float4 type; };
+template <> struct VecT<2> { typedef float2 type; };
+template <> struct VecT<1> { typedef float type; };
+template <int VEC> __device__ __forceinline__ void vec_get(const typename VecT<VEC>::type& v, float (&f)[VEC]);
+template <> __device__ __forceinline__ void vec_get<4>(const float4& v, float (&f)[4]) { f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w; }
+template <> __device__ __forceinline__ void vec_get<2>(const float2& v, float (&f)[2]) { f[0] = v.x; f[1] = v.y; }
+template <> __device__ __forceinline__ void vec_get<1>(const float& v, float (&f)[1]) { f[0] = v; }
+template <int VEC> __device__ __forceinline__ typename VecT<VEC>::type vec_zero();
+template <> __device__ __forceinline__ float4 vec_zero<4>() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+template <> __device__ __forceinline__ float2 vec_zero<2>() { return make_float2(0.f, 0.f); }
+template <> __device__ __forceinline__ float vec_zero<1>() { return 0.f; }
+
 static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // blocks of 256 threads for an element-wise kernel with a grid-stride loop over `total` elements, capped

@@ -14,15 +14,13 @@
 //     that nnr_token_sort turns into the (word, position) list of the backward pass.
 //   * wbag_bwd_kernel / wbag_bwd_fix_kernel: dtable[word] += sum over the word's live occurrences, in list order, of keep * scale * w *
 //     dout[row of the occurrence]: the gradient row is read through the sorted position from the na + nb rows of dout (they stay in L2).
-//     One wave sums a chunk of WB_BCH sorted occurrences; a word inside one chunk is added to its table row by that wave alone (plain
-//     read-add-write), a run that crosses a chunk boundary goes through partial rows and the fix-up pass, which adds them in chunk order:
-//     the geometry and the boundary rules are csrc/bag.hip's and csrc/sort.hip's.  Both streams go through one sorted list, so a table row
-//     has exactly one writer per launch: no float atomics, same bits every run.
+//     The reduction is csrc/sorted_rows.h's (chunks of WB_BCH, WB_FL gradient rows in flight, plain adds).  Both streams go through one
+//     sorted list, so a table row has exactly one writer per launch: no float atomics, same bits every run.
 //   * cosine_loss_kernel: logits[b, n] = <u_b, v_bn> / (|u_b| |v_bn|), loss = mean_b(-log_softmax(logits)[b, 0]) as a fixed-order sum
 //     (the last workgroup to arrive adds the per-sample terms in index order, as click_loss_kernel does), d loss / d logits, d user (the sum
 //     over the N candidates in ascending order) and d news.  One workgroup per sample.  A zero-norm row gives the reference's 0 / 0 = NaN.
 //   * tanh_drop_bwd_kernel: dz = mask(dy) * (1 - t^2) behind y = dropout(tanh(z)), t = tanh(z) (functional.LinearFn with ACT_TANH).
-#include "common.h"
+#include "sorted_rows.h"
 
 namespace {
 
@@ -32,19 +30,6 @@ constexpr int WB_CH = 128;       // positions per forward work item: two ballots
 constexpr int WB_FL = 4;         // table rows in flight per wave (forward) / gradient rows (backward)
 constexpr int WB_BCH = 64;       // sorted occurrences per backward wave
 constexpr int COS_MAXN = 64;
-
-template <int VEC> struct VecT;
-template <> struct VecT<4> { typedef float4 type; };
-template <> struct VecT<2> { typedef float2 type; };
-template <> struct VecT<1> { typedef float type; };
-template <int VEC> __device__ __forceinline__ void vec_get(const typename VecT<VEC>::type& v, float (&f)[VEC]);
-template <> __device__ __forceinline__ void vec_get<4>(const float4& v, float (&f)[4]) { f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w; }
-template <> __device__ __forceinline__ void vec_get<2>(const float2& v, float (&f)[2]) { f[0] = v.x; f[1] = v.y; }
-template <> __device__ __forceinline__ void vec_get<1>(const float& v, float (&f)[1]) { f[0] = v; }
-template <int VEC> __device__ __forceinline__ typename VecT<VEC>::type vec_zero();
-template <> __device__ __forceinline__ float4 vec_zero<4>() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-template <> __device__ __forceinline__ float2 vec_zero<2>() { return make_float2(0.f, 0.f); }
-template <> __device__ __forceinline__ float vec_zero<1>() { return 0.f; }
 
 // nnr_keep / nnr_keep4 (common.h) for an index below 2^32, given hhi = nnr_hash32(seed): the hash of the index's high word is then the same
 // for every element of the launch and leaves the per-element work (one hash per pair of elements instead of two)
@@ -216,174 +201,55 @@ __global__ __launch_bounds__(256) void wbag_combine_kernel(const float* __restri
   out[i] = partial_rows_sum(ws + base * E, nc, E, e);
 }
 
-// ---- backward, pass 1: one wave per chunk of WB_BCH sorted occurrences; lane + 64 j is the column
+// ---- backward: csrc/sorted_rows.h over the sorted occurrences of both streams.  An entry is a position p of `tok`; it adds keep * scale * w *
+// dout[stacked row], the dropout index being the forward's ((r * L + j) * E + col) within the occurrence's stream
+struct WbagRows {
+  struct Rec { int row, b; unsigned q; float w; };
+  static constexpr int NV = 1;
+  const float* dout;
+  const int* poss;
+  long cap, cap_a;
+  const Stream &sa, &sb;                                           // (the kernel's arguments)
+  int E;
+  uint32_t thr, hhi_a, hhi_b;
+  float scale;
+  bool lo;                                                         // every dropout index below 2^32
+  __device__ WbagRows(const float* dout_, const int* poss_, long cap_, const Stream& sa_, const Stream& sb_, int E_, uint32_t thr_, float scale_)
+      : dout(dout_), poss(poss_), cap(cap_), cap_a((long)sa_.n * sa_.L), sa(sa_), sb(sb_), E(E_), thr(thr_), hhi_a(nnr_hash32(sa_.seed)),
+        hhi_b(nnr_hash32(sb_.seed)), scale(scale_), lo((uint64_t)max(cap_a, cap_ - cap_a) * (uint64_t)E_ <= 0xFFFFFFFFull) {}
+  __device__ Rec pad() const { return {0, 0, 0u, 0.f}; }
+  __device__ Rec record(long i, bool live) const {
+    if (!live) return pad();
+    const long p = min(max((long)poss[i], 0L), cap - 1);
+    const int b = p >= cap_a;
+    const Stream& s = b ? sb : sa;
+    const long q = b ? p - cap_a : p;
+    const int r = (int)(q / s.L), j = (int)(q - (long)r * s.L);
+    const int src = s.sel ? s.sel[r] : r;
+    return {(b ? sa.n : 0) + r, b, (unsigned)q, (unsigned)src < (unsigned)s.R ? s.w[(long)src * s.L + j] : 0.f};
+  }
+  __device__ int nv() const { return 1; }
+  __device__ const float* row(const Rec& e, int) const { return dout + (long)e.row * E; }
+  struct Pre { uint32_t seed, hhi; uint64_t base; float w; };      // the occurrence's stream seed and first dropout index, its weight
+  __device__ Pre prep(const Rec& e) const { return {e.b ? sb.seed : sa.seed, e.b ? hhi_b : hhi_a, (uint64_t)e.q * (uint64_t)E, e.w}; }
+  __device__ float addend(const Pre& o, int col, bool in, const float (&v)[1]) const {
+    float g = in ? v[0] * o.w : 0.f;
+    if (thr) g = (in && (lo ? keep_lo(o.hhi, o.base + col, thr) : nnr_keep(o.seed, o.base + col, thr))) ? g * scale : 0.f;
+    return g;
+  }
+};
+
 template <int MAXJ>
 __global__ __launch_bounds__(256) void wbag_bwd_kernel(const float* __restrict__ dout, const unsigned* __restrict__ keys, const int* __restrict__ poss,
                                                        long cap, Stream sa, Stream sb, unsigned V, int E, uint32_t thr, float scale,
                                                        float* __restrict__ dtable, float* __restrict__ partial) {
-  constexpr int PITCH = 64 * MAXJ;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long c = blockIdx.x * 4L + wv;
-  const long p0 = c * WB_BCH;
-  if (p0 >= cap) return;
-  const long p1 = min(cap, p0 + WB_BCH);
-  const int cnt = (int)(p1 - p0);
-  const long cap_a = (long)sa.n * sa.L;
-  const uint32_t hhi_a = nnr_hash32(sa.seed), hhi_b = nnr_hash32(sb.seed);
-  const bool lo = (uint64_t)max(cap_a, cap - cap_a) * (uint64_t)E <= 0xFFFFFFFFull;                 // every dropout index below 2^32
-  unsigned myk = V, myq = 0;
-  int myrow = 0, myb = 0;
-  float myw = 0.f;
-  if (lane < cnt) {
-    myk = keys[p0 + lane];
-    if (myk < V) {
-      const long p = min(max((long)poss[p0 + lane], 0L), cap - 1);
-      myb = p >= cap_a;
-      const Stream& s = myb ? sb : sa;
-      const long q = myb ? p - cap_a : p;
-      const int r = (int)(q / s.L), j = (int)(q - (long)r * s.L);
-      const int src = s.sel ? s.sel[r] : r;
-      myw = (unsigned)src < (unsigned)s.R ? s.w[(long)src * s.L + j] : 0.f;
-      myrow = (myb ? sa.n : 0) + r;
-      myq = (unsigned)q;
-    }
-  }
-  const unsigned k0 = __shfl(myk, 0, 64);
-  if (k0 >= V) return;                                            // sorted: nothing but pad entries from here on
-  const unsigned prevK = p0 > 0 ? keys[p0 - 1] : 0xFFFFFFFFu;     // (0xFFFFFFFF equals no valid key)
-  const unsigned nextK = p1 < cap ? keys[p1] : 0xFFFFFFFFu;
-  float acc[MAXJ];
-#pragma unroll
-  for (int j = 0; j < MAXJ; ++j) acc[j] = 0.f;
-  unsigned run_key = k0;
-  bool first = true;
-  auto flush = [&](bool open_right) {
-    const bool open_left = first && prevK == run_key;
-    if (!open_left && !open_right) {                              // the whole segment of this word: this wave is the row's only writer
-#pragma unroll
-      for (int j = 0; j < MAXJ; ++j) {
-        const int col = lane + 64 * j;
-        if (col < E) dtable[(long)run_key * E + col] += acc[j];
-      }
-    } else {
-      float* dst = partial + (c * 2 + (first ? 0 : 1)) * (long)PITCH;
-#pragma unroll
-      for (int j = 0; j < MAXJ; ++j) dst[lane + 64 * j] = acc[j];
-    }
-  };
-  bool done = false;
-  const int elast = E - 1;
-  for (int i0 = 0; i0 < cnt && !done; i0 += WB_FL) {
-    float v[WB_FL][MAXJ];
-    unsigned kk[WB_FL], qq[WB_FL];
-    int rr[WB_FL], bb[WB_FL];
-    float ww[WB_FL];
-#pragma unroll
-    for (int u = 0; u < WB_FL; ++u) {
-      const int i = i0 + u;                                       // (< 64 + WB_FL: __shfl wraps; lanes >= cnt hold the pad key and row 0)
-      kk[u] = i < cnt ? __shfl(myk, i, 64) : V;
-      rr[u] = __shfl(myrow, i, 64);
-      bb[u] = __shfl(myb, i, 64);
-      qq[u] = __shfl(myq, i, 64);
-      ww[u] = __shfl(myw, i, 64);
-    }
-#pragma unroll
-    for (int u = 0; u < WB_FL; ++u) {
-      const float* src = dout + (long)rr[u] * E;
-#pragma unroll
-      for (int j = 0; j < MAXJ; ++j) v[u][j] = src[min(lane + 64 * j, elast)];
-    }
-#pragma unroll
-    for (int u = 0; u < WB_FL; ++u) {
-      if (done) break;
-      if (kk[u] >= V) { done = true; break; }
-      if (kk[u] != run_key) {
-        flush(false);
-        run_key = kk[u];
-        first = false;
-#pragma unroll
-        for (int j = 0; j < MAXJ; ++j) acc[j] = 0.f;
-      }
-      const uint32_t seed = bb[u] ? sb.seed : sa.seed, hhi = bb[u] ? hhi_b : hhi_a;
-      const uint64_t base = (uint64_t)qq[u] * (uint64_t)E;
-#pragma unroll
-      for (int j = 0; j < MAXJ; ++j) {
-        const int col = lane + 64 * j;
-        float g = col < E ? v[u][j] * ww[u] : 0.f;
-        if (thr) g = (col < E && (lo ? keep_lo(hhi, base + col, thr) : nnr_keep(seed, base + col, thr))) ? g * scale : 0.f;
-        acc[j] += g;
-      }
-    }
-  }
-  flush(nextK == run_key);                                        // (a chunk that ran into pad entries has nextK = pad: closed)
+  sorted_rows::pass1<WB_BCH, MAXJ, WB_FL, false, true>(WbagRows(dout, poss, cap, sa, sb, E, thr, scale), keys, cap, V, E, dtable, partial);
 }
 
-// ---- backward, pass 2: the workgroup of the chunk in which a multi-chunk word STARTS adds its partial rows in chunk order
 template <int MAXJ>
 __global__ __launch_bounds__(256) void wbag_bwd_fix_kernel(const unsigned* __restrict__ keys, long cap, unsigned V, int E, float* __restrict__ dtable,
                                                            const float* __restrict__ partial) {
-  constexpr int PITCH = 64 * MAXJ;
-  constexpr int U = MAXJ >= 16 ? 4 : 8;                           // partial rows in flight per wave
-  __shared__ float red[4][PITCH];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long nchunks = (cap + WB_BCH - 1) / WB_BCH;
-  for (int ci = 0; ci < 4; ++ci) {
-    const long c = blockIdx.x * 4L + ci;
-    const long p0 = c * WB_BCH;
-    if (p0 >= cap) break;                                          // (uniform over the workgroup, like every branch below)
-    const long p1 = min(cap, p0 + WB_BCH);
-    const unsigned k0 = keys[p0];
-    if (k0 >= V) break;
-    const unsigned prevK = p0 > 0 ? keys[p0 - 1] : 0xFFFFFFFFu;
-    const unsigned kl = keys[p1 - 1];
-    const unsigned nextK = p1 < cap ? keys[p1] : 0xFFFFFFFFu;
-    for (int cand = 0; cand < 2; ++cand) {
-      // cand 0: the chunk's first run, if the word STARTS here and runs on into the next chunk; cand 1: its last run, likewise
-      const unsigned key = cand == 0 ? k0 : kl;
-      const bool own = cand == 0 ? (prevK != k0 && kl == k0 && nextK == k0) : (kl != k0 && kl < V && nextK == kl);
-      if (!own) continue;
-      float acc[MAXJ];
-#pragma unroll
-      for (int j = 0; j < MAXJ; ++j) acc[j] = 0.f;
-      long cc = c + 1;
-      while (true) {
-        const bool cont = (cc + lane < nchunks) && keys[(cc + lane) * WB_BCH] == key;
-        const unsigned long long m = __ballot(cont);
-        const int nc = (m == ~0ull) ? 64 : __builtin_ctzll(~m);   // chunks cc .. cc + nc - 1 begin with this word: their slot 0 is its partial
-        for (int q = wv; q < nc; q += 4 * U) {                     // this wave: chunks q, q + 4, ... of the window, in order
-          float v[U][MAXJ];
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const float* sp = partial + ((cc + min(q + 4 * u, nc - 1)) * 2) * (long)PITCH;
-#pragma unroll
-            for (int j = 0; j < MAXJ; ++j) v[u][j] = sp[lane + 64 * j];
-          }
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            if (q + 4 * u < nc) {
-#pragma unroll
-              for (int j = 0; j < MAXJ; ++j) acc[j] += v[u][j];
-            }
-          }
-        }
-        cc += nc;
-        if (nc < 64) break;
-      }
-#pragma unroll
-      for (int j = 0; j < MAXJ; ++j) red[wv][lane + 64 * j] = acc[j];
-      __syncthreads();
-      if (wv == 0) {
-        const float* src = partial + (c * 2 + cand) * (long)PITCH;          // the run's own part in its first chunk
-#pragma unroll
-        for (int j = 0; j < MAXJ; ++j) {
-          const int col = lane + 64 * j;
-          const float t = (((src[col] + red[0][col]) + red[1][col]) + red[2][col]) + red[3][col];
-          if (col < E) dtable[(long)key * E + col] += t;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  sorted_rows::fix<WB_BCH, MAXJ, (MAXJ >= 16 ? 4 : 8), false>(keys, cap, V, E, dtable, partial);   // partial rows in flight: at most 64 registers
 }
 
 // ---- cosine click head + loss, one workgroup per sample
@@ -499,8 +365,7 @@ int launch_fwd(const float* table, int V, int E, const Stream& sa, const Stream&
 template <int MAXJ>
 int launch_bwd(const float* dout, const unsigned* keys, const int* poss, long cap, const Stream& sa, const Stream& sb, int V, int E, float p,
                float* dtable, float* partial, hipStream_t stream) {
-  const long nchunks = (cap + WB_BCH - 1) / WB_BCH;
-  const unsigned blocks = (unsigned)((nchunks + 3) / 4);
+  const unsigned blocks = sorted_rows::blocks(cap, WB_BCH);
   const float sc = p > 0.f ? 1.f / (1.f - p) : 1.f;
   hipLaunchKernelGGL(wbag_bwd_kernel<MAXJ>, dim3(blocks), dim3(256), 0, stream, dout, keys, poss, cap, sa, sb, (unsigned)V, E, nnr_drop_thresh(p), sc,
                      dtable, partial);
@@ -561,7 +426,7 @@ extern "C" int nnr_wbag_fwd(const float* table, int V, int E, const int* ids_a, 
 
 extern "C" size_t nnr_wbag_bwd_ws_floats(long cap, int E) {
   if (cap <= 0 || E < 1 || E > WB_MAXE) return 0;
-  return (size_t)((cap + WB_BCH - 1) / WB_BCH) * 2 * 64 * bwd_maxj(E);
+  return sorted_rows::ws_floats(cap, WB_BCH, bwd_maxj(E));
 }
 
 extern "C" int nnr_wbag_bwd(const float* dout, const unsigned* keys_sorted, const int* pos_sorted, long cap, const float* w_a, const int* sel_a,

@@ -1615,20 +1615,29 @@ def embed_scatter_sorted(dout, ts, dtable, p, seed):
 BAG_UNSUPPORTED = 'unsupported size (a stream of more than 128 positions or word_embedding_dim > 320)'
 
 
-class BagPlan:
-    """Occurrence list of one bag_mean_fwd call for its backward pass: `tok` [n, La + Lb] (written by the forward launch: word id of a live
+class OccurrencePlan:
+    """Occurrence list of one bag forward call for its backward pass: `tok` [cap] (written by the forward launch: word id of a live
     position, -1 elsewhere) sorted by word id on the LEAF stream behind the forward launch (csrc/sort.hip; stable, so a word's
-    occurrences keep the order news row, stream a, stream b, position).  Nothing is read on the host."""
+    occurrences keep their order in `tok`), and the workspace of the backward's reduction (csrc/sorted_rows.h).  Nothing is read on the
+    host."""
 
-    def __init__(self, n, La, Lb, vocab, dev):
-        self.n, self.La, self.Lb, self.vocab = n, La, Lb, int(vocab)
-        self.cap = cap = n * (La + Lb)
-        self.tok = torch.empty(cap, device=dev, dtype=torch.int32)
-        self.partial = torch.empty(L.lib().nnr_bag_mean_bwd_ws_floats(cap), device=dev, dtype=torch.float32)
+    def __init__(self, cap, ws_floats, vocab, dev):
+        self.cap, self.vocab = cap, int(vocab)
+        self.tok = torch.empty(max(cap, 1), device=dev, dtype=torch.int32)[:cap]
+        self.partial = torch.empty(max(ws_floats, 1), device=dev, dtype=torch.float32)
         self.event = None
 
     def sort(self):
         self.keys, self.pos, self.event = _sort_on_leaf(self.tok, None, self.vocab)
+
+
+class BagPlan(OccurrencePlan):
+    """The plan of one bag_mean_fwd call: `tok` is [n, La + Lb], so a word's occurrences keep the order news row, stream a, stream b, position."""
+
+    def __init__(self, n, La, Lb, vocab, dev):
+        self.n, self.La, self.Lb = n, La, Lb
+        cap = n * (La + Lb)
+        super().__init__(cap, L.lib().nnr_bag_mean_bwd_ws_floats(cap), vocab, dev)
 
 
 def bag_mean_fwd(table, ids_a, mask_a, ids_b, mask_b, separate, act, out, ldo, off_a, off_b, count, plan=None, live=None):
@@ -1704,19 +1713,11 @@ def _wstream(s):
     return ids, w, sel, R, (sel.numel() if sel is not None else R), Lx
 
 
-class WbagPlan:
-    """Occurrence list of one wbag_fwd call for its backward pass: `tok` [na * La + nb * Lb] (written by the forward launch: word id of a
-    live position, -1 elsewhere) sorted by word id on the LEAF stream behind the forward launch (csrc/sort.hip; stable, so a word's
-    occurrences keep the order stream a, stream b, row, position).  Nothing is read on the host."""
+class WbagPlan(OccurrencePlan):
+    """The plan of one wbag_fwd call: `tok` is [na * La + nb * Lb], so a word's occurrences keep the order stream a, stream b, row, position."""
 
     def __init__(self, cap, E, vocab, dev):
-        self.cap, self.vocab = cap, int(vocab)
-        self.tok = torch.empty(max(cap, 1), device=dev, dtype=torch.int32)[:cap]
-        self.partial = torch.empty(max(L.lib().nnr_wbag_bwd_ws_floats(cap, E), 1), device=dev, dtype=torch.float32)
-        self.event = None
-
-    def sort(self):
-        self.keys, self.pos, self.event = _sort_on_leaf(self.tok, None, self.vocab)
+        super().__init__(cap, L.lib().nnr_wbag_bwd_ws_floats(cap, E), vocab, dev)
 
 
 def wbag_fwd(table, sa, sb, p, seed_a, seed_b, out, plan=None):

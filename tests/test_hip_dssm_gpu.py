@@ -28,9 +28,26 @@ def _chunk():
 
 def _bag_shapes():
     """(na, La, nb, Lb, E, V): the smallest case | chunk boundaries, E on the 2-wide path | E odd | the workload's row lengths at two rows |
-    one word: a single run spanning every workgroup of the backward."""
+    one word: a single run spanning every workgroup of the backward | one word's run longer than one 64-chunk window of the backward's
+    fix walk (65 chunks of 64 occurrences and one more: _LONG_RUN) | E > 512, the widest backward instance, with a run across a chunk edge."""
     ch = _chunk()
-    return [(1, 1, 1, 1, 1, 2), (3, ch - 1, 2, ch + 1, 6, 11), (2, ch, 5, 3, 7, 5), (2, 3200, 3, 200, 512, 997), (4, 2 * ch + 5, 4, 9, 512, 1)]
+    return [(1, 1, 1, 1, 1, 2), (3, ch - 1, 2, ch + 1, 6, 11), (2, ch, 5, 3, 7, 5), (2, 3200, 3, 200, 512, 997), (4, 2 * ch + 5, 4, 9, 512, 1),
+            (4, 4096, 2, 9, 8, 1), (2, 129, 2, 3, 516, 3)]
+
+
+_BWD_CHUNK = 64                     # sorted occurrences per wave of the backward (csrc/dssm.hip: WB_BCH)
+_LONG_RUN = 65 * _BWD_CHUNK + 1
+
+
+def _live_words(c):
+    """Word ids of the case's live occurrences (non-zero weight, id inside the table) in ascending order: the backward's sorted list
+    without its pad entries."""
+    V = c['shape'][5]
+    words = []
+    for ids, w, _, rows in (c['a'], c['b']):
+        i, ww = ids[rows], w[rows]
+        words.append(i[(ww != 0) & (i >= 0) & (i < V)].reshape(-1))
+    return torch.cat(words).sort().values
 
 
 def _bar(exp, fp32, name, report):
@@ -124,12 +141,19 @@ def _bag_run(c, runs=2):
 
 @pytest.mark.parametrize('p', [0.0, 0.5], ids=['p0', 'p0.5'])
 @pytest.mark.parametrize('with_sel', [False, True], ids=['rows', 'sel'])
-@pytest.mark.parametrize('index', range(5))
+@pytest.mark.parametrize('index', range(7))
 def test_weighted_bag_kernels_match_the_float64_restatement(index, with_sel, p):
     shape = _bag_shapes()[index]
     cases = [_bag_case(shape, with_sel, p, seed=17 + 5 * index + 2 * with_sel + (p > 0))]
     if shape[0] == 1:                                  # the row patterns one row cannot hold: a second call at four rows per stream
         cases.append(_bag_case((4, 3, 4, 3) + shape[4:], with_sel, p, seed=91 + with_sel + 2 * (p > 0)))
+    # what the last two shapes are there for, checked on the CPU before anything runs
+    words = _live_words(cases[0])
+    if index == 5:
+        assert int((words == 0).sum()) >= _LONG_RUN, int((words == 0).sum())
+    if index == 6:
+        edges = torch.arange(_BWD_CHUNK, words.numel(), _BWD_CHUNK)
+        assert shape[4] > 512 and bool((words[edges] == words[edges - 1]).any()), words.numel()
     for c in cases:
         report = []
         exp_out, exp_dt = _bag_expected(c, f64)
