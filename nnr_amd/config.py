@@ -26,7 +26,8 @@ NEWS_ENCODERS = ['CNE', 'CNN', 'MHSA', 'PNE', 'DAE', 'Inception', 'HDC', 'KCNN']
 ALL_NEWS_ENCODERS = NEWS_ENCODERS + ['NAML_Title', 'NAML_Content']         # (NEWS_ENCODERS above is pinned by the host tests; nothing reads either list)
 USER_ENCODERS = ['SUE', 'MHSA', 'ATT', 'CATT', 'OMAP', 'PUE', 'FIM']  # in scope; the reference lists 11
 ALL_USER_ENCODERS = USER_ENCODERS + ['GRU']                            # (USER_ENCODERS above is pinned by the host tests; nothing reads either list)
-VARIANT_USER_ENCODERS = ['SUE_wo_GCN', 'SUE_wo_HCA']                  # the user-encoder ablations of the paper (variantEncoders.py:342-419)
+VARIANT_NEWS_ENCODERS = ['CNE_Title', 'CNE_Content', 'CNE_wo_CS', 'CNE_wo_CA']     # the news-encoder ablations of the paper (variantEncoders.py:14-99,190-339)
+VARIANT_USER_ENCODERS =['SUE_wo_GCN', 'SUE_wo_HCA']                  # the user-encoder ablations of the paper (variantEncoders.py:342-419)
 
 
 def build_parser():

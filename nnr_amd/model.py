@@ -104,9 +104,12 @@ class Model(nn.Module):
             self.news_encoder = newsEncoders.NAML_Title(config, word_table)
         elif config.news_encoder == 'NAML_Content':
             self.news_encoder = newsEncoders.NAML_Content(config, word_table)
+        elif config.news_encoder in ('CNE_Title', 'CNE_Content', 'CNE_wo_CS', 'CNE_wo_CA'):
+            self.news_encoder = getattr(newsEncoders, config.news_encoder)(config, word_table)
         else:
             raise Exception(config.news_encoder + ' is not on the MI355X hot path (in scope: CNE, CNN, MHSA, HDC, PNE, DAE, Inception, KCNN, NAML_Title, '
-                            'NAML_Content; SURVEY.md section 8a; of variantEncoders.py also the user encoders SUE_wo_GCN, SUE_wo_HCA)')
+                            'NAML_Content, CNE_Title, CNE_Content, CNE_wo_CS, CNE_wo_CA; SURVEY.md section 8a; of variantEncoders.py also the user '
+                            'encoders SUE_wo_GCN, SUE_wo_HCA)')
         if config.user_encoder == 'SUE':
             self.user_encoder = userEncoders.SUE(self.news_encoder, config)
         elif config.user_encoder == 'MHSA':
@@ -129,7 +132,7 @@ class Model(nn.Module):
             self.user_encoder = userEncoders.SUE_wo_HCA(self.news_encoder, config)
         else:
             raise Exception(config.user_encoder + ' is not on the MI355X hot path (in scope: SUE, MHSA, ATT, CATT, FIM, OMAP, PUE, GRU; SURVEY.md section 8a; '
-                            'of variantEncoders.py the ablations SUE_wo_GCN, SUE_wo_HCA)')
+                            'of variantEncoders.py, beside the news encoders CNE_Title, CNE_Content, CNE_wo_CS, CNE_wo_CA, the ablations SUE_wo_GCN, SUE_wo_HCA)')
         self.model_name = config.news_encoder + '-' + config.user_encoder
         self.news_embedding_dim = self.news_encoder.news_embedding_dim
         self.dropout = nn.Dropout(p=config.dropout_rate)                    # (model.py:77: part of the attribute surface; the user rows'

@@ -11,6 +11,10 @@ CNE (newsEncoders.py:57-141) pipeline per token stream (title L=32 / content L=1
 The backward pass is written by hand against the same kernels (no autograd graph inside the encoder); parameter
 gradients are accumulated straight into `param.grad`.
 
+The pipeline is driven by what a class keeps: `cne_streams` (title, content or both), `cne_gate` (the cross-selective gate with its rank
+pairing) and `cne_cross` (the cross pools).  CNE keeps everything; the paper's ablations CNE_Title / CNE_Content / CNE_wo_CS / CNE_wo_CA
+(variantEncoders.py) leave something out and issue the corresponding subset of CNE's launches.
+
 Tie order (see oracle/nnr_oracle.py:length_order): the reference sorts each stream by length with an unstable sort and
 gates the title at title-rank r with the content memory at content-rank r.  Because this implementation keeps each stream
 in its own sorted order end to end, that pairing is reproduced by construction; `tie_order` only selects how equal lengths
@@ -209,12 +213,13 @@ def cne_forward_many(mod, calls):
     phases of the first (small) call run on a second HIP stream, filling the gaps of the big call's kernels."""
     H, E = mod.hidden_dim, mod.word_embedding_dim
     dev = (calls[0][0][0] if isinstance(calls[0][0], tuple) else calls[0][0]).device
+    lstms = tuple(getattr(mod, k + '_lstm') for k in mod.cne_streams)
     if len(calls) > 1:
-        ops.lstm_pack(mod.title_lstm, H, E)             # (re)pack on the main stream BEFORE forking: both calls read them
-        ops.lstm_pack(mod.content_lstm, H, E)
+        for lstm in lstms:                              # (re)pack on the main stream BEFORE forking: both calls read them
+            ops.lstm_pack(lstm, H, E)
     else:
-        # one call (the union of candidate and history call): the two re-packs run on the leaf stream next to the planner / row gather
-        ops.lstm_prefetch(dev, (mod.title_lstm, mod.content_lstm), H, E)
+        # one call (the union of candidate and history call): the re-packs run on the leaf stream next to the planner / row gather
+        ops.lstm_prefetch(dev, lstms, H, E)
     if mod.training:
         # the bf16 images of the parameters (and of their cached transposes) the gate / attention / user-encoder GEMMs will read: re-split on the LEAF
         # stream HERE -- behind the weight packing (which the input projection waits for: in front of it the splits cost +0.3 ms) and in FRONT of the
@@ -222,7 +227,7 @@ def cne_forward_many(mod, calls):
         # CU, the 29 launches of ~5 us crawled at 70-160 us each and ended level with their first users: profiles/r06_ab.txt, first collection of the round.)
         ops.bx3_prefetch(dev)
     pre = _fork_join(len(calls), dev, lambda i, on_main: _cne_fwd_pre(mod, *calls[i], par=on_main))
-    items = [sv['streams'][1] for sv in pre] + [sv['streams'][0] for sv in pre]      # content streams first
+    items = [sv['streams'][k] for k in reversed(range(len(mod.cne_streams))) for sv in pre]      # content streams first
     for i in range(0, len(items), 4):
         ops.lstm_fwd(items[i:i + 4], H)
     return _fork_join(len(calls), dev, lambda i, on_main: _cne_fwd_post(mod, pre[i], on_main))
@@ -265,16 +270,20 @@ def _cne_fwd_pre(mod, title_text, title_mask, content_text, content_mask, catego
     seed = mod._next_seed()
     emb = mod.word_embedding.weight
 
-    streams = [None, None]
+    kinds = mod.cne_streams
+    streams = [None] * len(kinds)
 
-    def prepare(slot, name, ids, mask, Lx, lstm, Hlin, Mlin, satt, catt):
+    def prepare(slot, name, ids, mask, Lx):
+        lstm, satt = getattr(mod, name + '_lstm'), getattr(mod, name + '_self_attention')
+        Hlin, Mlin = (getattr(mod, name + '_H'), getattr(mod, name + '_M')) if mod.cne_gate else (None, None)
+        catt = getattr(mod, name + '_cross_attention') if mod.cne_cross else None
         parts = list(zip(ids, mask)) if union else [(ids, mask)]
         ids2 = [ops.ids32(i, -1, Lx) for i, _ in parts]
         mask2 = [m.view(-1, Lx) for _, m in parts]      # views: the in-place mask[:,0]=1 must reach the caller's tensors
         perm = _torch_tie_perm(mask2).to(dev) if mod.tie_order == 'torch' else None
         plan = ops.SeqPlan(mask2[0], ids2[0], perm, *((mask2[1], ids2[1]) if union else ()))
         plan_ev = None
-        if union and name == 'content':
+        if union and name == 'content' and mod.cne_gate:
             plan_ev = torch.cuda.Event()
             plan_ev.record()
         w = ops.lstm_pack(lstm, H, E)
@@ -302,13 +311,14 @@ def _cne_fwd_pre(mod, title_text, title_mask, content_text, content_mask, catego
 
     # the title and the content stream are independent up to the recurrence: plan + gather + input projection of the
     # (small) title stream run next to the content stream's on the big call
-    _two_chains(dev, par,
-                lambda: prepare(0, 'title', title_text, title_mask, mod.max_title_length, mod.title_lstm, mod.title_H, mod.title_M,
-                                mod.title_self_attention, mod.title_cross_attention),
-                lambda: prepare(1, 'content', content_text, content_mask, mod.max_content_length, mod.content_lstm, mod.content_H,
-                                mod.content_M, mod.content_self_attention, mod.content_cross_attention))
+    # (a variant without one of the streams never looks at that stream's text and mask: not planned, not gathered, not written)
+    inputs = dict(title=(title_text, title_mask, mod.max_title_length), content=(content_text, content_mask, mod.max_content_length))
+    if len(kinds) == 2:
+        _two_chains(dev, par, lambda: prepare(0, 'title', *inputs['title']), lambda: prepare(1, 'content', *inputs['content']))
+    else:
+        prepare(0, kinds[0], *inputs[kinds[0]])
     sv = dict(streams=streams, n=n, n0=n0, union=union, B=B, N=N, p=p, seed=seed, category=category, subCategory=subCategory)
-    if union:
+    if union and mod.cne_gate:
         # rank pairing (newsEncoders.py:128-129): inside ONE call the partner of sorted position r is the other stream's position r;
         # in a union of two calls it is the other stream's position with the same (call, position inside the call).  Needs both
         # plans and nothing else: issued on the title stream behind the title projection, it is done long before the recurrence ends
@@ -318,7 +328,7 @@ def _cne_fwd_pre(mod, title_text, title_mask, content_text, content_mask, catego
             sv['pm'] = ops.cne_pair_map(streams[0]['plan'], streams[1]['plan'])
         sv['pm_stream'] = s2
     if partner is not None:
-        assert not union
+        assert not union and mod.cne_gate
         pc_t, pt_c = partner
         pt, pc = streams[0]['plan'], streams[1]['plan']
         # title at sorted position s is sequence order_t[s]; its partner content is sequence pc_t[.], at content position rank_c[.]
@@ -328,20 +338,44 @@ def _cne_fwd_pre(mod, title_text, title_mask, content_text, content_mask, catego
 
 
 def _cne_fwd_post(mod, sv, par=False):
-    t_, c_ = sv['streams']
+    sts = sv['streams']
+    gate, cross, two = mod.cne_gate, mod.cne_cross, len(sts) == 2
     n, B, N, p, seed = sv['n'], sv['B'], sv['N'], sv['p'], sv['seed']
-    dev = t_['gates'].device
+    dev = sts[0]['gates'].device
     H, E, A = mod.hidden_dim, mod.word_embedding_dim, mod.attention_dim
     H2 = 2 * H
     D = mod.news_embedding_dim
     f32 = dict(device=dev, dtype=torch.float32)
 
-    if sv['union']:
-        torch.cuda.current_stream(dev).wait_stream(sv['pm_stream'])
-    t_['pm'], c_['pm'] = sv['pm'] if sv['union'] else sv.get('pm_override', (None, None))
+    if gate:
+        if sv['union']:
+            torch.cuda.current_stream(dev).wait_stream(sv['pm_stream'])
+        sts[0]['pm'], sts[1]['pm'] = sv['pm'] if sv['union'] else sv.get('pm_override', (None, None))
+    # without the cross pools the self pools' vectors ARE the representation's leading columns: pooled straight into them
+    rep = None if cross else torch.empty((n, D), **f32)
 
-    def gate_and_self(st, other):
+    def self_pool(st, col0):
+        plan, cap, sa = st['plan'], st['plan'].cap, st['satt']
+        st['th'] = torch.empty((cap, A), **f32)
+        ops.gemm(st['Ht'], sa.affine1.weight, st['th'], M=cap, N=A, K=H2, lda=H2, ldb=H2, ldc=A, dyn=plan.total, dyn_dim=1,
+                 bias=sa.affine1.bias, act=ops.ACT_TANH)
+        st['alpha_s'] = torch.empty(cap, **f32)
+        st['selfv'] = torch.empty((n, H2), **f32) if cross else rep[:, col0:col0 + H2]
+        ldo = H2 if cross else D
+        if A <= 256 and A % 4 == 0:
+            # the w2 . tanh(.) score is computed inside the pool's own pass over the tokens (one launch less on the chain)
+            ops.pool_fwd(x=st['Ht'], ldx=H2, D=H2, n=n, Lx=st['L'], plan=plan, th=st['th'], w2=sa.affine2.weight, alpha=st['alpha_s'],
+                         out=st['selfv'], ldo=ldo)
+        else:
+            score = torch.empty(cap, **f32)
+            ops.rowdot(st['th'], sa.affine2.weight, score, dyn=plan.total)
+            ops.pool_fwd(x=st['Ht'], ldx=H2, D=H2, n=n, Lx=st['L'], plan=plan, score=score, alpha=st['alpha_s'], out=st['selfv'], ldo=ldo)
+
+    def gate_and_self(st, other, col0):
         plan, cap = st['plan'], st['plan'].cap
+        if not gate:
+            st['Ht'] = st['hout']                        # the attention pools read the raw Bi-LSTM rows
+            return self_pool(st, col0)
         # title_M(sorted_content_m): both indexed by sorted RANK (newsEncoders.py:128-129)
         st['mproj'] = ops.linear_fwd(other['cn'], st['Mlin'].weight, st['Mlin'].bias, **({} if st['pm'] is None else {'a_idx': st['pm']}))
         st['G'] = torch.empty((cap, H2), **f32)
@@ -349,26 +383,18 @@ def _cne_fwd_post(mod, sv, par=False):
         ops.gemm(st['hout'], st['Hlin'].weight, st['Ht'], M=cap, N=H2, K=H2, lda=H2, ldb=H2, ldc=H2, dyn=plan.total, dyn_dim=1,
                  rowvec=st['mproj'], ldrv=H2, rowvec_map=plan.row_seq, act=ops.ACT_SIGMOID, aux_out=st['G'], ldaux=H2,
                  mul=st['hout'], ldmul=H2)
-        st['th'] = torch.empty((cap, A), **f32)
-        sa = st['satt']
-        ops.gemm(st['Ht'], sa.affine1.weight, st['th'], M=cap, N=A, K=H2, lda=H2, ldb=H2, ldc=A, dyn=plan.total, dyn_dim=1,
-                 bias=sa.affine1.bias, act=ops.ACT_TANH)
-        st['alpha_s'] = torch.empty(cap, **f32)
-        st['selfv'] = torch.empty((n, H2), **f32)
-        if A <= 256 and A % 4 == 0:
-            # the w2 . tanh(.) score is computed inside the pool's own pass over the tokens (one launch less on the chain)
-            ops.pool_fwd(x=st['Ht'], ldx=H2, D=H2, n=n, Lx=st['L'], plan=plan, th=st['th'], w2=sa.affine2.weight, alpha=st['alpha_s'],
-                         out=st['selfv'], ldo=H2)
-        else:
-            score = torch.empty(cap, **f32)
-            ops.rowdot(st['th'], sa.affine2.weight, score, dyn=plan.total)
-            ops.pool_fwd(x=st['Ht'], ldx=H2, D=H2, n=n, Lx=st['L'], plan=plan, score=score, alpha=st['alpha_s'], out=st['selfv'], ldo=H2)
+        self_pool(st, col0)
 
-    _two_chains(dev, par, lambda: gate_and_self(t_, c_), lambda: gate_and_self(c_, t_))
+    if two:
+        t_, c_ = sts
+        _two_chains(dev, par, lambda: gate_and_self(t_, c_, 0), lambda: gate_and_self(c_, t_, H2))
+    else:
+        gate_and_self(sts[0], None, 0)
 
-    rep = torch.empty((n, D), **f32)
+    if cross:
+        rep = torch.empty((n, D), **f32)
 
-    def cross(st, other, col0):
+    def cross_pool(st, other, col0):
         plan, ca = st['plan'], st['catt']
         st['qv'] = ops.linear_fwd(other['selfv'], ca.Q.weight, ca.Q.bias)                    # [n, A]
         st['v'] = torch.empty((n, H2), **f32)
@@ -377,7 +403,8 @@ def _cne_fwd_post(mod, sv, par=False):
         ops.pool_fwd(x=st['Ht'], ldx=H2, D=H2, n=n, Lx=st['L'], plan=plan, v=st['v'], ldv=H2, scale=1.0 / math.sqrt(A),
                      alpha=st['alpha_c'], out=rep[:, col0:], ldo=D, add_in=st['selfv'], ldadd=H2)
 
-    _two_chains(dev, par, lambda: cross(t_, c_, 0), lambda: cross(c_, t_, H2))
+    if cross:
+        _two_chains(dev, par, lambda: cross_pool(t_, c_, 0), lambda: cross_pool(c_, t_, H2))
     # feature fusion (newsEncoders.py:50-54): category + subCategory rows of both calls in ONE launch, the two calls' id tensors read
     # where they lie (round 2: torch.cat x 2 + two launches)
     if sv['union']:
@@ -387,10 +414,10 @@ def _cne_fwd_post(mod, sv, par=False):
         cat0, cat1 = ops.ids32(sv.pop('category'), n), None
         sub0, sub1 = ops.ids32(sv.pop('subCategory'), n), None
     cd, sd = mod.category_embedding.weight.shape[1], mod.subCategory_embedding.weight.shape[1]
-    ops.fusion_rows_fwd(mod.category_embedding.weight, mod.subCategory_embedding.weight, cat0, sub0, cat1, sub1, rep[:, 2 * H2:], D, p,
+    ops.fusion_rows_fwd(mod.category_embedding.weight, mod.subCategory_embedding.weight, cat0, sub0, cat1, sub1, rep[:, len(sts) * H2:], D, p,
                         seed + _SITE['cat'], seed + _SITE['sub'])
     sv.update(cats=(cat0, sub0, cat1, sub1), cd=cd, sd=sd)
-    for st in sv['streams']:                             # not needed by backward
+    for st in sts if gate else ():                       # not needed by backward
         st.pop('mproj')
     if sv['union']:
         n0 = sv['n0']
@@ -408,7 +435,7 @@ def cne_backward_many(mod, pairs):
     dev = pairs[0][1].device
     for q in mod.parameters():          # materialise (zero-fill) missing .grad buffers on the main stream BEFORE forking
         grad_of(q)
-    mod.__dict__['_table_scatters'] = 2 * len(pairs)      # embedding-row scatter GEMMs of this pass (title + content per call)
+    mod.__dict__['_table_scatters'] = len(mod.cne_streams) * len(pairs)      # embedding-row scatter GEMMs of this pass (one per stream and call)
     with ops.leaf_scope(dev) as leaf:        # weight-gradient GEMMs of the pre phase: leaves, joined after the recurrence + post phase
         _cne_bwd_rest(mod, pairs, H, dev, leaf)
 
@@ -422,22 +449,26 @@ def _cne_bwd_rest(mod, pairs, H, dev, leaf):
     main = torch.cuda.current_stream(dev)
     side = _side_stream(dev)
 
-    def run_kind(kind):
+    def run_kind(kind, kind_leaf):
         ops.lstm_bwd([sv['streams'][kind] for sv, _ in pairs], H)
         for sv, _ in pairs:
-            _cne_bwd_post(mod, sv, sv['streams'][kind], leaf if kind == 1 else None)
+            _cne_bwd_post(mod, sv, sv['streams'][kind], kind_leaf)
 
+    if len(mod.cne_streams) == 1:            # one stream kind: its launch on this stream, its weight gradients split with the leaf stream
+        return run_kind(0, leaf)
     side.wait_stream(main)
     with torch.cuda.stream(side):
-        run_kind(0)
-    run_kind(1)
+        run_kind(0, None)
+    run_kind(1, leaf)
     main.wait_stream(side)
 
 
 def _cne_bwd_pre(mod, sv, drep, par=False, leaf=None):
     if leaf is None:
         leaf = lambda fn, *tensors, **kw: fn()
-    t_, c_ = sv['streams']
+    sts = sv['streams']
+    gate, cross, two = mod.cne_gate, mod.cne_cross, len(sts) == 2
+    t_, c_ = sts if two else (sts[0], None)
     n, p, seed = sv['n'], sv['p'], sv['seed']
     H, E, A = mod.hidden_dim, mod.word_embedding_dim, mod.attention_dim
     H2 = 2 * H
@@ -448,14 +479,14 @@ def _cne_bwd_pre(mod, sv, drep, par=False, leaf=None):
     emb = mod.word_embedding.weight
 
     # (a leaf of the backward pass: nothing downstream reads the two table gradients -- on the leaf stream, off the dependent chain)
-    leaf(lambda: ops.fusion_rows_bwd(*sv['cats'], sv['cd'], sv['sd'], drep[:, 2 * H2:], D, grad_of(mod.category_embedding.weight),
+    leaf(lambda: ops.fusion_rows_bwd(*sv['cats'], sv['cd'], sv['sd'], drep[:, len(sts) * H2:], D, grad_of(mod.category_embedding.weight),
                                      grad_of(mod.subCategory_embedding.weight), p, seed + _SITE['cat'], seed + _SITE['sub']), drep)
 
     # the title stream's weight-gradient GEMMs on a SECOND leaf stream when the step is small and latency-bound (content stream <= 64 k token
     # rows = per-GPU batch 8: the leaf stream was the last to finish, 3.27-3.31 -> 3.23-3.24 ms); at batch 16 neutral, at batch 64 -- where the
     # leaf work is throughput-bound -- 0.1 ms SLOWER (10.72-10.77 vs 10.61-10.65), hence the bound
     def alt_leaf(st):
-        return st['name'] == 'title' and c_['plan'].cap <= _LEAF2_ROWS
+        return two and st['name'] == 'title' and c_['plan'].cap <= _LEAF2_ROWS
 
     # ---- cross attention pools: dv -> K / Q params and the gradient of the OTHER stream's self vector.  This pass does not write dHt:
     # it leaves its per-token d score (ds_c) behind, and the self pool's backward below writes dHt = alpha_s d self + alpha_c d cross +
@@ -473,19 +504,31 @@ def _cne_bwd_pre(mod, sv, drep, par=False, leaf=None):
                       ops.linear_bwd_weight(dqv, other['selfv'], grad_of(ca.Q.weight), db=grad_of(ca.Q.bias))), dv, dqv, alt=alt_leaf(st))      # (bias gradient fused: column sums of dqv)
         other['dself_x'] = ops.linear_bwd_data(dqv, ca.Q.weight)                              # grad of other.selfv via the query
 
-    _two_chains(dev, par, lambda: cross_bwd(t_, c_, 0), lambda: cross_bwd(c_, t_, H2))
+    if cross:
+        _two_chains(dev, par, lambda: cross_bwd(t_, c_, 0), lambda: cross_bwd(c_, t_, H2))
 
     # ---- self attention pools, additive score, gate
     def self_gate_bwd(st, other, col0):
         plan, sa, cap = st['plan'], st['satt'], st['plan'].cap
         ds = torch.empty(cap, **f32)
         st['dHt'] = torch.empty((cap, H2), **f32)
-        ops.pool_bwd(x=st['Ht'], ldx=H2, D=H2, n=n, Lx=st['L'], plan=plan, score=None, alpha=st['alpha_s'],
-                     dout=drep[:, col0:], lddo=D, dout2=st['dself_x'], lddo2=H2, dx=st['dHt'], lddx=H2, dscore=ds,
-                     alpha_b=st['alpha_c'], dout_b=drep[:, col0:], lddo_b=D, dscore_b=st['ds_c'], v_b=st['v'], ldv_b=H2, scale_b=1.0 / math.sqrt(A))
-        st['ds_c'] = None
+        if cross:
+            ops.pool_bwd(x=st['Ht'], ldx=H2, D=H2, n=n, Lx=st['L'], plan=plan, score=None, alpha=st['alpha_s'],
+                         dout=drep[:, col0:], lddo=D, dout2=st['dself_x'], lddo2=H2, dx=st['dHt'], lddx=H2, dscore=ds,
+                         alpha_b=st['alpha_c'], dout_b=drep[:, col0:], lddo_b=D, dscore_b=st['ds_c'], v_b=st['v'], ldv_b=H2, scale_b=1.0 / math.sqrt(A))
+            st['ds_c'] = None
+        else:
+            ops.pool_bwd(x=st['Ht'], ldx=H2, D=H2, n=n, Lx=st['L'], plan=plan, score=None, alpha=st['alpha_s'],
+                         dout=drep[:, col0:], lddo=D, dx=st['dHt'], lddx=H2, dscore=ds)
         th = st['th']
         ops.tanh_score_bwd(th, ds, sa.affine2.weight, grad_of(sa.affine2.weight), plan, A)    # th := dpre
+        if not gate:
+            # Ht is the recurrence's own output: dH = dHt + d tanh-projection . W1, the pool's store followed by an accumulating product
+            st['dH'], st['dHt'] = st['dHt'], None
+            ops.gemm(th, ops.wt(sa.affine1.weight), st['dH'], M=cap, N=H2, K=A, lda=A, ldb=A, ldc=H2, accumulate=True, dyn=plan.total, dyn_dim=1)
+            leaf(lambda: ops.linear_bwd_weight(th, st['hout'], grad_of(sa.affine1.weight), dyn=plan.total, db=grad_of(sa.affine1.bias)), th, st['hout'],
+                 alt=alt_leaf(st))
+            return
         st['dH'] = torch.empty((cap, H2), **f32)
         dpre = torch.empty((cap, H2), **f32)             # (not Ht's buffer: the deferred weight-gradient GEMM below still reads it)
         # the GEMM that completes dHt (+= d tanh-projection . W1) applies the gate's backward in its epilogue: Ht = hout * G ->
@@ -507,9 +550,12 @@ def _cne_bwd_pre(mod, sv, drep, par=False, leaf=None):
         other['dcn'] = ops.linear_bwd_data(dP, st['Mlin'].weight, **({} if opm is None else {'a_idx': opm}))   # [n, H2], rank-indexed
         st['dHt'] = None
 
-    _two_chains(dev, par, lambda: self_gate_bwd(t_, c_, 0), lambda: self_gate_bwd(c_, t_, H2))
+    if two:
+        _two_chains(dev, par, lambda: self_gate_bwd(t_, c_, 0), lambda: self_gate_bwd(c_, t_, H2))
+    else:
+        self_gate_bwd(t_, None, 0)
 
-    for st in (t_, c_):
+    for st in sts:
         st['dh'] = st['dH']
 
 
@@ -656,6 +702,7 @@ def _cne_fwd_pre_and_lstm(mod, tt, tm, ct, cm, cat, sub, partner):
 
 class CNE(NewsEncoder):
     """newsEncoders.py:57-141."""
+    cne_streams, cne_gate, cne_cross = ('title', 'content'), True, True      # what the packed pipeline above runs for this class
 
     def __init__(self, config, word_table=None):
         super().__init__(config, word_table)
@@ -704,6 +751,85 @@ class CNE(NewsEncoder):
         two calls' Bi-LSTM recurrences sharing one launch.  cand / hist = (title_text, title_mask, content_text, content_mask,
         category, subCategory)."""
         return _CNEPairFunction.apply(self.word_embedding.weight, self, *cand, *hist)
+
+
+class _CNEAblation(NewsEncoder):
+    """The news-encoder ablations of the paper (variantEncoders.py:14-99,190-339): CNE with a stream, the cross-selective gate or the cross
+    attention taken out.  A subclass names the streams it keeps and two flags; the packed CNE pipeline above runs what they describe, so an
+    ablation issues a subset of CNE's launches.  Parameters are registered in the reference's order under the reference's names.
+
+    tie_order is accepted by all four; without the gate nothing is paired by sorted rank, the order of equal lengths cannot reach a result
+    and a representation depends on its own news only (batch_independent).  pad_dedup = False: Model.forward's inference de-duplication of
+    PAD history slots (cne_history_dedup) is CNE's."""
+    pad_dedup = False
+
+    def __init__(self, config, word_table=None):
+        super().__init__(config, word_table)
+        self.max_title_length = config.max_title_length
+        self.max_content_length = config.max_abstract_length
+        self.hidden_dim = config.hidden_dim
+        self.attention_dim = config.attention_dim
+        h2 = self.hidden_dim * 2
+        self.news_embedding_dim = h2 * len(self.cne_streams) + config.category_embedding_dim + config.subCategory_embedding_dim
+        self.tie_order = getattr(config, 'tie_order', 'stable')
+        for k in self.cne_streams:
+            setattr(self, k + '_lstm', LSTMParams(self.word_embedding_dim, self.hidden_dim))
+        for k in self.cne_streams if self.cne_gate else ():
+            setattr(self, k + '_H', nn.Linear(h2, h2, bias=False))
+            setattr(self, k + '_M', nn.Linear(h2, h2, bias=True))
+        for k in self.cne_streams:
+            setattr(self, k + '_self_attention', Attention(h2, config.attention_dim))
+        for k in self.cne_streams if self.cne_cross else ():
+            setattr(self, k + '_cross_attention', ScaledDotProduct_CandidateAttention(h2, h2, config.attention_dim))
+
+    def initialize(self):
+        super().initialize()
+        for k in self.cne_streams:
+            for parameter in getattr(self, k + '_lstm').parameters():
+                if len(parameter.size()) >= 2:
+                    nn.init.orthogonal_(parameter.data)
+                else:
+                    nn.init.zeros_(parameter.data)
+        for k in self.cne_streams if self.cne_gate else ():
+            nn.init.xavier_uniform_(getattr(self, k + '_H').weight)
+            nn.init.xavier_uniform_(getattr(self, k + '_M').weight)
+            nn.init.zeros_(getattr(self, k + '_M').bias)
+        for k in self.cne_streams:
+            getattr(self, k + '_self_attention').initialize()
+        for k in self.cne_streams if self.cne_cross else ():
+            getattr(self, k + '_cross_attention').initialize()
+
+    def forward(self, title_text, title_mask, title_entity, content_text, content_mask, content_entity, category, subCategory, user_embedding):
+        return _CNEFunction.apply(self.word_embedding.weight, self, title_text, title_mask, content_text, content_mask, category, subCategory)
+
+    def forward_pair(self, cand, hist):
+        """As CNE.forward_pair: the candidate call and the history call as one packed plan."""
+        return _CNEPairFunction.apply(self.word_embedding.weight, self, *cand, *hist)
+
+
+class CNE_Title(_CNEAblation):
+    """variantEncoders.py:14-55: the title stream alone, Bi-LSTM rows -> self attention.  content_text / content_mask are never looked at."""
+    cne_streams, cne_gate, cne_cross = ('title',), False, False
+    batch_independent = True
+
+
+class CNE_Content(_CNEAblation):
+    """variantEncoders.py:58-99: the content stream alone; title_text / title_mask are never looked at."""
+    cne_streams, cne_gate, cne_cross = ('content',), False, False
+    batch_independent = True
+
+
+class CNE_wo_CS(_CNEAblation):
+    """variantEncoders.py:190-260, CNE without the cross-selective gate: both attentions read the raw Bi-LSTM rows; self + cross per stream."""
+    cne_streams, cne_gate, cne_cross = ('title', 'content'), False, True
+    batch_independent = True
+
+
+class CNE_wo_CA(_CNEAblation):
+    """variantEncoders.py:263-339, CNE without the cross attention: gated rows -> self attention, [title_self, content_self].  The gate pairs
+    the two streams by sorted rank as CNE's does, so a representation depends on the other news of its call and on the tie order."""
+    cne_streams, cne_gate, cne_cross = ('title', 'content'), True, False
+    batch_independent = False
 
 
 # ================================================================================================== MHSA / CNN

@@ -30,7 +30,7 @@ from make_goldens import stable_sort_patch          # noqa: E402
 from oracle.nnr_oracle import default_config        # noqa: E402  (attribute bag only)
 
 
-def run(tag, news, user, stable, min_gap=None, batch_size=8, zero_ties=False, **cfg_over):
+def run(tag, news, user, stable, min_gap=None, batch_size=8, zero_ties=False, init_seed=5, **cfg_over):
     """`cfg_over`: flags default_config lacks (OMAP_head_num, HiFi_Ark_regularizer_coefficient: config.py:74-75; user_embedding_dim,
     personalized_embedding_dim: config.py:64-65).  `batch_size` is stored: PNE's scores depend on it (newsEncoders.py:359 pairs title row r
     of a batch with user r % batch).  `zero_ties`: impressions whose scores are ALL exactly zero (GRU: a user without history has a zero user
@@ -55,7 +55,7 @@ def run(tag, news, user, stable, min_gap=None, batch_size=8, zero_ties=False, **
                          train_root='../MIND-tiny/train', dev_root='../MIND-tiny/dev', test_root='../MIND-tiny/test')
             flags.update(cfg_over)                              # (Inception overrides the two category dimensions)
             cfg = default_config(**flags)
-            torch.manual_seed(5)
+            torch.manual_seed(init_seed)            # (initialize() draws from it; 5 unless a case needs another draw for its min_gap)
             corpus = MIND_corpus.MIND_Corpus(cfg)
             m = ref_model.Model(cfg)
             m.initialize()
@@ -196,8 +196,20 @@ def run_sue_ablation():
     run('tiny_CNN_SUE_wo_HCA', 'CNN', 'SUE_wo_HCA', False, min_gap=1e-4)
 
 
+def run_cne_ablation():
+    """`python tools/make_eval_goldens.py cne_ablation`: two of the news-encoder ablations of variantEncoders.py under ATT -- CNE_wo_CS, whose
+    representations depend on their own news only (the cached evaluation path), and CNE_wo_CA, whose gate pairs the news of a call by
+    sorted rank (the per-sample path; torch.sort forced stable as for the CNE fixtures)."""
+    run('tiny_CNE_wo_CS_ATT', 'CNE_wo_CS', 'ATT', False, min_gap=1e-4, init_seed=6)     # (seed 5: two scores of an impression 1.6e-5 apart)
+    with stable_sort_patch():
+        run('tiny_CNE_wo_CA_ATT_stable', 'CNE_wo_CA', 'ATT', True, min_gap=1e-4)
+
+
 if __name__ == '__main__':
     torch.set_num_threads(4)
+    if len(sys.argv) > 1 and sys.argv[1] == 'cne_ablation':
+        run_cne_ablation()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'sue_ablation':
         run_sue_ablation()
         sys.exit(0)
@@ -238,3 +250,4 @@ if __name__ == '__main__':
     run_gru()
     run_naml()
     run_sue_ablation()
+    run_cne_ablation()

@@ -23,6 +23,7 @@ Usage:  python tools/make_goldens.py            (rewrites every fixture)
         python tools/make_goldens.py gru        (the GRU user encoder of DAE-GRU)
         python tools/make_goldens.py naml       (the single-view NAML news encoders NAML_Title / NAML_Content)
         python tools/make_goldens.py sue_ablation   (the user-encoder ablations SUE_wo_GCN / SUE_wo_HCA)
+        python tools/make_goldens.py cne_ablation   (the news-encoder ablations CNE_Title / CNE_Content / CNE_wo_CS / CNE_wo_CA)
 """
 import os
 import pickle
@@ -119,10 +120,14 @@ class record_dropout:
         self.F.dropout = self.orig
 
 
-def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True, adam_steps=3, dropout_seed=None, _rec_drop=None, user_ids=None, f64_step=False, entity_seed=None):
+def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True, adam_steps=3, dropout_seed=None, _rec_drop=None, user_ids=None, f64_step=False, entity_seed=None,
+             batch_hook=None, all_masks=False, rep_grads=False):
     """mode: 'train' (dropout_rate must be 0 unless dropout_seed is given) or 'eval' (for MHSA-user's hard-wired F.dropout).
     user_ids: the batch's user_ID (int64 [batch_size]) instead of the synthetic corpus's arange -- the personalised encoders read it.
-    entity_seed: write entity ids into the batch's title_entity fields (tests/kcnn_ref.py:fill_entities; the synthetic corpus leaves them zero)."""
+    entity_seed: write entity ids into the batch's title_entity fields (tests/kcnn_ref.py:fill_entities; the synthetic corpus leaves them zero).
+    batch_hook: edits the batch's arrays in place before anything reads them.  all_masks: store the mutated copies of all four text masks
+    (`mutated_{news,user}_{title,content}_mask`).  rep_grads (with f64_step): store the float64 run's gradients of the loss with respect to
+    the two news-encoder outputs (`f64/dcand_rep`, `f64/dhist_rep`)."""
     if dropout_seed is not None:
         assert adam_steps == 1 and mode == 'train'
         with record_dropout(dropout_seed) as rec_drop:
@@ -135,6 +140,8 @@ def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True
     if entity_seed is not None:
         from kcnn_ref import fill_entities
         fill_entities(batch, cfg.entity_size, entity_seed)
+    if batch_hook is not None:
+        batch_hook(batch)
     rngw = np.random.default_rng(seed + 7)
     table = (rngw.standard_normal((cfg.vocabulary_size, cfg.word_embedding_dim)) * 0.3).astype(np.float32)
     table[0] = 0
@@ -194,6 +201,9 @@ def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True
             grads = {k: p.grad.detach().clone().numpy() for k, p in m.named_parameters()}
             out['mutated_news_title_mask'] = inp[16].numpy().copy()
             out['mutated_user_history_category_mask'] = inp[11].numpy().copy()
+            if all_masks:
+                for key, idx in (('news_title', 16), ('news_content', 19), ('user_title', 4), ('user_content', 7)):
+                    out['mutated_%s_mask' % key] = inp[idx].numpy().copy()
         total_norm = torch.nn.utils.clip_grad_norm_(m.parameters(), cfg.gradient_clip_norm)
         if step == 0:
             out['grad_total_norm'] = np.float32(float(total_norm))
@@ -231,6 +241,11 @@ def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True
                 getattr(m64.user_encoder, name).register_forward_hook(lambda mod, i, o, name=name: (fim64.setdefault(name, o.detach().clone().numpy()), None)[1])
         else:
             m64.news_encoder.register_forward_hook(lambda mod, i, o: rec64.append(o.detach().clone().numpy()))
+        drep64 = {}
+        if rep_grads:                           # d loss / d (news-encoder output) of the candidate call (0) and of the history call (1)
+            calls64 = []
+            m64.news_encoder.register_forward_hook(lambda mod, i, o: (calls64.append(0), o.register_hook(
+                lambda g, c=len(calls64) - 1: drep64.__setitem__(c, g.detach().clone().numpy())))[0] and None)
         conv64 = []
         if cfg.news_encoder == 'KCNN':          # the raw convolution outputs of both calls as [titles, positions, C]: the argmax margins
             m64.news_encoder.knowledge_cnn.conv.register_forward_hook(lambda mod, i, o: conv64.append(o.detach().squeeze(3).permute(0, 2, 1).clone().numpy()))
@@ -261,6 +276,8 @@ def run_case(tag, cfg, spec, batch_size, seed, mode, gain=None, full_arrays=True
                                                  for k in ('conv_3D_a', 'conv_3D_b')))
         else:
             out['f64/cand_rep'], out['f64/hist_rep'] = rec64[0], rec64[1]
+        if rep_grads:
+            out['f64/dcand_rep'], out['f64/dhist_rep'] = drep64[0], drep64[1]
         if conv64:
             out['f64/kcnn/z_cand'], out['f64/kcnn/z_hist'] = conv64[0], conv64[1]
         for k, v in naml64.items():
@@ -805,6 +822,95 @@ def sue_ablation_cases():
     check('tiny_CNN_SUE_wo_HCA_ln', True)
 
 
+CNE_ABLATION_PAIR_MOVE = 100 * 2e-5      # a wrong gate partner must move hist_rep by 100 x the GPU tests' output bar
+CNE_ABLATION_TINY = (('tiny_CNE_Title_ATT', 'CNE_Title', 'ATT'), ('tiny_CNE_Content_ATT', 'CNE_Content', 'ATT'), ('tiny_CNE_wo_CS_ATT', 'CNE_wo_CS', 'ATT'),
+                     ('tiny_CNE_wo_CS_SUE_stable', 'CNE_wo_CS', 'SUE'), ('tiny_CNE_wo_CA_ATT_stable', 'CNE_wo_CA', 'ATT'),
+                     ('tiny_CNE_wo_CA_SUE_stable', 'CNE_wo_CA', 'SUE'))
+
+
+def cne_ablation_empty_title(batch):
+    """The synthetic corpus has no news with an all-zero title mask (its PAD news sets position 0, MIND_corpus.py:352-353): the second
+    candidate of the first sample and the first history slot of the first user that has one lose theirs, so that the encoders' own
+    `title_mask[:, 0] = 1` acts on both calls."""
+    batch['news_title_mask'][0, 1, :] = False
+    b = int(np.argmax(batch['user_history_mask'][:, 0]))
+    assert batch['user_history_mask'][b, 0]
+    batch['user_title_mask'][b, 0, :] = False
+
+
+def cne_ablation_conditions(z):
+    """What a tiny cne_ablation batch must hold (tests/test_cne_ablation_host.py asserts the same), per condition over both encoder calls:
+    a title with an all-zero mask, a title of full length, a content of length 1, an empty content, two equal lengths above 1 in each stream
+    of the history call, and a padded history slot (news 0: one token, id 0)."""
+    tm = np.concatenate([z['in/%s_title_mask' % c].reshape(-1, z['in/news_title_mask'].shape[-1]) for c in ('news', 'user')]).astype(bool)
+    cm = np.concatenate([z['in/%s_content_mask' % c].reshape(-1, z['in/news_content_mask'].shape[-1]) for c in ('news', 'user')]).astype(bool)
+
+    def tie(mask):
+        lens = mask.reshape(-1, mask.shape[-1]).astype(bool).sum(axis=1)
+        vals, counts = np.unique(lens[lens > 1], return_counts=True)
+        return bool((counts >= 2).any())
+    return dict(empty_title=bool((tm.sum(1) == 0).any()), full_title=bool(tm.all(axis=1).any()), content_of_one=bool((cm.sum(1) == 1).any()),
+                empty_content=bool((cm.sum(1) == 0).any()), title_tie=tie(z['in/user_title_mask']), content_tie=tie(z['in/user_content_mask']),
+                pad_slot=bool((~z['in/user_history_mask'].astype(bool)).any() and (z['in/user_title_text'][~z['in/user_history_mask'].astype(bool)] == 0).all()))
+
+
+def cne_ablation_cases():
+    """The news-encoder ablations of the paper's own model (`python tools/make_goldens.py cne_ablation`; variantEncoders.py:14-99,190-339)
+    under the ATT and SUE user encoders, make_state weights (gain 2.0 tiny, 1.0 full), three Adam steps, the tiny cases at batch 8 with step 0
+    of a float64 run of the same classes (`f64/...`, with its gradients with respect to the two encoder outputs) and the mutated copies of
+    all four text masks.  The `_stable` cases -- every case in which the gate's rank pairing or SUE's inputs depend on the order of equal
+    lengths -- run with torch.sort forced stable, as the CNE fixtures do.  Every tiny batch meets cne_ablation_conditions (one title mask of
+    each call is cleared by cne_ablation_empty_title), and for CNE_wo_CA pairing the gate by index instead of by sorted rank moves hist_rep by
+    at least CNE_ABLATION_PAIR_MOVE (tests/cne_ablation_ref.py, pair='index'): the corpus seed is the first from 3 for which both hold."""
+    import cne_ablation_ref as R
+    from nnr_amd.model import Model
+
+    def pick(cfg, news, bs, seed, sseed):
+        while True:
+            b = SynthCorpus(tiny_spec(cfg, sseed)).batch(bs, np.random.default_rng(seed + 100))
+            cne_ablation_empty_title(b)
+            ok = cne_ablation_conditions({'in/' + k: v for k, v in b.items()})
+            move = float('inf')
+            if all(ok.values()) and news == 'CNE_wo_CA':
+                st = make_state({k: tuple(v.shape) for k, v in Model(cfg, torch.zeros(cfg.vocabulary_size, cfg.word_embedding_dim)).named_parameters()}, seed, 2.0)
+                a, c = (R.encode_batch(news, st, cfg, b, pair=pr)['hist_rep'] for pr in ('rank', 'index'))
+                move = float((a - c).abs().max())
+            print('  corpus seed %d: %s, pair move %.3e' % (sseed, ok, move))
+            if all(ok.values()) and move >= CNE_ABLATION_PAIR_MOVE:
+                return sseed
+            sseed += 1
+
+    def check(tag, tiny):
+        z = np.load(os.path.join(OUT, tag + '.npz'))
+        total = float(z['grad_total_norm'])
+        share = {k[len('gradnorm/news_encoder.'):]: round(float(z[k]) / total, 4) for k in z.files if k.startswith('gradnorm/news_encoder.') and k.endswith('weight')}
+        print('  %s: |g| / |g_total| %s, %d bytes' % (tag, share, os.path.getsize(os.path.join(OUT, tag + '.npz'))))
+        assert os.path.getsize(os.path.join(OUT, tag + '.npz')) < 350000, tag
+        if tiny:
+            ok = cne_ablation_conditions(z)
+            assert all(ok.values()), (tag, ok)
+
+    for tag, news, user in CNE_ABLATION_TINY:
+        cfg = tiny_cfg(news, user)
+        sseed = pick(cfg, news, 8, 19, 3)
+        kw = dict(batch_size=8, seed=19, mode='train', gain=2.0, f64_step=True, batch_hook=cne_ablation_empty_title, all_masks=True, rep_grads=True)
+        if tag.endswith('_stable'):
+            with stable_sort_patch():
+                run_case(tag, cfg, tiny_spec(cfg, sseed), **kw)
+        else:
+            run_case(tag, cfg, tiny_spec(cfg, sseed), **kw)
+        check(tag, True)
+    for tag, news in (('full_CNE_Title_ATT_g1p0', 'CNE_Title'), ('full_CNE_wo_CS_ATT_g1p0', 'CNE_wo_CS'), ('full_CNE_wo_CA_ATT_g1p0_stable', 'CNE_wo_CA')):
+        cfg = full_cfg(news, 'ATT', V=400)
+        kw = dict(batch_size=2, seed=17, mode='train', gain=1.0, full_arrays=False, all_masks=True)
+        if tag.endswith('_stable'):
+            with stable_sort_patch():
+                run_case(tag, cfg, full_spec(cfg, 9), **kw)
+        else:
+            run_case(tag, cfg, full_spec(cfg, 9), **kw)
+        check(tag, False)
+
+
 class _NoFiles(dict):
     """A plain dict of batch arrays as sue_ablation_conditions' argument: no stored parameters."""
     files = ()
@@ -826,6 +932,9 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == 'sue_ablation':
         torch.set_num_threads(8)
         return sue_ablation_cases()
+    if len(sys.argv) > 1 and sys.argv[1] == 'cne_ablation':
+        torch.set_num_threads(8)
+        return cne_ablation_cases()
     if len(sys.argv) > 1 and sys.argv[1] == 'kcnn':
         torch.set_num_threads(8)
         return kcnn_cases()
