@@ -368,7 +368,8 @@ int nnr_sue_x0_bwd(const float* dx0, const float* dx0_add, float* dhist, float* 
 int nnr_sue_slice_fwd(const float* gcn, const float* x0, float* gfeat, int B, int Hn, int G, int D, hipStream_t stream);   /* :81-82 */
 int nnr_sue_slice_bwd(const float* dgfeat, float* dpad, int B, int Hn, int G, int D, hipStream_t stream);
 /* torch_scatter.scatter_softmax + scatter_sum (userEncoders.py:85-89): kf [B,Hn,A], qc [B,N,A], g [B,Hn,D], cidx int64 [B,Hn]
- * -> alpha [B,N,Hn], feat [B,N,C,D] */
+ * (clamped into [0, C)) -> alpha [B,N,Hn], feat [B,N,C,D]; ds_ws [B*N*Hn] scratch.  Sizes as for the GEMV form below, and A >= 1: anything else is
+ * NNR_ERR_UNSUPPORTED before any launch; a null pointer is NNR_ERR_ARG. */
 int nnr_sue_intra_fwd(const float* kf, const float* qc, const float* g, const long* cidx, int B, int N, int Hn, int C, int A, int D,
                       float* alpha, float* feat, hipStream_t stream);
 int nnr_sue_intra_bwd(const float* kf, const float* qc, const float* g, const long* cidx, const float* alpha, const float* dfeat, int B,

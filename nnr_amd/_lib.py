@@ -284,7 +284,7 @@ def build_id():
     return {'src_sha256': h.hexdigest()[:16], 'lib_sha256': lib_hash}
 
 
-NNR_ERR_UNSUPPORTED = -3
+NNR_ERR_ARG, NNR_ERR_UNSUPPORTED = -1, -3
 CALLS = [0]          # C-ABI calls checked so far (bench.py reports calls per step; each is one or a few kernel launches)
 
 

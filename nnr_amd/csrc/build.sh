@@ -8,11 +8,13 @@ mkdir -p build
 pids=()
 compiled=""
 kept=""
+objs=""
 # incremental: a source is recompiled when it, any header here or the public header is newer than its object (NNR_BUILD_FORCE=1: everything);
 # what was compiled and what was kept is printed, so a caller can see which it got
 newest_h=$(ls -t *.h ../../include/nnr_hip.h | head -1)
-for f in gemm seq_plan lstm pool misc mhsa corpus dp gcn tape fuse sort cand_attn omap pers_attn kcnn hdc fim gru naml dssm seg_pool bag; do
+for f in gemm seq_plan lstm pool misc mhsa corpus dp gcn tape fuse sort cand_attn omap pers_attn kcnn hdc fim gru naml dssm sue_cluster bag; do
   [ -f $f.hip ] || continue
+  objs="$objs build/$f.o"
   if [ "${NNR_BUILD_FORCE}" = "1" ] || [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ $newest_h -nt build/$f.o ]; then
     hipcc $FLAGS -c $f.hip -o build/$f.o &
     pids+=($!)
@@ -23,5 +25,6 @@ for f in gemm seq_plan lstm pool misc mhsa corpus dp gcn tape fuse sort cand_att
 done
 for p in "${pids[@]}"; do wait $p; done
 echo "compiled:${compiled:- (none)}; up to date:${kept:- (none)}"
-hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT build/*.o -ldl
+# exactly the objects of the list: an object left in build/ by a source that was renamed or removed is not linked
+hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT $objs -ldl
 echo "built $(realpath $OUT)"

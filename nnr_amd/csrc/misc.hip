@@ -482,283 +482,6 @@ __global__ void relu_bwd_kernel(const float* __restrict__ dy, const float* __res
     dx[i] = (y[i] > 0.f) ? dy[i] : 0.f;
 }
 
-// ---- SUE intra-cluster attention (userEncoders.py:85-89; replaces torch_scatter.scatter_softmax / scatter_sum).
-// One workgroup per (sample b, candidate n).  scores over the Hn history items, softmax WITHIN each cluster id
-// (segments held in LDS), cluster-wise weighted sum of the [Hn, D] features -> [C, D]; empty clusters give 0.
-constexpr int SUE_MAXH = 64, SUE_MAXC = 32;
-// cluster member lists of one sample in LDS: order[cstart[c] .. cstart[c] + ccnt[c]) = the items of cluster c, ascending
-__device__ __forceinline__ void sue_members(const int* cid, int Hn, int C, int* ccnt, int* cstart, int* order) {
-  const int tid = threadIdx.x;
-  if (tid < C) {
-    int n = 0;
-    for (int j = 0; j < Hn; ++j) n += (cid[j] == tid);
-    ccnt[tid] = n;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int acc = 0;
-    for (int c = 0; c < C; ++c) { cstart[c] = acc; acc += ccnt[c]; }
-  }
-  __syncthreads();
-  if (tid < C) {
-    int k = cstart[tid];
-    for (int j = 0; j < Hn; ++j) if (cid[j] == tid) order[k++] = j;
-  }
-  __syncthreads();
-}
-
-// forward: one workgroup per (b, n, 256-column slice) -- every workgroup recomputes the (tiny) scores and segment softmax of its (b, n) and
-// produces one slice of the C cluster features, walking each cluster's member list once.
-// Round 6: the N candidates of a user all read the user's g [Hn, D] (180 KB; the launch's algorithmic bytes count it ONCE), and consecutive
-// workgroup ids go to different XCDs, whose L2s do not share: as a (B N, slices) grid the five readers of a g slice sat in five L2s and the counter
-// traffic was 2.6x the algorithmic bytes.  The grid is 1-D now and workgroup id -> (XCD x = id & 7, slot = id >> 3) -> user b = 8 (slot / (N S)) + x:
-// every workgroup of a user runs on ONE XCD, the N readers of a slice back to back (n fastest).
-__device__ __forceinline__ bool sue_xcd_map(int id, int B, int per_user, int* b, int* w) {
-  const int x = id & 7, slot = id >> 3;
-  *b = (slot / per_user) * 8 + x;
-  *w = slot % per_user;
-  return *b < B;
-}
-__global__ __launch_bounds__(256) void sue_intra_fwd_kernel(const float* __restrict__ kf, const float* __restrict__ qc,
-                                                            const float* __restrict__ g, const long* __restrict__ cidx,
-                                                            int B, int N, int Hn, int C, int A, int D, float inv_scale,
-                                                            float* __restrict__ alpha, float* __restrict__ feat) {
-  __shared__ float sc[SUE_MAXH], al[SUE_MAXH], cmax[SUE_MAXC], csum[SUE_MAXC];
-  __shared__ int cid[SUE_MAXH], order[SUE_MAXH], ccnt[SUE_MAXC], cstart[SUE_MAXC];
-  int b, wi;
-  if (!sue_xcd_map(blockIdx.x, B, N * ((D + 255) / 256), &b, &wi)) return;
-  const int slice = wi / N, bn = b * N + (wi - slice * N);
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  for (int j = tid; j < Hn; j += 256) cid[j] = (int)cidx[(long)b * Hn + j];
-  const float* q = qc + (long)bn * A;
-  for (int j0 = w; j0 < Hn; j0 += 16) {                     // 4 items per wave and trip: their loads are in flight together
-    float p[4] = {0.f, 0.f, 0.f, 0.f};
-    const float* k[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) k[u] = kf + ((long)b * Hn + min(j0 + 4 * u, Hn - 1)) * A;
-    for (int x = lane; x < A; x += 64) {
-      const float qv = q[x];
-      float kv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) kv[u] = k[u][x];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) p[u] += kv[u] * qv;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float t = wave_sum(p[u]);
-      if (lane == 0 && j0 + 4 * u < Hn) sc[j0 + 4 * u] = t * inv_scale;
-    }
-  }
-  __syncthreads();
-  sue_members(cid, Hn, C, ccnt, cstart, order);
-  if (tid < C) {
-    float m = -INFINITY;
-    for (int k = 0; k < ccnt[tid]; ++k) m = fmaxf(m, sc[order[cstart[tid] + k]]);
-    float sm = 0.f;
-    for (int k = 0; k < ccnt[tid]; ++k) sm += expf(sc[order[cstart[tid] + k]] - m);
-    cmax[tid] = m; csum[tid] = sm;
-  }
-  __syncthreads();
-  for (int j = tid; j < Hn; j += 256) {
-    const float v = expf(sc[j] - cmax[cid[j]]) / csum[cid[j]];
-    al[j] = v;
-    if (slice == 0) alpha[(long)bn * Hn + j] = v;
-  }
-  __syncthreads();
-  const int col = slice * 256 + tid;
-  if (col >= D) return;
-  const float* gb = g + (long)b * Hn * D + col;
-  float* fo = feat + (long)bn * C * D + col;
-  // One walk over the cluster-sorted member list, 8 loads in flight per trip (cluster by cluster the walk was up to Hn dependent
-  // loads: clusters hold 2-3 members on average).  Every cluster still sums its members in ascending order.
-  for (int c = 0; c < C; ++c)
-    if (ccnt[c] == 0) fo[(long)c * D] = 0.f;            // empty cluster -> 0, as scatter_sum
-  const int total = cstart[C - 1] + ccnt[C - 1];
-  if (total == 0) return;
-  int cur = cid[order[0]];
-  float acc = 0.f;
-  for (int p0 = 0; p0 < total; p0 += 8) {
-    int jj[8];
-    float gv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      jj[u] = order[min(p0 + u, total - 1)];
-      gv[u] = gb[(long)jj[u] * D];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      if (p0 + u < total) {
-        const int cl = cid[jj[u]];
-        if (cl != cur) {
-          fo[(long)cur * D] = acc;
-          acc = 0.f;
-          cur = cl;
-        }
-        acc += al[jj[u]] * gv[u];
-      }
-    }
-  }
-  fo[(long)cur * D] = acc;
-}
-
-// backward part 1, grid B*N: d alpha, segment-softmax backward -> ds[b, n, :] (workspace), dqc[b, n, :].
-// (B*N = 320 workgroups of 4 waves at batch 64.  16 waves per workgroup take the Hn items in one trip and are no faster alone
-// (30 vs 27 us) but 126 vs 82 us inside the step: a 1024-thread workgroup needs a whole CU at once, and the CUs are shared with the
-// weight-gradient GEMM of the other stream.  The kernel is written for any multiple of 64 threads.)
-__global__ __launch_bounds__(256) void sue_intra_bwd_ds_kernel(const float* __restrict__ kf, const float* __restrict__ g,
-                                                                const long* __restrict__ cidx, const float* __restrict__ alpha,
-                                                                const float* __restrict__ dfeat, int B, int N, int Hn, int C, int A, int D,
-                                                                float inv_scale, float* __restrict__ ds_ws, float* __restrict__ dqc) {
-  __shared__ float al[SUE_MAXH], da[SUE_MAXH], ds[SUE_MAXH], csum[SUE_MAXC];
-  __shared__ int cid[SUE_MAXH];
-  int b, ni;
-  if (!sue_xcd_map(blockIdx.x, B, N, &b, &ni)) return;             // (the N workgroups of a user read the same g[b]: one XCD, see the forward)
-  const int bn = b * N + ni, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int nt = blockDim.x, nw = nt >> 6;
-  for (int j = tid; j < Hn; j += nt) { cid[j] = (int)cidx[(long)b * Hn + j]; al[j] = alpha[(long)bn * Hn + j]; }
-  __syncthreads();
-  const float* gb = g + (long)b * Hn * D;
-  const float* df = dfeat + (long)bn * C * D;
-  // dalpha_j = <dfeat[cid_j], g_j>
-  if (!(D & 3)) {
-    // 4 items per wave at a time, float4 lanes, two column trips per pass: 16 independent 16-byte loads in flight, 2 passes at D = 900
-    const int D4 = D >> 2;
-    for (int j0 = w; j0 < Hn; j0 += 4 * nw) {
-      float p[4] = {0.f, 0.f, 0.f, 0.f};
-      const f32x4* dr[4];
-      const f32x4* gr[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int j = min(j0 + nw * u, Hn - 1);
-        dr[u] = reinterpret_cast<const f32x4*>(df + (long)cid[j] * D);
-        gr[u] = reinterpret_cast<const f32x4*>(gb + (long)j * D);
-      }
-      for (int x = lane; x < D4; x += 128) {
-        const int x2 = x + 64;
-        const bool two = x2 < D4;
-        f32x4 a[4], c[4], a2[4], c2[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { a[u] = dr[u][x]; c[u] = gr[u][x]; }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          a2[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-          c2[u] = a2[u];
-          if (two) { a2[u] = dr[u][x2]; c2[u] = gr[u][x2]; }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) p[u] += a[u][0] * c[u][0] + a[u][1] * c[u][1] + a[u][2] * c[u][2] + a[u][3] * c[u][3];
-        if (two) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) p[u] += a2[u][0] * c2[u][0] + a2[u][1] * c2[u][1] + a2[u][2] * c2[u][2] + a2[u][3] * c2[u][3];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float t = wave_sum(p[u]);
-        if (lane == 0 && j0 + nw * u < Hn) da[j0 + nw * u] = t;
-      }
-    }
-  } else {
-    for (int j = w; j < Hn; j += nw) {
-      const float* dr = df + (long)cid[j] * D;
-      const float* gr = gb + (long)j * D;
-      float p = 0.f;
-      for (int x = lane; x < D; x += 64) p += dr[x] * gr[x];
-      p = wave_sum(p);
-      if (lane == 0) da[j] = p;
-    }
-  }
-  __syncthreads();
-  if (tid < C) {
-    float sm = 0.f;
-    for (int j = 0; j < Hn; ++j) if (cid[j] == tid) sm += al[j] * da[j];
-    csum[tid] = sm;
-  }
-  __syncthreads();
-  for (int j = tid; j < Hn; j += nt) {
-    const float v = al[j] * (da[j] - csum[cid[j]]) * inv_scale;
-    ds[j] = v;
-    ds_ws[(long)bn * Hn + j] = v;
-  }
-  __syncthreads();
-  // dqc[b, n, :] = sum_j ds[j] * kf[b, j, :]
-  for (int x = tid; x < A; x += nt) {
-    float acc = 0.f;
-    int j = 0;
-    for (; j + 8 <= Hn; j += 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = kf[((long)b * Hn + j + u) * A + x];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc += ds[j + u] * v[u];
-    }
-    for (; j < Hn; ++j) acc += ds[j] * kf[((long)b * Hn + j) * A + x];
-    dqc[(long)bn * A + x] = acc;
-  }
-}
-
-// backward part 2, grid (B, ceil(D/256) + 1): slices y < last -> dg[b, j, cols] = sum_n alpha[b,n,j] * dfeat[b,n,cid_j,cols]
-// (each row written exactly once, no read-modify-write); the last slice -> dkf[b, j, :] = sum_n ds[b,n,j] * qc[b,n,:]
-__global__ __launch_bounds__(256) void sue_intra_bwd_dg_kernel(const float* __restrict__ qc, const long* __restrict__ cidx,
-                                                               const float* __restrict__ alpha, const float* __restrict__ dfeat,
-                                                               const float* __restrict__ ds_ws, int N, int Hn, int C, int A, int D,
-                                                               float* __restrict__ dg, float* __restrict__ dkf) {
-  __shared__ float al[8][SUE_MAXH];
-  __shared__ int cid[SUE_MAXH], order[SUE_MAXH], ccnt[SUE_MAXC], cstart[SUE_MAXC];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const bool last = blockIdx.y == gridDim.y - 1;
-  for (int i = tid; i < N * Hn; i += 256) {
-    const int n = i / Hn, j = i - n * Hn;
-    al[n][j] = last ? ds_ws[((long)b * N + n) * Hn + j] : alpha[((long)b * N + n) * Hn + j];
-  }
-  for (int j = tid; j < Hn; j += 256) cid[j] = (int)cidx[(long)b * Hn + j];
-  __syncthreads();
-  if (last) {
-    if (blockIdx.z) return;
-    for (int x = tid; x < A; x += 256) {
-      float qv[8];
-#pragma unroll
-      for (int n = 0; n < 8; ++n) qv[n] = n < N ? qc[((long)b * N + n) * A + x] : 0.f;
-      for (int j = 0; j < Hn; ++j) {
-        float acc = 0.f;
-#pragma unroll
-        for (int n = 0; n < 8; ++n) if (n < N) acc += al[n][j] * qv[n];      // rows n >= N of `al` are never written (stale LDS may hold NaN)
-        dkf[((long)b * Hn + j) * A + x] = acc;
-      }
-    }
-    return;
-  }
-  sue_members(cid, Hn, C, ccnt, cstart, order);
-  const int col = blockIdx.y * 256 + tid;
-  if (col >= D) return;
-  // blockIdx.z deals the clusters (c = z, z + Z, ...): B * slices workgroups alone are 1.25 waves per SIMD at batch 64, and their C
-  // dependent load groups were pure latency.  The next cluster's d feat values are loaded before this cluster's rows are stored.
-  const int Z = gridDim.z;
-  int c = blockIdx.z;
-  while (c < C && ccnt[c] == 0) c += Z;
-  float nx[8];
-#pragma unroll
-  for (int n = 0; n < 8; ++n) nx[n] = (n < N && c < C) ? dfeat[(((long)b * N + n) * C + c) * D + col] : 0.f;
-  while (c < C) {
-    float dv[8];
-#pragma unroll
-    for (int n = 0; n < 8; ++n) dv[n] = nx[n];
-    int cn = c + Z;
-    while (cn < C && ccnt[cn] == 0) cn += Z;
-#pragma unroll
-    for (int n = 0; n < 8; ++n) nx[n] = (n < N && cn < C) ? dfeat[(((long)b * N + n) * C + cn) * D + col] : 0.f;
-    for (int k = 0; k < ccnt[c]; ++k) {
-      const int j = order[cstart[c] + k];
-      float acc = 0.f;
-#pragma unroll
-      for (int n = 0; n < 8; ++n) if (n < N) acc += al[n][j] * dv[n];
-      dg[((long)b * Hn + j) * D + col] = acc;
-    }
-    c = cn;
-  }
-}
-
 // ---- click predictor + loss (model.py:126-127, trainer.py:64-66), one workgroup for the whole (tiny) batch tail.
 // logits[b, n] = <user[b, n], cand[b, n]> ; loss = mean_b( -log_softmax(logits[b])[0] )
 // dlogits[b, n] = (softmax(logits[b])[n] - [n == 0]) * loss_scale / B   (loss_scale = 1, or 1 for DP: grads are averaged later)
@@ -1205,28 +928,6 @@ extern "C" int nnr_layernorm_bwd(const float* dv, const float* xhat, const float
 }
 extern "C" int nnr_relu_bwd(const float* dy, const float* y, float* dx, long n, hipStream_t stream) {
   EW_LAUNCH(relu_bwd_kernel, n, dy, y, dx, n);
-}
-
-extern "C" int nnr_sue_intra_fwd(const float* kf, const float* qc, const float* g, const long* cidx, int B, int N, int Hn, int C, int A,
-                                 int D, float* alpha, float* feat, hipStream_t stream) {
-  if (Hn > SUE_MAXH || C > SUE_MAXC) return NNR_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(sue_intra_fwd_kernel, dim3((B + 7) / 8 * 8 * N * ((D + 255) / 256)), dim3(256), 0, stream, kf, qc, g, cidx, B, N, Hn, C, A, D,
-                     1.f / sqrtf((float)A), alpha, feat);
-  NNR_CHECK_LAUNCH();
-  return NNR_OK;
-}
-extern "C" int nnr_sue_intra_bwd(const float* kf, const float* qc, const float* g, const long* cidx, const float* alpha,
-                                 const float* dfeat, int B, int N, int Hn, int C, int A, int D, float* dg, float* dkf, float* dqc,
-                                 float* ds_ws, hipStream_t stream) {
-  if (Hn > SUE_MAXH || C > SUE_MAXC || N > 8) return NNR_ERR_UNSUPPORTED;
-  if (!ds_ws) return NNR_ERR_ARG;
-  hipLaunchKernelGGL(sue_intra_bwd_ds_kernel, dim3((B + 7) / 8 * 8 * N), dim3(256), 0, stream, kf, g, cidx, alpha, dfeat, B, N, Hn, C, A, D,
-                     1.f / sqrtf((float)A), ds_ws, dqc);
-  NNR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sue_intra_bwd_dg_kernel, dim3(B, (D + 255) / 256 + 1, C >= 3 ? 3 : 1), dim3(256), 0, stream, qc, cidx, alpha, dfeat, ds_ws, N, Hn, C,
-                     A, D, dg, dkf);
-  NNR_CHECK_LAUNCH();
-  return NNR_OK;
 }
 
 extern "C" int nnr_logits_loss_fwd(const float* user, const float* cand, int B, int N, int D, float* logits, float* loss, float* dlogits,

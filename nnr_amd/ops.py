@@ -1219,12 +1219,13 @@ def _sue_intra_bwd(kf, qc, g, cidx, alpha, dfeat, B, N, Hn, Cn, A, D, dg, dkf, d
                                       _p(ws), _s()), 'nnr_sue_intra_bwd')
 
 
-SEG_POOL_MAXH, SEG_POOL_MAXC, SEG_POOL_MAXN = 64, 32, 8      # nnr_sue_seg_pool_*'s rule (the limits of sue_intra_*), restated for the constructors
+SEG_POOL_MAXH, SEG_POOL_MAXC, SEG_POOL_MAXN = 64, 32, 8      # SUE_MAXH / SUE_MAXC / SUE_MAXN of csrc/sue_cluster.hip, for the constructors
 SEG_POOL_UNSUPPORTED = 'unsupported size (the segmented candidate pool takes 1 <= history slots <= 64, 1 <= clusters <= 32 and 1 <= candidates <= 8)'
 
 
 def seg_pool_supported(Hn, Cn, N=1, D=1, B=1):
-    """Host mirror of nnr_sue_seg_pool_*'s rule (csrc/seg_pool.hip), for the constructors: no library call, no device."""
+    """The one host mirror of sue_cluster_ok (csrc/sue_cluster.hip), the size rule of nnr_sue_seg_pool_* and nnr_sue_intra_* (which also
+    want A >= 1): no library call, no device."""
     return int(B) >= 1 and 1 <= int(N) <= SEG_POOL_MAXN and 1 <= int(Hn) <= SEG_POOL_MAXH and 1 <= int(Cn) <= SEG_POOL_MAXC and int(D) >= 1
 
 

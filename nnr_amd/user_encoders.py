@@ -172,104 +172,161 @@ CAPTURE = [None]      # diagnostics / parity tests: set CAPTURE[0] = [] and ever
                       # layers in sv['gcn']['rs'], of the cluster affine in sv['rc']); a replayed step rewrites the SAME buffers
 
 
-def sue_forward(mod, hist, cand, graph, cmask, cidx):
-    B, Hn, D = hist.shape
-    N = cand.shape[1]
-    Kc = mod.proxy_node_embedding.shape[0]
-    G, Cn, A = Hn + Kc, Kc + 1, mod.attention_dim
-    dev = hist.device
-    f32 = dict(device=dev, dtype=torch.float32)
-    p = mod.dropout_rate if mod.training else 0.0
-    seed = mod._next_seed()
-    sv = dict(B=B, Hn=Hn, D=D, N=N, Kc=Kc, G=G, Cn=Cn, A=A, p=p, seed=seed, hist=hist, cand=cand, cidx=cidx, cmask=cmask,
-              graph=graph)
-    x0 = torch.empty((B, G, D), **f32)
-    # ---- the candidate-side projections need nothing but `cand`: three small launches (q of the intra-cluster attention, q and v of the
-    # inter-cluster attention; 15-30 us each, latency-bound) that sat on the dependent chain behind the GCN run beside it instead
-    cand2 = cand.view(B * N, D)
-    ia = mod.interClusterAttention
-    qc = torch.empty((B * N, A), **f32)
-    qv = torch.empty((B * N, A), **f32)
-    v = torch.empty((B * N, D), **f32)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# SUE's pipeline in stages, each a forward / backward pair written once:  GCN feature -> intra-cluster attention (two forms) -> tail (cluster
+# affine + inter-cluster pool).  SUE runs all three, SUE_wo_GCN the last two on the raw history rows, SUE_wo_HCA the first alone.
 
-    def cand_side():
-        ops.linear_fwd(cand2, mod.intraCluster_Q.weight, mod.intraCluster_Q.bias, out=qc)                # [B*N, A]
-        ops.linear_fwd(cand2, ia.Q.weight, ia.Q.bias, out=qv)                                            # [B*N, A]
-        ops.gemm(qv, ia.K.weight, v, M=B * N, N=D, K=A, lda=A, ldb=D, ldc=D, trans_b=True)
-    side = _sue_side(dev)
-    side_ev = None
-    if side is not None:
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            cand_side()
-            side_ev = torch.cuda.Event()
-            side_ev.record()
-    # (+ the in-place `user_history_category_mask[:, -1] = 1` of userEncoders.py:73 in the same launch)
-    fix = cmask if (cmask.is_cuda and cmask.dim() == 2 and cmask.is_contiguous() and tuple(cmask.shape) == (B, Kc + 1)) else None
-    if fix is None:
-        if cmask.is_cuda and cmask.dim() == 2 and cmask.is_contiguous() and cmask.element_size() == 1:
-            ops.fill_column_u8(cmask, -1, 1)            # (a C-ABI call: recordable)
-        else:
-            cmask[:, -1] = 1
-    ops.sue_x0_fwd(hist, mod.proxy_node_embedding, x0, B, Hn, Kc, D, p, seed + 1, cmask_fix=fix)
-    # ---- GCN
+def _fix_cluster_mask(cmask, fused=None):
+    """user_history_category_mask[:, -1] = 1, in place on the caller's tensor (userEncoders.py:73, variantEncoders.py:369).  fused: the
+    (B, Kc + 1) shape at which ops.sue_x0_fwd writes the column in its own launch: the mask is then returned for that launch's cmask_fix and
+    nothing is issued here.  Otherwise the column is written now (a C-ABI call where the layout allows: recordable) and None is returned."""
+    flat = cmask.is_cuda and cmask.dim() == 2 and cmask.is_contiguous()
+    if flat and fused is not None and tuple(cmask.shape) == fused:
+        return cmask
+    if flat and cmask.element_size() == 1:
+        ops.fill_column_u8(cmask, -1, 1)
+    else:
+        cmask[:, -1] = 1
+    return None
+
+
+def gcn_feature_fwd(mod, hist, graph, p, seed, cmask_fix=None):
+    """(gcn([history ; dropout_(proxy nodes)]) + X0)[:, :Hn] (userEncoders.py:80-82, variantEncoders.py:414-416).  Dropout sites: the proxy
+    nodes at seed + 1, GCN layer l at seed + 10 + l with p / 2.  -> gfeat [B, Hn, D], the GCN's saved state."""
+    B, Hn, D = hist.shape
+    Kc = mod.proxy_node_embedding.shape[0]
+    G = Hn + Kc
+    f32 = dict(device=hist.device, dtype=torch.float32)
+    x0 = torch.empty((B, G, D), **f32)
+    ops.sue_x0_fwd(hist, mod.proxy_node_embedding, x0, B, Hn, Kc, D, p, seed + 1, cmask_fix=cmask_fix)
     x, gsv = gcn_forward(mod.gcn, x0, graph, seed + 10, mod.training)
-    sv['gcn'] = gsv
     gfeat = torch.empty((B, Hn, D), **f32)
     ops.sue_slice_fwd(x, x0, gfeat, B, Hn, G, D)
-    # ---- intra-cluster attention
-    kf = ops.linear_fwd(gfeat.view(B * Hn, D), mod.intraCluster_K.weight)                                # [B*Hn, A]
-    if side is None:
-        cand_side()
-    else:
-        torch.cuda.current_stream(dev).wait_event(side_ev)
-    alpha_i = torch.empty((B, N, Hn), **f32)
-    feat = torch.empty((B * N * Cn, D), **f32)
-    ops.sue_intra_fwd(kf, qc, gfeat, cidx, B, N, Hn, Cn, A, D, alpha_i, feat)
-    # ---- cluster feature affine: dropout(relu(W F + b) + F)
-    rc = torch.empty((B * N * Cn, D), **f32)
-    f2 = torch.empty((B * N * Cn, D), **f32)
-    ops.gemm(feat, mod.clusterFeatureAffine.weight, f2, M=B * N * Cn, N=D, K=D, lda=D, ldb=D, ldc=D, bias=mod.clusterFeatureAffine.bias,
-             act=ops.ACT_RELU, aux_out=rc, ldaux=D, resid=feat, ldres=D, drop=(3, p, seed + 2, D))
-    # ---- inter-cluster attention (layers.py:196-203) in GEMV form
-    alpha_o = torch.empty(B * N * Cn, **f32)
-    out = torch.empty((B * N, D), **f32)
-    ops.pool_fwd(x=f2, ldx=D, D=D, n=B * N, Lx=Cn, mask=cmask, mask_div=N, v=v, ldv=D, scale=1.0 / math.sqrt(A), alpha=alpha_o, out=out,
-                 ldo=D)
-    sv.update(gfeat=gfeat, kf=kf, qc=qc, alpha_i=alpha_i, feat=feat, rc=rc, f2=f2, qv=qv, v=v, alpha_o=alpha_o)
-    if CAPTURE[0] is not None:
-        CAPTURE[0].append(sv)
-    return out.view(B, N, D), sv
+    return gfeat, gsv
 
 
-def sue_backward(mod, sv, dout, dhist_out=None, dcand_accum=None):
-    """dhist_out [B, Hn, D] (optional): where the history gradient is written; dcand_accum [B*N, D] (optional): the candidate
-    gradient is ADDED into it (the step without autograd sums the click predictor's and this encoder's share there)."""
-    B, Hn, D, N, Kc, G, Cn, A, p, seed = (sv[k] for k in ('B', 'Hn', 'D', 'N', 'Kc', 'G', 'Cn', 'A', 'p', 'seed'))
-    dev = dout.device
-    f32 = dict(device=dev, dtype=torch.float32)
-    cand2 = sv['cand'].view(B * N, D)
-    dout = dout.view(B * N, D)
+def gcn_feature_bwd(mod, gsv, graph, dg, p, seed, leaf, dhist_out=None):
+    """dg [B, Hn, D] -> the history gradient (written to dhist_out if given); GCN and proxy-node gradients accumulate into .grad."""
+    B, Hn, D = dg.shape
+    Kc = mod.proxy_node_embedding.shape[0]
+    G = Hn + Kc
+    f32 = dict(device=dg.device, dtype=torch.float32)
+    dpad = torch.empty((B, G, D), **f32)
+    ops.sue_slice_bwd(dg, dpad, B, Hn, G, D)
+    dy = gcn_backward(mod.gcn, gsv, dpad, graph, leaf)
+    dhist = torch.empty((B, Hn, D), **f32) if dhist_out is None else dhist_out
+    ops.sue_x0_bwd(dy, dhist, grad_of(mod.proxy_node_embedding), B, Hn, Kc, D, p, seed + 1, dx0_add=dpad)      # d(gcn(X0) + X0)
+    return dhist
+
+
+class _IntraKeys:
+    """Intra-cluster attention on a projected key buffer (ops.sue_intra_*): the key projection is evaluated once per history item."""
+    cand_widths = staticmethod(lambda A, D: dict(qc=A))
+
+    @staticmethod
+    def cand_fwd(mod, cand2, cs):
+        ops.linear_fwd(cand2, mod.intraCluster_Q.weight, mod.intraCluster_Q.bias, out=cs['qc'])         # [B*N, A]
+
+    @staticmethod
+    def fwd(mod, x, cand_ready, cidx, N, Cn):
+        B, Hn, D = x.shape
+        A = mod.attention_dim
+        f32 = dict(device=x.device, dtype=torch.float32)
+        kf = ops.linear_fwd(x.view(B * Hn, D), mod.intraCluster_K.weight)                               # [B*Hn, A]
+        cs = cand_ready()
+        alpha_i = torch.empty((B, N, Hn), **f32)
+        feat = torch.empty((B * N * Cn, D), **f32)
+        ops.sue_intra_fwd(kf, cs['qc'], x, cidx, B, N, Hn, Cn, A, D, alpha_i, feat)
+        return alpha_i, feat, dict(kf=kf)
+
+    @staticmethod
+    def bwd(mod, sv, dfeat, dcand, leaf, on_side):
+        B, Hn, D, N, Cn, A = (sv[k] for k in ('B', 'Hn', 'D', 'N', 'Cn', 'A'))
+        f32 = dict(device=dfeat.device, dtype=torch.float32)
+        cand2 = sv['cand'].view(B * N, D)
+        dg = torch.empty((B, Hn, D), **f32)
+        dkf = torch.empty((B * Hn, A), **f32)
+        dqc = torch.empty((B * N, A), **f32)
+        ops.sue_intra_bwd(sv['kf'], sv['qc'], sv['x'], sv['cidx'], sv['alpha_i'], dfeat, B, N, Hn, Cn, A, D, dg, dkf, dqc)
+        ops.linear_bwd_data(dkf, mod.intraCluster_K.weight, out=dg.view(B * Hn, D), accumulate=True)
+        on_side(lambda: ops.linear_bwd_data(dqc, mod.intraCluster_Q.weight, out=dcand, accumulate=True))
+        leaf(lambda: (ops.linear_bwd_weight(dkf, sv['x'].view(B * Hn, D), grad_of(mod.intraCluster_K.weight)),
+                      ops.linear_bwd_weight(dqc, cand2, grad_of(mod.intraCluster_Q.weight), db=grad_of(mod.intraCluster_Q.bias))), dkf, dqc)
+        return dg
+
+
+class _IntraGemv:
+    """Intra-cluster attention in GEMV form (ops.sue_seg_pool_*): a bias of intraCluster_K shifts every score of a (user, candidate) alike and
+    cancels in each segment softmax, so the scores are x_h . u_n / sqrt(A) with u = Q(c) W_K -- one [B N, A] x [A, D] product instead of the
+    [B Hn, D] x [D, A] key projection and its two backward products.  The bias' gradient is exactly zero."""
+    cand_widths = staticmethod(lambda A, D: dict(qc=A, u=D))
+
+    @staticmethod
+    def cand_fwd(mod, cand2, cs):
+        A, D = cs['qc'].shape[1], cs['u'].shape[1]
+        ops.linear_fwd(cand2, mod.intraCluster_Q.weight, mod.intraCluster_Q.bias, out=cs['qc'])         # [B*N, A]
+        ops.gemm(cs['qc'], mod.intraCluster_K.weight, cs['u'], M=cand2.shape[0], N=D, K=A, lda=A, ldb=D, ldc=D, trans_b=True)   # W_K^T q
+
+    @staticmethod
+    def fwd(mod, x, cand_ready, cidx, N, Cn):
+        B, Hn, D = x.shape
+        f32 = dict(device=x.device, dtype=torch.float32)
+        cs = cand_ready()
+        alpha_i = torch.empty((B, N, Hn), **f32)
+        feat = torch.empty((B * N * Cn, D), **f32)
+        ops.sue_seg_pool_fwd(x, cs['u'], cidx, B, N, Hn, Cn, D, 1.0 / math.sqrt(mod.attention_dim), alpha_i, feat)
+        return alpha_i, feat, {}
+
+    @staticmethod
+    def bwd(mod, sv, dfeat, dcand, leaf, on_side):
+        B, Hn, D, N, Cn, A = (sv[k] for k in ('B', 'Hn', 'D', 'N', 'Cn', 'A'))
+        f32 = dict(device=dfeat.device, dtype=torch.float32)
+        cand2 = sv['cand'].view(B * N, D)
+        dx = torch.empty((B, Hn, D), **f32)
+        du = torch.empty((B * N, D), **f32)
+        ops.sue_seg_pool_bwd(sv['x'], sv['u'], sv['cidx'], sv['alpha_i'], dfeat, B, N, Hn, Cn, D, 1.0 / math.sqrt(A), dx, du)
+        dqc = torch.empty((B * N, A), **f32)
+        ops.gemm(du, mod.intraCluster_K.weight, dqc, M=B * N, N=A, K=D, lda=D, ldb=D, ldc=A)           # du W_K^T
+        if mod.intraCluster_K.bias is not None:
+            grad_of(mod.intraCluster_K.bias)                                                            # (exactly zero: the bias cancels)
+        leaf(lambda: (ops.linear_bwd_weight(sv['qc'], du, grad_of(mod.intraCluster_K.weight)),
+                      ops.linear_bwd_weight(dqc, cand2, grad_of(mod.intraCluster_Q.weight), db=grad_of(mod.intraCluster_Q.bias))), du, dqc)
+        on_side(lambda: ops.linear_bwd_data(dqc, mod.intraCluster_Q.weight, out=dcand, accumulate=True))
+        return dx
+
+
+def _tail_cand_fwd(mod, cand2, cs):
+    """q and v of the inter-cluster attention (layers.py:196-203 in GEMV form): inputs are the candidates only."""
     ia = mod.interClusterAttention
-    hook = mod.__dict__.get('_grads_ready_hook')
-    # a data-parallel trainer starts reducing this encoder's gradients right after this function (early bucket): then they must be
-    # ordered on the current stream when it returns.  Otherwise nobody needs them before the optimizer: the leaf stream is joined at
-    # the end of the backward pass, and the news encoder's backward starts without waiting for the last weight-gradient GEMMs (round 4, joined
-    # vs deferred: batch 8 3.33-3.40 vs 3.20-3.21 ms -- the main stream sat idle for ~200 us behind four 65 us GEMMs --, batch 64 10.47-10.55 vs 10.43-10.49)
-    exchange = getattr(hook, '__self__', None)
-    need_now = (exchange is not None and exchange.active()) or not ops._DEFER.get('step_joins')      # (only the native step ends with its own join)
-    with ops.leaf_scope(dev, defer_join=not need_now) as leaf:
-        res = _sue_backward_body(mod, sv, dout, leaf, B, Hn, D, N, Kc, G, Cn, A, p, seed, dev, f32, cand2, ia, dhist_out, dcand_accum)
-    # (joined form) every parameter gradient of this encoder is now ordered on the current stream:
-    # a data-parallel trainer starts reducing them while the news encoder's backward is still to come (dp.GradientExchange).
-    # (Measured and rejected: issuing this encoder's weight-gradient GEMMs only after its data-gradient chain, so that they
-    # overlap the news encoder's backward prologue instead of slowing the 4 352-row chain: 13.05 vs 12.84 ms/step.)
-    if hook is not None:
-        hook()
-    return res
+    A, D = cs['qv'].shape[1], cs['v'].shape[1]
+    ops.linear_fwd(cand2, ia.Q.weight, ia.Q.bias, out=cs['qv'])                                          # [B*N, A]
+    ops.gemm(cs['qv'], ia.K.weight, cs['v'], M=cand2.shape[0], N=D, K=A, lda=A, ldb=D, ldc=D, trans_b=True)
 
 
-def _sue_backward_body(mod, sv, dout, leaf, B, Hn, D, N, Kc, G, Cn, A, p, seed, dev, f32, cand2, ia, dhist_out=None, dcand_accum=None):
+def _tail_fwd(mod, feat, v, cmask, N, p, seed):
+    """F <- dropout(relu(F W_c^T + b_c) + F) (GEMM epilogue, dropout site seed + 2, flat over [B N C, D]), then the inter-cluster pool."""
+    R, D = feat.shape
+    Cn = R // v.shape[0]
+    f32 = dict(device=feat.device, dtype=torch.float32)
+    aff = mod.clusterFeatureAffine
+    rc = torch.empty((R, D), **f32)
+    f2 = torch.empty((R, D), **f32)
+    ops.gemm(feat, aff.weight, f2, M=R, N=D, K=D, lda=D, ldb=D, ldc=D, bias=aff.bias, act=ops.ACT_RELU, aux_out=rc, ldaux=D, resid=feat, ldres=D,
+             drop=(3, p, seed + 2, D))
+    alpha_o = torch.empty(R, **f32)
+    out = torch.empty((v.shape[0], D), **f32)
+    ops.pool_fwd(x=f2, ldx=D, D=D, n=v.shape[0], Lx=Cn, mask=cmask, mask_div=N, v=v, ldv=D, scale=1.0 / math.sqrt(mod.attention_dim), alpha=alpha_o,
+                 out=out, ldo=D)
+    return out, dict(rc=rc, f2=f2, alpha_o=alpha_o)
+
+
+def _tail_bwd(mod, sv, dout, leaf, on_side, dcand_accum=None):
+    """dout [B*N, D] -> (d cluster features [B*N*Cn, D], the candidate gradient so far).  dcand_accum [B*N, D] (optional): the candidate gradient
+    is ADDED into it.  Nobody reads the candidate gradient (or d q_v) before the news encoder's backward: those launches go through on_side."""
+    B, D, N, Cn, A, p, seed = (sv[k] for k in ('B', 'D', 'N', 'Cn', 'A', 'p', 'seed'))
+    f32 = dict(device=dout.device, dtype=torch.float32)
+    cand2 = sv['cand'].view(B * N, D)
+    ia, aff = mod.interClusterAttention, mod.clusterFeatureAffine
     # ---- inter-cluster pool
     df2 = torch.empty((B * N * Cn, D), **f32)
     dv = torch.empty((B * N, D), **f32)
@@ -278,16 +335,6 @@ def _sue_backward_body(mod, sv, dout, leaf, B, Hn, D, N, Kc, G, Cn, A, p, seed, 
     dqv = torch.empty((B * N, A), **f32)
     # the step without autograd: the candidate gradient goes straight into the union gradient buffer's candidate rows
     dcand = dcand_accum if dcand_accum is not None else torch.empty((B * N, D), **f32)
-    main = torch.cuda.current_stream(dev)
-    side = _sue_side(dev)
-
-    def on_side(fn):
-        # nobody reads the candidate gradient (or d q_v) before the news encoder's backward: off the chain, joined when this function returns
-        if side is None:
-            return fn()
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            return fn()
 
     def inter_q():
         ops.gemm(dv, ia.K.weight, dqv, M=B * N, N=A, K=D, lda=D, ldb=D, ldc=A)
@@ -299,61 +346,151 @@ def _sue_backward_body(mod, sv, dout, leaf, B, Hn, D, N, Kc, G, Cn, A, p, seed, 
     dS = torch.empty((B * N * Cn, D), **f32)
     dfeat = torch.empty((B * N * Cn, D), **f32)
     ops.relu_drop_bwd(df2, sv['rc'], dS, dfeat, p, seed + 2)
-    ops.linear_bwd_data(dS, mod.clusterFeatureAffine.weight, out=dfeat, accumulate=True)
-    dS_aff = dS
+    ops.linear_bwd_data(dS, aff.weight, out=dfeat, accumulate=True)
     # (Measured and rejected in round 3: handing the five 900 x 900 weight-gradient GEMMs of this encoder to the news encoder's backward,
     # to run beside the backward recurrence on the 19 KB tile instead of beside this chain's data-gradient GEMMs: 11.41-11.43 vs
     # 11.19-11.25 ms/step.)
-    leaf(lambda: ops.linear_bwd_weight(dS_aff, sv['feat'], grad_of(mod.clusterFeatureAffine.weight), db=grad_of(mod.clusterFeatureAffine.bias)), dS_aff)
-    # ---- intra-cluster attention
-    dg = torch.empty((B, Hn, D), **f32)
-    dkf = torch.empty((B * Hn, A), **f32)
-    dqc = torch.empty((B * N, A), **f32)
-    ops.sue_intra_bwd(sv['kf'], sv['qc'], sv['gfeat'], sv['cidx'], sv['alpha_i'], dfeat, B, N, Hn, Cn, A, D, dg, dkf, dqc)
-    ops.linear_bwd_data(dkf, mod.intraCluster_K.weight, out=dg.view(B * Hn, D), accumulate=True)
-    on_side(lambda: ops.linear_bwd_data(dqc, mod.intraCluster_Q.weight, out=dcand, accumulate=True))
-    leaf(lambda: (ops.linear_bwd_weight(dkf, sv['gfeat'].view(B * Hn, D), grad_of(mod.intraCluster_K.weight)),
-                  ops.linear_bwd_weight(dqc, cand2, grad_of(mod.intraCluster_Q.weight), db=grad_of(mod.intraCluster_Q.bias))), dkf, dqc)
-    # ---- GCN (+ outer residual)
-    dpad = torch.empty((B, G, D), **f32)
-    ops.sue_slice_bwd(dg, dpad, B, Hn, G, D)
-    dy = gcn_backward(mod.gcn, sv['gcn'], dpad, sv['graph'], leaf)
-    dhist = torch.empty((B, Hn, D), **f32) if dhist_out is None else dhist_out
-    ops.sue_x0_bwd(dy, dhist, grad_of(mod.proxy_node_embedding), B, Hn, Kc, D, p, seed + 1, dx0_add=dpad)      # d(gcn(X0) + X0)
+    leaf(lambda: ops.linear_bwd_weight(dS, sv['feat'], grad_of(aff.weight), db=grad_of(aff.bias)), dS)
+    return dfeat, dcand
+
+
+def _cluster_fwd(mod, hist, cand, cmask, cidx, side, features):
+    """Intra stage (mod.intra_form) + tail on the rows features(sv) returns (called after the candidate-side launches have been issued on `side`;
+    it also fixes the cluster mask).  side: a stream for the candidate-side projections -- three or four small launches (15-30 us each,
+    latency-bound) that need nothing but `cand` and would sit on the dependent chain -- or None: they are issued where the first is read."""
+    form = mod.intra_form
+    B, Hn, D = hist.shape
+    N, Cn, A = cand.shape[1], mod.category_num, mod.attention_dim
+    dev = hist.device
+    f32 = dict(device=dev, dtype=torch.float32)
+    p = mod.dropout_rate if mod.training else 0.0
+    seed = mod._next_seed()
+    sv = dict(B=B, Hn=Hn, D=D, N=N, Cn=Cn, A=A, p=p, seed=seed, hist=hist, cand=cand, cidx=cidx, cmask=cmask)
+    cand2 = cand.view(B * N, D)
+    cs = {k: torch.empty((B * N, w), **f32) for k, w in dict(form.cand_widths(A, D), qv=A, v=D).items()}
+
+    def cand_side():
+        form.cand_fwd(mod, cand2, cs)
+        _tail_cand_fwd(mod, cand2, cs)
+    side_ev = None
     if side is not None:
-        main.wait_stream(side)                        # the candidate gradient is complete
-    return dhist, dcand.view(B, N, D)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            cand_side()
+            side_ev = torch.cuda.Event()
+            side_ev.record()
+
+    def cand_ready():
+        if side is None:
+            cand_side()
+        else:
+            torch.cuda.current_stream(dev).wait_event(side_ev)
+        return cs
+    x = features(sv)
+    alpha_i, feat, isv = form.fwd(mod, x, cand_ready, cidx, N, Cn)
+    out, tsv = _tail_fwd(mod, feat, cs['v'], cmask, N, p, seed)
+    sv.update(cs, x=x, alpha_i=alpha_i, feat=feat, **isv, **tsv)
+    return out.view(B, N, D), sv
+
+
+def _cluster_bwd(mod, sv, dout, leaf, side, dcand_accum=None):
+    """-> (gradient of the intra stage's history rows, candidate gradient [B*N, D]).  With a side stream the candidate gradient is complete once
+    the caller has made its stream wait for `side`."""
+    B, N, D = sv['B'], sv['N'], sv['D']
+    main = torch.cuda.current_stream(dout.device)
+
+    def on_side(fn):
+        if side is None:
+            return fn()
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            return fn()
+    dfeat, dcand = _tail_bwd(mod, sv, dout.view(B * N, D), leaf, on_side, dcand_accum)
+    return mod.intra_form.bwd(mod, sv, dfeat, dcand, leaf, on_side), dcand
+
+
+def sue_forward(mod, hist, cand, graph, cmask, cidx):
+    def features(sv):
+        # (the in-place `user_history_category_mask[:, -1] = 1` of userEncoders.py:73 in sue_x0_fwd's launch where the mask's layout allows)
+        Kc = mod.proxy_node_embedding.shape[0]
+        fix = _fix_cluster_mask(cmask, (sv['B'], Kc + 1))
+        gfeat, gsv = gcn_feature_fwd(mod, hist, graph, sv['p'], sv['seed'], cmask_fix=fix)
+        sv.update(Kc=Kc, G=sv['Hn'] + Kc, graph=graph, gcn=gsv, gfeat=gfeat)
+        return gfeat
+    out, sv = _cluster_fwd(mod, hist, cand, cmask, cidx, _sue_side(hist.device), features)
+    if CAPTURE[0] is not None:
+        CAPTURE[0].append(sv)
+    return out, sv
+
+
+def sue_backward(mod, sv, dout, dhist_out=None, dcand_accum=None):
+    """dhist_out [B, Hn, D] (optional): where the history gradient is written; dcand_accum [B*N, D] (optional): the candidate
+    gradient is ADDED into it (the step without autograd sums the click predictor's and this encoder's share there)."""
+    dev = dout.device
+    hook = mod.__dict__.get('_grads_ready_hook')
+    # a data-parallel trainer starts reducing this encoder's gradients right after this function (early bucket): then they must be
+    # ordered on the current stream when it returns.  Otherwise nobody needs them before the optimizer: the leaf stream is joined at
+    # the end of the backward pass, and the news encoder's backward starts without waiting for the last weight-gradient GEMMs (round 4, joined
+    # vs deferred: batch 8 3.33-3.40 vs 3.20-3.21 ms -- the main stream sat idle for ~200 us behind four 65 us GEMMs --, batch 64 10.47-10.55 vs 10.43-10.49)
+    exchange = getattr(hook, '__self__', None)
+    need_now = (exchange is not None and exchange.active()) or not ops._DEFER.get('step_joins')      # (only the native step ends with its own join)
+    side = _sue_side(dev)
+    with ops.leaf_scope(dev, defer_join=not need_now) as leaf:
+        dg, dcand = _cluster_bwd(mod, sv, dout, leaf, side, dcand_accum)
+        dhist = gcn_feature_bwd(mod, sv['gcn'], sv['graph'], dg, sv['p'], sv['seed'], leaf, dhist_out)
+        if side is not None:
+            torch.cuda.current_stream(dev).wait_stream(side)      # the candidate gradient is complete
+    # (joined form) every parameter gradient of this encoder is now ordered on the current stream:
+    # a data-parallel trainer starts reducing them while the news encoder's backward is still to come (dp.GradientExchange).
+    # (Measured and rejected: issuing this encoder's weight-gradient GEMMs only after its data-gradient chain, so that they
+    # overlap the news encoder's backward prologue instead of slowing the 4 352-row chain: 13.05 vs 12.84 ms/step.)
+    if hook is not None:
+        hook()
+    return dhist, dcand.view(sv['B'], sv['N'], sv['D'])
+
+
+def _cluster_layers(mod, config, key_bias):
+    """The layers of the hierarchical cluster attention (userEncoders.py:52-60, variantEncoders.py:349-358), registered in the reference's order."""
+    D = mod.news_embedding_dim
+    mod.attention_dim = max(config.attention_dim, D // 4)
+    mod.intraCluster_K = nn.Linear(D, mod.attention_dim, bias=key_bias)
+    mod.intraCluster_Q = nn.Linear(D, mod.attention_dim, bias=True)
+    mod.clusterFeatureAffine = nn.Linear(D, D, bias=True)
+    mod.interClusterAttention = ScaledDotProduct_CandidateAttention(D, D, mod.attention_dim)
+    mod.dropout_rate = float(config.dropout_rate)
+    mod.category_num = config.category_num + 1     # extra one category index for padding news
+    mod.max_history_num = config.max_history_num
+    mod.attention_scalar = math.sqrt(float(mod.attention_dim))
+
+
+def _cluster_layers_initialize(mod):
+    nn.init.xavier_uniform_(mod.intraCluster_K.weight)
+    if mod.intraCluster_K.bias is not None:
+        nn.init.zeros_(mod.intraCluster_K.bias)
+    nn.init.xavier_uniform_(mod.intraCluster_Q.weight)
+    nn.init.zeros_(mod.intraCluster_Q.bias)
+    nn.init.xavier_uniform_(mod.clusterFeatureAffine.weight, gain=nn.init.calculate_gain('relu'))
+    nn.init.zeros_(mod.clusterFeatureAffine.bias)
+    mod.interClusterAttention.initialize()
 
 
 class SUE(UserEncoder):
     """userEncoders.py:42-98."""
     needs_history_graph = True           # evaluate.compute_scores_cached builds the graph / cluster inputs for such an encoder
+    intra_form = _IntraKeys              # what the cluster pipeline runs as its intra stage (as _CNEAblation states what it keeps)
 
     def __init__(self, news_encoder: NewsEncoder, config):
         super().__init__(news_encoder, config)
-        self.attention_dim = max(config.attention_dim, self.news_embedding_dim // 4)
         self.proxy_node_embedding = nn.Parameter(torch.zeros([config.category_num, self.news_embedding_dim]))
         self.gcn = GCN(in_dim=self.news_embedding_dim, out_dim=self.news_embedding_dim, hidden_dim=self.news_embedding_dim,
                        num_layers=config.gcn_layer_num, dropout=config.dropout_rate / 2, residual=not config.no_gcn_residual,
                        layer_norm=config.gcn_layer_norm)
-        self.intraCluster_K = nn.Linear(self.news_embedding_dim, self.attention_dim, bias=False)
-        self.intraCluster_Q = nn.Linear(self.news_embedding_dim, self.attention_dim, bias=True)
-        self.clusterFeatureAffine = nn.Linear(self.news_embedding_dim, self.news_embedding_dim, bias=True)
-        self.interClusterAttention = ScaledDotProduct_CandidateAttention(self.news_embedding_dim, self.news_embedding_dim, self.attention_dim)
-        self.dropout_rate = float(config.dropout_rate)
-        self.category_num = config.category_num + 1     # extra one category index for padding news
-        self.max_history_num = config.max_history_num
-        self.attention_scalar = math.sqrt(float(self.attention_dim))
+        _cluster_layers(self, config, key_bias=False)
 
     def initialize(self):
         self.gcn.initialize()
         nn.init.zeros_(self.proxy_node_embedding)
-        nn.init.xavier_uniform_(self.intraCluster_K.weight)
-        nn.init.xavier_uniform_(self.intraCluster_Q.weight)
-        nn.init.zeros_(self.intraCluster_Q.bias)
-        nn.init.xavier_uniform_(self.clusterFeatureAffine.weight, gain=nn.init.calculate_gain('relu'))
-        nn.init.zeros_(self.clusterFeatureAffine.bias)
-        self.interClusterAttention.initialize()
+        _cluster_layers_initialize(self)
 
     def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
                     user_history_category_indices, candidate_news_representation):
@@ -365,125 +502,44 @@ class SUE(UserEncoder):
         return _SUEFunction.apply(history_embedding, candidate_news_representation, self, graph, user_history_category_mask, cidx)
 
 
-def _fix_cluster_mask(cmask):
-    """user_history_category_mask[:, -1] = 1, in place on the caller's tensor (userEncoders.py:73, variantEncoders.py:369)."""
-    if cmask.is_cuda and cmask.dim() == 2 and cmask.is_contiguous() and cmask.element_size() == 1:
-        ops.fill_column_u8(cmask, -1, 1)                # (a C-ABI call: recordable)
-    else:
-        cmask[:, -1] = 1
-
-
 class _SueWoGcnFn(torch.autograd.Function):
     """SUE_wo_GCN after the news encoder (variantEncoders.py:369-390): SUE's pipeline from the intra-cluster attention on, straight on the
-    history representations.  The intra stage runs in GEMV form (ops.sue_seg_pool_*): intraCluster_K.bias shifts every score of a
-    (user, candidate) alike and cancels in each segment softmax, so the scores are x_h . u_n / sqrt(A) with u = Q(c) W_K -- one [B N, A] x
-    [A, D] product instead of the [B Hn, D] x [D, A] key projection and its two backward products.  Dropout site as SUE's: seed + 2, flat
-    over [B N C, D].  Parameter gradients accumulate into .grad (weight-gradient GEMMs on the leaf stream, joined before this returns);
-    the data-parallel early-bucket hook is SUE's alone and is not fired here."""
+    history representations, on one stream.  Parameter gradients accumulate into .grad (weight-gradient GEMMs on the leaf stream, joined
+    before this returns); the data-parallel early-bucket hook is SUE's alone and is not fired here."""
 
     @staticmethod
     def forward(ctx, hist, cand, mod, cmask, cidx):
-        hist, cand = hist.contiguous(), cand.contiguous()
-        B, Hn, D = hist.shape
-        N, Cn, A = cand.shape[1], mod.category_num, mod.attention_dim
-        f32 = dict(device=hist.device, dtype=torch.float32)
-        p = mod.dropout_rate if mod.training else 0.0
-        seed = mod._next_seed()
-        scale = 1.0 / math.sqrt(A)
-        _fix_cluster_mask(cmask)
-        cand2 = cand.view(B * N, D)
-        ia = mod.interClusterAttention
-        qc = ops.linear_fwd(cand2, mod.intraCluster_Q.weight, mod.intraCluster_Q.bias)                  # [B*N, A]
-        u = torch.empty((B * N, D), **f32)
-        ops.gemm(qc, mod.intraCluster_K.weight, u, M=B * N, N=D, K=A, lda=A, ldb=D, ldc=D, trans_b=True)   # W_K^T q
-        qv = ops.linear_fwd(cand2, ia.Q.weight, ia.Q.bias)                                               # [B*N, A]
-        v = torch.empty((B * N, D), **f32)
-        ops.gemm(qv, ia.K.weight, v, M=B * N, N=D, K=A, lda=A, ldb=D, ldc=D, trans_b=True)
-        # ---- intra-cluster attention
-        alpha_i = torch.empty((B, N, Hn), **f32)
-        feat = torch.empty((B * N * Cn, D), **f32)
-        ops.sue_seg_pool_fwd(hist, u, cidx, B, N, Hn, Cn, D, scale, alpha_i, feat)
-        # ---- cluster feature affine: dropout(relu(W F + b) + F)
-        rc = torch.empty((B * N * Cn, D), **f32)
-        f2 = torch.empty((B * N * Cn, D), **f32)
-        aff = mod.clusterFeatureAffine
-        ops.gemm(feat, aff.weight, f2, M=B * N * Cn, N=D, K=D, lda=D, ldb=D, ldc=D, bias=aff.bias, act=ops.ACT_RELU, aux_out=rc, ldaux=D,
-                 resid=feat, ldres=D, drop=(3, p, seed + 2, D))
-        # ---- inter-cluster attention (layers.py:196-203) in GEMV form
-        alpha_o = torch.empty(B * N * Cn, **f32)
-        out = torch.empty((B * N, D), **f32)
-        ops.pool_fwd(x=f2, ldx=D, D=D, n=B * N, Lx=Cn, mask=cmask, mask_div=N, v=v, ldv=D, scale=scale, alpha=alpha_o, out=out, ldo=D)
+        def features(sv):
+            _fix_cluster_mask(cmask)
+            return sv['hist']
+        out, ctx.saved = _cluster_fwd(mod, hist.contiguous(), cand.contiguous(), cmask, cidx, None, features)
         ctx.mod = mod
-        ctx.saved = dict(B=B, Hn=Hn, D=D, N=N, Cn=Cn, A=A, p=p, seed=seed, scale=scale, hist=hist, cand2=cand2, cmask=cmask, cidx=cidx, qc=qc,
-                         u=u, qv=qv, v=v, alpha_i=alpha_i, feat=feat, rc=rc, f2=f2, alpha_o=alpha_o)
-        return out.view(B, N, D)
+        return out
 
     @staticmethod
     def backward(ctx, dout):
         mod, sv = ctx.mod, ctx.saved
         ctx.saved = None
-        B, Hn, D, N, Cn, A, p, seed, scale = (sv[k] for k in ('B', 'Hn', 'D', 'N', 'Cn', 'A', 'p', 'seed', 'scale'))
-        f32 = dict(device=dout.device, dtype=torch.float32)
-        dout = dout.contiguous().view(B * N, D)
-        cand2, ia, aff = sv['cand2'], mod.interClusterAttention, mod.clusterFeatureAffine
         with ops.leaf_scope(dout.device) as leaf:
-            # ---- inter-cluster pool
-            df2 = torch.empty((B * N * Cn, D), **f32)
-            dv = torch.empty((B * N, D), **f32)
-            ops.pool_bwd(x=sv['f2'], ldx=D, D=D, n=B * N, Lx=Cn, mask=sv['cmask'], mask_div=N, v=sv['v'], ldv=D, scale=scale, alpha=sv['alpha_o'],
-                         dout=dout, lddo=D, dx=df2, lddx=D, dv=dv, lddv=D)
-            dqv = torch.empty((B * N, A), **f32)
-            ops.gemm(dv, ia.K.weight, dqv, M=B * N, N=A, K=D, lda=D, ldb=D, ldc=A)
-            leaf(lambda: (ops.linear_bwd_weight(sv['qv'], dv, grad_of(ia.K.weight)),
-                          ops.linear_bwd_weight(dqv, cand2, grad_of(ia.Q.weight), db=grad_of(ia.Q.bias))), dv, dqv)
-            dcand = ops.linear_bwd_data(dqv, ia.Q.weight)                                                # [B*N, D]
-            # ---- cluster affine
-            dS = torch.empty((B * N * Cn, D), **f32)
-            dfeat = torch.empty((B * N * Cn, D), **f32)
-            ops.relu_drop_bwd(df2, sv['rc'], dS, dfeat, p, seed + 2)
-            ops.linear_bwd_data(dS, aff.weight, out=dfeat, accumulate=True)
-            leaf(lambda: ops.linear_bwd_weight(dS, sv['feat'], grad_of(aff.weight), db=grad_of(aff.bias)), dS)
-            # ---- intra-cluster attention
-            dhist = torch.empty((B, Hn, D), **f32)
-            du = torch.empty((B * N, D), **f32)
-            ops.sue_seg_pool_bwd(sv['hist'], sv['u'], sv['cidx'], sv['alpha_i'], dfeat, B, N, Hn, Cn, D, scale, dhist, du)
-            dqc = torch.empty((B * N, A), **f32)
-            ops.gemm(du, mod.intraCluster_K.weight, dqc, M=B * N, N=A, K=D, lda=D, ldb=D, ldc=A)      # du W_K^T
-            grad_of(mod.intraCluster_K.bias)                                                            # (exactly zero: the bias cancels)
-            leaf(lambda: (ops.linear_bwd_weight(sv['qc'], du, grad_of(mod.intraCluster_K.weight)),
-                          ops.linear_bwd_weight(dqc, cand2, grad_of(mod.intraCluster_Q.weight), db=grad_of(mod.intraCluster_Q.bias))), du, dqc)
-            ops.linear_bwd_data(dqc, mod.intraCluster_Q.weight, out=dcand, accumulate=True)
-        return dhist, dcand.view(B, N, D), None, None, None
+            dhist, dcand = _cluster_bwd(mod, sv, dout.contiguous(), leaf, None)
+        return dhist, dcand.view(sv['B'], sv['N'], sv['D']), None, None, None
 
 
 class SUE_wo_GCN(UserEncoder):
     """variantEncoders.py:342-390, the ablation of SUE without the GCN: hierarchical cluster attention on the news encoder's history output
-    (no proxy nodes, no graph, no slice).  intraCluster_K carries the reference's bias, which cannot change the output (see _SueWoGcnFn): it
+    (no proxy nodes, no graph, no slice).  intraCluster_K carries the reference's bias, which cannot change the output (see _IntraGemv): it
     stays a parameter so that a reference state_dict loads unchanged, and its gradient is exactly zero."""
     needs_history_graph = True
+    intra_form = _IntraGemv
 
     def __init__(self, news_encoder: NewsEncoder, config):
         super().__init__(news_encoder, config)
-        self.attention_dim = max(config.attention_dim, self.news_embedding_dim // 4)
-        self.intraCluster_K = nn.Linear(self.news_embedding_dim, self.attention_dim, bias=True)
-        self.intraCluster_Q = nn.Linear(self.news_embedding_dim, self.attention_dim, bias=True)
-        self.clusterFeatureAffine = nn.Linear(self.news_embedding_dim, self.news_embedding_dim, bias=True)
-        self.interClusterAttention = ScaledDotProduct_CandidateAttention(self.news_embedding_dim, self.news_embedding_dim, self.attention_dim)
-        self.dropout_rate = float(config.dropout_rate)
-        self.category_num = config.category_num + 1     # extra one category index for padding news
-        self.max_history_num = config.max_history_num
-        self.attention_scalar = math.sqrt(float(self.attention_dim))
+        _cluster_layers(self, config, key_bias=True)
         if not ops.seg_pool_supported(self.max_history_num, self.category_num, config.negative_sample_num + 1):
             raise Exception('SUE_wo_GCN: ' + ops.SEG_POOL_UNSUPPORTED)
 
     def initialize(self):
-        nn.init.xavier_uniform_(self.intraCluster_K.weight)
-        nn.init.zeros_(self.intraCluster_K.bias)
-        nn.init.xavier_uniform_(self.intraCluster_Q.weight)
-        nn.init.zeros_(self.intraCluster_Q.bias)
-        nn.init.xavier_uniform_(self.clusterFeatureAffine.weight, gain=nn.init.calculate_gain('relu'))
-        nn.init.zeros_(self.clusterFeatureAffine.bias)
-        self.interClusterAttention.initialize()
+        _cluster_layers_initialize(self)
 
     def encode_user(self, history_embedding, user_history_mask, user_history_graph, user_history_category_mask,
                     user_history_category_indices, candidate_news_representation):
@@ -493,38 +549,22 @@ class SUE_wo_GCN(UserEncoder):
 
 
 class _SueGcnFeatureFn(torch.autograd.Function):
-    """(gcn([history ; dropout_(proxy nodes)]) + X0)[:, :max_history_num] (variantEncoders.py:414-416) on SUE's own launches, with SUE's
-    dropout sites: the proxy nodes at seed + 1, GCN layer l at seed + 10 + l with p / 2.  The cluster mask is not touched."""
+    """The GCN feature stage alone, on SUE's own launches and dropout sites.  The cluster mask is not touched."""
 
     @staticmethod
     def forward(ctx, hist, mod, graph):
-        hist = hist.contiguous()
-        B, Hn, D = hist.shape
-        Kc = mod.proxy_node_embedding.shape[0]
-        G = Hn + Kc
-        f32 = dict(device=hist.device, dtype=torch.float32)
         p = mod.dropout_rate if mod.training else 0.0
         seed = mod._next_seed()
-        x0 = torch.empty((B, G, D), **f32)
-        ops.sue_x0_fwd(hist, mod.proxy_node_embedding, x0, B, Hn, Kc, D, p, seed + 1)
-        x, gsv = gcn_forward(mod.gcn, x0, graph, seed + 10, mod.training)
-        gfeat = torch.empty((B, Hn, D), **f32)
-        ops.sue_slice_fwd(x, x0, gfeat, B, Hn, G, D)
-        ctx.mod, ctx.saved = mod, (gsv, graph, B, Hn, Kc, G, D, p, seed)
+        gfeat, gsv = gcn_feature_fwd(mod, hist.contiguous(), graph, p, seed)
+        ctx.mod, ctx.saved = mod, (gsv, graph, p, seed)
         return gfeat
 
     @staticmethod
     def backward(ctx, dg):
-        mod = ctx.mod
-        gsv, graph, B, Hn, Kc, G, D, p, seed = ctx.saved
+        gsv, graph, p, seed = ctx.saved
         ctx.saved = None
-        f32 = dict(device=dg.device, dtype=torch.float32)
-        dpad = torch.empty((B, G, D), **f32)
-        ops.sue_slice_bwd(dg.contiguous(), dpad, B, Hn, G, D)
         with ops.leaf_scope(dg.device) as leaf:
-            dy = gcn_backward(mod.gcn, gsv, dpad, graph, leaf)
-            dhist = torch.empty((B, Hn, D), **f32)
-            ops.sue_x0_bwd(dy, dhist, grad_of(mod.proxy_node_embedding), B, Hn, Kc, D, p, seed + 1, dx0_add=dpad)      # d(gcn(X0) + X0)
+            dhist = gcn_feature_bwd(ctx.mod, gsv, graph, dg.contiguous(), p, seed, leaf)
         return dhist, None, None
 
 

@@ -1,7 +1,7 @@
 """float64 restatement of the user-encoder ablations of variantEncoders.py (SUE_wo_GCN :342-390, SUE_wo_HCA :393-419) in plain torch on the
 CPU, from the history / candidate representations to the user representation, with every gradient by autograd.  The intra-cluster stage of
 SUE_wo_GCN is written both ways: through the keys K(x) + b_K as the reference has it, and in the GEMV form the kernels use
-(x . (W_K^T q), csrc/seg_pool.hip); tests/test_sue_ablation_host.py pins both to the fixtures captured from the reference's own
+(x . (W_K^T q), csrc/sue_cluster.hip); tests/test_sue_ablation_host.py pins both to the fixtures captured from the reference's own
 code.  Dropout: keep-masks are handed in (tests/hip_masks.py:flat_keep gives the kernels' own), sites as SUE's."""
 import math
 

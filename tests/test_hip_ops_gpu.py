@@ -875,21 +875,17 @@ def test_pool_dense_masked_dot():
 
 
 # ------------------------------------------------------------------------------------------------ SUE intra-cluster, misc
-@pytest.mark.parametrize('Bn,N,Hn,Cn,A,D', [(7, 5, 50, 19, 225, 900), (3, 2, 17, 2, 64, 52), (2, 8, 64, 32, 128, 50), (2, 1, 5, 7, 32, 260),
-                                            (66, 5, 50, 18, 128, 900)])
-def test_sue_intra_cluster_matches_scatter_semantics(Bn, N, Hn, Cn, A, D):
-    """Cluster attention of SUE (csrc/misc.hip sue_intra_*): the default shape, fewer clusters than the backward's cluster split, the
-    kernels' maxima (64 items, 32 clusters, 8 candidates, D not a multiple of 4), one candidate, and the headline launch shape."""
+def _sue_intra_case(Bn, N, Hn, Cn, A, D, cidx):
+    """sue_intra_fwd / _bwd (outputs prefilled with NaN) against explicit float64 per-cluster loops = torch_scatter's definition; -> (alpha, feat,
+    dg, dkf, dqc) of the kernels."""
     from nnr_amd import ops
     d = dev()
     kf, qc, g = rnd(Bn, Hn, A, seed=1, scale=0.3), rnd(Bn, N, A, seed=2), rnd(Bn, Hn, D, seed=3)
-    cidx = torch.randint(0, Cn, (Bn, Hn), generator=torch.Generator().manual_seed(4))
-    cidx[0] = Cn - 1
     kr, qr, gr = (t.double().requires_grad_(True) for t in (kf, qc, g))
     s = torch.einsum('bja,bna->bnj', kr, qr) / math.sqrt(A)
     feat_ref = torch.zeros(Bn, N, Cn, D, dtype=torch.float64)
     alpha_ref = torch.zeros(Bn, N, Hn, dtype=torch.float64)
-    for b in range(Bn):                                  # explicit per-cluster loops = torch_scatter's definition
+    for b in range(Bn):
         for c in range(Cn):
             sel = (cidx[b] == c).nonzero().flatten()
             if sel.numel():
@@ -898,18 +894,45 @@ def test_sue_intra_cluster_matches_scatter_semantics(Bn, N, Hn, Cn, A, D):
                 feat_ref[b, :, c] = a @ gr[b, sel]
     dfeat = rnd(Bn, N, Cn, D, seed=5)
     (feat_ref * dfeat.double()).sum().backward()
-    f32 = dict(device=d, dtype=torch.float32)
-    alpha = torch.empty(Bn, N, Hn, **f32)
-    feat = torch.empty(Bn * N * Cn, D, **f32)
+    nan = lambda *shape: torch.full(shape, float('nan'), device=d, dtype=torch.float32)
+    alpha, feat = nan(Bn, N, Hn), nan(Bn * N * Cn, D)
     kd, qd, gd, cd = kf.to(d), qc.to(d), g.to(d), cidx.to(d)
     ops.sue_intra_fwd(kd, qd, gd, cd, Bn, N, Hn, Cn, A, D, alpha, feat)
     close(alpha, alpha_ref, what='intra alpha')
     close(feat.view(Bn, N, Cn, D), feat_ref, what='intra feat')
-    dg, dk, dq = torch.empty(Bn, Hn, D, **f32), torch.empty(Bn * Hn, A, **f32), torch.empty(Bn * N, A, **f32)
+    dg, dk, dq = nan(Bn, Hn, D), nan(Bn * Hn, A), nan(Bn * N, A)
     ops.sue_intra_bwd(kd, qd, gd, cd, alpha, dfeat.to(d).view(-1, D), Bn, N, Hn, Cn, A, D, dg, dk, dq)
     close(dg, gr.grad, what='intra dg')
     close(dk.view(Bn, Hn, A), kr.grad, what='intra dkf')
     close(dq.view(Bn, N, A), qr.grad, what='intra dqc')
+    return alpha, feat.view(Bn, N, Cn, D), dg, dk, dq
+
+
+@pytest.mark.parametrize('Bn,N,Hn,Cn,A,D', [(7, 5, 50, 19, 225, 900), (3, 2, 17, 2, 64, 52), (2, 8, 64, 32, 128, 50), (2, 1, 5, 7, 32, 260),
+                                            (66, 5, 50, 18, 128, 900)])
+def test_sue_intra_cluster_matches_scatter_semantics(Bn, N, Hn, Cn, A, D):
+    """Cluster attention of SUE (csrc/sue_cluster.hip sue_intra_*): the default shape, fewer clusters than the backward's cluster split, the
+    kernels' maxima (64 items, 32 clusters, 8 candidates, D not a multiple of 4), one candidate, and the headline launch shape."""
+    cidx = torch.randint(0, Cn, (Bn, Hn), generator=torch.Generator().manual_seed(4))
+    cidx[0] = Cn - 1
+    _sue_intra_case(Bn, N, Hn, Cn, A, D, cidx)
+
+
+@pytest.mark.parametrize('shape,pattern', [((3, 2, 6, 4, 8, 7), 'one_cluster'), ((3, 2, 6, 4, 8, 7), 'empty_ends'), ((2, 3, 5, 8, 16, 12), 'one_per_cluster'),
+                                           ((9, 5, 50, 19, 32, 300), 'last_user')], ids=lambda v: 'x'.join(map(str, v)) if isinstance(v, tuple) else v)
+def test_sue_intra_cluster_at_the_gemv_forms_edge_cases(shape, pattern):
+    """The keys form at the cluster patterns the GEMV form is held to (tests/test_hip_sue_ablation_gpu.py): every item in one cluster, empty first
+    and last clusters, one item per cluster (Hn <= C), a user whose items all sit in the last cluster.  Every output element is written, an
+    empty cluster's feature rows are exactly zero, and two runs give the same bits."""
+    from test_hip_sue_ablation_gpu import _clusters
+    Bn, N, Hn, Cn, A, D = shape
+    cidx = _clusters(Bn, Hn, Cn, pattern, torch.Generator().manual_seed(sum(shape) + len(pattern)))
+    first, second = _sue_intra_case(*shape, cidx), _sue_intra_case(*shape, cidx)
+    for a, b in zip(first, second):
+        assert bool(torch.isfinite(a).all()) and torch.equal(a, b)
+    empty = (torch.nn.functional.one_hot(cidx, Cn).sum(dim=1) == 0).unsqueeze(1).expand(-1, N, -1)       # [B, N, C]
+    assert bool(empty.any())                                                                             # (in each of the four cases)
+    assert float(first[1].cpu()[empty].abs().sum()) == 0.0
 
 
 def test_elementwise_and_optimizer():

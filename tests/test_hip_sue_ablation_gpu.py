@@ -1,4 +1,4 @@
-"""The user-encoder ablations SUE_wo_GCN / SUE_wo_HCA on the GPU: the segmented candidate pool in GEMV form (csrc/seg_pool.hip)
+"""The user-encoder ablations SUE_wo_GCN / SUE_wo_HCA on the GPU: the segmented candidate pool in GEMV form (csrc/sue_cluster.hip)
 against the float64 restatement (tests/sue_ablation_ref.py, pinned to the reference by tests/test_sue_ablation_host.py), its edge rules and
 reproducibility; both encoders on random inputs with dropout off and on (the kernels' own keep-masks handed to the restatement); and the
 model / evaluation paths against golden vectors captured from the reference's own code.  Bars as in tests/test_hip_catt_gpu.py."""
@@ -154,15 +154,15 @@ class _Rows(torch.nn.Module):
         self.news_embedding_dim = D
 
 
-def _enc_cfg(Hn, K, N, p, seed):
-    return SimpleNamespace(attention_dim=8, category_num=K, max_history_num=Hn, dropout_rate=p, negative_sample_num=N - 1, gcn_layer_num=3,
+def _enc_cfg(Hn, K, N, p, seed, layers=3):
+    return SimpleNamespace(attention_dim=8, category_num=K, max_history_num=Hn, dropout_rate=p, negative_sample_num=N - 1, gcn_layer_num=layers,
                            no_gcn_residual=False, gcn_layer_norm=False, seed=seed)
 
 
-def _encoder(name, shape, p, seed):
+def _encoder(name, shape, p, seed, layers=3):
     from nnr_amd import user_encoders
     B, N, Hn, K, D = shape
-    cfg = _enc_cfg(Hn, K, N, p, seed)
+    cfg = _enc_cfg(Hn, K, N, p, seed, layers)
     torch.manual_seed(seed)
     enc = getattr(user_encoders, name)(_Rows(D), cfg)
     enc.initialize()
@@ -265,6 +265,54 @@ def test_parameter_gradients_accumulate_reproducibly():
     for k in runs[0]:
         assert torch.equal(runs[0][k], runs[2][k]), k
         assert torch.equal(runs[1][k], 2 * runs[0][k]), k
+
+
+# ------------------------------------------------------------------------------------------------ the shared stages
+STAGE_SHAPE = (3, 2, 6, 3, 20)          # (B, N, Hn, K, D); two GCN layers, dropout on
+
+
+def test_gcn_feature_stage_is_one_stage_in_sue_and_sue_wo_hca():
+    """A SUE and a SUE_wo_HCA with the same proxy nodes, GCN weights and seed counter: SUE_wo_HCA's GCN feature is SUE's captured one bit for
+    bit, and so are the GCN / proxy / history gradients of the stage's backward for the same d gfeat."""
+    from nnr_amd import ops, user_encoders as UE
+    sue, _ = _encoder('SUE', STAGE_SHAPE, 0.2, 11, layers=2)
+    hca, _ = _encoder('SUE_wo_HCA', STAGE_SHAPE, 0.2, 11, layers=2)
+    with torch.no_grad():
+        hca.proxy_node_embedding.copy_(sue.proxy_node_embedding)
+    hca.gcn.load_state_dict(sue.gcn.state_dict())
+    hist, cand, dout, hmask, cidx, cmask, graph = (t.cuda() for t in _enc_inputs(STAGE_SHAPE, 11))
+    UE.CAPTURE[0] = []
+    try:
+        sue.encode_user(hist, hmask, graph, cmask, cidx, cand)
+    finally:
+        (sv,), UE.CAPTURE[0] = UE.CAPTURE[0], None
+    h = hist.clone().requires_grad_()
+    gfeat = UE._SueGcnFeatureFn.apply(h, hca, graph)
+    assert torch.equal(gfeat, sv['gfeat']) and sv['p'] == 0.2 and len(sv['gcn']['rs']) == 2
+    dg = torch.randn(gfeat.shape, generator=torch.Generator().manual_seed(12)).cuda()
+    gfeat.backward(dg)
+    with ops.leaf_scope(dg.device) as leaf:
+        dhist = UE.gcn_feature_bwd(sue, sv['gcn'], sv['graph'], dg, sv['p'], sv['seed'], leaf)
+    torch.cuda.synchronize()
+    assert torch.equal(dhist, h.grad)
+    assert torch.equal(sue.proxy_node_embedding.grad, hca.proxy_node_embedding.grad) and float(sue.proxy_node_embedding.grad.abs().max()) > 0
+    for (k, a), (_, b) in zip(sue.gcn.named_parameters(), hca.gcn.named_parameters()):
+        assert torch.equal(a.grad, b.grad) and float(a.grad.abs().max()) > 0, k
+
+
+@pytest.mark.parametrize('name,calls', [('SUE', 36), ('SUE_wo_GCN', 21), ('SUE_wo_HCA', 25)])
+def test_launch_budget_of_one_forward_and_backward(name, calls):
+    """C-ABI calls of one encode_user + backward (forward + backward: SUE 13 + 23, SUE_wo_GCN 8 + 13, SUE_wo_HCA 10 + 15), counted on the
+    commit before the three encoders were built from shared stages: exact."""
+    from nnr_amd import _lib
+    enc, _ = _encoder(name, STAGE_SHAPE, 0.2, 11, layers=2)
+    hist, cand, dout, hmask, cidx, cmask, graph = (t.cuda() for t in _enc_inputs(STAGE_SHAPE, 11))
+    h, c = hist.requires_grad_(), cand.requires_grad_()
+    torch.cuda.synchronize()
+    c0 = _lib.CALLS[0]
+    enc.encode_user(h, hmask, graph, cmask, cidx, c).backward(dout)
+    torch.cuda.synchronize()
+    assert _lib.CALLS[0] - c0 == calls
 
 
 # ------------------------------------------------------------------------------------------------ model level

@@ -203,6 +203,12 @@ def test_host_mirror_of_the_rule_is_the_librarys():
         rc_b = lib.nnr_sue_seg_pool_bwd(None, None, None, None, None, B, N, Hn, C, D, 1.0, None, None, None, None)
         assert (rc_f != _lib.NNR_ERR_UNSUPPORTED) == want and (rc_b != _lib.NNR_ERR_UNSUPPORTED) == want, (B, N, Hn, C, D)
         assert rc_f != 0 and rc_b != 0                     # (a supported size with null pointers is an argument error, not a launch)
+        # the keys pair (nnr_sue_intra_*) answers by the same rule, plus A >= 1
+        assert rc_f == rc_b == (_lib.NNR_ERR_ARG if want else _lib.NNR_ERR_UNSUPPORTED)
+        for A in (0, 1, 230):
+            for rc in (lib.nnr_sue_intra_fwd(None, None, None, None, B, N, Hn, C, A, D, None, None, None),
+                       lib.nnr_sue_intra_bwd(None, None, None, None, None, None, B, N, Hn, C, A, D, None, None, None, None, None)):
+                assert rc == (_lib.NNR_ERR_ARG if want and A >= 1 else _lib.NNR_ERR_UNSUPPORTED), (B, N, Hn, C, A, D)
     assert (ops.SEG_POOL_MAXH, ops.SEG_POOL_MAXC, ops.SEG_POOL_MAXN) == (64, 32, 8)
 
 

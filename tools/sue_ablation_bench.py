@@ -117,40 +117,17 @@ def intra_keys(mod, x, qc, cidx, dfeat, B, N, Hn, Cn, A, D):
     return feat, dx, dqc
 
 
-def wo_gcn_pipeline(mod, inp, intra):
-    """SUE_wo_GCN forward + backward as user_encoders._SueWoGcnFn issues it (dropout off, one stream), with the intra stage handed in."""
-    hist, cand, dout, cmask, cidx = inp['hist'], inp['cand'], inp['dout'], inp['cmask'], inp['cidx']
-    B, Hn, D = hist.shape
-    N, Cn, A = cand.shape[1], mod.category_num, mod.attention_dim
-    f32 = dict(device=hist.device, dtype=torch.float32)
-    scale = 1.0 / math.sqrt(A)
-    ia, aff = mod.interClusterAttention, mod.clusterFeatureAffine
-    cand2 = cand.view(B * N, D)
-    qc = ops.linear_fwd(cand2, mod.intraCluster_Q.weight, mod.intraCluster_Q.bias)
-    qv = ops.linear_fwd(cand2, ia.Q.weight, ia.Q.bias)
-    v = torch.empty((B * N, D), **f32)
-    ops.gemm(qv, ia.K.weight, v, M=B * N, N=D, K=A, lda=A, ldb=D, ldc=D, trans_b=True)
-    feat = intra(mod, hist, qc, cidx, None, B, N, Hn, Cn, A, D)
-    rc, f2 = torch.empty((B * N * Cn, D), **f32), torch.empty((B * N * Cn, D), **f32)
-    ops.gemm(feat, aff.weight, f2, M=B * N * Cn, N=D, K=D, lda=D, ldb=D, ldc=D, bias=aff.bias, act=ops.ACT_RELU, aux_out=rc, ldaux=D, resid=feat,
-             ldres=D, drop=(3, 0.0, 1, D))
-    alpha_o, out = torch.empty(B * N * Cn, **f32), torch.empty((B * N, D), **f32)
-    ops.pool_fwd(x=f2, ldx=D, D=D, n=B * N, Lx=Cn, mask=cmask, mask_div=N, v=v, ldv=D, scale=scale, alpha=alpha_o, out=out, ldo=D)
-    df2, dv = torch.empty((B * N * Cn, D), **f32), torch.empty((B * N, D), **f32)
-    ops.pool_bwd(x=f2, ldx=D, D=D, n=B * N, Lx=Cn, mask=cmask, mask_div=N, v=v, ldv=D, scale=scale, alpha=alpha_o, dout=dout.view(B * N, D), lddo=D,
-                 dx=df2, lddx=D, dv=dv, lddv=D)
-    dqv = torch.empty((B * N, A), **f32)
-    ops.gemm(dv, ia.K.weight, dqv, M=B * N, N=A, K=D, lda=D, ldb=D, ldc=A)
-    ops.linear_bwd_weight(qv, dv, grad_of(ia.K.weight))
-    ops.linear_bwd_weight(dqv, cand2, grad_of(ia.Q.weight), db=grad_of(ia.Q.bias))
-    dcand = ops.linear_bwd_data(dqv, ia.Q.weight)
-    dS, dfeat = torch.empty((B * N * Cn, D), **f32), torch.empty((B * N * Cn, D), **f32)
-    ops.relu_drop_bwd(df2, rc, dS, dfeat, 0.0, 1)
-    ops.linear_bwd_data(dS, aff.weight, out=dfeat, accumulate=True)
-    ops.linear_bwd_weight(dS, feat, grad_of(aff.weight), db=grad_of(aff.bias))
-    _, dx, dqc = intra(mod, hist, qc, cidx, dfeat, B, N, Hn, Cn, A, D)
-    ops.linear_bwd_weight(dqc, cand2, grad_of(mod.intraCluster_Q.weight), db=grad_of(mod.intraCluster_Q.bias))
-    ops.linear_bwd_data(dqc, mod.intraCluster_Q.weight, out=dcand, accumulate=True)
+def wo_gcn_pipeline(mod, inp, form):
+    """SUE_wo_GCN forward + backward through user_encoders' own stages (dropout off, one stream, weight gradients in line), with the intra stage
+    in the given form (user_encoders._IntraGemv / _IntraKeys)."""
+    from nnr_amd import user_encoders as UE
+    mod.intra_form = form
+    try:
+        out, sv = UE._cluster_fwd(mod, inp['hist'], inp['cand'], inp['cmask'], inp['cidx'], None, lambda sv: sv['hist'])
+        with ops.leaf_scope(out.device, enable=False) as leaf:
+            dx, dcand = UE._cluster_bwd(mod, sv, inp['dout'], leaf, None)
+    finally:
+        del mod.intra_form                                        # (back to the class attribute)
     return out, dx, dcand
 
 
@@ -249,8 +226,8 @@ def mode_encoder(a):
                 err = float((ref_fn(ref_mod, inp) - mod.encode_user(h, inp['hmask'], inp['graph'], inp['cmask'].clone(), inp['cidx'], c)).abs().max())
             variants = {'torch_reference_formulation': ref, 'encode_user': ours}
             if name == 'SUE_wo_GCN':
-                variants['pipeline_gemv_form'] = lambda i, mod=mod, inp=inp: wo_gcn_pipeline(mod, inp, intra_gemv)
-                variants['pipeline_keys_form'] = lambda i, mod=mod, inp=inp: wo_gcn_pipeline(mod, inp, intra_keys)
+                variants['pipeline_gemv_form'] = lambda i, mod=mod, inp=inp: wo_gcn_pipeline(mod, inp, UE._IntraGemv)
+                variants['pipeline_keys_form'] = lambda i, mod=mod, inp=inp: wo_gcn_pipeline(mod, inp, UE._IntraKeys)
             t = alternate(variants, a.steps, a.warmup, a.rounds)
             out[name] = {'ms_fwd_bwd': t, 'summary': summary(t), 'max_abs_diff_of_outputs': err}
         res['batch%d' % B] = out
