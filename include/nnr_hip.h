@@ -608,6 +608,25 @@ int nnr_corpus_batch(const nnr_corpus_tables* t, const nnr_batch_out* o, const i
                      int S, hipStream_t stream);
 int nnr_history_graph(const int* cats, const uint8_t* hmask, int B, int H, int K, int norm, float* graph, uint8_t* cmask, long* cidx,
                       hipStream_t stream);
+/* Negative sampling (the rule of MIND_Train_Dataset.negative_sampling, MIND_dataset.py:27-47) as a pure
+ * function of (seed, epoch, behaviour): ranks agree without talking, any subset of rows can be redrawn, and the table is rewritten
+ * in place.  clicks [behaviours]; neg_offsets [behaviours + 1] indexes neg_ids (CSR: behaviour b's non-clicked news are
+ * neg_ids[neg_offsets[b] .. neg_offsets[b + 1]), m of them, 1 <= m < 2^31); beh_idx: the n behaviours to draw, NULL = 0 .. n - 1.
+ * Row b is written at samples + b * ld_samples, whichever way it was named: column 0 = clicks[b], columns 1 .. K as follows, columns
+ * beyond 1 + K untouched.
+ *   m <= K : column j + 1 = list[j % m] (exact, no randomness).
+ *   m >  K : the list's entries at K pairwise distinct POSITIONS, uniform over ordered K-tuples of positions, by a partial
+ *            Fisher-Yates walk over the virtual array a[p] = p: for j = 0 .. K - 1, p = j + bounded(r_j, m - j), column j + 1 =
+ *            list[a[p]], then a[p] = a[j] (the at most K displaced entries live in registers).  No rejection loop: every loop has at
+ *            most K trips.
+ *   With H = the lowbias32 finaliser (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16) and every sum and
+ *   product taken mod 2^32:   key = H(seed ^ H(epoch + 0x9E3779B9)),   r_j = H(H(b ^ key) + j * 0x9E3779B9 + 1),
+ *   bounded(r, range) = (uint64(r) * range) >> 32, whose relative bias is at most range / 2^32.  Two chained rounds per draw: a single
+ *   hash of a structured counter fails a per-column chi-square at list lengths >= 1000 (tests/test_negsample_host.py gates this one).
+ * NNR_ERR_UNSUPPORTED for K outside 1 .. 16; NNR_ERR_ARG for ld_samples < 1 + K, n < 1 or a null table; nothing is written then.
+ * A list of length 0 is the caller's to refuse (the reference divides by zero there); such a row is left untouched. */
+int nnr_negative_sample(const int* clicks, const long* neg_offsets, const int* neg_ids, const int* beh_idx, int n, int K, uint32_t seed,
+                        int epoch, int* samples, int ld_samples, hipStream_t stream);
 /* Evaluation tail: util.py:50-59 (per-impression ranks by descending score, ties in file order) +
  * evaluate.py:8-29,76-81 (AUC, MRR, nDCG@5, nDCG@10 per impression, float64).  offsets [n_impressions + 1] delimit the
  * (contiguous) candidates of each impression; per_impression [n_impressions, 4]; NaN row for a single-class impression. */

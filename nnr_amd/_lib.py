@@ -55,7 +55,7 @@ class PoolArgs(C.Structure):
 # The C-ABI, stated once: entry point -> 'return kind, then the kind of every parameter in header order' (tests/test_cabi_exports.py
 # compares every word with include/nnr_hip.h).  lib() derives argtypes / restype from it, so call sites pass plain Python values, and the
 # tape (nnr_amd/tape.py) encodes a recorded call by these kinds.  i32 int | i64 long, int64_t | u64 size_t, uint64_t | f32 float |
-# seed uint32_t (every scalar one is a dropout seed) | ptr data pointer | handle nnr_tape*, nnr_dp_ctx* (opaque host objects, also as **
+# seed uint32_t (every scalar one is a dropout seed, but the sampler's run seed: tape.RUN_SEED_ARGS) | ptr data pointer | handle nnr_tape*, nnr_dp_ctx* (opaque host objects, also as **
 # out-parameters) | cstr char* | stream hipStream_t | a mirror class's name: pointer to that struct.
 SIGNATURES = {
     'nnr_version': 'i32',
@@ -166,6 +166,7 @@ SIGNATURES = {
     'nnr_conv3d_pool_bwd': 'i32 ptr ptr ptr ptr i64 i64 i64 i64 i64 ptr i32 i32 i32 i32 i32 i32 i32 i32 i32 i32 ptr ptr ptr ptr stream',
     'nnr_corpus_batch': 'i32 CorpusTables BatchOut ptr ptr i32 i32 i32 stream',
     'nnr_history_graph': 'i32 ptr ptr i32 i32 i32 i32 ptr ptr ptr stream',
+    'nnr_negative_sample': 'i32 ptr ptr ptr ptr i32 i32 seed i32 ptr i32 stream',
     'nnr_rank_metrics': 'i32 ptr ptr ptr i32 ptr ptr stream',
     'nnr_logits_loss_fwd': 'i32 ptr ptr i32 i32 i32 ptr ptr ptr stream',
     'nnr_logits_fwd': 'i32 ptr ptr i32 i32 i32 ptr stream',

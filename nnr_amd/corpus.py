@@ -54,8 +54,80 @@ def negative_sampling(behaviors, negative_sample_num, randint):
     return out
 
 
+NEG_K_MAX = 16           # nnr_negative_sample: 1 <= K <= 16
+
+
+def impression_lists(behaviors):
+    """[(click, [non-clicks]), ...] -> (clicks int32 [n], neg_offsets int64 [n + 1], neg_ids int32): the CSR form the device sampler reads."""
+    clicks = np.asarray([c for c, _ in behaviors], dtype=np.int32)
+    neg_offsets = np.zeros(len(behaviors) + 1, dtype=np.int64)
+    np.cumsum([len(n) for _, n in behaviors], out=neg_offsets[1:])
+    neg_ids = np.asarray([v for _, n in behaviors for v in n], dtype=np.int32)
+    return clicks, neg_offsets, neg_ids
+
+
+def check_impressions(clicks, neg_offsets, neg_ids):
+    """Validate CSR impression lists on the host (the kernel trusts them) and return them as contiguous int32 / int64 / int32 arrays.
+    An empty non-click list is refused: the reference's sampler divides by zero there (MIND_dataset.py:36)."""
+    clicks = np.ascontiguousarray(clicks, dtype=np.int32).reshape(-1)
+    neg_offsets = np.ascontiguousarray(neg_offsets, dtype=np.int64).reshape(-1)
+    neg_ids = np.ascontiguousarray(neg_ids, dtype=np.int32).reshape(-1)
+    n = clicks.shape[0]
+    if n < 1 or neg_offsets.shape[0] != n + 1:
+        raise ValueError('impression lists: %d clicks need %d offsets, got %d' % (n, n + 1, neg_offsets.shape[0]))
+    if neg_offsets[0] != 0 or neg_offsets[-1] != neg_ids.shape[0]:
+        raise ValueError('impression lists: offsets run from %d to %d, the non-click ids from 0 to %d'
+                         % (neg_offsets[0], neg_offsets[-1], neg_ids.shape[0]))
+    lens = np.diff(neg_offsets)
+    if (lens <= 0).any():
+        b = int(np.argmax(lens <= 0))
+        raise ValueError('impression lists: behaviour %d has %s: nothing to sample from'
+                         % (b, 'an empty non-click list' if lens[b] == 0 else 'decreasing offsets'))
+    if int(lens.max()) >= 2 ** 31:
+        raise ValueError('impression lists: a non-click list of %d entries (the sampler draws 32-bit positions)' % int(lens.max()))
+    return clicks, neg_offsets, neg_ids
+
+
+class NegativeSampler:
+    """Impression lists in HBM + the sample table nnr_negative_sample writes: table[b] = (click, K sampled non-clicks) of behaviour b, a
+    pure function of (seed, epoch, b) -- include/nnr_hip.h states the construction.  The table is allocated on the first draw and rewritten
+    in place afterwards (same data_ptr() from epoch to epoch, as long as K stays), so a launch tape that recorded nnr_corpus_batch keeps
+    reading the current epoch's samples.  Shared by DeviceCorpus and dssm.DssmCorpus."""
+
+    def __init__(self, clicks, neg_offsets, neg_ids, device):
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise L.NnrHipError('NegativeSampler needs a GPU: the sampler lives in libnnr_hip.so (no CPU path)')
+        clicks, neg_offsets, neg_ids = check_impressions(clicks, neg_offsets, neg_ids)
+        self.device, self.num, self.table = dev, clicks.shape[0], None
+        self.clicks, self.neg_offsets, self.neg_ids = (torch.from_numpy(a).to(dev) for a in (clicks, neg_offsets, neg_ids))
+
+    def draw(self, epoch, seed=0, negative_sample_num=4, beh_idx=None):
+        """Draw `epoch`'s samples of the behaviours `beh_idx` (int tensor on the device, or a sequence; None: all) into the table and return
+        the table.  Recorded on a launch tape, `epoch` and `seed` are recorded arguments: a replay redraws the recorded epoch."""
+        K = int(negative_sample_num)
+        if not 1 <= K <= NEG_K_MAX:
+            raise L.NnrHipError('negative_sample_num=%d: the device sampler draws 1..%d negatives' % (K, NEG_K_MAX))
+        if self.table is None or self.table.shape[1] != 1 + K:
+            if beh_idx is not None:
+                raise L.NnrHipError('the first draw (of a given negative_sample_num) fills the whole table: beh_idx must be None')
+            self.table = torch.empty((self.num, 1 + K), device=self.device, dtype=torch.int32)
+        idx, n = None, self.num
+        if beh_idx is not None:
+            idx = beh_idx if torch.is_tensor(beh_idx) else torch.as_tensor(np.asarray(beh_idx), dtype=torch.int32)
+            idx = idx.to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+            n = idx.numel()
+            if n == 0:
+                return self.table
+            if int(idx.min()) < 0 or int(idx.max()) >= self.num:
+                raise L.NnrHipError('beh_idx outside 0..%d' % (self.num - 1))
+        L.check(L.lib().nnr_negative_sample(_p(self.clicks), _p(self.neg_offsets), _p(self.neg_ids), _p(idx), n, K, int(seed) & 0xFFFFFFFF,
+                                            int(epoch), _p(self.table), 1 + K, _s()), 'nnr_negative_sample')
+        return self.table
+
+
 class DeviceCorpus:
-    """Corpus tables in HBM.  `arrays`: news_* tables [news(, T|C)], beh_user [n] int64, beh_history [n, H] int32 (news
+    """Corpus tables in HBM. `arrays`: news_* tables [news(, T|C)], beh_user [n] int64, beh_history [n, H] int32 (news
     indices, 0 = PAD news), beh_history_mask [n, H] bool, optionally beh_line [n] + train_user_history_graph /
     _category_mask / _category_indices (the reference's pre-built tables; used when graph='table')."""
 
@@ -87,6 +159,7 @@ class DeviceCorpus:
         self.t = t
         self.num = t['beh_user'].shape[0]
         self.samples = None
+        self.sampler = None
         ct = L.CorpusTables()
         ct.news_category, ct.news_subCategory = _p(t['news_category']), _p(t['news_subCategory'])
         ct.title_text, ct.title_mask, ct.title_entity = _p(t['news_title_text']), _p(t['news_title_mask']), _p(t['news_title_entity'])
@@ -101,8 +174,25 @@ class DeviceCorpus:
         self.samples = torch.as_tensor(np.ascontiguousarray(samples), dtype=torch.int32).to(self.device)
         assert self.samples.shape[0] == self.num
 
+    def set_impressions(self, clicks, neg_offsets, neg_ids):
+        """Upload, once, every behaviour's click and non-click list (CSR, impression_lists' layout) for sample_negatives()."""
+        sampler = NegativeSampler(clicks, neg_offsets, neg_ids, self.device)
+        if sampler.num != self.num:
+            raise ValueError('impression lists of %d behaviours for a corpus of %d' % (sampler.num, self.num))
+        self.sampler = sampler
+
+    def sample_negatives(self, epoch, seed=0, negative_sample_num=4, beh_idx=None):
+        """This epoch's samples, drawn on the device (NegativeSampler.draw): `self.samples` is allocated on first use and rewritten in place
+        afterwards (same data_ptr() across epochs); `beh_idx` redraws only those rows.  Returns self.samples."""
+        if self.sampler is None:
+            raise L.NnrHipError('call set_impressions() before sample_negatives()')
+        self.samples = self.sampler.draw(epoch, seed, negative_sample_num, beh_idx)
+        return self.samples
+
     def resident_bytes(self):
-        return sum(v.numel() * v.element_size() for v in self.t.values()) + (self.samples.numel() * 4 if self.samples is not None else 0)
+        lists = (self.sampler.clicks, self.sampler.neg_offsets, self.sampler.neg_ids) if self.sampler is not None else ()
+        return (sum(v.numel() * v.element_size() for v in list(self.t.values()) + list(lists))
+                + (self.samples.numel() * 4 if self.samples is not None else 0))
 
     def train_batch(self, beh_idx):
         """The 21 tensors of trainer.py:105-106 for the behaviours `beh_idx` (int32 tensor on the device, or a sequence)."""

@@ -9,6 +9,8 @@
 //   host memory on MIND-large) built on the fly from the history's category ids: one workgroup per impression, the
 //   G x G adjacency assembled in LDS, normalised with correctly rounded fp32 div / sqrt / mul (no contraction) so the result is
 //   bit-identical to numpy's, written once (18.5 KB).
+// * negative_sample_kernel : the epoch's (1 + K) sampled news ids per behaviour (MIND_dataset.py:27-47) as a pure function of
+//   (seed, epoch, behaviour), written in place into the table corpus_batch_kernel reads.
 #include "common.h"
 
 namespace {
@@ -161,6 +163,66 @@ extern "C" int nnr_history_graph(const int* cats, const uint8_t* hmask, int B, i
   if (!cats || !hmask || !graph || !cmask || !cidx || B <= 0) return NNR_ERR_ARG;
   if (H + K > GMAX || norm < 0 || norm > 3) return NNR_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(history_graph_kernel, dim3(B), dim3(256), 0, stream, cats, hmask, B, H, K, norm, graph, cmask, cidx);
+  NNR_CHECK_LAUNCH();
+  return NNR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ negative sampling (f-1)
+// MIND_Train_Dataset.negative_sampling (MIND_dataset.py:27-47) on the device: one thread per behaviour, a few hundred bytes per row.
+// The construction (generator, mapping, walk) is written down once, at nnr_negative_sample in include/nnr_hip.h.
+namespace {
+constexpr int NEG_KMAX = 16;
+
+// every loop is bounded by NEG_KMAX (no rejection loop); all register indices are static after unrolling: no scratch
+__global__ __launch_bounds__(256) void negative_sample_kernel(const int* __restrict__ clicks, const long* __restrict__ neg_offsets,
+                                                              const int* __restrict__ neg_ids, const int* __restrict__ beh_idx, int n, int K,
+                                                              uint32_t seed, int epoch, int* __restrict__ samples, int ld_samples) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int beh = beh_idx ? beh_idx[i] : i;
+  const long off = neg_offsets[beh];
+  const long len = neg_offsets[beh + 1] - off;
+  if (len <= 0 || len > 0x7fffffffL) return;             // refused on the host when the lists are uploaded
+  const int* __restrict__ list = neg_ids + off;
+  int* __restrict__ row = samples + (long)beh * ld_samples;
+  row[0] = clicks[beh];
+  const uint32_t m = (uint32_t)len;
+  if (m <= (uint32_t)K) {                                  // cyclic fill, exact
+    for (int j = 0; j < K; ++j) row[j + 1] = list[(uint32_t)j % m];
+    return;
+  }
+  // partial Fisher-Yates over the virtual array a[p] = p: (pos[t], val[t]) is the one entry step t displaced, pos[t] < 0: none
+  const uint32_t key = nnr_hash32(seed ^ nnr_hash32((uint32_t)epoch + 0x9E3779B9u));
+  const uint32_t h = nnr_hash32((uint32_t)beh ^ key);
+  int pos[NEG_KMAX], val[NEG_KMAX];
+#pragma unroll
+  for (int j = 0; j < NEG_KMAX; ++j) {
+    if (j >= K) break;
+    const uint32_t r = nnr_hash32(h + (uint32_t)j * 0x9E3779B9u + 1u);
+    const int p = j + (int)(((uint64_t)r * (uint64_t)(m - (uint32_t)j)) >> 32);       // uniform in [j, m)
+    int ap = p, aj = j, hit = -1;
+#pragma unroll
+    for (int t = 0; t < j; ++t) {
+      if (pos[t] == p) { ap = val[t]; hit = t; }
+      if (pos[t] == j) aj = val[t];
+    }
+#pragma unroll
+    for (int t = 0; t < j; ++t)
+      if (t == hit) val[t] = aj;                           // a[p] = a[j]; position j itself is never read again
+    pos[j] = hit < 0 ? p : -1;
+    val[j] = aj;
+    row[j + 1] = list[ap];
+  }
+}
+}  // namespace
+
+extern "C" int nnr_negative_sample(const int* clicks, const long* neg_offsets, const int* neg_ids, const int* beh_idx, int n, int K,
+                                   uint32_t seed, int epoch, int* samples, int ld_samples, hipStream_t stream) {
+  if (!clicks || !neg_offsets || !neg_ids || !samples || n <= 0) return NNR_ERR_ARG;
+  if (K < 1 || K > NEG_KMAX) return NNR_ERR_UNSUPPORTED;
+  if (ld_samples < 1 + K) return NNR_ERR_ARG;
+  hipLaunchKernelGGL(negative_sample_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, clicks, neg_offsets, neg_ids, beh_idx, n, K, seed,
+                     epoch, samples, ld_samples);
   NNR_CHECK_LAUNCH();
   return NNR_OK;
 }

@@ -61,6 +61,7 @@ const Entry REGISTRY[] = {
   R(nnr_gru_pack_weights), R(nnr_gru_unpack_grads), R(nnr_gru_fwd), R(nnr_gru_bwd), R(nnr_gru_zero_empty), R(nnr_gru_tanh_bwd),
   R(nnr_wbag_fwd), R(nnr_wbag_bwd), R(nnr_cosine_loss), R(nnr_tanh_drop_bwd),
   R(nnr_sue_seg_pool_fwd), R(nnr_sue_seg_pool_bwd),
+  R(nnr_negative_sample),
 };
 #undef R
 constexpr int NREG = (int)(sizeof(REGISTRY) / sizeof(REGISTRY[0]));

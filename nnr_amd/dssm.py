@@ -18,7 +18,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import functional as Fn
 from . import ops
-from .corpus import negative_sampling
+from .corpus import NegativeSampler, impression_lists, negative_sampling
 from .trainer import FlatParams
 
 
@@ -66,6 +66,7 @@ class DssmCorpus:
         assert self.user_ids.shape == self.user_w.shape and self.news_ids.shape == self.news_w.shape
         self.behaviors = list(behaviors) if behaviors is not None else []
         self.negatives = None
+        self._sampler = None
         if samples is not None:
             self.sample_user = torch.as_tensor(np.asarray(samples[0], dtype=np.int32)).to(dev)
             self.sample_news = torch.as_tensor(np.asarray(samples[1], dtype=np.int32)).to(dev)
@@ -77,6 +78,15 @@ class DssmCorpus:
         table = negative_sampling([(c, n) for _, c, n in self.behaviors], negative_sample_num, randint)
         self.negatives = torch.as_tensor(table).to(self.device)
         self.beh_user = torch.as_tensor(np.asarray([u for u, _, _ in self.behaviors], dtype=np.int32)).to(self.device)
+        return self.negatives
+
+    def negative_sampling_device(self, negative_sample_num, epoch, seed=0):
+        """Draw this epoch's negatives on the device (corpus.NegativeSampler: a pure function of (seed, epoch, behaviour), the rule of
+        DSSM_dataset.py:53-66); the lists are uploaded on first use and `self.negatives` is rewritten in place afterwards."""
+        if self._sampler is None:
+            self._sampler = NegativeSampler(*impression_lists([(c, n) for _, c, n in self.behaviors]), self.device)
+            self.beh_user = torch.as_tensor(np.asarray([u for u, _, _ in self.behaviors], dtype=np.int32)).to(self.device)
+        self.negatives = self._sampler.draw(epoch, seed, negative_sample_num)
         return self.negatives
 
     def train_batch(self, beh_idx):

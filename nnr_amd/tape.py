@@ -24,6 +24,7 @@ MASK64 = (1 << 64) - 1
 ACTIVE = [None]            # the tape that is recording right now
 VALUE_KINDS = {'news_seed': 0, 'user_seed': 1, 'adam_step': 2}
 ADAM_STEP_ARG = ('nnr_clip_adam', 13)      # the one plain integer that changes from step to step: the parameter the header calls `step`
+RUN_SEED_ARGS = {('nnr_negative_sample', 6)}      # a uint32 that names the RUN, not the step: recorded as is (so is its `epoch`: a replay redraws the recorded epoch)
 _BLOB_KINDS = {c.__name__ for c in L.STRUCTS.values()} - L.DEVICE_STRUCTS      # host structs: copied into the tape
 
 
@@ -93,7 +94,7 @@ class Tape:
         self.lib = L.lib()
         self.known = [t for t in known if torch.is_tensor(t)]
         self.violations = []                # (entry point, argument / field, pointer) that resolved to nothing the tape can vouch for
-        self._ranges, self._ranged = [], 0
+        self._ranges, self._ranged = None, 0
         self.h = C.c_void_p()
         L.check(self.lib.nnr_tape_create(C.byref(self.h)), 'nnr_tape_create')
         self.inputs = [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), tuple(t.shape), t.dtype) for t in inputs]
@@ -187,7 +188,8 @@ class Tape:
 
     def _vouched(self, ptr):
         """Is `ptr` inside a buffer that stays valid for the tape's lifetime (kept by the tape, or `known`)?"""
-        if self._ranged == 0:
+        if self._ranges is None:
+            self._ranges = []
             for t in self.known:
                 st = t.untyped_storage()
                 self._ranges.append((st.data_ptr(), st.data_ptr() + st.nbytes()))
@@ -198,7 +200,6 @@ class Tape:
             if torch.is_tensor(t):
                 st = t.untyped_storage()
                 self._ranges.append((st.data_ptr(), st.data_ptr() + st.nbytes()))
-        self._ranged = max(self._ranged, 1)
         for lo, hi in reversed(self._ranges):          # the most recent allocations are the likeliest hits
             if lo <= ptr < hi:
                 return True
@@ -237,7 +238,7 @@ class Tape:
                 v = struct.unpack('<I', struct.pack('<f', v))[0]
             elif kind == 'seed':
                 v &= 0xFFFFFFFF                      # the one place a seed is masked: the eager call leaves that to c_uint32
-                if v:
+                if v and (name, i) not in RUN_SEED_ARGS:
                     k, d = self._seed_kind(v)
                     patches.append(('slot', 8 * i, k, 4, d))
             elif kind in ('i32', 'i64', 'u64'):
