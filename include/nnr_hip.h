@@ -627,6 +627,19 @@ int nnr_history_graph(const int* cats, const uint8_t* hmask, int B, int H, int K
  * A list of length 0 is the caller's to refuse (the reference divides by zero there); such a row is left untouched. */
 int nnr_negative_sample(const int* clicks, const long* neg_offsets, const int* neg_ids, const int* beh_idx, int n, int K, uint32_t seed,
                         int epoch, int* samples, int ld_samples, hipStream_t stream);
+/* Listwise evaluation: the click scores of n (impression, candidate) samples against a user table that was
+ * encoded once per impression (or once per row of K candidates):
+ *   scores[j] = sum_d user[row[j] * ldu + d] * reps[cand[j] * ldr + d]      for j < n.
+ * user [n_user, D] with row stride ldu >= D, reps [n_reps, D] with row stride ldr >= D (the table of distinct news representations),
+ * row / cand int32 [n], scores float [n]; entries of scores beyond n are not touched.  Summation order: one wave per sample; lane l
+ * accumulates d = l, l + 64, ... in ascending order with fmaf from 0, then the 64 lane sums are folded by a butterfly (partner l ^ 32,
+ * l ^ 16, ..., l ^ 1, each step v += partner's v).  16-byte loads when D, ldu and ldr are multiples of 4 and both tables are 16-byte
+ * aligned, 4-byte loads otherwise, in the same order: a sample's score is a pure function of its two rows, to the bit, wherever it
+ * stands and whichever path the launch took.  No atomics, no LDS.
+ * NNR_ERR_ARG for a null pointer, n < 1, D < 1, ldu < D, ldr < D, n_user < 1 or n_reps < 1; nothing is launched then.  The indices
+ * are trusted: row[j] in 0 .. n_user - 1 and cand[j] in 0 .. n_reps - 1 are the caller's to check (ops.list_scores does). */
+int nnr_list_scores(const float* user, long n_user, int ldu, const float* reps, long n_reps, int ldr, const int* row, const int* cand,
+                    long n, int D, float* scores, hipStream_t stream);
 /* Evaluation tail: util.py:50-59 (per-impression ranks by descending score, ties in file order) +
  * evaluate.py:8-29,76-81 (AUC, MRR, nDCG@5, nDCG@10 per impression, float64).  offsets [n_impressions + 1] delimit the
  * (contiguous) candidates of each impression; per_impression [n_impressions, 4]; NaN row for a single-class impression. */

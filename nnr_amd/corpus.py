@@ -251,3 +251,28 @@ def from_synth(synth, n_behaviors, rng, device, graph='build'):
     dc = DeviceCorpus(arrays, device, s.category_num, graph=graph)
     dc.set_samples(rng.integers(1, s.news_pool, size=(n_behaviors, S)).astype(np.int32))
     return dc
+
+
+def from_synth_lists(synth, sizes, rng, device, distinct_users=None):
+    """A dev-shaped DeviceCorpus over a SynthCorpus news pool (bench / tests): impression i is sizes[i] contiguous (impression, candidate)
+    samples that repeat one behaviour row (user, history, mask), each with one candidate drawn from the pool.  distinct_users: the
+    impressions draw their behaviour row from that many distinct rows (a user's history is the same in all their impressions of a split);
+    None: one row per impression."""
+    s = synth.spec
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    H, n_rows = s.max_history_num, int(distinct_users or sizes.size)
+    counts = rng.integers(0, H + 1, size=n_rows)
+    counts[rng.random(n_rows) < s.empty_history_frac] = 0
+    hist = np.zeros((n_rows, H), dtype=np.int32)
+    hmask = np.arange(H)[None, :] < counts[:, None]
+    for b in range(n_rows):
+        hist[b, :counts[b]] = rng.integers(1, s.news_pool, size=counts[b])
+    owner = np.arange(sizes.size, dtype=np.int64) if distinct_users is None else rng.integers(0, n_rows, size=sizes.size)
+    beh = np.repeat(owner, sizes)
+    arrays = dict(news_category=synth.category, news_subCategory=synth.subCategory, news_title_text=synth.title_text,
+                  news_title_mask=synth.title_mask, news_title_entity=synth.title_entity, news_abstract_text=synth.content_text,
+                  news_abstract_mask=synth.content_mask, news_abstract_entity=synth.content_entity,
+                  beh_user=beh, beh_history=hist[beh], beh_history_mask=hmask[beh])
+    dc = DeviceCorpus(arrays, device, s.category_num)
+    dc.set_samples(rng.integers(1, s.news_pool, size=(beh.size, 1)).astype(np.int32))
+    return dc

@@ -11,6 +11,8 @@
 //   bit-identical to numpy's, written once (18.5 KB).
 // * negative_sample_kernel : the epoch's (1 + K) sampled news ids per behaviour (MIND_dataset.py:27-47) as a pure function of
 //   (seed, epoch, behaviour), written in place into the table corpus_batch_kernel reads.
+// * list_scores_kernel : the click scores of a whole evaluation as one gather (listwise evaluation): sample j's score is the dot product
+//   of row row[j] of the user table and row cand[j] of the news table, one wave per sample.
 #include "common.h"
 
 namespace {
@@ -300,6 +302,89 @@ extern "C" int nnr_rank_metrics(const float* scores, const uint8_t* labels, cons
                                 double* per_impression, hipStream_t stream) {
   if (!scores || !labels || !offsets || !ranks || !per_impression || n_impressions <= 0) return NNR_ERR_ARG;
   hipLaunchKernelGGL(rank_metrics_kernel, dim3(n_impressions), dim3(256), 0, stream, scores, labels, offsets, ranks, per_impression);
+  NNR_CHECK_LAUNCH();
+  return NNR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ listwise scores
+// scores[j] = <user[row[j]], reps[cand[j]]>: the click predictor of a whole dev / test split in one launch, after the user encoder ran once
+// per impression (or once per row of K candidates) instead of once per sample.  One wave per sample, four per workgroup, grid-stride.  The
+// summation order is the one nnr_list_scores states in include/nnr_hip.h: lane l folds d = l, l + 64, ... in ascending order with fmaf,
+// wave_sum folds the lanes.  Both load paths keep it to the bit: the 16-byte path lets lane 4g + q load the float4 at 64q + 4g of each
+// 256-float chunk (a wave still reads the chunk's 1 KB contiguously) and transposes the 4 x 4 block inside the quad with two DPP swaps, after
+// which lane l = 4g + c holds the elements l, l + 64, l + 128, l + 192 of the chunk -- what the scalar path loads.  No LDS, no atomics.
+namespace {
+constexpr int LS_GRID_MAX = 2048;                          // 8 workgroups (32 waves) per CU on 256 CUs: every wave slot taken, no more
+
+template <int CTRL> __device__ __forceinline__ float quad_perm(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+// a[c] of quad lane t  ->  a[s] = (a[t] of quad lane s); every lane of the wave must be active
+__device__ __forceinline__ void quad_transpose(float (&a)[4], bool b0, bool b1) {
+#pragma unroll
+  for (int p = 0; p < 4; p += 2) {                         // lanes t, t ^ 1 swap the off-diagonal of each 2 x 2 block
+    const float got = quad_perm<0xB1>(b0 ? a[p] : a[p + 1]);      // quad_perm [1, 0, 3, 2]
+    if (b0) a[p] = got; else a[p + 1] = got;
+  }
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {                            // lanes t, t ^ 2 swap the off-diagonal 2 x 2 blocks
+    const float got = quad_perm<0x4E>(b1 ? a[p] : a[p + 2]);      // quad_perm [2, 3, 0, 1]
+    if (b1) a[p] = got; else a[p + 2] = got;
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void list_scores_kernel(const float* __restrict__ user, int ldu, const float* __restrict__ reps, int ldr,
+                                                          const int* __restrict__ row, const int* __restrict__ cand, long n, int D,
+                                                          float* __restrict__ scores) {
+  const int lane = threadIdx.x & 63;
+  const long step = gridDim.x * 4L;
+  long j = blockIdx.x * 4L + (threadIdx.x >> 6);           // wave-uniform: a wave is wholly inside the loop or wholly out
+  if (j >= n) return;
+  int ru = row[j], rc = cand[j];
+  while (true) {
+    const float* __restrict__ u = user + (long)ru * ldu;
+    const float* __restrict__ r = reps + (long)rc * ldr;
+    const long jn = j + step;
+    if (jn < n) { ru = row[jn]; rc = cand[jn]; }           // the next trip's indices travel under this trip's rows
+    float acc = 0.f;
+    if (VEC) {
+      const int q = lane & 3, g = lane >> 2;
+      const bool b0 = lane & 1, b1 = lane & 2;
+      for (int base = 0; base < D; base += 256) {
+        const int off = base + 64 * q + 4 * g;             // D % 4 == 0: a float4 is wholly inside the row or wholly outside
+        float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
+        if (off < D) {
+          const float4 ua = *reinterpret_cast<const float4*>(u + off), ra = *reinterpret_cast<const float4*>(r + off);
+          a[0] = ua.x; a[1] = ua.y; a[2] = ua.z; a[3] = ua.w;
+          b[0] = ra.x; b[1] = ra.y; b[2] = ra.z; b[3] = ra.w;
+        }
+        quad_transpose(a, b0, b1);
+        quad_transpose(b, b0, b1);
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+          if (base + 64 * s + lane < D) acc = fmaf(a[s], b[s], acc);
+      }
+    } else {
+      for (int d = lane; d < D; d += 64) acc = fmaf(u[d], r[d], acc);
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) scores[j] = acc;
+    if (jn >= n) break;
+    j = jn;
+  }
+}
+}  // namespace
+
+extern "C" int nnr_list_scores(const float* user, long n_user, int ldu, const float* reps, long n_reps, int ldr, const int* row,
+                               const int* cand, long n, int D, float* scores, hipStream_t stream) {
+  if (!user || !reps || !row || !cand || !scores) return NNR_ERR_ARG;
+  if (n < 1 || D < 1 || ldu < D || ldr < D || n_user < 1 || n_reps < 1) return NNR_ERR_ARG;
+  const bool vec = D % 4 == 0 && ldu % 4 == 0 && ldr % 4 == 0 && ((uintptr_t)user | (uintptr_t)reps) % 16 == 0;
+  const long blocks = (n + 3) / 4;
+  const dim3 grid((unsigned)(blocks < LS_GRID_MAX ? blocks : LS_GRID_MAX));
+  if (vec) hipLaunchKernelGGL(list_scores_kernel<true>, grid, dim3(256), 0, stream, user, ldu, reps, ldr, row, cand, n, D, scores);
+  else hipLaunchKernelGGL(list_scores_kernel<false>, grid, dim3(256), 0, stream, user, ldu, reps, ldr, row, cand, n, D, scores);
   NNR_CHECK_LAUNCH();
   return NNR_OK;
 }

@@ -62,6 +62,7 @@ const Entry REGISTRY[] = {
   R(nnr_wbag_fwd), R(nnr_wbag_bwd), R(nnr_cosine_loss), R(nnr_tanh_drop_bwd),
   R(nnr_sue_seg_pool_fwd), R(nnr_sue_seg_pool_bwd),
   R(nnr_negative_sample),
+  R(nnr_list_scores),
 };
 #undef R
 constexpr int NREG = (int)(sizeof(REGISTRY) / sizeof(REGISTRY[0]));

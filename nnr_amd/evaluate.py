@@ -101,6 +101,144 @@ def compute_scores(model, corpus, batch_size, cache='auto'):
     return scores
 
 
+# ------------------------------------------------------------------------------------------------ listwise evaluation
+# All candidates of an impression share one user and one history, so the user encoder needs to run once per impression, not once per
+# (impression, candidate) sample.  Two modes, by what the encoder reads:
+#   candidate_independent (ATT, MHSA, GRU, PUE, SUE_wo_HCA): ONE user vector per impression (or per distinct user row), whatever the candidates.
+#   candidate-aware (SUE, SUE_wo_GCN, CATT, OMAP): an impression's candidates go through encode_user K at a time -- a row of K candidates is a
+#   training-shaped sample with news_num = K -- and every candidate's user vector depends on its own candidate only.
+# Either way the scores are one nnr_list_scores launch over (user row, candidate row) pairs.
+class ListPlan:
+    """Where every sample of a split sits (list_plan).  n samples, R user rows of K slots:
+      imp int64 [n]           the impression of sample j
+      first int64 [n_imp]     the impression's first sample
+      row_imp int64 [R]       the impression of row r
+      row_slots int64 [R, K]  the sample in slot k of row r; a pad slot holds the row's first sample   (candidate-aware mode only,
+      slot_valid bool [R, K]  False for a pad slot                                                     None in the independent mode)
+      row int32 [n]           the slot of sample j, r * K + k; in the independent mode the row itself = the impression of sample j"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def list_plan(sizes, candidates_per_row=None):
+    """The row / slot layout of listwise evaluation for impressions of `sizes` contiguous samples each (host, numpy).  candidates_per_row=None:
+    one row per impression (independent mode); K: impression i takes ceil(size_i / K) rows of K slots, filled in sample order."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    if sizes.size < 1 or int(sizes.min()) < 1:
+        raise ValueError('list_plan: every impression needs at least one candidate')
+    K = 1 if candidates_per_row is None else int(candidates_per_row)
+    if K < 1:
+        raise ValueError('list_plan: candidates_per_row=%d' % K)
+    n_imp, n = sizes.size, int(sizes.sum())
+    first = np.zeros(n_imp, dtype=np.int64)
+    np.cumsum(sizes[:-1], out=first[1:])
+    imp = np.repeat(np.arange(n_imp, dtype=np.int64), sizes)
+    if candidates_per_row is None:
+        row_first = row_imp = np.arange(n_imp, dtype=np.int64)
+        pos = np.zeros(n, dtype=np.int64)                              # every sample of an impression reads the impression's one row
+        row_slots = slot_valid = None                                  # no slots: a row serves every sample of its impression
+    else:
+        rows_of = (sizes + K - 1) // K
+        row_first = np.zeros(n_imp, dtype=np.int64)
+        np.cumsum(rows_of[:-1], out=row_first[1:])
+        pos = np.arange(n, dtype=np.int64) - first[imp]                # position inside the impression
+        row_imp = np.repeat(np.arange(n_imp, dtype=np.int64), rows_of)
+        in_imp = (np.arange(row_imp.size, dtype=np.int64) - row_first[row_imp])[:, None] * K + np.arange(K, dtype=np.int64)[None, :]
+        slot_valid = in_imp < sizes[row_imp][:, None]
+        head = first[row_imp] + in_imp[:, 0]                           # the row's first sample: what a pad slot holds
+        row_slots = np.where(slot_valid, first[row_imp][:, None] + in_imp, head[:, None])
+    row = row_first[imp] * K + pos
+    if row.size and int(row.max()) >= 2 ** 31:
+        raise ValueError('list_plan: %d slots do not fit the kernel\'s int32 row indices' % (int(row.max()) + 1))
+    return ListPlan(n=n, K=K, candidates_per_row=candidates_per_row, imp=imp, first=first, row_imp=row_imp, row_slots=row_slots,
+                    slot_valid=slot_valid, row=row.astype(np.int32))
+
+
+LISTWISE_REFUSAL = ('listwise evaluation needs news representations that do not depend on their batch-mates (news_reps_cacheable): %s is not '
+                    'batch_independent -- the reference pairs the news of one encoder call, so scoring an impression as a list would change its scores')
+
+
+def listwise_supported(model):
+    """Listwise evaluation gathers every representation from the table of distinct news: the rule is news_reps_cacheable's."""
+    return news_reps_cacheable(model)
+
+
+def _check_lists(t, plan, dev):
+    """Every sample's (user, history, mask) row equals its impression's first sample's: one device reduction, one sync."""
+    fs = torch.from_numpy(plan.first[plan.imp]).to(dev)
+    same = ((t['beh_user'] == t['beh_user'][fs]).all() & (t['beh_history'] == t['beh_history'][fs]).all()
+            & (t['beh_history_mask'] == t['beh_history_mask'][fs]).all())
+    if not bool(same):
+        raise ValueError('listwise evaluation: a sample\'s user, history or history mask differs from its impression\'s first sample '
+                         '(sizes must delimit impressions whose samples share one behaviour row)')
+
+
+@torch.no_grad()
+def compute_scores_listwise(model, corpus, sizes, batch_size, candidates_per_row=8, dedup_users=True, check=True):
+    """One score per dev sample in dataset order, float32 [n] on the device, as compute_scores -- with the user encoder run once per
+    impression (candidate_independent encoders; once per distinct (user, history, mask) row with dedup_users) or once per row of
+    `candidates_per_row` candidates of one impression (candidate-aware encoders), and ONE nnr_list_scores launch for all scores.
+    `sizes`: candidates per impression (contiguous, file order).  check=True verifies that the samples of an impression share their behaviour
+    row.  Refused (NnrHipError naming the reason) for encoders whose news representations cannot be cached."""
+    from . import ops
+    if not listwise_supported(model):
+        raise L.NnrHipError(LISTWISE_REFUSAL % type(model.news_encoder).__name__)
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    if int(sizes.sum()) != corpus.num:
+        raise ValueError('listwise evaluation: sizes sum to %d, the corpus holds %d samples' % (int(sizes.sum()), corpus.num))
+    ue = model.user_encoder
+    independent = bool(getattr(ue, 'candidate_independent', False))
+    plan = list_plan(sizes, None if independent else candidates_per_row)
+    t, dev = corpus.t, corpus.device
+    if check:
+        _check_lists(t, plan, dev)
+    was_training = model.training
+    model.eval()
+    try:
+        first = torch.from_numpy(plan.first).to(dev)
+        row = torch.from_numpy(plan.row).to(dev)
+        if independent:
+            users, hist, hmask = t['beh_user'][first], t['beh_history'][first], t['beh_history_mask'][first]
+            if dedup_users:
+                H = hist.shape[1]
+                key, inv = torch.unique(torch.cat([users.view(-1, 1), hist.long(), hmask.long()], dim=1), dim=0, return_inverse=True)
+                users, hist, hmask = key[:, 0].contiguous(), key[:, 1:1 + H].to(torch.int32), key[:, 1 + H:] != 0
+                row = inv[torch.from_numpy(plan.imp).to(dev)].to(torch.int32)
+            slots = None
+        else:
+            rf = first[torch.from_numpy(plan.row_imp).to(dev)]                      # a row reads its impression's behaviour row
+            users, hist, hmask = t['beh_user'][rf], t['beh_history'][rf], t['beh_history_mask'][rf]
+            slots = torch.from_numpy(plan.row_slots).to(dev)
+        R, K = users.numel(), plan.K
+        cand = corpus.samples[:, 0].long()
+        hist = hist.long()
+        used, inv = torch.unique(torch.cat([hist.reshape(-1), cand]), return_inverse=True)
+        reps = encode_news_table(model, corpus, used)
+        slot_h, slot_c = inv[:hist.numel()].view_as(hist), inv[hist.numel():]
+        D = reps.shape[1]
+        table = torch.empty((R * K, D), device=dev, dtype=torch.float32)
+        need_graph = getattr(ue, 'needs_history_graph', False)
+        blank = torch.zeros((min(batch_size, R), 1, D), device=dev, dtype=torch.float32) if independent else None
+        for s in range(0, R, batch_size):
+            e = min(s + batch_size, R)
+            h = reps[slot_h[s:e]]                                                  # [r, H, D]
+            c = blank[:e - s] if independent else reps[slot_c[slots[s:e]]]         # [r, 1, D] (never read) / [r, K, D]
+            m = hmask[s:e].contiguous()
+            graph = cmask = cidx = None
+            if need_graph:
+                from .corpus import history_graph
+                graph, cmask, cidx = history_graph(t['news_category'][hist[s:e]].contiguous(), m, corpus.category_num, corpus.norm_name)
+            extra = (model.user_rows(users[s:e].long()),) if getattr(ue, 'needs_user_embedding', False) else ()
+            table[s * K:e * K] = ue.encode_user(h, m, graph, cmask, cidx, c, *extra).reshape((e - s) * K, D)
+        scores = ops.list_scores(table, reps, row.contiguous(), slot_c.to(torch.int32).contiguous(), check=check)
+    finally:
+        model.train(was_training)
+    LAST_STATS.update(mode='listwise', user_rows=int(R), per_sample_user_rows=int(corpus.num), encoder_rows=int(used.numel()),
+                      candidates_per_row=plan.candidates_per_row)
+    return scores
+
+
 def rank_metrics(scores, labels, sizes):
     """scores float32 [n], labels uint8/bool [n], sizes: candidates per impression (contiguous, file order).
     Returns (ranks int32 [n], per_impression float64 [n_imp, 4], means float64 [4]) -- all device tensors."""
@@ -117,9 +255,13 @@ def rank_metrics(scores, labels, sizes):
     return ranks, per, per.mean(dim=0)
 
 
-def evaluate(model, corpus, labels, sizes, batch_size):
-    """compute_scores + scoring: -> (auc, mrr, ndcg5, ndcg10) as Python floats, plus the ranks (for the result file)."""
-    scores = compute_scores(model, corpus, batch_size)
+def evaluate(model, corpus, labels, sizes, batch_size, listwise=False):
+    """compute_scores + scoring: -> (auc, mrr, ndcg5, ndcg10) as Python floats, plus the ranks (for the result file).  listwise=True scores
+    each impression as a list (compute_scores_listwise) when the model allows it (listwise_supported), and as without the keyword otherwise."""
+    if listwise and listwise_supported(model):
+        scores = compute_scores_listwise(model, corpus, sizes, batch_size)
+    else:
+        scores = compute_scores(model, corpus, batch_size)
     ranks, _, means = rank_metrics(scores, torch.as_tensor(np.asarray(labels)), sizes)
     return tuple(float(v) for v in means.cpu()), ranks
 

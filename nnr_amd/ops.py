@@ -1368,6 +1368,35 @@ def logits_fwd(user, cand, B, N, D, logits):
     L.check(L.lib().nnr_logits_fwd(_p(user), _p(cand), B, N, D, _p(logits), _s()), 'nnr_logits_fwd')
 
 
+def list_scores(user, reps, row, cand, scores=None, check=True):
+    """scores[j] = <user[row[j]], reps[cand[j]]> (nnr_list_scores; its summation order is stated in include/nnr_hip.h): user [n_user, D] and
+    reps [n_reps, D] float32 with unit column stride (any row stride >= D), row / cand int32 [n] -> float32 [n] (written into `scores` when
+    given; entries beyond n stay).  The kernel trusts the indices: check=True reads their ranges back (two reductions, one sync) and raises
+    before the launch."""
+    n, D = row.numel(), user.shape[1]
+    if user.dim() != 2 or reps.dim() != 2 or reps.shape[1] != D or user.dtype != torch.float32 or reps.dtype != torch.float32:
+        raise L.NnrHipError('list_scores: user [n_user, D] and reps [n_reps, D] must be float32 tables of one width')
+    if row.dtype != torch.int32 or cand.dtype != torch.int32 or cand.numel() != n or not (row.is_contiguous() and cand.is_contiguous()):
+        raise L.NnrHipError('list_scores: row and cand must be contiguous int32 tensors of one length')
+    if (D > 1 and (user.stride(1) != 1 or reps.stride(1) != 1)) or n < 1 or user.shape[0] < 1 or reps.shape[0] < 1:
+        raise L.NnrHipError('list_scores: empty input or a table whose columns are not adjacent')
+    if scores is None:
+        scores = torch.empty(n, device=user.device, dtype=torch.float32)
+    elif scores.dtype != torch.float32 or scores.numel() < n or not scores.is_contiguous():
+        raise L.NnrHipError('list_scores: scores must be a contiguous float32 tensor of at least n entries')
+    if check:
+        _p(row), _p(cand)
+        lo_r, hi_r, lo_c, hi_c = torch.stack(torch.aminmax(row) + torch.aminmax(cand)).tolist()
+        if lo_r < 0 or hi_r >= user.shape[0] or lo_c < 0 or hi_c >= reps.shape[0]:
+            raise L.NnrHipError('list_scores: row indices %d..%d for %d user rows, cand indices %d..%d for %d news rows'
+                                % (lo_r, hi_r, user.shape[0], lo_c, hi_c, reps.shape[0]))
+    ldu = user.stride(0) if user.shape[0] > 1 else D
+    ldr = reps.stride(0) if reps.shape[0] > 1 else D
+    L.check(L.lib().nnr_list_scores(_p(user), user.shape[0], ldu, _p(reps), reps.shape[0], ldr, _p(row), _p(cand), n, D, _p(scores), _s()),
+            'nnr_list_scores')
+    return scores
+
+
 def nls_loss(logits, B, N, loss, dlogits):
     L.check(L.lib().nnr_nls_loss(_p(logits), B, N, _p(loss), _p(dlogits), _s()), 'nnr_nls_loss')
 

@@ -22,6 +22,8 @@ from .news_encoders import NewsEncoder
 class UserEncoder(nn.Module):
     """userEncoders.py:12-39: holds a reference to the SAME news-encoder instance (:16)."""
     needs_user_embedding = False         # True: encode_user takes the user embedding rows as a seventh argument (model.Model passes them)
+    candidate_independent = False        # True: encode_user expands ONE vector per user over the candidates and never reads them (listwise evaluation
+                                         # then encodes a user once per impression, evaluate.compute_scores_listwise)
 
     def __init__(self, news_encoder: NewsEncoder, config):
         super().__init__()
@@ -573,6 +575,7 @@ class SUE_wo_HCA(UserEncoder):
     its outer residual, the first max_history_num rows, one UNMASKED additive attention (padded history slots take part), the user vector
     repeated over the candidates.  Reads neither the candidates nor any mask nor the cluster indices, and does not write the cluster mask."""
     needs_history_graph = True
+    candidate_independent = True
 
     def __init__(self, news_encoder: NewsEncoder, config):
         super().__init__(news_encoder, config)
@@ -600,6 +603,7 @@ class SUE_wo_HCA(UserEncoder):
 
 class MHSA(UserEncoder):
     """userEncoders.py:151-173.  Note F.dropout's default p = 0.5 (not dropout_rate) at :171 and the UNMASKED pool at :172."""
+    candidate_independent = True
 
     def __init__(self, news_encoder: NewsEncoder, config):
         super().__init__(news_encoder, config)
@@ -629,6 +633,7 @@ class MHSA(UserEncoder):
 
 class ATT(UserEncoder):
     """userEncoders.py:176-191: unmasked additive attention over the history slots (padded slots participate)."""
+    candidate_independent = True
 
     def __init__(self, news_encoder: NewsEncoder, config):
         super().__init__(news_encoder, config)
@@ -647,6 +652,7 @@ class GRU(UserEncoder):
     """userEncoders.py:287-332 (the user encoder of the DAE-GRU baseline): nn.GRU over the first user_history_mask.sum() history slots from
     h = 0, user vector tanh(dec(h_final)), exactly zero for a user without history.  The sort / pack / de-sort of the reference is replaced by
     running every user for t < len and freezing h afterwards (csrc/gru.hip): same values, no planner, no host sync."""
+    candidate_independent = True
 
     def __init__(self, news_encoder: NewsEncoder, config):
         super().__init__(news_encoder, config)
@@ -787,6 +793,7 @@ class PUE(UserEncoder):
     layers.CandidateAttention's kernel (csrc/cand_attn.hip) was built for.  encode_user takes the user embedding rows as a seventh argument
     (needs_user_embedding tells model.Model to pass them)."""
     needs_user_embedding = True
+    candidate_independent = True
 
     def __init__(self, news_encoder: NewsEncoder, config):
         super().__init__(news_encoder, config)
