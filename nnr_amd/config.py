@@ -1,17 +1,18 @@
 """Flag namespace of the hot path: the reference's `main.py` / `config.py` flag names and defaults (config.py:15-76)
 plus its per-dataset override block (config.py:84-98).  Unlike the reference's Config it has no side effects: no GPU
-assert, no dataset download, no directory creation (those belong to the control plane, out of scope)."""
+assert, no dataset download, no directory creation (the run directories are nnr_amd.run.RunDirs', created on use)."""
 import argparse
 import json
 import os
 from types import SimpleNamespace
 
 _FLAGS = [
-    ('mode', str, 'train'), ('news_encoder', str, 'CNE'), ('user_encoder', str, 'SUE'), ('device_id', int, 0), ('seed', int, 0),
+    ('mode', str, 'train'), ('news_encoder', str, 'CNE'), ('user_encoder', str, 'SUE'),
+    ('dev_model_path', str, ''), ('test_model_path', str, ''), ('test_output_file', str, ''), ('device_id', int, 0), ('seed', int, 0),
     ('config_file', str, ''), ('dataset', str, '200k'), ('tokenizer', str, 'MIND'), ('word_threshold', int, 3),
     ('max_title_length', int, 32), ('max_abstract_length', int, 128), ('negative_sample_num', int, 4), ('max_history_num', int, 50),
     ('epoch', int, 16), ('batch_size', int, 64), ('lr', float, 1e-4), ('weight_decay', float, 0.0), ('gradient_clip_norm', float, 4.0),
-    ('world_size', int, 1), ('word_embedding_dim', int, 300), ('entity_embedding_dim', int, 100), ('context_embedding_dim', int, 100),
+    ('world_size', int, 1), ('dev_criterion', str, 'avg'), ('early_stopping_epoch', int, 5), ('word_embedding_dim', int, 300), ('entity_embedding_dim', int, 100), ('context_embedding_dim', int, 100),
     ('cnn_method', str, 'naive'), ('cnn_kernel_num', int, 400), ('cnn_window_size', int, 3), ('attention_dim', int, 200),
     ('head_num', int, 20), ('head_dim', int, 20), ('user_embedding_dim', int, 50), ('personalized_embedding_dim', int, 200), ('category_embedding_dim', int, 50),
     ('subCategory_embedding_dim', int, 50), ('dropout_rate', float, 0.2), ('gcn_normalization_type', str, 'symmetric'), ('gcn_layer_num', int, 4), ('hidden_dim', int, 200),
@@ -20,6 +21,8 @@ _FLAGS = [
     ('HDC_window_size', int, 3), ('HDC_filter_num', int, 150), ('conv3D_filter_num_first', int, 32), ('conv3D_kernel_size_first', int, 3),
     ('conv3D_filter_num_second', int, 16), ('conv3D_kernel_size_second', int, 3), ('maxpooling3D_size', int, 3), ('maxpooling3D_stride', int, 3),
 ]
+_CHOICES = {'mode': ['train', 'dev', 'test'], 'gcn_normalization_type': ['symmetric', 'asymmetric'],
+            'dev_criterion': ['auc', 'mrr', 'ndcg5', 'ndcg10', 'avg']}           # config.py:15,40,57
 _BOOL_FLAGS = ['no_self_connection', 'no_adjacent_normalization', 'no_gcn_residual', 'gcn_layer_norm']
 
 NEWS_ENCODERS = ['CNE', 'CNN', 'MHSA', 'PNE', 'DAE', 'Inception', 'HDC', 'KCNN']    # in scope; the reference lists 15
@@ -33,7 +36,7 @@ VARIANT_USER_ENCODERS =['SUE_wo_GCN', 'SUE_wo_HCA']                  # the user-
 def build_parser():
     p = argparse.ArgumentParser(description='NNR hot path on MI355X (flag names follow the reference config.py)')
     for name, typ, default in _FLAGS:
-        p.add_argument('--' + name, type=typ, default=default, **({'choices': ['symmetric', 'asymmetric']} if name == 'gcn_normalization_type' else {}))
+        p.add_argument('--' + name, type=typ, default=default, **({'choices': _CHOICES[name]} if name in _CHOICES else {}))
     for name in _BOOL_FLAGS:
         p.add_argument('--' + name, default=False, action='store_true')
     p.add_argument('--tie_order', type=str, default='stable', choices=['stable', 'torch'],

@@ -1,7 +1,7 @@
 """Inner training step of the reference's `Trainer.train` / `distributed_train` (trainer.py:81-120, 261-300):
 forward, loss, zero_grad, backward, [gradient all-reduce], clip_grad_norm_(gradient_clip_norm), Adam.step -- with the
 optimizer state in flat fp32 buffers and clip+Adam fused into one HBM-bound kernel.  The epoch loop, dev evaluation and
-checkpoint bookkeeping of the reference are control plane and out of scope."""
+checkpoint bookkeeping of the reference are nnr_amd/run.py."""
 import os
 
 import torch
