@@ -640,6 +640,26 @@ int nnr_negative_sample(const int* clicks, const long* neg_offsets, const int* n
  * are trusted: row[j] in 0 .. n_user - 1 and cand[j] in 0 .. n_reps - 1 are the caller's to check (ops.list_scores does). */
 int nnr_list_scores(const float* user, long n_user, int ldu, const float* reps, long n_reps, int ldr, const int* row, const int* cand,
                     long n, int D, float* scores, hipStream_t stream);
+/* De-duplicated evaluation of the rank-pairing CNE encoders: the pairing plan of every encoder call of a range of
+ * reference batches, in one launch.  The reference scores dev samples in batches of batch_size consecutive samples (the last one short) and
+ * runs two encoder calls per batch of b samples: the candidate call over the b sequences cand[s] and the history call over the b * H
+ * sequences beh_history[s, h], sequence index s * H + h.  Inside a call it sorts the sequences by title length and by content length,
+ * descending, equal lengths in ascending sequence index (torch.sort(descending=True, stable=True)), and gates the title at title-rank r with
+ * the content memory at content-rank r and the content at content-rank r with the title memory at title-rank r.  For sequence i of a call,
+ *   pc(i) = order_c[rank_t[i]]   the sequence whose content memory gates title i,
+ *   pt(i) = order_t[rank_c[i]]   the sequence whose title memory gates content i,
+ * and this entry point writes the NEWS of pc(i) and pt(i) for every sequence of every call of the samples first .. first + count - 1:
+ *   pc_hist / pt_hist [count, H] and pc_cand / pt_cand [count], row j = sample first + j.
+ * beh_history int32 [n, H], cand int32 [n], tlen / clen int32 [n_news]: a news' title / content length (ones of its mask with position 0
+ * forced to 1), 0 .. 255.  The range's batches must be the reference's: first is a multiple of batch_size, and the range ends at a batch
+ * boundary or at sample n.  tmp: count * (H + 1) * 2 ints of workspace.  One workgroup of two waves per call, one wave per stream: a counting sort over the 256 length bins whose rank inside a
+ * bin is a prefix count in sequence order (a ballot per length bit, the population count of the lower lanes); integer work only, no atomics:
+ * the output is a pure function of the inputs, to the bit.
+ * NNR_ERR_ARG for a null pointer, H < 1, batch_size < 1, count < 1, first < 0, first % batch_size != 0, first + count > n, a range that
+ * ends inside a batch or n_news < 1; nothing is launched then.  A news id outside 0 .. n_news - 1 counts as length 0 and a length is clamped to 0 .. 255, so no access leaves
+ * the tables; both are the caller's to refuse (ops.cne_pair_triples does). */
+int nnr_cne_pair_triples(const int* beh_history, const int* cand, const int* tlen, const int* clen, long n, int H, int n_news, int batch_size,
+                         long first, long count, int* pc_hist, int* pt_hist, int* pc_cand, int* pt_cand, int* tmp, hipStream_t stream);
 /* Evaluation tail: util.py:50-59 (per-impression ranks by descending score, ties in file order) +
  * evaluate.py:8-29,76-81 (AUC, MRR, nDCG@5, nDCG@10 per impression, float64).  offsets [n_impressions + 1] delimit the
  * (contiguous) candidates of each impression; per_impression [n_impressions, 4]; NaN row for a single-class impression. */

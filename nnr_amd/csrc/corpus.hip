@@ -13,6 +13,8 @@
 //   (seed, epoch, behaviour), written in place into the table corpus_batch_kernel reads.
 // * list_scores_kernel : the click scores of a whole evaluation as one gather (listwise evaluation): sample j's score is the dot product
 //   of row row[j] of the user table and row cand[j] of the news table, one wave per sample.
+// * cne_pair_triples_kernel : the pairing plan of de-duplicated evaluation: for every encoder call of a range of reference batches, the news
+//   whose memories gate each sequence of the call under CNE's rank pairing -- a stable counting sort per call, integers only.
 #include "common.h"
 
 namespace {
@@ -385,6 +387,140 @@ extern "C" int nnr_list_scores(const float* user, long n_user, int ldu, const fl
   const dim3 grid((unsigned)(blocks < LS_GRID_MAX ? blocks : LS_GRID_MAX));
   if (vec) hipLaunchKernelGGL(list_scores_kernel<true>, grid, dim3(256), 0, stream, user, ldu, reps, ldr, row, cand, n, D, scores);
   else hipLaunchKernelGGL(list_scores_kernel<false>, grid, dim3(256), 0, stream, user, ldu, reps, ldr, row, cand, n, D, scores);
+  NNR_CHECK_LAUNCH();
+  return NNR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ CNE pairing plan
+// De-duplicated evaluation of the rank-pairing encoders: which news gate which, for every encoder call of a range of reference batches.
+// Block k < batches plans the history call of batch k (b * H sequences, sequence s * H + h = beh_history[s, h]: contiguous in memory),
+// block batches + k its candidate call (b sequences).  Wave 0 ranks the call by title length, wave 1 by content length: a counting sort
+// over 256 length bins in LDS, three passes of 64 sequences per trip in ascending sequence order --
+//   count    bin[l] = sequences of length l                       (the first lane of every group of equal lengths adds the group's size)
+//   starts   bin[l] = sequences longer than l                     (descending order: a suffix sum, four bins per lane + a shuffle scan)
+//   place    position = bin[l] + equal lengths in lower lanes;    bin[l] += the group's size
+// -- so equal lengths keep their sequence order: torch.sort(descending=True, stable=True).  A group is found with one ballot per length
+// bit; one lane per bin touches the bin and a wave's LDS operations complete in order, so there are no atomics anywhere.  The wave leaves
+// rank[i] in its output row and the news in sorted order in the workspace; after the barrier sequence i picks news_sorted_c[rank_t[i]]
+// and news_sorted_t[rank_c[i]].  Integers only: the same bits on every run.
+namespace {
+constexpr int PT_BINS = 256;
+
+// the valid lanes of this trip whose length equals this lane's
+__device__ __forceinline__ uint64_t same_length_lanes(int l, bool valid) {
+  uint64_t peers = __ballot(valid);
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    const bool bit = (l >> b) & 1;
+    const uint64_t m = __ballot(bit);
+    peers &= bit ? m : ~m;
+  }
+  return peers;
+}
+
+__global__ __launch_bounds__(128) void cne_pair_triples_kernel(const int* __restrict__ hist, const int* __restrict__ cand,
+                                                               const int* __restrict__ tlen, const int* __restrict__ clen, int H, int n_news,
+                                                               int batch_size, long first, long count, int* pc_hist, int* pt_hist,
+                                                               int* pc_cand, int* pt_cand, int* tmp) {
+  __shared__ int bins[2][PT_BINS];
+  const int x = threadIdx.x >> 6, lane = threadIdx.x & 63;          // wave 0: the title stream, wave 1: the content stream
+  const long batches = (count + batch_size - 1) / batch_size;
+  const bool is_cand = (long)blockIdx.x >= batches;
+  const long k = is_cand ? (long)blockIdx.x - batches : (long)blockIdx.x;
+  const long s0 = k * batch_size;                                    // the call's first sample, counted from `first`
+  if (s0 >= count) return;                                           // (block-uniform; the grid is exactly 2 * batches)
+  const int b = (int)(count - s0 < (long)batch_size ? count - s0 : (long)batch_size);
+  const int m = is_cand ? b : b * H;                                 // sequences of the call
+  const int* __restrict__ ids = is_cand ? cand + first + s0 : hist + (first + s0) * H;
+  const long o = is_cand ? s0 : s0 * H;
+  int* pc = (is_cand ? pc_cand : pc_hist) + o;
+  int* pt = (is_cand ? pt_cand : pt_hist) + o;
+  int* ws = is_cand ? tmp + 2 * count * H : tmp;                     // [2][count * H] history calls, then [2][count] candidate calls
+  const long stride = is_cand ? count : count * H;
+  int* sorted_t = ws + o;
+  int* sorted_c = ws + stride + o;
+
+  const int* __restrict__ len = x ? clen : tlen;
+  int* rank_out = x ? pt : pc;                                       // rank_t waits in pc's row, rank_c in pt's
+  int* sorted = x ? sorted_c : sorted_t;
+  volatile int* bin = bins[x];
+  const uint64_t lower = (1ull << lane) - 1ull;
+
+  for (int q = lane; q < PT_BINS; q += 64) bin[q] = 0;
+  __builtin_amdgcn_wave_barrier();
+  for (int base = 0; base < m; base += 64) {                         // count
+    const int i = base + lane;
+    const bool valid = i < m;
+    int l = 0;
+    if (valid) {
+      const int id = ids[i];
+      l = (unsigned)id < (unsigned)n_news ? len[id] : 0;
+      l = l < 0 ? 0 : (l > PT_BINS - 1 ? PT_BINS - 1 : l);
+    }
+    const uint64_t peers = same_length_lanes(l, valid);
+    if (valid && (peers & lower) == 0) bin[l] = bin[l] + __popcll(peers);
+    __builtin_amdgcn_wave_barrier();
+  }
+  {                                                                  // starts: bin[l] = sequences longer than l
+    int h[4], s = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { h[u] = bin[4 * lane + u]; s += h[u]; }
+    int incl = s;                                                    // this lane's bins and every higher lane's
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int v = __shfl_down(incl, d, 64);
+      if (lane + d < 64) incl += v;
+    }
+    const int above = incl - s;
+    __builtin_amdgcn_wave_barrier();
+    bin[4 * lane + 3] = above;
+    bin[4 * lane + 2] = above + h[3];
+    bin[4 * lane + 1] = above + h[3] + h[2];
+    bin[4 * lane + 0] = above + h[3] + h[2] + h[1];
+    __builtin_amdgcn_wave_barrier();
+  }
+  for (int base = 0; base < m; base += 64) {                         // place
+    const int i = base + lane;
+    const bool valid = i < m;
+    int l = 0, id = 0;
+    if (valid) {
+      id = ids[i];
+      l = (unsigned)id < (unsigned)n_news ? len[id] : 0;
+      l = l < 0 ? 0 : (l > PT_BINS - 1 ? PT_BINS - 1 : l);
+    }
+    const uint64_t peers = same_length_lanes(l, valid);
+    const int before = __popcll(peers & lower);
+    int pos = 0;
+    if (valid) pos = bin[l] + before;
+    __builtin_amdgcn_wave_barrier();
+    if (valid && before == 0) bin[l] = pos + __popcll(peers);
+    __builtin_amdgcn_wave_barrier();
+    if (valid) {                                                     // pos < m: the bins were counted from the same lengths
+      rank_out[i] = pos;
+      sorted[pos] = id;
+    }
+  }
+  __threadfence_block();
+  __syncthreads();
+  for (int i = threadIdx.x; i < m; i += 128) {
+    const int rt = pc[i], rc = pt[i];
+    pc[i] = sorted_c[rt];
+    pt[i] = sorted_t[rc];
+  }
+}
+}  // namespace
+
+extern "C" int nnr_cne_pair_triples(const int* beh_history, const int* cand, const int* tlen, const int* clen, long n, int H, int n_news,
+                                    int batch_size, long first, long count, int* pc_hist, int* pt_hist, int* pc_cand, int* pt_cand, int* tmp,
+                                    hipStream_t stream) {
+  if (!beh_history || !cand || !tlen || !clen || !pc_hist || !pt_hist || !pc_cand || !pt_cand || !tmp) return NNR_ERR_ARG;
+  if (H < 1 || n_news < 1 || batch_size < 1 || count < 1 || first < 0 || first % batch_size != 0 || first + count > n ||
+      (first + count < n && count % batch_size != 0))
+    return NNR_ERR_ARG;
+  const long batches = (count + batch_size - 1) / batch_size;
+  if ((long)batch_size * H > 0x7fffffffL || 2 * batches > 0x7fffffffL) return NNR_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(cne_pair_triples_kernel, dim3((unsigned)(2 * batches)), dim3(128), 0, stream, beh_history, cand, tlen, clen, H, n_news,
+                     batch_size, first, count, pc_hist, pt_hist, pc_cand, pt_cand, tmp);
   NNR_CHECK_LAUNCH();
   return NNR_OK;
 }

@@ -63,6 +63,7 @@ const Entry REGISTRY[] = {
   R(nnr_sue_seg_pool_fwd), R(nnr_sue_seg_pool_bwd),
   R(nnr_negative_sample),
   R(nnr_list_scores),
+  R(nnr_cne_pair_triples),
 };
 #undef R
 constexpr int NREG = (int)(sizeof(REGISTRY) / sizeof(REGISTRY[0]));

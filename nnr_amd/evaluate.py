@@ -17,7 +17,7 @@ def dev_corpus(arrays, device, category_num, graph='build', norm='symmetric'):
     return dc
 
 
-LAST_STATS = {}          # filled by compute_scores: how many news rows the news encoder processed (cached vs per-sample form)
+LAST_STATS = {}          # filled by compute_scores: how many news rows the news encoder processed (cached / per-sample / listwise / dedup form)
 
 
 def news_reps_cacheable(model):
@@ -239,6 +239,131 @@ def compute_scores_listwise(model, corpus, sizes, batch_size, candidates_per_row
     return scores
 
 
+# ------------------------------------------------------------------------------------------------ de-duplicated evaluation
+# CNE and CNE_wo_CA gate the title at title-rank r of an encoder call with the content memory (final cell state) at content-rank r of the
+# same call, and the other way round: a representation depends on its batch-mates, so nothing above applies.  But only through TWO of them:
+# with the 'stable' tie order  rep(i) = f(news_i, news_pc(i), news_pt(i)),  pc(i) / pt(i) = the sequence whose content / title memory gates
+# title / content i, and both follow from the per-news lengths and the composition of the call.  So the pairing of every call of the
+# reference's batches is planned on the device (nnr_cne_pair_triples), the memories are computed once per distinct news of the split, and a
+# full representation once per distinct (news, partner, partner) triple of a window of batches -- with the scores of the reference's batches.
+def dedup_refusal(model):
+    """None when compute_scores_dedup can score `model`, else the reason it cannot."""
+    ne, ue = model.news_encoder, model.user_encoder
+    name = type(ne).__name__
+    if not getattr(ne, 'cne_gate', False) or getattr(ne, 'batch_independent', False):
+        return ('de-duplicated evaluation is for the news encoders that pair the sequences of a call by sorted rank (CNE, CNE_wo_CA): %s does '
+                'not (cne_gate) -- %s' % (name, 'its representations are cached per news instead (compute_scores_cached)'
+                                          if getattr(ne, 'batch_independent', False) else 'its dependence on the call is not a pairing'))
+    if getattr(ne, 'tie_order', 'stable') != 'stable':
+        return ('de-duplicated evaluation plans the pairing on the device in the stable order of equal lengths: %s has tie_order=%r, whose '
+                'order is the host sort\'s, call by call' % (name, ne.tie_order))
+    if not hasattr(ue, 'encode_user'):
+        return 'de-duplicated evaluation hands gathered representations to the user encoder: %s has no encode_user' % type(ue).__name__
+    return None
+
+
+def dedup_supported(model):
+    return dedup_refusal(model) is None
+
+
+def news_lengths(corpus):
+    """(tlen, clen) int32 [news]: the ones of every news' title / abstract mask with position 0 forced to 1 (newsEncoders.py:108-109)."""
+    out = []
+    for k in ('news_title_mask', 'news_abstract_mask'):
+        m = corpus.t[k] != 0
+        out.append((m.sum(dim=1) + (~m[:, 0]).long()).to(torch.int32).contiguous())
+    return tuple(out)
+
+
+def _news_fields(t, sel):
+    """The encoder inputs of the news `sel` as ONE call of len(sel) sequences: [1, n, ...] copies (the encoder fixes its masks in place)."""
+    f = lambda k: t[k][sel].unsqueeze(0).contiguous()
+    return (f('news_title_text'), f('news_title_mask'), f('news_abstract_text'), f('news_abstract_mask'), f('news_category'),
+            f('news_subCategory'))
+
+
+@torch.no_grad()
+def compute_scores_dedup(model, corpus, batch_size, window=64, chunk=4096):
+    """The scores of compute_scores(model, corpus, batch_size, cache=False) -- the reference's batches of `batch_size` consecutive samples,
+    its pairing inside every encoder call -- with every distinct news' memories computed once per split and every distinct
+    (news, partner, partner) triple encoded once per window of `window` batches, in calls of up to `chunk` sequences.  Exact up to the
+    regrouping of the products' rows.  Refused (NnrHipError naming the reason, dedup_refusal) for every model but CNE / CNE_wo_CA with the
+    stable tie order and a user encoder that has encode_user."""
+    from . import ops
+    from . import news_encoders as NE
+    from .model import _DotProductFn
+    why = dedup_refusal(model)
+    if why is not None:
+        raise L.NnrHipError(why)
+    if window < 1:
+        raise ValueError('compute_scores_dedup: window=%d' % window)
+    if corpus.t['news_title_mask'].shape[0] ** 3 >= 2 ** 63:
+        raise L.NnrHipError('compute_scores_dedup packs a triple of news ids into one int64 word: %d news are too many' % corpus.t['news_title_mask'].shape[0])
+    ne, ue = model.news_encoder, model.user_encoder
+    t, dev = corpus.t, corpus.device
+    hist, cand = t['beh_history'].contiguous(), corpus.samples[:, 0].contiguous()
+    n, H = hist.shape
+    V = t['news_title_mask'].shape[0]
+    tlen, clen = news_lengths(corpus)
+    was_training = model.training
+    model.eval()
+    try:
+        # the memories (final cell states of both streams) of every distinct news: they depend on the news alone
+        used = torch.unique(torch.cat([hist.reshape(-1), cand]).long())
+        U, H2 = used.numel(), 2 * ne.hidden_dim
+        row_of = torch.full((V,), -1, device=dev, dtype=torch.int32)
+        row_of[used] = torch.arange(U, device=dev, dtype=torch.int32)
+        mem_t, mem_c = (torch.empty((U, H2), device=dev, dtype=torch.float32) for _ in range(2))
+        for s in range(0, U, chunk):
+            sel = used[s:s + chunk]
+            sv = NE._cne_fwd_pre_and_lstm(ne, *_news_fields(t, sel), None)
+            for mem, st in zip((mem_t, mem_c), sv['streams']):
+                mem[s:s + sel.numel()] = st['cn'][st['plan'].rank.long()]             # cn is stored by sorted rank
+        scores = torch.zeros(n, device=dev, dtype=torch.float32)
+        need_graph = getattr(ue, 'needs_history_graph', False)
+        triples = windows = 0
+        span = window * batch_size
+        for w0 in range(0, n, span):
+            cnt = min(span, n - w0)
+            pc_h, pt_h, pc_c, pt_c = ops.cne_pair_triples(hist, cand, tlen, clen, batch_size, w0, cnt, check=w0 == 0)
+            own = torch.cat([hist[w0:w0 + cnt].reshape(-1), cand[w0:w0 + cnt]]).long()
+            key = torch.stack([own, torch.cat([pc_h.reshape(-1), pc_c]).long(), torch.cat([pt_h.reshape(-1), pt_c]).long()], dim=1)
+            word, inv = torch.unique((key[:, 0] * V + key[:, 1]) * V + key[:, 2], return_inverse=True)      # one sortable word per triple
+            trip = torch.stack([word // (V * V), word // V % V, word % V], dim=1)
+            T = trip.shape[0]
+            reps = torch.empty((T, ne.news_embedding_dim), device=dev, dtype=torch.float32)
+            for s in range(0, T, chunk):
+                part = trip[s:s + chunk]
+                sv = NE._cne_fwd_pre_and_lstm(ne, *_news_fields(t, part[:, 0]), None)
+                pt_, pc_ = sv['streams'][0]['plan'], sv['streams'][1]['plan']
+                # the title at sorted position s is sequence order_t[s]: gated by the content memory of its triple's second news
+                sv['cn_override'] = ((mem_c, row_of[part[:, 1]][pt_.order.long()].contiguous()),
+                                     (mem_t, row_of[part[:, 2]][pc_.order.long()].contiguous()))
+                rep, _ = NE._cne_fwd_post(ne, sv, False)
+                reps[s:s + part.shape[0]] = rep.view(part.shape[0], -1)
+            slot_h, slot_c = inv[:cnt * H].view(cnt, H), inv[cnt * H:]
+            for start in range(w0, w0 + cnt, batch_size):                            # users and scores: as compute_scores_cached, batch by batch
+                e = min(start + batch_size, w0 + cnt)
+                idx = torch.arange(start, e, device=dev)
+                h = reps[slot_h[start - w0:e - w0]]                                   # [b, H, D]
+                c = reps[slot_c[start - w0:e - w0]].unsqueeze(1)                      # [b, 1, D]
+                hmask = t['beh_history_mask'][idx]
+                graph = cmask = cidx = None
+                if need_graph:
+                    from .corpus import history_graph
+                    graph, cmask, cidx = history_graph(t['news_category'][hist[idx].long()].contiguous(), hmask.contiguous(), corpus.category_num,
+                                                       corpus.norm_name)
+                extra = (model.user_rows(t['beh_user'][idx].long()),) if getattr(ue, 'needs_user_embedding', False) else ()
+                user = ue.encode_user(h, hmask, graph, cmask, cidx, c, *extra)
+                scores[start:e] = _DotProductFn.apply(user, c).squeeze(dim=1)
+            triples += T
+            windows += 1
+    finally:
+        model.train(was_training)
+    LAST_STATS.update(mode='dedup', triples=int(triples), distinct_news=int(U), per_sample_rows=int(n * (H + 1)), windows=int(windows))
+    return scores
+
+
 def rank_metrics(scores, labels, sizes):
     """scores float32 [n], labels uint8/bool [n], sizes: candidates per impression (contiguous, file order).
     Returns (ranks int32 [n], per_impression float64 [n_imp, 4], means float64 [4]) -- all device tensors."""
@@ -255,11 +380,15 @@ def rank_metrics(scores, labels, sizes):
     return ranks, per, per.mean(dim=0)
 
 
-def evaluate(model, corpus, labels, sizes, batch_size, listwise=False):
+def evaluate(model, corpus, labels, sizes, batch_size, listwise=False, dedup=False):
     """compute_scores + scoring: -> (auc, mrr, ndcg5, ndcg10) as Python floats, plus the ranks (for the result file).  listwise=True scores
-    each impression as a list (compute_scores_listwise) when the model allows it (listwise_supported), and as without the keyword otherwise."""
+    each impression as a list (compute_scores_listwise) when the model allows it (listwise_supported), and as without the keyword otherwise.
+    dedup=True scores the rank-pairing CNE encoders triple by triple (compute_scores_dedup) when the model allows it (dedup_supported); any
+    other model, a news_reps_cacheable one included, keeps the path it has without the keyword."""
     if listwise and listwise_supported(model):
         scores = compute_scores_listwise(model, corpus, sizes, batch_size)
+    elif dedup and dedup_supported(model):
+        scores = compute_scores_dedup(model, corpus, batch_size)
     else:
         scores = compute_scores(model, corpus, batch_size)
     ranks, _, means = rank_metrics(scores, torch.as_tensor(np.asarray(labels)), sizes)

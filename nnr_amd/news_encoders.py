@@ -351,6 +351,10 @@ def _cne_fwd_post(mod, sv, par=False):
         if sv['union']:
             torch.cuda.current_stream(dev).wait_stream(sv['pm_stream'])
         sts[0]['pm'], sts[1]['pm'] = sv['pm'] if sv['union'] else sv.get('pm_override', (None, None))
+    # cn_override (de-duplicated evaluation, evaluate.compute_scores_dedup): ((content memories [U, 2H], row per TITLE sorted position),
+    # (title memories [U, 2H], row per CONTENT sorted position)) -- the gate reads its partner's memory from a table of the split's
+    # distinct news instead of this call's own cn.  Forward only: set by that one caller on a call it made itself, never saved.
+    cn_override = sv.get('cn_override') if gate else None
     # without the cross pools the self pools' vectors ARE the representation's leading columns: pooled straight into them
     rep = None if cross else torch.empty((n, D), **f32)
 
@@ -377,7 +381,12 @@ def _cne_fwd_post(mod, sv, par=False):
             st['Ht'] = st['hout']                        # the attention pools read the raw Bi-LSTM rows
             return self_pool(st, col0)
         # title_M(sorted_content_m): both indexed by sorted RANK (newsEncoders.py:128-129)
-        st['mproj'] = ops.linear_fwd(other['cn'], st['Mlin'].weight, st['Mlin'].bias, **({} if st['pm'] is None else {'a_idx': st['pm']}))
+        if cn_override is not None:
+            table, rows = cn_override[0 if st is sts[0] else 1]
+            st['mproj'] = torch.empty((n, H2), **f32)
+            ops.gemm(table, st['Mlin'].weight, st['mproj'], M=n, N=H2, K=H2, lda=table.stride(0), ldb=H2, ldc=H2, bias=st['Mlin'].bias, a_idx=rows)
+        else:
+            st['mproj'] = ops.linear_fwd(other['cn'], st['Mlin'].weight, st['Mlin'].bias, **({} if st['pm'] is None else {'a_idx': st['pm']}))
         st['G'] = torch.empty((cap, H2), **f32)
         st['Ht'] = torch.empty((cap, H2), **f32)
         ops.gemm(st['hout'], st['Hlin'].weight, st['Ht'], M=cap, N=H2, K=H2, lda=H2, ldb=H2, ldc=H2, dyn=plan.total, dyn_dim=1,

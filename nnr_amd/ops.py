@@ -1397,6 +1397,41 @@ def list_scores(user, reps, row, cand, scores=None, check=True):
     return scores
 
 
+def cne_pair_triples(hist, cand, tlen, clen, batch_size, first=0, count=None, check=True):
+    """The pairing plan of the rank-pairing CNE encoders for the reference batches of the samples first .. first + count - 1
+    (nnr_cne_pair_triples, include/nnr_hip.h): hist int32 [n, H], cand int32 [n], tlen / clen int32 [news] ->
+    (pc_hist, pt_hist) int32 [count, H] and (pc_cand, pt_cand) int32 [count]: the news whose content memory gates the title, and whose
+    title memory gates the content, of every history slot / candidate.  The range is whole reference batches: `first` is a multiple of batch_size
+    and the range ends at a batch boundary or with the split.  check=True reads the
+    ranges of the ids and lengths back (one sync) and raises before the launch; a caller that plans many windows checks once."""
+    i32 = torch.int32
+    if hist.dim() != 2 or cand.dim() != 1 or cand.numel() != hist.shape[0] or tlen.dim() != 1 or clen.numel() != tlen.numel():
+        raise L.NnrHipError('cne_pair_triples: hist [n, H], cand [n] and two length tables of one size')
+    if any(x.dtype != i32 or not x.is_contiguous() for x in (hist, cand, tlen, clen)):
+        raise L.NnrHipError('cne_pair_triples: hist, cand, tlen and clen must be contiguous int32 tensors')
+    n, H = hist.shape
+    count = n - first if count is None else count
+    if batch_size < 1 or H < 1 or count < 1 or first < 0 or first % batch_size or first + count > n or (first + count < n and count % batch_size):
+        raise L.NnrHipError('cne_pair_triples: samples %d .. %d of %d in batches of %d (the range starts and ends at a batch boundary inside the split)'
+                            % (first, first + count - 1, n, batch_size))
+    if check:
+        _p(hist), _p(cand), _p(tlen), _p(clen)
+        lo_h, hi_h, lo_c, hi_c, lo_t, hi_t, lo_l, hi_l = torch.stack(torch.aminmax(hist) + torch.aminmax(cand) + torch.aminmax(tlen)
+                                                                       + torch.aminmax(clen)).tolist()
+        if min(lo_h, lo_c) < 0 or max(hi_h, hi_c) >= tlen.numel():
+            raise L.NnrHipError('cne_pair_triples: news ids %d..%d for %d news' % (min(lo_h, lo_c), max(hi_h, hi_c), tlen.numel()))
+        if min(lo_t, lo_l) < 0 or max(hi_t, hi_l) > 255:
+            raise L.NnrHipError('cne_pair_triples: lengths %d..%d outside the 256 bins of the counting sort' % (min(lo_t, lo_l), max(hi_t, hi_l)))
+    out = torch.empty(2 * count * (H + 1), device=hist.device, dtype=i32)
+    tmp = torch.empty(2 * count * (H + 1), device=hist.device, dtype=i32)
+    pc_h, pt_h = out[:count * H].view(count, H), out[count * H:2 * count * H].view(count, H)
+    pc_c, pt_c = out[2 * count * H:2 * count * H + count], out[2 * count * H + count:]
+    L.check(L.lib().nnr_cne_pair_triples(_p(hist), _p(cand), _p(tlen), _p(clen), n, H, tlen.numel(), batch_size, first, count, _p(pc_h), _p(pt_h),
+                                         _p(pc_c), _p(pt_c), _p(tmp), _s()), 'nnr_cne_pair_triples',
+            unsupported='batch_size * H or the number of calls beyond 2^31')
+    return pc_h, pt_h, pc_c, pt_c
+
+
 def nls_loss(logits, B, N, loss, dlogits):
     L.check(L.lib().nnr_nls_loss(_p(logits), B, N, _p(loss), _p(dlogits), _s()), 'nnr_nls_loss')
 

@@ -194,12 +194,13 @@ def _refuse(config, train=None):
 
 
 # ------------------------------------------------------------------------------------------------ train
-def fit(model, config, train, dev, dirs, run_index=None, trainer=None, listwise=False, on_step=None, log=print):
+def fit(model, config, train, dev, dirs, run_index=None, trainer=None, listwise=False, on_step=None, log=print, dedup=False):
     """Trainer.train (trainer.py:74-196) on the device.  `train`: a DeviceCorpus with impression lists (set_impressions); `dev`: a Split with
     labels; `dirs`: RunDirs.  Per epoch e = 1 .. config.epoch: redraw the negatives in place (sample_negatives(e)), visit the behaviours in
     dp.sampler_indices(n, 0, 1, e) order in batches of config.batch_size (the last one short), evaluate the dev split at batch_size * 3 // 2,
     write its rank file, and on improvement (Selection) the '#<run>-dev' line and the epoch's checkpoint; leave on Selection.stop.  Afterwards
     the dev log, the best model's copy and the flag values.  on_step(e, step, trainer) is called after every step (steps count from 1).
+    listwise / dedup: evaluate()'s keywords (the opt-in evaluation forms; a model neither applies to keeps its path).
     -> RunResult."""
     _refuse(config, train)
     from .trainer import Trainer
@@ -226,7 +227,7 @@ def fit(model, config, train, dev, dirs, run_index=None, trainer=None, listwise=
                 on_step(e, step, trainer)
         losses.append(float(total) / n)                                         # the epoch's one read-back (trainer.py:122)
         log('Epoch %d : train done\nloss = %s' % (e, losses[-1]))
-        m, ranks = E.evaluate(model, dev.corpus, dev.labels, dev.sizes, B * 3 // 2, listwise=listwise)
+        m, ranks = E.evaluate(model, dev.corpus, dev.labels, dev.sizes, B * 3 // 2, listwise=listwise, dedup=dedup)
         E.write_result_file(os.path.join(res_dir, '%s-%d.txt' % (name, e)), ranks, dev.sizes.tolist())
         metrics.append(m)
         log('Epoch %d : dev done\nDev criterions\nAUC = %.4f\nMRR = %.4f\nnDCG@5 = %.4f\nnDCG@10 = %.4f' % ((e,) + m))
