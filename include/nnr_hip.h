@@ -640,6 +640,29 @@ int nnr_negative_sample(const int* clicks, const long* neg_offsets, const int* n
  * are trusted: row[j] in 0 .. n_user - 1 and cand[j] in 0 .. n_reps - 1 are the caller's to check (ops.list_scores does). */
 int nnr_list_scores(const float* user, long n_user, int ldu, const float* reps, long n_reps, int ldr, const int* row, const int* cand,
                     long n, int D, float* scores, hipStream_t stream);
+/* Top-K recommendation: for every user row the K eligible news rows of the largest inner products, without a
+ * [n_user, n_reps] score buffer.  user [n_user, D] with row stride ldu >= D, reps [n_reps, D] with row stride ldr >= D.  News row r is
+ * ELIGIBLE for user u when (valid is NULL or valid[r] != 0) and r does not occur in exclude[u * ld_ex + 0 .. E) (exclude NULL or E = 0:
+ * no list; entries outside 0 .. n_reps - 1 are ignored, so -1 pads a list; duplicates are allowed).
+ *   score(u, r) = sum_d user[u * ldu + d] * reps[r * ldr + d]
+ * idx [n_user, K] / score [n_user, K]: the eligible rows of the largest scores, by score descending, equal scores by ascending row,
+ * ties at the cut broken the same way; score[u, k] is the value computed for idx[u, k].  With fewer than K eligible rows the tail is
+ * idx = -1, score = -inf.  The inputs are finite by contract (a NaN or an infinity in either table makes the order undefined).
+ * Summation order: ONE chain  acc = fmaf(user[u, d], reps[r, d], acc)  over d = 0, 1, .., D - 1 from acc = +0 (the exact-fp32 matrix
+ * instruction v_mfma_f32_32x32x2_f32 is this chain, two steps per instruction; the zero-filled tail of the last slab of 32 leaves it as it
+ * is).  So score(u, r) is a pure function of the two rows, to the bit, wherever they stand in their tables and whatever n_user, n_reps, the
+ * strides, the alignment (16-byte loads when D, ldu and ldr are multiples of 4 and both tables are 16-byte aligned, 4-byte loads otherwise)
+ * and the number of news splits of the launch; the selection is a function of the scores and rows alone.  No atomics, no order that depends
+ * on which workgroup finishes first.  Launches with few user rows split the news over several workgroups per 64 users, which leave
+ * partial lists [n_user, splits, K] in `workspace`; a second launch merges them.  nnr_topk_workspace_bytes (host only, no launch) is the
+ * size that needs, 0 when the launch does not split (workspace may be NULL then) and 0 for sizes nnr_topk_scores refuses.
+ * NNR_ERR_UNSUPPORTED for K > 64 (a list is one entry per lane) or n_reps >= 2^31.  NNR_ERR_ARG, with nothing launched, for a null user,
+ * reps, idx or score, n_user < 1, n_reps < 1, D < 1, K < 1, ldu < D, ldr < D, E < 0, ld_ex < E, E > 0 with a null list, or a workspace that
+ * is smaller than nnr_topk_workspace_bytes says (or null, or not 4-byte aligned, when that is not 0). */
+size_t nnr_topk_workspace_bytes(long n_user, long n_reps, int K);
+int nnr_topk_scores(const float* user, long n_user, int ldu, const float* reps, long n_reps, int ldr, int D, const uint8_t* valid,
+                    const int* exclude, int E, int ld_ex, int K, int* idx, float* score, void* workspace, long workspace_bytes,
+                    hipStream_t stream);
 /* De-duplicated evaluation of the rank-pairing CNE encoders: the pairing plan of every encoder call of a range of
  * reference batches, in one launch.  The reference scores dev samples in batches of batch_size consecutive samples (the last one short) and
  * runs two encoder calls per batch of b samples: the candidate call over the b sequences cand[s] and the history call over the b * H

@@ -12,7 +12,7 @@ objs=""
 # incremental: a source is recompiled when it, any header here or the public header is newer than its object (NNR_BUILD_FORCE=1: everything);
 # what was compiled and what was kept is printed, so a caller can see which it got
 newest_h=$(ls -t *.h ../../include/nnr_hip.h | head -1)
-for f in gemm seq_plan lstm pool misc mhsa corpus dp gcn tape fuse sort cand_attn omap pers_attn kcnn hdc fim gru naml dssm sue_cluster bag; do
+for f in gemm seq_plan lstm pool misc mhsa corpus dp gcn tape fuse sort cand_attn omap pers_attn kcnn hdc fim gru naml dssm sue_cluster topk bag; do
   [ -f $f.hip ] || continue
   objs="$objs build/$f.o"
   if [ "${NNR_BUILD_FORCE}" = "1" ] || [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ $newest_h -nt build/$f.o ]; then

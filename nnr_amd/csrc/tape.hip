@@ -64,6 +64,7 @@ const Entry REGISTRY[] = {
   R(nnr_negative_sample),
   R(nnr_list_scores),
   R(nnr_cne_pair_triples),
+  R(nnr_topk_scores),
 };
 #undef R
 constexpr int NREG = (int)(sizeof(REGISTRY) / sizeof(REGISTRY[0]));

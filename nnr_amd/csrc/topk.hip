@@ -1,0 +1,259 @@
+// Top-K recommendation: idx / score [n_user, K] = the K eligible news rows of the largest inner products
+// <user[u], reps[r]>, without the [n_user, n_reps] score matrix ever reaching global memory.
+//
+// topk_tile_kernel: one workgroup (4 waves) owns a tile of 64 users and a contiguous range of 128-news tiles, which it walks in ascending
+// order.  Per news tile the 64 x 128 scores are accumulated on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32; wave w holds the 32 users
+// (w & 1) x the 64 news (w >> 1) in two accumulators), with the D dimension streamed through LDS in slabs of 32 (k-major images; the
+// next slab travels in registers under the current one's products; the tail of the last slab is zero-filled, which leaves every sum as it is).
+// The finished tile goes to LDS (over the operand images), ineligible positions are overwritten with -inf -- columns beyond n_reps
+// or with valid == 0 as whole columns, the exclusion lists scatter-wise, one store per (user, entry) that falls into the tile -- and each
+// wave folds its 16 users' rows into their running lists: a list is 64 (score, row) entries in LDS, one per lane, sorted by score
+// descending; a score is admitted only when it is strictly greater than the list's K-th entry and goes behind every entry >= it.
+// News ascend, so an earlier (smaller) row wins every tie, inside the list and at the cut.  After the first tiles almost nothing passes
+// the ballot: a user costs one broadcast read, two reads and two compares per tile.
+// Launches with few user tiles split the news tiles over `splits` workgroups per user tile, which leave [n_user, splits, K] partial lists
+// in the workspace; topk_merge_kernel (one wave per user) folds them in (split, k) order with the same admission rule, which is the
+// order (score descending, row ascending) again.  A score is one fmaf chain over d ascending whatever the tile, the split or the load
+// path, and the selection is a function of the scores and rows alone: nothing depends on the launch shape.  No atomics.
+#include <limits.h>
+#include "common.h"
+
+namespace {
+constexpr int TK_TU = 64, TK_TN = 128, TK_KS = 32;         // user tile, news tile, slab of the D dimension
+constexpr int TK_SA = TK_TU + 2, TK_SB = TK_TN + 2;        // k-major image strides: = 2 mod 8, so a slab's stores are at most 2-way on a bank
+constexpr int TK_STAGE = TK_KS * (TK_SA + TK_SB);          // floats of one slab's two operand images (25 KB; the score tile needs 32 KB)
+constexpr int TK_WORKGROUPS_WANTED = 2048;                 // workgroups a launch aims for: 4 rounds of 2 per CU on 256 CUs
+constexpr int TK_MAX_SPLITS = 256;
+
+__host__ __device__ inline int topk_splits(long n_user, long n_reps) {
+  const long ut = (n_user + TK_TU - 1) / TK_TU, nt = (n_reps + TK_TN - 1) / TK_TN;
+  long s = (TK_WORKGROUPS_WANTED + ut - 1) / ut;
+  if (s > nt / 2) s = nt / 2;                               // a split walks at least two tiles: its first slab's latency is paid once
+  if (s > TK_MAX_SPLITS) s = TK_MAX_SPLITS;
+  return (int)(s < 1 ? 1 : s);
+}
+
+// The candidate (s, r) into a list sorted by score descending, one entry per lane: behind every entry >= s, the rest moves down one lane
+// and the last entry falls off.  Wave-uniform s, r and control flow.
+__device__ __forceinline__ void list_insert(float& ls, int& li, float s, int r, int lane) {
+  const int p = __popcll(__ballot(ls >= s));               // the entries >= s are a prefix of the lanes: the list is sorted
+  const float us = __shfl_up(ls, 1, 64);
+  const int ui = __shfl_up(li, 1, 64);
+  if (lane == p) { ls = s; li = r; }
+  else if (lane > p) { ls = us; li = ui; }
+}
+// The candidates c (row cr; lanes of `m`) in ascending lane order, each admitted only if strictly greater than the K-th entry.
+__device__ __forceinline__ void list_admit(float& ls, int& li, unsigned long long m, float c, int cr, int K, int lane) {
+  while (m) {
+    const int src = __ffsll((long long)m) - 1;
+    m &= m - 1;
+    const float s = __shfl(c, src, 64);
+    const int r = __shfl(cr, src, 64);
+    if (s > __shfl(ls, K - 1, 64)) list_insert(ls, li, s, r, lane);
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void topk_tile_kernel(const float* __restrict__ user, long n_user, int ldu, const float* __restrict__ reps,
+                                                        long n_reps, int ldr, int D, const uint8_t* __restrict__ valid,
+                                                        const int* __restrict__ exclude, int E, int ld_ex, int K, long user_tiles,
+                                                        int splits, int* __restrict__ out_idx, float* __restrict__ out_score) {
+  __shared__ float tile[TK_TU * TK_TN];                     // the score tile [user][news]; before that, the slab's operand images
+  __shared__ float lst_s[TK_TU * 64];
+  __shared__ int lst_i[TK_TU * 64];
+  static_assert(TK_STAGE <= TK_TU * TK_TN, "the operand images live inside the score tile");
+  float* As = tile;                                         // [k][TK_SA]: As[k * TK_SA + u]
+  float* Bs = tile + TK_KS * TK_SA;                         // [k][TK_SB]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long ut = blockIdx.x % user_tiles;
+  const int split = (int)(blockIdx.x / user_tiles);
+  const long u0 = ut * TK_TU;
+  const long nt = (n_reps + TK_TN - 1) / TK_TN;
+  const long t_begin = nt * split / splits, t_end = nt * (split + 1) / splits;
+  const int nslab = (D + TK_KS - 1) / TK_KS;
+
+  for (int u = wave * 16; u < wave * 16 + 16; ++u) {        // a wave's lists are its own from here to the end: no barrier guards them
+    lst_s[u * 64 + lane] = -INFINITY;
+    lst_i[u * 64 + lane] = -1;
+  }
+
+  // one slab of both operands, global -> registers: 2048 user floats and 4096 news floats over 256 threads
+  float pre[24];
+  auto gload = [&](long n0, int k0) {
+    if (VEC) {                                              // thread: float4 column kq of rows r, r + 32, ...   (D % 4 == 0)
+      const int kq = tid & 7, r = tid >> 3, k = k0 + 4 * kq;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        const bool is_u = i < 2;
+        const long row = is_u ? u0 + r + 32 * i : n0 + r + 32 * (i - 2);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (k < D && row < (is_u ? n_user : n_reps))
+          v = *reinterpret_cast<const float4*>(is_u ? user + row * ldu + k : reps + row * ldr + k);
+        pre[4 * i] = v.x; pre[4 * i + 1] = v.y; pre[4 * i + 2] = v.z; pre[4 * i + 3] = v.w;
+      }
+    } else {                                                // thread: column k of rows r, r + 8, ...
+      const int kk = tid & 31, r = tid >> 5, k = k0 + kk;
+#pragma unroll
+      for (int i = 0; i < 24; ++i) {
+        const bool is_u = i < 8;
+        const long row = is_u ? u0 + r + 8 * i : n0 + r + 8 * (i - 8);
+        float v = 0.f;
+        if (k < D && row < (is_u ? n_user : n_reps)) v = is_u ? user[row * ldu + k] : reps[row * ldr + k];
+        pre[i] = v;
+      }
+    }
+  };
+  auto lstore = [&]() {
+    if (VEC) {
+      const int kq = tid & 7, r = tid >> 3;
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          if (i < 2) As[(4 * kq + c) * TK_SA + r + 32 * i] = pre[4 * i + c];
+          else Bs[(4 * kq + c) * TK_SB + r + 32 * (i - 2)] = pre[4 * i + c];
+        }
+    } else {
+      const int kk = tid & 31, r = tid >> 5;
+#pragma unroll
+      for (int i = 0; i < 24; ++i) {
+        if (i < 8) As[kk * TK_SA + r + 8 * i] = pre[i];
+        else Bs[kk * TK_SB + r + 8 * (i - 8)] = pre[i];
+      }
+    }
+  };
+
+  const int wu = (wave & 1) * 32, wn = (wave >> 1) * 64;   // this wave's 32 users x 64 news of the tile
+  const int half = lane >> 5, l31 = lane & 31;
+  if (t_begin < t_end) gload(t_begin * TK_TN, 0);
+  for (long t = t_begin; t < t_end; ++t) {
+    const long n0 = t * TK_TN;
+    f32x16 acc0, acc1;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
+    for (int sl = 0; sl < nslab; ++sl) {
+      __syncthreads();                                      // the previous slab's products / the previous tile's selection have read `tile`
+      lstore();
+      __syncthreads();
+      if (sl + 1 < nslab) gload(n0, (sl + 1) * TK_KS);
+      else if (t + 1 < t_end) gload(n0 + TK_TN, 0);
+#pragma unroll
+      for (int s = 0; s < TK_KS / 2; ++s) {                 // A[i = lane & 31][k = lane >> 5], B[k = lane >> 5][j = lane & 31]
+        const int k = 2 * s + half;
+        const float a = As[k * TK_SA + wu + l31];
+        const float b0 = Bs[k * TK_SB + wn + l31], b1 = Bs[k * TK_SB + wn + 32 + l31];
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc1, 0, 0, 0);
+      }
+    }
+    __syncthreads();                                        // every wave is done with the operand images
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {                          // C/D: column = lane & 31, row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5)
+      const int u = wu + (i & 3) + 8 * (i >> 2) + 4 * half;
+      tile[u * TK_TN + wn + l31] = acc0[i];
+      tile[u * TK_TN + wn + 32 + l31] = acc1[i];
+    }
+    __syncthreads();
+    {                                                       // columns out of the pool: thread = column tid & 127 of users (tid >> 7) * 32 ..
+      const int j = tid & 127;
+      const long r = n0 + j;
+      if (r >= n_reps || (valid && valid[r] == 0)) {
+        const int ub = (tid >> 7) * 32;
+        for (int u = ub; u < ub + 32; ++u) tile[u * TK_TN + j] = -INFINITY;
+      }
+    }
+    for (long p = tid; p < (long)TK_TU * E; p += 256) {            // exclusion lists: one store per entry that falls into this tile
+      const int u = (int)(p / E), e = (int)(p - (long)u * E);
+      if (u0 + u < n_user) {
+        const long r = exclude[(u0 + u) * ld_ex + e];
+        if (r >= n0 && r < n0 + TK_TN && r < n_reps) tile[u * TK_TN + (int)(r - n0)] = -INFINITY;
+      }
+    }
+    __syncthreads();
+    for (int u = wave * 16; u < wave * 16 + 16; ++u) {      // wave-uniform
+      if (u0 + u >= n_user) break;
+      const float thr = lst_s[u * 64 + K - 1];
+      const float c0 = tile[u * TK_TN + lane], c1 = tile[u * TK_TN + 64 + lane];
+      const unsigned long long m0 = __ballot(c0 > thr), m1 = __ballot(c1 > thr);
+      if (m0 | m1) {
+        float ls = lst_s[u * 64 + lane];
+        int li = lst_i[u * 64 + lane];
+        list_admit(ls, li, m0, c0, (int)(n0 + lane), K, lane);
+        list_admit(ls, li, m1, c1, (int)(n0 + 64 + lane), K, lane);
+        lst_s[u * 64 + lane] = ls;
+        lst_i[u * 64 + lane] = li;
+      }
+    }
+  }
+  if (lane < K)
+    for (int u = wave * 16; u < wave * 16 + 16; ++u) {
+      if (u0 + u >= n_user) break;
+      const long o = ((u0 + u) * splits + split) * K + lane;
+      out_score[o] = lst_s[u * 64 + lane];
+      out_idx[o] = lst_i[u * 64 + lane];
+    }
+}
+
+// idx / score [n_user, K] from the partial lists [n_user, splits, K]: one wave per user, the entries in (split, k) order
+__global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict__ ws_score, const int* __restrict__ ws_idx, long n_user,
+                                                         int splits, int K, int* __restrict__ idx, float* __restrict__ score) {
+  const int lane = threadIdx.x & 63;
+  const long u = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (u >= n_user) return;                                  // wave-uniform
+  const int n = splits * K;
+  const float* __restrict__ ps = ws_score + u * n;
+  const int* __restrict__ pi = ws_idx + u * n;
+  float ls = -INFINITY;
+  int li = -1;
+  for (int base = 0; base < n; base += 64) {
+    const int e = base + lane;
+    const float c = e < n ? ps[e] : -INFINITY;
+    const int cr = e < n ? pi[e] : -1;
+    const unsigned long long m = __ballot(c > __shfl(ls, K - 1, 64));
+    list_admit(ls, li, m, c, cr, K, lane);
+  }
+  if (lane < K) {
+    score[u * K + lane] = ls;
+    idx[u * K + lane] = li;
+  }
+}
+}  // namespace
+
+extern "C" size_t nnr_topk_workspace_bytes(long n_user, long n_reps, int K) {
+  if (n_user < 1 || n_reps < 1 || K < 1 || K > 64) return 0;
+  const int splits = topk_splits(n_user, n_reps);
+  return splits > 1 ? (size_t)n_user * splits * K * (sizeof(float) + sizeof(int)) : 0;
+}
+
+extern "C" int nnr_topk_scores(const float* user, long n_user, int ldu, const float* reps, long n_reps, int ldr, int D, const uint8_t* valid,
+                               const int* exclude, int E, int ld_ex, int K, int* idx, float* score, void* workspace, long workspace_bytes,
+                               hipStream_t stream) {
+  if (!user || !reps || !idx || !score) return NNR_ERR_ARG;
+  if (n_user < 1 || n_reps < 1 || D < 1 || ldu < D || ldr < D || E < 0 || ld_ex < E || (E > 0 && !exclude) || K < 1) return NNR_ERR_ARG;
+  if (K > 64 || n_reps > INT_MAX) return NNR_ERR_UNSUPPORTED;
+  const int splits = topk_splits(n_user, n_reps);
+  const size_t need = nnr_topk_workspace_bytes(n_user, n_reps, K);
+  if (need > 0 && (!workspace || workspace_bytes < 0 || (size_t)workspace_bytes < need || ((uintptr_t)workspace & 3))) return NNR_ERR_ARG;
+  const long user_tiles = (n_user + TK_TU - 1) / TK_TU;
+  if (user_tiles * splits > INT_MAX || (n_user + 3) / 4 > INT_MAX) return NNR_ERR_UNSUPPORTED;
+  float* ws_score = reinterpret_cast<float*>(workspace);
+  int* ws_idx = reinterpret_cast<int*>(ws_score + (size_t)n_user * splits * K);
+  int* t_idx = splits > 1 ? ws_idx : idx;
+  float* t_score = splits > 1 ? ws_score : score;
+  if (!exclude) E = 0;
+  const bool vec = D % 4 == 0 && ldu % 4 == 0 && ldr % 4 == 0 && al16(user) && al16(reps);
+  const dim3 grid((unsigned)(user_tiles * splits));
+  if (vec)
+    hipLaunchKernelGGL(topk_tile_kernel<true>, grid, dim3(256), 0, stream, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex, K,
+                       user_tiles, splits, t_idx, t_score);
+  else
+    hipLaunchKernelGGL(topk_tile_kernel<false>, grid, dim3(256), 0, stream, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex, K,
+                       user_tiles, splits, t_idx, t_score);
+  NNR_CHECK_LAUNCH();
+  if (splits > 1) {
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((n_user + 3) / 4)), dim3(256), 0, stream, ws_score, ws_idx, n_user, splits, K, idx,
+                       score);
+    NNR_CHECK_LAUNCH();
+  }
+  return NNR_OK;
+}

@@ -17,7 +17,7 @@ def dev_corpus(arrays, device, category_num, graph='build', norm='symmetric'):
     return dc
 
 
-LAST_STATS = {}          # filled by compute_scores: how many news rows the news encoder processed (cached / per-sample / listwise / dedup form)
+LAST_STATS = {}          # filled by compute_scores: how many news rows the news encoder processed (cached / per-sample / listwise / dedup form), or what recommend ranked
 
 
 def news_reps_cacheable(model):
@@ -175,6 +175,31 @@ def _check_lists(t, plan, dev):
 
 
 @torch.no_grad()
+def _user_table(model, corpus, reps, users, hist, hmask, slot_h, slot_cand, batch_size):
+    """The user vectors [R * K, D] of R behaviour rows (users [R], hist int64 [R, H], hmask [R, H]; slot_h [R, H]: the rows of `reps` of the
+    history news), `batch_size` rows per encode_user call.  slot_cand None: one vector per row (candidate_independent encoders, which never
+    read the candidates); int64 [R, K]: the rows of `reps` of K candidates per row, one vector per candidate."""
+    t, dev, ue = corpus.t, corpus.device, model.user_encoder
+    R, D = users.numel(), reps.shape[1]
+    K = 1 if slot_cand is None else slot_cand.shape[1]
+    table = torch.empty((R * K, D), device=dev, dtype=torch.float32)
+    need_graph = getattr(ue, 'needs_history_graph', False)
+    blank = torch.zeros((min(batch_size, R), 1, D), device=dev, dtype=torch.float32) if slot_cand is None else None
+    for s in range(0, R, batch_size):
+        e = min(s + batch_size, R)
+        h = reps[slot_h[s:e]]                                                  # [r, H, D]
+        c = blank[:e - s] if slot_cand is None else reps[slot_cand[s:e]]       # [r, 1, D] (never read) / [r, K, D]
+        m = hmask[s:e].contiguous()
+        graph = cmask = cidx = None
+        if need_graph:
+            from .corpus import history_graph
+            graph, cmask, cidx = history_graph(t['news_category'][hist[s:e]].contiguous(), m, corpus.category_num, corpus.norm_name)
+        extra = (model.user_rows(users[s:e].long()),) if getattr(ue, 'needs_user_embedding', False) else ()
+        table[s * K:e * K] = ue.encode_user(h, m, graph, cmask, cidx, c, *extra).reshape((e - s) * K, D)
+    return table
+
+
+@torch.no_grad()
 def compute_scores_listwise(model, corpus, sizes, batch_size, candidates_per_row=8, dedup_users=True, check=True):
     """One score per dev sample in dataset order, float32 [n] on the device, as compute_scores -- with the user encoder run once per
     impression (candidate_independent encoders; once per distinct (user, history, mask) row with dedup_users) or once per row of
@@ -210,33 +235,92 @@ def compute_scores_listwise(model, corpus, sizes, batch_size, candidates_per_row
             rf = first[torch.from_numpy(plan.row_imp).to(dev)]                      # a row reads its impression's behaviour row
             users, hist, hmask = t['beh_user'][rf], t['beh_history'][rf], t['beh_history_mask'][rf]
             slots = torch.from_numpy(plan.row_slots).to(dev)
-        R, K = users.numel(), plan.K
+        R = users.numel()
         cand = corpus.samples[:, 0].long()
         hist = hist.long()
         used, inv = torch.unique(torch.cat([hist.reshape(-1), cand]), return_inverse=True)
         reps = encode_news_table(model, corpus, used)
         slot_h, slot_c = inv[:hist.numel()].view_as(hist), inv[hist.numel():]
-        D = reps.shape[1]
-        table = torch.empty((R * K, D), device=dev, dtype=torch.float32)
-        need_graph = getattr(ue, 'needs_history_graph', False)
-        blank = torch.zeros((min(batch_size, R), 1, D), device=dev, dtype=torch.float32) if independent else None
-        for s in range(0, R, batch_size):
-            e = min(s + batch_size, R)
-            h = reps[slot_h[s:e]]                                                  # [r, H, D]
-            c = blank[:e - s] if independent else reps[slot_c[slots[s:e]]]         # [r, 1, D] (never read) / [r, K, D]
-            m = hmask[s:e].contiguous()
-            graph = cmask = cidx = None
-            if need_graph:
-                from .corpus import history_graph
-                graph, cmask, cidx = history_graph(t['news_category'][hist[s:e]].contiguous(), m, corpus.category_num, corpus.norm_name)
-            extra = (model.user_rows(users[s:e].long()),) if getattr(ue, 'needs_user_embedding', False) else ()
-            table[s * K:e * K] = ue.encode_user(h, m, graph, cmask, cidx, c, *extra).reshape((e - s) * K, D)
+        table = _user_table(model, corpus, reps, users, hist, hmask, slot_h, None if independent else slot_c[slots], batch_size)
         scores = ops.list_scores(table, reps, row.contiguous(), slot_c.to(torch.int32).contiguous(), check=check)
     finally:
         model.train(was_training)
     LAST_STATS.update(mode='listwise', user_rows=int(R), per_sample_user_rows=int(corpus.num), encoder_rows=int(used.numel()),
                       candidates_per_row=plan.candidates_per_row)
     return scores
+
+
+# ------------------------------------------------------------------------------------------------ top-K recommendation
+# Every form above scores (impression, candidate) pairs that the behaviours file chose.  recommend answers the other question: the K news of
+# a pool that the model ranks highest for a user.  With cacheable news representations, ONE user vector per row and the dot-product head
+# that is [users, D] x [news, D] -> [users, K], which nnr_topk_scores computes without the [users, news] scores ever existing.
+def recommend_refusal(model):
+    """None when recommend can serve `model`, else the reason it cannot."""
+    ne, ue = model.news_encoder, model.user_encoder
+    if getattr(model, 'click_predictor', 'dot_product') != 'dot_product':
+        return ('recommend ranks a pool by inner products of one user vector with the news representations (the dot_product click predictor): '
+                'this model\'s click predictor is %s' % model.click_predictor)
+    if not news_reps_cacheable(model):
+        return LISTWISE_REFUSAL % type(ne).__name__
+    if not getattr(ue, 'candidate_independent', False):
+        return ('recommend needs ONE user vector per behaviour row (candidate_independent: ATT, MHSA, GRU, PUE, SUE_wo_HCA): the user vector of '
+                '%s is a function of the candidate, so a pool-wide search would need one encoder run per (user, news)' % type(ue).__name__)
+    return None
+
+
+def _index_list(what, x, hi, dev):
+    """`x` as an int64 device vector of indices in 0 .. hi - 1 (ValueError otherwise; one sync)."""
+    x = torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).to(device=dev, dtype=torch.int64).reshape(-1)
+    if x.numel() and not (0 <= int(x.min()) and int(x.max()) < hi):
+        raise ValueError('recommend: %s %d..%d outside 0..%d' % (what, int(x.min()), int(x.max()), hi - 1))
+    return x
+
+
+@torch.no_grad()
+def recommend(model, corpus, K, rows=None, pool=None, exclude_history=True, batch_size=256, dedup_users=True, check=True):
+    """(news int64 [R, K], scores float32 [R, K]) on the device: for each of the behaviour rows `rows` of `corpus` (default: all) the K news of
+    `pool` (news indices; default: every news of the corpus but PAD news 0) with the largest click scores, best first, equal scores by
+    ascending position in the sorted table of distinct news (= ascending news index); -1 / -inf where the pool ran out.  exclude_history: a
+    news in a live history slot of the row is not recommended to it.  The distinct news are encoded once, the user encoder runs once per
+    row (once per distinct (user, history, mask) row with dedup_users), and ONE nnr_topk_scores launch ranks the pool.  1 <= K <= 64.
+    Refused (NnrHipError naming the reason, recommend_refusal) for news encoders whose representations cannot be cached, user encoders
+    whose vector depends on the candidate, and any click predictor but dot_product."""
+    from . import ops
+    why = recommend_refusal(model)
+    if why is not None:
+        raise L.NnrHipError(why)
+    t, dev = corpus.t, corpus.device
+    V = t['news_title_mask'].shape[0]
+    rows = torch.arange(t['beh_user'].shape[0], device=dev) if rows is None else _index_list('rows', rows, t['beh_user'].shape[0], dev)
+    pool = torch.arange(1, V, device=dev) if pool is None else torch.unique(_index_list('pool news', pool, V, dev))
+    if rows.numel() < 1:
+        raise ValueError('recommend: no rows')
+    was_training = model.training
+    model.eval()
+    try:
+        users, hist, hmask = t['beh_user'][rows], t['beh_history'][rows], t['beh_history_mask'][rows] != 0
+        back = None
+        if dedup_users:
+            H = hist.shape[1]
+            key, back = torch.unique(torch.cat([users.view(-1, 1), hist.long(), hmask.long()], dim=1), dim=0, return_inverse=True)
+            users, hist, hmask = key[:, 0].contiguous(), key[:, 1:1 + H], key[:, 1 + H:] != 0
+        hist = hist.long()
+        used, inv = torch.unique(torch.cat([hist.reshape(-1), pool]), return_inverse=True)
+        reps = encode_news_table(model, corpus, used)
+        slot_h = inv[:hist.numel()].view_as(hist)
+        table = _user_table(model, corpus, reps, users, hist, hmask, slot_h, None, batch_size)
+        valid = torch.zeros(used.numel(), device=dev, dtype=torch.uint8)
+        valid[inv[hist.numel():]] = 1
+        exclude = torch.where(hmask, slot_h, -1).to(torch.int32).contiguous() if exclude_history else None      # a dead slot is -1
+        idx, scores = ops.topk_scores(table, reps, K, valid=valid, exclude=exclude, check=check)
+        news = torch.where(idx >= 0, used[idx.long().clamp_min(0)], -1)
+        if back is not None:
+            news, scores = news[back], scores[back]
+    finally:
+        model.train(was_training)
+    LAST_STATS.update(mode='recommend', rows=int(rows.numel()), user_rows=int(users.numel()), encoder_rows=int(used.numel()),
+                      pool=int(pool.numel()), K=int(K))
+    return news, scores
 
 
 # ------------------------------------------------------------------------------------------------ de-duplicated evaluation (DESIGN.md section 24)

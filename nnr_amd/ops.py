@@ -1397,6 +1397,66 @@ def list_scores(user, reps, row, cand, scores=None, check=True):
     return scores
 
 
+_TOPK_WS = {}
+
+
+def _topk_ws(dev, nbytes):
+    """Partial-list workspace of the CURRENT stream (nnr_topk_workspace_bytes): the tile launch fills it and the merge launch behind it on
+    the same stream reads it, so the calls of one stream share one buffer, grown when a bigger launch comes along."""
+    if nbytes == 0:
+        return None
+    key = torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device())
+    ws = _TOPK_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
+        _TOPK_WS[key] = ws
+    tape_keep(ws)
+    return ws
+
+
+def topk_scores(user, reps, K, valid=None, exclude=None, check=True):
+    """(idx int32 [n_user, K], score float32 [n_user, K]): for every user row the K eligible rows of `reps` with the largest <user, reps row>,
+    by score descending, equal scores by ascending row; idx = -1 / score = -inf where fewer than K rows are eligible (nnr_topk_scores,
+    include/nnr_hip.h, which states the summation order).  user [n_user, D] and reps [n_reps, D] float32 with unit column stride (any row stride
+    >= D); valid: bool / uint8 [n_reps], nonzero = in the pool, or None; exclude: int32 [n_user, E] (unit column stride) of rows a user must
+    not get, entries outside 0 .. n_reps - 1 (a -1 pad) ignored, or None.  1 <= K <= 64.  The [n_user, n_reps] scores never exist.  The
+    tables are finite by contract: check=True verifies that (two reductions, one sync) and raises before the launch."""
+    if user.dim() != 2 or reps.dim() != 2 or reps.shape[1] != user.shape[1] or user.dtype != torch.float32 or reps.dtype != torch.float32:
+        raise L.NnrHipError('topk_scores: user [n_user, D] and reps [n_reps, D] must be float32 tables of one width')
+    (n_user, D), n_reps = user.shape, reps.shape[0]
+    if n_user < 1 or n_reps < 1 or D < 1 or (D > 1 and (user.stride(1) != 1 or reps.stride(1) != 1)):
+        raise L.NnrHipError('topk_scores: empty input or a table whose columns are not adjacent')
+    if not isinstance(K, int) or K < 1:
+        raise L.NnrHipError('topk_scores: K = %r (an integer from 1 to 64)' % (K,))
+    if valid is not None and (valid.dtype not in (torch.bool, torch.uint8) or valid.dim() != 1 or valid.numel() != n_reps
+                              or not valid.is_contiguous()):
+        raise L.NnrHipError('topk_scores: valid must be a contiguous bool / uint8 vector of one entry per row of reps (%d)' % n_reps)
+    E = ld_ex = 0
+    if exclude is not None:
+        if exclude.dtype != torch.int32 or exclude.dim() != 2 or exclude.shape[0] != n_user or (exclude.shape[1] > 1 and exclude.stride(1) != 1):
+            raise L.NnrHipError('topk_scores: exclude must be int32 [n_user = %d, E] with adjacent columns' % n_user)
+        E = exclude.shape[1]
+        ld_ex = exclude.stride(0) if n_user > 1 else E
+        if E == 0:
+            exclude = None
+        elif ld_ex < E:
+            raise L.NnrHipError('topk_scores: exclude rows overlap (row stride %d for %d entries)' % (ld_ex, E))
+    ldu = user.stride(0) if n_user > 1 else D
+    ldr = reps.stride(0) if n_reps > 1 else D
+    if ldu < D or ldr < D:
+        raise L.NnrHipError('topk_scores: overlapping rows (row strides %d, %d for width %d)' % (ldu, ldr, D))
+    _p(user), _p(reps), _p(valid), _p(exclude)
+    if check and not bool(torch.isfinite(user).all() & torch.isfinite(reps).all()):
+        raise L.NnrHipError('topk_scores: user and reps must be finite (a NaN or an infinity leaves the order undefined)')
+    idx = torch.empty((n_user, K), device=user.device, dtype=torch.int32)
+    score = torch.empty((n_user, K), device=user.device, dtype=torch.float32)
+    nbytes = L.lib().nnr_topk_workspace_bytes(n_user, n_reps, K)
+    ws = _topk_ws(user.device, nbytes)
+    L.check(L.lib().nnr_topk_scores(_p(user), n_user, ldu, _p(reps), n_reps, ldr, D, _p(_u8(valid)), _p(exclude), E, ld_ex, K, _p(idx), _p(score),
+                                    _p(ws), nbytes, _s()), 'nnr_topk_scores', unsupported='K = %d is unsupported beyond 64 (a running list is one entry per lane of a wave), as are 2^31 news rows and more' % K)
+    return idx, score
+
+
 def cne_pair_triples(hist, cand, tlen, clen, batch_size, first=0, count=None, check=True):
     """The pairing plan of the rank-pairing CNE encoders for the reference batches of the samples first .. first + count - 1
     (nnr_cne_pair_triples, include/nnr_hip.h): hist int32 [n, H], cand int32 [n], tlen / clen int32 [news] ->
