@@ -170,8 +170,10 @@ typedef struct nnr_lstm_problem {
   unsigned* sync;     /* optional workspace of nnr_lstm_sync_bytes(n) bytes, ZERO-FILLED ONCE BY THE CALLER before its first launch
                        * and reusable by later launches without clearing (exchange words carry a per-launch epoch; one workspace
                        * must not be shared by two launches that can be in flight together): when every problem of a
-                       * launch has one and H = 200, each 16-sequence tile runs on a PAIR of CUs with W_hh resident in
-                       * registers/LDS, exchanging half of h_t per step; after the launch the 64 bytes at
+                       * launch has one and H is even with 13 unit blocks (194 <= H <= 208; the product's H = 200), each
+                       * 16-sequence tile runs on a PAIR of CUs with W_hh resident in registers/LDS, exchanging half of
+                       * h_t per step (every other H, odd ones included, runs the one-CU kernels and leaves the
+                       * workspace alone); after the launch the 64 bytes at
                        * nnr_lstm_sync_diag_offset(n) hold diagnostics (word 0 = spin-wait time-outs of that launch, must be 0) */
 } nnr_lstm_problem;
 size_t nnr_lstm_sync_bytes(int n);

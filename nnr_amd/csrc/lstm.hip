@@ -1434,7 +1434,9 @@ static int lstm_run(const nnr_lstm_problem* probs, int nprob, int H, bool backwa
     const char* e = getenv("NNR_LSTM_QUAD_T");
     a.quad_T = e ? atoi(e) : (maxn <= 1024 ? 16 : (maxn <= 2048 ? 64 : 96));
   }
-  // 2-CU weights-stationary recurrence when the caller provides the exchange workspace
+  // 2-CU weights-stationary recurrence when the caller provides the exchange workspace: every even H with 13 unit blocks, 194 .. 208
+  // (the pair bodies are instantiated for UB = 13 and use H only as a bound -- unit < H, the partner's real width pw -- and as the row
+  // stride of hout / dh / c_n; tests/test_hip_lstm_gpu.py runs both ends of the interval).  nnr_hip.h and ops.LSTM_PAIR say the same.
   bool pair = UB == 13 && (H % 2 == 0);
   for (int i = 0; i < nprob; ++i) pair = pair && a.p[i].sync != nullptr;
   { const char* e = getenv("NNR_LSTM_PAIR"); if (e && atoi(e) == 0) pair = false; }

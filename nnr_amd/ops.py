@@ -822,7 +822,10 @@ def lstm_unpack_grads(dw_ihp, db_p, dw_hhp, H, E, grads, zero_src=False):
                                           'nnr_lstm_unpack_grads')
 
 
-LSTM_PAIR = os.environ.get('NNR_LSTM_PAIR', '1') != '0'      # 2-CU weights-stationary recurrence (lstm.hip) when H = 200
+# 2-CU weights-stationary recurrence (lstm.hip).  The library takes it for every even H in 194 .. 208 (13 unit blocks) when each problem of a
+# launch carries a `sync` workspace (include/nnr_hip.h); this module hands workspaces out at the product's H = 200 only and passes a caller's
+# own `sync` through untouched at any other H.
+LSTM_PAIR = os.environ.get('NNR_LSTM_PAIR', '1') != '0'
 LAST_LSTM_SYNC = []                                           # exchange workspaces of the last launch (diagnostics)
 _TMO = {}                                                     # per device: persistent exchange time-out counter (uint32 as int32)
 
@@ -899,7 +902,7 @@ def _lstm_flops(items, H):
         tok = sum(float(vals[t.data_ptr()]) if vals is not None else float(t.item()) for t in totals)
         return tok * 2 * (2.0 * H * 4 * H)                                          # tokens x 2 directions x [1,H]x[H,4H]
     flops.dyn = totals
-    flops.scale = 4.0 * H / max(4 * H, -(-H // 16) * 64)      # the kernels multiply NP = ceil(H / 16) x 64 gate columns per direction (H = 200: 832 for 800)
+    flops.scale = 4.0 * H / max(4 * H, -(-H // 16) * 64, 1)   # (H = 0: the entry point refuses the size, not this division)  the kernels multiply NP = ceil(H / 16) x 64 gate columns per direction (H = 200: 832 for 800)
     return flops
 
 
