@@ -665,6 +665,30 @@ size_t nnr_topk_workspace_bytes(long n_user, long n_reps, int K);
 int nnr_topk_scores(const float* user, long n_user, int ldu, const float* reps, long n_reps, int ldr, int D, const uint8_t* valid,
                     const int* exclude, int E, int ld_ex, int K, int* idx, float* score, void* workspace, long workspace_bytes,
                     hipStream_t stream);
+/* Full-pool ranks: where named news rows (targets) land when a user's whole pool is ranked, without a
+ * [n_user, n_reps] score buffer.  user, reps, valid and exclude are nnr_topk_scores' (above), with its eligibility rule and its score.
+ * t_off int32 [n_user + 1], ascending, t_off[0] = 0, t_off[n_user] = n_target; t_news int32 [n_target]: entries t_off[u] .. t_off[u + 1] - 1
+ * are the targets of user row u, given as rows of reps.  A user may have none, many, or one twice.
+ *   t_score[j]   = score(u, t_news[j]), the chain  acc = fmaf(user[u, d], reps[t, d], acc)  over d ascending from +0, computed on its own
+ *                  by a pre-pass; it has the bits of the value the tile walk computes for that pair (and nnr_topk_scores returns);
+ *   pool_size[u] = the number of rows eligible for u;
+ *   ahead[j]     = the number of eligible rows r with score(u, r) > t_score[j], or score(u, r) == t_score[j] and r < t_news[j]: the number
+ *                  of entries nnr_topk_scores places before the target (its position in an unbounded list); -1 when the target is itself
+ *                  ineligible for its user (valid == 0, or in the user's exclusion list).
+ * The inputs are finite by contract; a score that overflows to -inf counts as ineligible in pool_size.  Integer counts of exact
+ * comparisons: nothing depends on n_user, n_reps, the strides, the load path or the number of news splits.  No atomics: a counter belongs
+ * to the one wave that owns its user.  Launches with few user rows split the news as nnr_topk_scores does and leave partial counts
+ * [n_target + n_user, splits] int32 in `workspace`; a second launch adds them in split order.  nnr_pool_rank_workspace_bytes (host only) is
+ * that size, 0 when the launch does not split (workspace may be NULL then) and 0 for sizes nnr_pool_ranks refuses.
+ * NNR_ERR_ARG, with nothing launched, for a null user, reps, t_off or pool_size, n_user < 1, n_reps < 1, D < 1, ldu < D, ldr < D, E < 0,
+ * ld_ex < E, E > 0 with a null list, n_target < 0, n_target > 0 with a null t_news, ahead or t_score, or a workspace that is smaller than
+ * the query says (or null, or not 4-byte aligned, when that is not 0).  NNR_ERR_UNSUPPORTED for 2^31 - 1 user rows and more, n_reps or
+ * n_target >= 2^31, or a grid beyond 2^31 - 1 workgroups.  t_off and t_news are trusted (ops.pool_ranks checks them), but no access leaves
+ * the tables whatever they hold: offsets are clamped into 0 .. n_target, and a target outside 0 .. n_reps - 1 reports ahead = -1 and a NaN score. */
+size_t nnr_pool_rank_workspace_bytes(long n_user, long n_reps, long n_target);
+int nnr_pool_ranks(const float* user, long n_user, int ldu, const float* reps, long n_reps, int ldr, int D, const uint8_t* valid,
+                   const int* exclude, int E, int ld_ex, const int* t_off, const int* t_news, long n_target, int* ahead, float* t_score,
+                   int* pool_size, void* workspace, long workspace_bytes, hipStream_t stream);
 /* De-duplicated evaluation of the rank-pairing CNE encoders: the pairing plan of every encoder call of a range of
  * reference batches, in one launch.  The reference scores dev samples in batches of batch_size consecutive samples (the last one short) and
  * runs two encoder calls per batch of b samples: the candidate call over the b sequences cand[s] and the history call over the b * H

@@ -65,6 +65,7 @@ const Entry REGISTRY[] = {
   R(nnr_list_scores),
   R(nnr_cne_pair_triples),
   R(nnr_topk_scores),
+  R(nnr_pool_ranks),
 };
 #undef R
 constexpr int NREG = (int)(sizeof(REGISTRY) / sizeof(REGISTRY[0]));

@@ -15,6 +15,13 @@
 // in the workspace; topk_merge_kernel (one wave per user) folds them in (split, k) order with the same admission rule, which is the
 // order (score descending, row ascending) again.  A score is one fmaf chain over d ascending whatever the tile, the split or the load
 // path, and the selection is a function of the scores and rows alone: nothing depends on the launch shape.  No atomics.
+//
+// Full-pool ranks (nnr_pool_ranks): the same walk (score_tile_walk, shared by both kernels) with another fold.
+// pool_rank_target_kernel computes each named target's score as the literal fmaf chain, which is the tile's value to the bit, and its
+// eligibility; pool_rank_tile_kernel counts per (user, target) the tile entries that precede the target -- greater, or equal with a
+// smaller row: one compare of 64-bit (score, row) keys -- as the population counts of two ballots, and per user the entries that are not -inf.  A counter is touched by the one
+// wave that owns its user: LDS for the first 2048 targets of a user tile, the counter's own destination in global memory beyond.  With
+// splits the partial counts [n_target + n_user, splits] go through the workspace and pool_rank_merge_kernel adds them in split order.
 #include <limits.h>
 #include "common.h"
 
@@ -53,29 +60,18 @@ __device__ __forceinline__ void list_admit(float& ls, int& li, unsigned long lon
   }
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void topk_tile_kernel(const float* __restrict__ user, long n_user, int ldu, const float* __restrict__ reps,
-                                                        long n_reps, int ldr, int D, const uint8_t* __restrict__ valid,
-                                                        const int* __restrict__ exclude, int E, int ld_ex, int K, long user_tiles,
-                                                        int splits, int* __restrict__ out_idx, float* __restrict__ out_score) {
-  __shared__ float tile[TK_TU * TK_TN];                     // the score tile [user][news]; before that, the slab's operand images
-  __shared__ float lst_s[TK_TU * 64];
-  __shared__ int lst_i[TK_TU * 64];
+// The walk both kernels of this file share: the 64 users from u0 against the news tiles t_begin .. t_end - 1 in ascending order.  For each
+// tile the finished, masked 64 x 128 scores stand in `tile` ([user][news]; -inf over every ineligible position) and fold(n0) is called by
+// all 256 threads behind a barrier; the next tile's first barrier guards `tile` against its readers, so fold needs none of its own.
+template <bool VEC, class Fold>
+__device__ __forceinline__ void score_tile_walk(float* tile, const float* __restrict__ user, long n_user, int ldu, const float* __restrict__ reps,
+                                                long n_reps, int ldr, int D, const uint8_t* __restrict__ valid, const int* __restrict__ exclude,
+                                                int E, int ld_ex, long u0, long t_begin, long t_end, Fold&& fold) {
   static_assert(TK_STAGE <= TK_TU * TK_TN, "the operand images live inside the score tile");
   float* As = tile;                                         // [k][TK_SA]: As[k * TK_SA + u]
   float* Bs = tile + TK_KS * TK_SA;                         // [k][TK_SB]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long ut = blockIdx.x % user_tiles;
-  const int split = (int)(blockIdx.x / user_tiles);
-  const long u0 = ut * TK_TU;
-  const long nt = (n_reps + TK_TN - 1) / TK_TN;
-  const long t_begin = nt * split / splits, t_end = nt * (split + 1) / splits;
   const int nslab = (D + TK_KS - 1) / TK_KS;
-
-  for (int u = wave * 16; u < wave * 16 + 16; ++u) {        // a wave's lists are its own from here to the end: no barrier guards them
-    lst_s[u * 64 + lane] = -INFINITY;
-    lst_i[u * 64 + lane] = -1;
-  }
 
   // one slab of both operands, global -> registers: 2048 user floats and 4096 news floats over 256 threads
   float pre[24];
@@ -132,7 +128,7 @@ __global__ __launch_bounds__(256) void topk_tile_kernel(const float* __restrict_
 #pragma unroll
     for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
     for (int sl = 0; sl < nslab; ++sl) {
-      __syncthreads();                                      // the previous slab's products / the previous tile's selection have read `tile`
+      __syncthreads();                                      // the previous slab's products / the previous tile's fold have read `tile`
       lstore();
       __syncthreads();
       if (sl + 1 < nslab) gload(n0, (sl + 1) * TK_KS);
@@ -170,6 +166,30 @@ __global__ __launch_bounds__(256) void topk_tile_kernel(const float* __restrict_
       }
     }
     __syncthreads();
+    fold(t, n0);
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void topk_tile_kernel(const float* __restrict__ user, long n_user, int ldu, const float* __restrict__ reps,
+                                                        long n_reps, int ldr, int D, const uint8_t* __restrict__ valid,
+                                                        const int* __restrict__ exclude, int E, int ld_ex, int K, long user_tiles,
+                                                        int splits, int* __restrict__ out_idx, float* __restrict__ out_score) {
+  __shared__ float tile[TK_TU * TK_TN];                     // the score tile [user][news]; before that, the slab's operand images
+  __shared__ float lst_s[TK_TU * 64];
+  __shared__ int lst_i[TK_TU * 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long ut = blockIdx.x % user_tiles;
+  const int split = (int)(blockIdx.x / user_tiles);
+  const long u0 = ut * TK_TU;
+  const long nt = (n_reps + TK_TN - 1) / TK_TN;
+  const long t_begin = nt * split / splits, t_end = nt * (split + 1) / splits;
+
+  for (int u = wave * 16; u < wave * 16 + 16; ++u) {        // a wave's lists are its own from here to the end: no barrier guards them
+    lst_s[u * 64 + lane] = -INFINITY;
+    lst_i[u * 64 + lane] = -1;
+  }
+  score_tile_walk<VEC>(tile, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex, u0, t_begin, t_end, [&](long, long n0) {
     for (int u = wave * 16; u < wave * 16 + 16; ++u) {      // wave-uniform
       if (u0 + u >= n_user) break;
       const float thr = lst_s[u * 64 + K - 1];
@@ -184,7 +204,7 @@ __global__ __launch_bounds__(256) void topk_tile_kernel(const float* __restrict_
         lst_i[u * 64 + lane] = li;
       }
     }
-  }
+  });
   if (lane < K)
     for (int u = wave * 16; u < wave * 16 + 16; ++u) {
       if (u0 + u >= n_user) break;
@@ -217,7 +237,188 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
     idx[u * K + lane] = li;
   }
 }
+
+// ------------------------------------------------------------------------------------------------ full-pool ranks
+// ahead[j] = the number of eligible rows that nnr_topk_scores would place before target j of its user, for targets (t_off, t_news) that
+// the caller names: the same walk, with counters where the top-K kernel keeps lists.
+constexpr int PR_CAP = 2048;                               // targets of one 64-user tile whose key and counter live in LDS: 24 KB
+
+// (score, row) as one unsigned number whose order is "score ascending, equal scores by DESCENDING row": the float's bits made monotone (-0
+// first turned into +0, so that scores which compare equal have equal keys) above the complement of the row.  An entry precedes a target
+// exactly when its key is greater.  Finite scores and -inf; rows from 0.
+__device__ __forceinline__ unsigned long long rank_key(float s, int r) {
+  const unsigned b = __float_as_uint(s + 0.f);
+  const unsigned o = b ^ ((unsigned)((int)b >> 31) | 0x80000000u);
+  return ((unsigned long long)o << 32) | (unsigned)~r;
+}
+
+// t_score[j] = the header's chain for (user of j, t_news[j]); ahead[j] = 0 for an eligible target and -1 for an ineligible one (the
+// counters behind it leave a -1 alone).  One thread per target; its user is the last u with t_off[u] <= j.
+__global__ __launch_bounds__(256) void pool_rank_target_kernel(const float* __restrict__ user, long n_user, int ldu, const float* __restrict__ reps,
+                                                               long n_reps, int ldr, int D, const uint8_t* __restrict__ valid,
+                                                               const int* __restrict__ exclude, int E, int ld_ex, const int* __restrict__ t_off,
+                                                               const int* __restrict__ t_news, long n_target, int* __restrict__ ahead,
+                                                               float* __restrict__ t_score) {
+  const long j = (long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n_target) return;
+  long lo = 0, hi = n_user;                                 // t_off[lo] <= j < t_off[hi] (t_off[0] = 0, t_off[n_user] = n_target)
+  while (hi - lo > 1) {
+    const long mid = (lo + hi) >> 1;
+    if (t_off[mid] <= j) lo = mid; else hi = mid;
+  }
+  const long u = lo, r = t_news[j];
+  if (r < 0 || r >= n_reps) {                               // not a row of the table: nothing is read for it
+    t_score[j] = __builtin_nanf("");
+    ahead[j] = -1;
+    return;
+  }
+  const float* __restrict__ a = user + u * ldu;
+  const float* __restrict__ b = reps + r * ldr;
+  float acc = 0.f;
+  for (int d = 0; d < D; ++d) acc = __fmaf_rn(a[d], b[d], acc);
+  if (D % TK_KS) acc = __fmaf_rn(0.f, 0.f, acc);            // the tile's zero-filled tail, literally (it turns a -0 into +0 and nothing else)
+  bool el = !valid || valid[r] != 0;
+  for (int e = 0; e < E; ++e) el = el && exclude[u * ld_ex + e] != (int)r;
+  t_score[j] = acc;
+  ahead[j] = el ? 0 : -1;
+}
+
+// cnt_t[j * splits + split] = the entries of this workgroup's news tiles that precede target j; cnt_u[u * splits + split] = the eligible
+// ones among them.  A tile's targets are the contiguous range t_off[u0] .. t_off[u0 + 64); position p in it has its key and its counter
+// in LDS while p < PR_CAP and works on global memory beyond that: the counter's own destination, read and written by ONE lane of the wave
+// that owns the user, tile after tile.  Without splits the destination of a counter is ahead[j] itself, where the pre-pass left 0 or -1.
+template <bool VEC>
+__global__ __launch_bounds__(256) void pool_rank_tile_kernel(const float* __restrict__ user, long n_user, int ldu, const float* __restrict__ reps,
+                                                             long n_reps, int ldr, int D, const uint8_t* __restrict__ valid,
+                                                             const int* __restrict__ exclude, int E, int ld_ex, long user_tiles, int splits,
+                                                             const int* __restrict__ t_off, const int* __restrict__ t_news,
+                                                             const float* __restrict__ t_score, long n_target, int* cnt_t,
+                                                             int* __restrict__ cnt_u) {
+  __shared__ float tile[TK_TU * TK_TN];
+  __shared__ unsigned long long tg_k[PR_CAP];              // rank_key of the tile's first PR_CAP targets
+  __shared__ int tg_c[PR_CAP];                              // and their counters
+  __shared__ int u_off[TK_TU + 1];                          // the targets of tile user u: u_off[u] .. u_off[u + 1] - 1
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long ut = blockIdx.x % user_tiles;
+  const int split = (int)(blockIdx.x / user_tiles);
+  const long u0 = ut * TK_TU;
+  const long nt = (n_reps + TK_TN - 1) / TK_TN;
+  const long t_begin = nt * split / splits, t_end = nt * (split + 1) / splits;   // never empty: topk_splits gives a split two tiles or more
+
+  if (tid <= TK_TU) {                                       // clamped into 0 .. n_target: whatever t_off holds, no access leaves t_news / t_score
+    const long u = u0 + tid < n_user ? u0 + tid : n_user;
+    const long o = t_off[u];
+    u_off[tid] = (int)(o < 0 ? 0 : (o > n_target ? n_target : o));
+  }
+  __syncthreads();
+  const int tb = __builtin_amdgcn_readfirstlane(u_off[0]);  // (what LDS returns is the same in every lane; said so, the loops below stay scalar)
+  {
+    const int n = min(max(u_off[TK_TU] - tb, 0), PR_CAP);
+    for (int p = tid; p < n; p += 256) {
+      tg_k[p] = rank_key(t_score[tb + p], t_news[tb + p]);
+      tg_c[p] = 0;
+    }
+  }
+  __syncthreads();
+  int psz = 0;                                              // lane l of a wave: the eligible entries of its user wave * 16 + l (l < 16)
+  score_tile_walk<VEC>(tile, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex, u0, t_begin, t_end, [&](long t, long n0) {
+    for (int u = wave * 16; u < wave * 16 + 16; ++u) {      // wave-uniform
+      if (u0 + u >= n_user) break;
+      const float c0 = tile[u * TK_TN + lane], c1 = tile[u * TK_TN + 64 + lane];
+      const unsigned long long k0 = rank_key(c0, (int)(n0 + lane)), k1 = rank_key(c1, (int)(n0 + 64 + lane));
+      const int np = __popcll(__ballot(c0 != -INFINITY)) + __popcll(__ballot(c1 != -INFINITY));
+      if (lane == u - wave * 16) psz += np;
+      const int b = max(__builtin_amdgcn_readfirstlane(u_off[u]) - tb, 0), e = __builtin_amdgcn_readfirstlane(u_off[u + 1]) - tb;
+      for (int base = b; base < e; base += 64) {            // 64 targets at a time, one per lane
+        const int p = base + lane;
+        const bool live = p < e, in_lds = p < PR_CAP;
+        unsigned long long kt = 0;
+        if (live) kt = in_lds ? tg_k[p] : rank_key(t_score[tb + p], t_news[tb + p]);
+        const int hi = (int)(kt >> 32), lo = (int)kt;
+        int cnt = 0;
+        const int m = min(64, e - base);
+        for (int k = 0; k < m; ++k) {                       // target k of the 64, broadcast from its lane; scalar from here to the count
+          const unsigned long long key = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(hi, k) << 32) |
+                                         (unsigned)__builtin_amdgcn_readlane(lo, k);
+          const int c = __popcll(__builtin_amdgcn_ballot_w64(k0 > key)) + __popcll(__builtin_amdgcn_ballot_w64(k1 > key));
+          if (lane == k) cnt = c;
+        }
+        if (live) {
+          if (in_lds) tg_c[p] += cnt;
+          else {
+            int* q = cnt_t + (long)(tb + p) * splits + split;
+            const int a = (splits > 1 && t == t_begin) ? 0 : *q;
+            if (a >= 0) *q = a + cnt;
+          }
+        }
+      }
+    }
+  });
+  if (lane < 16 && u0 + wave * 16 + lane < n_user) cnt_u[(u0 + wave * 16 + lane) * splits + split] = psz;
+  {                                                         // a wave's own counters: no barrier
+    const int b = max(__builtin_amdgcn_readfirstlane(u_off[wave * 16]) - tb, 0), e = min(__builtin_amdgcn_readfirstlane(u_off[wave * 16 + 16]) - tb, PR_CAP);
+    for (int p = b + lane; p < e; p += 64) {
+      int* q = cnt_t + (long)(tb + p) * splits + split;
+      if (splits > 1 || *q >= 0) *q = tg_c[p];
+    }
+  }
+}
+
+// ahead[j] = sum of ws[j, 0 .. splits) unless the pre-pass left -1 there; pool_size[u] = sum of ws[n_target + u, 0 .. splits); split order
+__global__ __launch_bounds__(256) void pool_rank_merge_kernel(const int* __restrict__ ws, long n_target, long n_user, int splits,
+                                                              int* __restrict__ ahead, int* __restrict__ pool_size) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_target + n_user) return;
+  int sum = 0;
+  for (int s = 0; s < splits; ++s) sum += ws[i * splits + s];
+  if (i >= n_target) pool_size[i - n_target] = sum;
+  else if (ahead[i] >= 0) ahead[i] = sum;
+}
 }  // namespace
+
+extern "C" size_t nnr_pool_rank_workspace_bytes(long n_user, long n_reps, long n_target) {
+  if (n_user < 1 || n_reps < 1 || n_target < 0 || n_user >= INT_MAX || n_reps > INT_MAX || n_target > INT_MAX) return 0;
+  const int splits = topk_splits(n_user, n_reps);
+  return splits > 1 ? (size_t)(n_target + n_user) * splits * sizeof(int) : 0;
+}
+
+extern "C" int nnr_pool_ranks(const float* user, long n_user, int ldu, const float* reps, long n_reps, int ldr, int D, const uint8_t* valid,
+                              const int* exclude, int E, int ld_ex, const int* t_off, const int* t_news, long n_target, int* ahead,
+                              float* t_score, int* pool_size, void* workspace, long workspace_bytes, hipStream_t stream) {
+  if (!user || !reps || !pool_size || !t_off) return NNR_ERR_ARG;
+  if (n_user < 1 || n_reps < 1 || D < 1 || ldu < D || ldr < D || E < 0 || ld_ex < E || (E > 0 && !exclude) || n_target < 0) return NNR_ERR_ARG;
+  if (n_target > 0 && (!t_news || !ahead || !t_score)) return NNR_ERR_ARG;
+  if (n_user >= INT_MAX || n_reps > INT_MAX || n_target > INT_MAX) return NNR_ERR_UNSUPPORTED;
+  const int splits = topk_splits(n_user, n_reps);
+  const size_t need = nnr_pool_rank_workspace_bytes(n_user, n_reps, n_target);
+  if (need > 0 && (!workspace || workspace_bytes < 0 || (size_t)workspace_bytes < need || ((uintptr_t)workspace & 3))) return NNR_ERR_ARG;
+  const long user_tiles = (n_user + TK_TU - 1) / TK_TU;
+  if (user_tiles * splits > INT_MAX) return NNR_ERR_UNSUPPORTED;
+  if (!exclude) E = 0;
+  if (n_target > 0) {
+    hipLaunchKernelGGL(pool_rank_target_kernel, dim3((unsigned)((n_target + 255) / 256)), dim3(256), 0, stream, user, n_user, ldu, reps, n_reps,
+                       ldr, D, valid, exclude, E, ld_ex, t_off, t_news, n_target, ahead, t_score);
+    NNR_CHECK_LAUNCH();
+  }
+  int* ws = reinterpret_cast<int*>(workspace);
+  int* cnt_t = splits > 1 ? ws : ahead;
+  int* cnt_u = splits > 1 ? ws + (size_t)n_target * splits : pool_size;
+  const bool vec = D % 4 == 0 && ldu % 4 == 0 && ldr % 4 == 0 && al16(user) && al16(reps);
+  const dim3 grid((unsigned)(user_tiles * splits));
+  if (vec)
+    hipLaunchKernelGGL(pool_rank_tile_kernel<true>, grid, dim3(256), 0, stream, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex,
+                       user_tiles, splits, t_off, t_news, t_score, n_target, cnt_t, cnt_u);
+  else
+    hipLaunchKernelGGL(pool_rank_tile_kernel<false>, grid, dim3(256), 0, stream, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex,
+                       user_tiles, splits, t_off, t_news, t_score, n_target, cnt_t, cnt_u);
+  NNR_CHECK_LAUNCH();
+  if (splits > 1) {
+    hipLaunchKernelGGL(pool_rank_merge_kernel, dim3((unsigned)((n_target + n_user + 255) / 256)), dim3(256), 0, stream, ws, n_target, n_user,
+                       splits, ahead, pool_size);
+    NNR_CHECK_LAUNCH();
+  }
+  return NNR_OK;
+}
 
 extern "C" size_t nnr_topk_workspace_bytes(long n_user, long n_reps, int K) {
   if (n_user < 1 || n_reps < 1 || K < 1 || K > 64) return 0;

@@ -268,12 +268,49 @@ def recommend_refusal(model):
     return None
 
 
-def _index_list(what, x, hi, dev):
+def _index_list(what, x, hi, dev, name='recommend'):
     """`x` as an int64 device vector of indices in 0 .. hi - 1 (ValueError otherwise; one sync)."""
     x = torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).to(device=dev, dtype=torch.int64).reshape(-1)
     if x.numel() and not (0 <= int(x.min()) and int(x.max()) < hi):
-        raise ValueError('recommend: %s %d..%d outside 0..%d' % (what, int(x.min()), int(x.max()), hi - 1))
+        raise ValueError('%s: %s %d..%d outside 0..%d' % (name, what, int(x.min()), int(x.max()), hi - 1))
     return x
+
+
+def _pool_rows(name, corpus, rows, pool):
+    """(rows, pool, V) of recommend / rank_in_pool as int64 device vectors: the behaviour rows (default: all) and the distinct pool news in
+    ascending order (default: every news of the corpus but PAD news 0)."""
+    t, dev = corpus.t, corpus.device
+    V = t['news_title_mask'].shape[0]
+    rows = torch.arange(t['beh_user'].shape[0], device=dev) if rows is None else _index_list('rows', rows, t['beh_user'].shape[0], dev, name)
+    pool = torch.arange(1, V, device=dev) if pool is None else torch.unique(_index_list('pool news', pool, V, dev, name))
+    if rows.numel() < 1:
+        raise ValueError('%s: no rows' % name)
+    return rows, pool, V
+
+
+def _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_users, extra=None):
+    """What recommend and rank_in_pool hand to their launch (model in eval mode): the distinct news of the histories, the pool and `extra`
+    (news indices, may be None) are encoded once into `reps` (row i = news used[i], ascending), the user encoder runs once per row of `rows`
+    (once per distinct (user, history, mask) row with dedup_users) into `table`; valid marks the pool's rows of reps; exclude holds the
+    table rows of the live history slots with -1 in the dead ones (None unless exclude_history).  back: the user row of every entry of
+    `rows` (None: its own position); slot_x: the rows of reps of `extra`."""
+    t, dev = corpus.t, corpus.device
+    users, hist, hmask = t['beh_user'][rows], t['beh_history'][rows], t['beh_history_mask'][rows] != 0
+    back = None
+    if dedup_users:
+        H = hist.shape[1]
+        key, back = torch.unique(torch.cat([users.view(-1, 1), hist.long(), hmask.long()], dim=1), dim=0, return_inverse=True)
+        users, hist, hmask = key[:, 0].contiguous(), key[:, 1:1 + H], key[:, 1 + H:] != 0
+    hist = hist.long()
+    parts = [hist.reshape(-1), pool] + ([] if extra is None else [extra])
+    used, inv = torch.unique(torch.cat(parts), return_inverse=True)
+    reps = encode_news_table(model, corpus, used)
+    slot_h = inv[:hist.numel()].view_as(hist)
+    table = _user_table(model, corpus, reps, users, hist, hmask, slot_h, None, batch_size)
+    valid = torch.zeros(used.numel(), device=dev, dtype=torch.uint8)
+    valid[inv[hist.numel():hist.numel() + pool.numel()]] = 1
+    exclude = torch.where(hmask, slot_h, -1).to(torch.int32).contiguous() if exclude_history else None      # a dead slot is -1
+    return table, reps, used, valid, exclude, back, inv[hist.numel() + pool.numel():]
 
 
 @torch.no_grad()
@@ -289,38 +326,95 @@ def recommend(model, corpus, K, rows=None, pool=None, exclude_history=True, batc
     why = recommend_refusal(model)
     if why is not None:
         raise L.NnrHipError(why)
-    t, dev = corpus.t, corpus.device
-    V = t['news_title_mask'].shape[0]
-    rows = torch.arange(t['beh_user'].shape[0], device=dev) if rows is None else _index_list('rows', rows, t['beh_user'].shape[0], dev)
-    pool = torch.arange(1, V, device=dev) if pool is None else torch.unique(_index_list('pool news', pool, V, dev))
-    if rows.numel() < 1:
-        raise ValueError('recommend: no rows')
+    rows, pool, _ = _pool_rows('recommend', corpus, rows, pool)
     was_training = model.training
     model.eval()
     try:
-        users, hist, hmask = t['beh_user'][rows], t['beh_history'][rows], t['beh_history_mask'][rows] != 0
-        back = None
-        if dedup_users:
-            H = hist.shape[1]
-            key, back = torch.unique(torch.cat([users.view(-1, 1), hist.long(), hmask.long()], dim=1), dim=0, return_inverse=True)
-            users, hist, hmask = key[:, 0].contiguous(), key[:, 1:1 + H], key[:, 1 + H:] != 0
-        hist = hist.long()
-        used, inv = torch.unique(torch.cat([hist.reshape(-1), pool]), return_inverse=True)
-        reps = encode_news_table(model, corpus, used)
-        slot_h = inv[:hist.numel()].view_as(hist)
-        table = _user_table(model, corpus, reps, users, hist, hmask, slot_h, None, batch_size)
-        valid = torch.zeros(used.numel(), device=dev, dtype=torch.uint8)
-        valid[inv[hist.numel():]] = 1
-        exclude = torch.where(hmask, slot_h, -1).to(torch.int32).contiguous() if exclude_history else None      # a dead slot is -1
+        table, reps, used, valid, exclude, back, _ = _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_users)
         idx, scores = ops.topk_scores(table, reps, K, valid=valid, exclude=exclude, check=check)
         news = torch.where(idx >= 0, used[idx.long().clamp_min(0)], -1)
         if back is not None:
             news, scores = news[back], scores[back]
     finally:
         model.train(was_training)
-    LAST_STATS.update(mode='recommend', rows=int(rows.numel()), user_rows=int(users.numel()), encoder_rows=int(used.numel()),
+    LAST_STATS.update(mode='recommend', rows=int(rows.numel()), user_rows=int(table.shape[0]), encoder_rows=int(used.numel()),
                       pool=int(pool.numel()), K=int(K))
     return news, scores
+
+
+# ------------------------------------------------------------------------------------------------ full-pool ranks
+# recommend returns lists; rank_in_pool says how good they are: the place of the news a row actually clicked among the eligible news of the
+# pool, which is the number of entries recommend's list would hold before it -- counted by nnr_pool_ranks without the list, for any depth.
+def clicked_targets(corpus, labels):
+    """(rows, targets) for rank_in_pool: the samples of a dev corpus with label 1 (sample i reads behaviour row i) and their candidates, int64
+    device vectors in sample order."""
+    lab = torch.as_tensor(np.asarray(labels) if not torch.is_tensor(labels) else labels).to(corpus.device).reshape(-1)
+    if lab.numel() != corpus.num:
+        raise ValueError('clicked_targets: %d labels for %d samples' % (lab.numel(), corpus.num))
+    rows = torch.nonzero(lab == 1).reshape(-1)
+    return rows, corpus.samples[rows, 0].long()
+
+
+def pool_rank_metrics(ahead, pool_size, ks=(5, 10)):
+    """The full-ranking metrics of `ahead` / `pool_size` (integer device vectors of one length) as Python numbers, float64 on the device, one
+    read-back.  Over the counted targets (ahead >= 0): hr@k = mean[ahead < k], ndcg@k = mean[ahead < k ? 1 / log2(ahead + 2) : 0],
+    mrr = mean[1 / (ahead + 1)]; percentile = mean[1 - ahead / (pool_size - 1)] over the counted ones with pool_size > 1; counted and skipped
+    are integers.  A mean over nothing is NaN."""
+    counted = ahead >= 0
+    a = ahead.clamp_min(0).to(torch.float64)
+    zero = torch.zeros((), device=ahead.device, dtype=torch.float64)
+    n = counted.sum().to(torch.float64)
+    names, vals = ['counted', 'skipped'], [n, (~counted).sum().to(torch.float64)]
+    for k in ks:
+        hit = counted & (ahead < k)
+        names += ['hr@%d' % k, 'ndcg@%d' % k]
+        vals += [hit.sum().to(torch.float64) / n, torch.where(hit, 1.0 / torch.log2(a + 2.0), zero).sum() / n]
+    ranked = counted & (pool_size > 1)
+    names += ['mrr', 'percentile']
+    vals += [torch.where(counted, 1.0 / (a + 1.0), zero).sum() / n,
+             torch.where(ranked, 1.0 - a / (pool_size.to(torch.float64) - 1.0).clamp_min(1.0), zero).sum() / ranked.sum().to(torch.float64)]
+    out = dict(zip(names, torch.stack(vals).tolist()))
+    out['counted'], out['skipped'] = int(out['counted']), int(out['skipped'])
+    return out
+
+
+@torch.no_grad()
+def rank_in_pool(model, corpus, rows, targets, pool=None, exclude_history=True, ks=(5, 10), batch_size=256, dedup_users=True, check=True):
+    """(ahead int32 [R], pool_size int32 [R], metrics) for the behaviour rows `rows` of `corpus` (repeats allowed) and one target news index per
+    entry of `rows`: ahead[i] = the number of eligible news of `pool` that the model ranks before targets[i] for rows[i] -- the number of
+    entries recommend's list would hold before it, with recommend's pool, history exclusion and tie order --, -1 when the target is itself
+    not eligible for the row (outside the pool, or in a live history slot with exclude_history); pool_size[i] = the row's eligible news.
+    Both on the device, in the order of `rows`.  metrics: pool_rank_metrics over the counted targets, Python numbers.  Other targets of the
+    same row count as ahead of a target when they precede it.  The path is recommend's (news encoded once, the user encoder once per
+    distinct row), followed by ONE nnr_pool_ranks launch; refused for the models recommend refuses, with recommend_refusal's words."""
+    from . import ops
+    why = recommend_refusal(model)
+    if why is not None:
+        raise L.NnrHipError(why)
+    rows, pool, V = _pool_rows('rank_in_pool', corpus, rows, pool)
+    dev = corpus.device
+    targets = _index_list('targets', targets, V, dev, 'rank_in_pool')
+    if targets.numel() != rows.numel():
+        raise ValueError('rank_in_pool: %d targets for %d rows (one target per entry of rows)' % (targets.numel(), rows.numel()))
+    was_training = model.training
+    model.eval()
+    try:
+        table, reps, used, valid, exclude, back, slot_t = _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_users, targets)
+        urow = back if back is not None else torch.arange(rows.numel(), device=dev)
+        order = torch.argsort(urow, stable=True)                                # the targets grouped by user row
+        t_off = torch.zeros(table.shape[0] + 1, device=dev, dtype=torch.int64)
+        t_off[1:] = torch.cumsum(torch.bincount(urow, minlength=table.shape[0]), dim=0)
+        a, _, psz = ops.pool_ranks(table, reps, t_off.to(torch.int32), slot_t[order].to(torch.int32).contiguous(), valid=valid, exclude=exclude,
+                                   check=check)
+        ahead = torch.empty_like(a)
+        ahead[order] = a                                                        # back into the order of `rows`
+        pool_size = psz[urow]
+        metrics = pool_rank_metrics(ahead, pool_size, ks)
+    finally:
+        model.train(was_training)
+    LAST_STATS.update(mode='rank_in_pool', rows=int(rows.numel()), user_rows=int(table.shape[0]), encoder_rows=int(used.numel()),
+                      pool=int(pool.numel()), targets=int(targets.numel()))
+    return ahead, pool_size, metrics
 
 
 # ------------------------------------------------------------------------------------------------ de-duplicated evaluation (DESIGN.md section 24)

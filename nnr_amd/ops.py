@@ -1417,6 +1417,38 @@ def _topk_ws(dev, nbytes):
     return ws
 
 
+def _pool_tables(name, user, reps, valid, exclude):
+    """The argument checks topk_scores and pool_ranks share, before anything is launched: (n_user, n_reps, D, ldu, ldr, exclude, E, ld_ex)."""
+    if user.dim() != 2 or reps.dim() != 2 or reps.shape[1] != user.shape[1] or user.dtype != torch.float32 or reps.dtype != torch.float32:
+        raise L.NnrHipError('%s: user [n_user, D] and reps [n_reps, D] must be float32 tables of one width' % name)
+    (n_user, D), n_reps = user.shape, reps.shape[0]
+    if n_user < 1 or n_reps < 1 or D < 1 or (D > 1 and (user.stride(1) != 1 or reps.stride(1) != 1)):
+        raise L.NnrHipError('%s: empty input or a table whose columns are not adjacent' % name)
+    if valid is not None and (valid.dtype not in (torch.bool, torch.uint8) or valid.dim() != 1 or valid.numel() != n_reps
+                              or not valid.is_contiguous()):
+        raise L.NnrHipError('%s: valid must be a contiguous bool / uint8 vector of one entry per row of reps (%d)' % (name, n_reps))
+    E = ld_ex = 0
+    if exclude is not None:
+        if exclude.dtype != torch.int32 or exclude.dim() != 2 or exclude.shape[0] != n_user or (exclude.shape[1] > 1 and exclude.stride(1) != 1):
+            raise L.NnrHipError('%s: exclude must be int32 [n_user = %d, E] with adjacent columns' % (name, n_user))
+        E = exclude.shape[1]
+        ld_ex = exclude.stride(0) if n_user > 1 else E
+        if E == 0:
+            exclude = None
+        elif ld_ex < E:
+            raise L.NnrHipError('%s: exclude rows overlap (row stride %d for %d entries)' % (name, ld_ex, E))
+    ldu = user.stride(0) if n_user > 1 else D
+    ldr = reps.stride(0) if n_reps > 1 else D
+    if ldu < D or ldr < D:
+        raise L.NnrHipError('%s: overlapping rows (row strides %d, %d for width %d)' % (name, ldu, ldr, D))
+    return n_user, n_reps, D, ldu, ldr, exclude, E, ld_ex
+
+
+def _finite_tables(name, user, reps):
+    if not bool(torch.isfinite(user).all() & torch.isfinite(reps).all()):
+        raise L.NnrHipError('%s: user and reps must be finite (a NaN or an infinity leaves the order undefined)' % name)
+
+
 def topk_scores(user, reps, K, valid=None, exclude=None, check=True):
     """(idx int32 [n_user, K], score float32 [n_user, K]): for every user row the K eligible rows of `reps` with the largest <user, reps row>,
     by score descending, equal scores by ascending row; idx = -1 / score = -inf where fewer than K rows are eligible (nnr_topk_scores,
@@ -1424,33 +1456,12 @@ def topk_scores(user, reps, K, valid=None, exclude=None, check=True):
     >= D); valid: bool / uint8 [n_reps], nonzero = in the pool, or None; exclude: int32 [n_user, E] (unit column stride) of rows a user must
     not get, entries outside 0 .. n_reps - 1 (a -1 pad) ignored, or None.  1 <= K <= 64.  The [n_user, n_reps] scores never exist.  The
     tables are finite by contract: check=True verifies that (two reductions, one sync) and raises before the launch."""
-    if user.dim() != 2 or reps.dim() != 2 or reps.shape[1] != user.shape[1] or user.dtype != torch.float32 or reps.dtype != torch.float32:
-        raise L.NnrHipError('topk_scores: user [n_user, D] and reps [n_reps, D] must be float32 tables of one width')
-    (n_user, D), n_reps = user.shape, reps.shape[0]
-    if n_user < 1 or n_reps < 1 or D < 1 or (D > 1 and (user.stride(1) != 1 or reps.stride(1) != 1)):
-        raise L.NnrHipError('topk_scores: empty input or a table whose columns are not adjacent')
+    n_user, n_reps, D, ldu, ldr, exclude, E, ld_ex = _pool_tables('topk_scores', user, reps, valid, exclude)
     if not isinstance(K, int) or K < 1:
         raise L.NnrHipError('topk_scores: K = %r (an integer from 1 to 64)' % (K,))
-    if valid is not None and (valid.dtype not in (torch.bool, torch.uint8) or valid.dim() != 1 or valid.numel() != n_reps
-                              or not valid.is_contiguous()):
-        raise L.NnrHipError('topk_scores: valid must be a contiguous bool / uint8 vector of one entry per row of reps (%d)' % n_reps)
-    E = ld_ex = 0
-    if exclude is not None:
-        if exclude.dtype != torch.int32 or exclude.dim() != 2 or exclude.shape[0] != n_user or (exclude.shape[1] > 1 and exclude.stride(1) != 1):
-            raise L.NnrHipError('topk_scores: exclude must be int32 [n_user = %d, E] with adjacent columns' % n_user)
-        E = exclude.shape[1]
-        ld_ex = exclude.stride(0) if n_user > 1 else E
-        if E == 0:
-            exclude = None
-        elif ld_ex < E:
-            raise L.NnrHipError('topk_scores: exclude rows overlap (row stride %d for %d entries)' % (ld_ex, E))
-    ldu = user.stride(0) if n_user > 1 else D
-    ldr = reps.stride(0) if n_reps > 1 else D
-    if ldu < D or ldr < D:
-        raise L.NnrHipError('topk_scores: overlapping rows (row strides %d, %d for width %d)' % (ldu, ldr, D))
     _p(user), _p(reps), _p(valid), _p(exclude)
-    if check and not bool(torch.isfinite(user).all() & torch.isfinite(reps).all()):
-        raise L.NnrHipError('topk_scores: user and reps must be finite (a NaN or an infinity leaves the order undefined)')
+    if check:
+        _finite_tables('topk_scores', user, reps)
     idx = torch.empty((n_user, K), device=user.device, dtype=torch.int32)
     score = torch.empty((n_user, K), device=user.device, dtype=torch.float32)
     nbytes = L.lib().nnr_topk_workspace_bytes(n_user, n_reps, K)
@@ -1458,6 +1469,45 @@ def topk_scores(user, reps, K, valid=None, exclude=None, check=True):
     L.check(L.lib().nnr_topk_scores(_p(user), n_user, ldu, _p(reps), n_reps, ldr, D, _p(_u8(valid)), _p(exclude), E, ld_ex, K, _p(idx), _p(score),
                                     _p(ws), nbytes, _s()), 'nnr_topk_scores', unsupported='K = %d is unsupported beyond 64 (a running list is one entry per lane of a wave), as are 2^31 news rows and more' % K)
     return idx, score
+
+
+def pool_ranks(user, reps, t_off, t_news, valid=None, exclude=None, check=True):
+    """(ahead int32 [T], t_score float32 [T], pool_size int32 [n_user]): where the targets land when each user's whole pool is ranked
+    (nnr_pool_ranks, include/nnr_hip.h).  user, reps, valid and exclude as for topk_scores, with its eligibility rule.  t_off: int32
+    [n_user + 1], non-decreasing from 0 to T; t_news: int32 [T], rows of `reps`; entries t_off[u] .. t_off[u + 1] - 1 are the targets of user
+    row u (none, many, repeats).  ahead[j] = the number of eligible rows that topk_scores would place before target j (greater score, or equal
+    score and smaller row), -1 when the target is itself ineligible for its user; t_score[j] = its score, with the bits topk_scores returns;
+    pool_size[u] = the user's eligible rows.  check=True verifies that the tables are finite, t_off is ordered from 0 to T and t_news lies
+    inside the table (reductions on the device, one sync) and raises before the launch."""
+    n_user, n_reps, D, ldu, ldr, exclude, E, ld_ex = _pool_tables('pool_ranks', user, reps, valid, exclude)
+    if (t_off.dtype != torch.int32 or t_news.dtype != torch.int32 or t_off.dim() != 1 or t_news.dim() != 1
+            or not (t_off.is_contiguous() and t_news.is_contiguous())):
+        raise L.NnrHipError('pool_ranks: t_off and t_news must be contiguous int32 vectors')
+    T = t_news.numel()
+    if t_off.numel() != n_user + 1:
+        raise L.NnrHipError('pool_ranks: t_off has %d entries for %d user rows (one more than rows)' % (t_off.numel(), n_user))
+    if check:                                               # three reductions where the tensors live, one read-back
+        bad_off = (t_off[0] != 0) | (t_off[-1] != T) | (t_off[1:] < t_off[:-1]).any()
+        bad_news = ((t_news < 0) | (t_news >= n_reps)).any() if T else torch.zeros_like(bad_off)
+        finite = torch.isfinite(user).all() & torch.isfinite(reps).all()
+        bad_off, bad_news, finite = torch.stack([bad_off.to(user.device), bad_news.to(user.device), finite]).tolist()
+        if bad_off:
+            raise L.NnrHipError('pool_ranks: t_off must be non-decreasing from 0 to the number of targets (%d)' % T)
+        if bad_news:
+            raise L.NnrHipError('pool_ranks: t_news outside 0 .. %d (the rows of reps)' % (n_reps - 1))
+        if not finite:
+            raise L.NnrHipError('pool_ranks: user and reps must be finite (a NaN or an infinity leaves the order undefined)')
+    _p(user), _p(reps), _p(valid), _p(exclude), _p(t_off), _p(t_news)
+    dev = user.device
+    ahead = torch.empty(T, device=dev, dtype=torch.int32)
+    t_score = torch.empty(T, device=dev, dtype=torch.float32)
+    pool_size = torch.empty(n_user, device=dev, dtype=torch.int32)
+    nbytes = L.lib().nnr_pool_rank_workspace_bytes(n_user, n_reps, T)
+    ws = _topk_ws(dev, nbytes)
+    L.check(L.lib().nnr_pool_ranks(_p(user), n_user, ldu, _p(reps), n_reps, ldr, D, _p(_u8(valid)), _p(exclude), E, ld_ex, _p(t_off),
+                                   _p(t_news) if T else None, T, _p(ahead) if T else None, _p(t_score) if T else None, _p(pool_size), _p(ws),
+                                   nbytes, _s()), 'nnr_pool_ranks', unsupported='2^31 user rows, news rows or targets and more are unsupported')
+    return ahead, t_score, pool_size
 
 
 def cne_pair_triples(hist, cand, tlen, clen, batch_size, first=0, count=None, check=True):
