@@ -19,6 +19,7 @@ from . import _lib as L
 from . import functional as Fn
 from . import ops
 from .corpus import NegativeSampler, impression_lists, negative_sampling
+from .evaluate import eval_mode
 from .trainer import FlatParams
 
 
@@ -243,11 +244,9 @@ def compute_scores(model, corpus, batch_size, cache='auto'):
     """One score per (impression, candidate) sample of `corpus`, in dataset order (DSSM_util.py:193-209, N = 1): float32 [n] on the device.
     cache 'auto' / True: every distinct user and every distinct news of the split goes through its tower ONCE (in eval mode both towers
     are functions of the row alone), then each sample is the cosine of two gathered rows; False: the reference's per-sample form."""
-    was_training = model.training
-    model.eval()
     dev, n = corpus.device, corpus.num
     scores = torch.empty(n, device=dev, dtype=torch.float32)
-    with torch.no_grad():
+    with eval_mode(model), torch.no_grad():
         if cache is False:
             for s in range(0, n, batch_size):
                 e = min(s + batch_size, n)
@@ -270,5 +269,4 @@ def compute_scores(model, corpus, batch_size, cache='auto'):
                 logits = torch.empty((e - s, 1), device=dev, dtype=torch.float32)
                 ops.cosine_loss(u, v, e - s, 1, model.feature_dim, logits)
                 scores[s:e] = logits.reshape(-1)
-    model.train(was_training)
     return scores

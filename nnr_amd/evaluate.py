@@ -2,11 +2,14 @@
 (evaluate.py:32-89).  Dev / test samples are (impression, candidate) pairs; the model scores each with news_num = 1
 (util.py:43-50), candidates are ranked inside their impression and AUC / MRR / nDCG@5 / nDCG@10 are averaged over
 impressions.  Batches come from a DeviceCorpus (id-only), scores never leave HBM until the four means are read back."""
+import contextlib
+
 import numpy as np
 import torch
 
 from . import _lib as L
-from .corpus import DeviceCorpus
+from . import ops
+from .corpus import DeviceCorpus, history_graph
 from .ops import _p, _s
 
 
@@ -25,7 +28,18 @@ def news_reps_cacheable(model):
     other news of its encoder call.  True for the MHSA / CNN encoders; NOT for CNE: the reference gates the title at
     title-rank r with the content memory at content-rank r of the SAME call (newsEncoders.py:112-115,128-129), so its
     representations depend on their batch-mates and caching would change the reference's scores."""
-    return getattr(model.news_encoder, 'batch_independent', False) and hasattr(model.user_encoder, 'encode_user')
+    return model.news_encoder.batch_independent and hasattr(model.user_encoder, 'encode_user')
+
+
+@contextlib.contextmanager
+def eval_mode(model):
+    """`model` in eval mode for the body; the mode it had before comes back however the body ends."""
+    was_training = model.training
+    model.eval()
+    try:
+        yield model
+    finally:
+        model.train(was_training)
 
 
 @torch.no_grad()
@@ -43,38 +57,65 @@ def encode_news_table(model, corpus, ids, chunk=4096):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ what the table-driven paths share
+def _split_like(inv, groups):
+    """The inverse of a unique over the concatenated, flattened `groups`, cut back into one tensor per group, each in its group's shape."""
+    out, o = [], 0
+    for g in groups:
+        out.append(inv[o:o + g.numel()].view_as(g))
+        o += g.numel()
+    return out
+
+
+def _news_table(model, corpus, *groups):
+    """(used, reps, slots): the distinct news of the int64 index tensors `groups`, ascending, each encoded once (row i of reps = news used[i]),
+    and per group the rows of reps of its news, in the group's shape."""
+    used, inv = torch.unique(torch.cat([g.reshape(-1) for g in groups]), return_inverse=True)
+    return used, encode_news_table(model, corpus, used), _split_like(inv, groups)
+
+
+def _distinct_rows(users, hist, hmask):
+    """(users int64 [R], hist int64 [R, H], hmask bool [R, H], back int64 [n]): the distinct (user, history, mask) rows of n behaviour rows in
+    sorted order, and for every input row its distinct row."""
+    H = hist.shape[1]
+    key, back = torch.unique(torch.cat([users.view(-1, 1), hist.long(), hmask.long()], dim=1), dim=0, return_inverse=True)
+    return key[:, 0].contiguous(), key[:, 1:1 + H], key[:, 1 + H:] != 0, back
+
+
+def _encoded_users(model, corpus, reps, users, hist, hmask, slot_h, slot_cand, batch_size):
+    """The user encoder over R behaviour rows (users [R], hist [R, H] news indices, hmask [R, H]; slot_h [R, H]: the rows of `reps` of the
+    history news), `batch_size` rows per encode_user call in eval mode: yields (s, e, user [e - s, K, D], c) for rows s .. e - 1.  slot_cand
+    int64 [R, K]: the rows of `reps` of K candidates per row, c = their representations [e - s, K, D]; None: c is a blank [e - s, 1, D] that
+    candidate_independent encoders never read.  Per batch: the gathers, then the graph / cluster inputs for the encoders that read them (SUE
+    and its ablations), then the user rows where the model has a user table (without dropout), then encode_user."""
+    R, ue = users.numel(), model.user_encoder
+    blank = torch.zeros((min(batch_size, R), 1, reps.shape[1]), device=corpus.device, dtype=torch.float32) if slot_cand is None else None
+    for s in range(0, R, batch_size):
+        e = min(s + batch_size, R)
+        h = reps[slot_h[s:e]]                                                  # [r, H, D]
+        c = blank[:e - s] if slot_cand is None else reps[slot_cand[s:e]]       # [r, 1, D] (never read) / [r, K, D]
+        m = hmask[s:e].contiguous()
+        graph = cmask = cidx = None
+        if ue.needs_history_graph:
+            graph, cmask, cidx = history_graph(corpus.t['news_category'][hist[s:e].long()].contiguous(), m, corpus.category_num, corpus.norm_name)
+        rows = model.user_rows(users[s:e].long()) if model.use_user_embedding else None
+        yield s, e, model._encode_user(rows, h, m, graph, cmask, cidx, c), c
+
+
 @torch.no_grad()
 def compute_scores_cached(model, corpus, batch_size):
     """compute_scores for encoders with batch-independent news representations (the reference's README
     lists the missing cache as a known cost, README.md:125): every DISTINCT news of the split is encoded once, a sample's history
     / candidate representations are gathered by news id, and only the user encoder + click predictor run per sample."""
-    assert news_reps_cacheable(model)
-    was_training = model.training
-    model.eval()
-    t, dev = corpus.t, corpus.device
-    hist, cand = t['beh_history'].long(), corpus.samples[:, 0].long()
-    used, inv = torch.unique(torch.cat([hist.reshape(-1), cand]), return_inverse=True)
-    reps = encode_news_table(model, corpus, used)
-    slot_h, slot_c = inv[:hist.numel()].view_as(hist), inv[hist.numel():]
-    scores = torch.zeros(corpus.num, device=dev, dtype=torch.float32)
-    ue = model.user_encoder
     from .model import _DotProductFn
-    need_graph = getattr(ue, 'needs_history_graph', False)     # SUE and its ablations read the graph / cluster inputs
-    for start in range(0, corpus.num, batch_size):
-        idx = torch.arange(start, min(start + batch_size, corpus.num), device=dev)
-        h = reps[slot_h[idx]]                                  # [B, H, D]
-        c = reps[slot_c[idx]].unsqueeze(1)                     # [B, 1, D]
-        hmask = t['beh_history_mask'][idx]
-        graph = cmask = cidx = None
-        if need_graph:
-            from .corpus import history_graph
-            graph, cmask, cidx = history_graph(t['news_category'][hist[idx]].contiguous(), hmask.contiguous(), corpus.category_num, corpus.norm_name)
-        if getattr(ue, 'needs_user_embedding', False):           # (eval mode: the user rows without dropout)
-            user = ue.encode_user(h, hmask, graph, cmask, cidx, c, model.user_rows(t['beh_user'][idx].long()))
-        else:
-            user = ue.encode_user(h, hmask, graph, cmask, cidx, c)
-        scores[start:start + idx.numel()] = _DotProductFn.apply(user, c).squeeze(dim=1)
-    model.train(was_training)
+    assert news_reps_cacheable(model)
+    t = corpus.t
+    hist, cand = t['beh_history'].long(), corpus.samples[:, 0].long()
+    scores = torch.zeros(corpus.num, device=corpus.device, dtype=torch.float32)
+    with eval_mode(model):
+        used, reps, (slot_h, slot_c) = _news_table(model, corpus, hist, cand.view(-1, 1))
+        for s, e, user, c in _encoded_users(model, corpus, reps, t['beh_user'], hist, t['beh_history_mask'], slot_h, slot_c, batch_size):
+            scores[s:e] = _DotProductFn.apply(user, c).squeeze(dim=1)
     LAST_STATS.update(mode='cached', encoder_rows=int(used.numel()), per_sample_rows=int(corpus.num * (hist.shape[1] + 1)))
     return scores
 
@@ -85,15 +126,13 @@ def compute_scores(model, corpus, batch_size, cache='auto'):
     representations when the encoder allows it, see news_reps_cacheable), True, False (the reference's per-sample form)."""
     if cache is True or (cache == 'auto' and news_reps_cacheable(model)):
         return compute_scores_cached(model, corpus, batch_size)
-    was_training = model.training
-    model.eval()
     model.news_encoder.__dict__['_dedup_stats'] = [0, 0]
     scores = torch.zeros(corpus.num, device=corpus.device, dtype=torch.float32)
-    for start in range(0, corpus.num, batch_size):
-        idx = torch.arange(start, min(start + batch_size, corpus.num), device=corpus.device, dtype=torch.int32)
-        batch = corpus.train_batch(idx)                       # candidate fields are [B, 1, ...] = the unsqueeze of util.py:43-48
-        scores[start:start + idx.numel()] = model(*batch).squeeze(dim=1)
-    model.train(was_training)
+    with eval_mode(model):
+        for start in range(0, corpus.num, batch_size):
+            idx = torch.arange(start, min(start + batch_size, corpus.num), device=corpus.device, dtype=torch.int32)
+            batch = corpus.train_batch(idx)                       # candidate fields are [B, 1, ...] = the unsqueeze of util.py:43-48
+            scores[start:start + idx.numel()] = model(*batch).squeeze(dim=1)
     rows = int(corpus.num * (corpus.H + 1))
     enc, of = model.news_encoder.__dict__.get('_dedup_stats', [0, 0])
     # CNE: history slots whose representation is the constant PAD representation are not encoded (news_encoders.cne_history_dedup)
@@ -179,23 +218,11 @@ def _user_table(model, corpus, reps, users, hist, hmask, slot_h, slot_cand, batc
     """The user vectors [R * K, D] of R behaviour rows (users [R], hist int64 [R, H], hmask [R, H]; slot_h [R, H]: the rows of `reps` of the
     history news), `batch_size` rows per encode_user call.  slot_cand None: one vector per row (candidate_independent encoders, which never
     read the candidates); int64 [R, K]: the rows of `reps` of K candidates per row, one vector per candidate."""
-    t, dev, ue = corpus.t, corpus.device, model.user_encoder
     R, D = users.numel(), reps.shape[1]
     K = 1 if slot_cand is None else slot_cand.shape[1]
-    table = torch.empty((R * K, D), device=dev, dtype=torch.float32)
-    need_graph = getattr(ue, 'needs_history_graph', False)
-    blank = torch.zeros((min(batch_size, R), 1, D), device=dev, dtype=torch.float32) if slot_cand is None else None
-    for s in range(0, R, batch_size):
-        e = min(s + batch_size, R)
-        h = reps[slot_h[s:e]]                                                  # [r, H, D]
-        c = blank[:e - s] if slot_cand is None else reps[slot_cand[s:e]]       # [r, 1, D] (never read) / [r, K, D]
-        m = hmask[s:e].contiguous()
-        graph = cmask = cidx = None
-        if need_graph:
-            from .corpus import history_graph
-            graph, cmask, cidx = history_graph(t['news_category'][hist[s:e]].contiguous(), m, corpus.category_num, corpus.norm_name)
-        extra = (model.user_rows(users[s:e].long()),) if getattr(ue, 'needs_user_embedding', False) else ()
-        table[s * K:e * K] = ue.encode_user(h, m, graph, cmask, cidx, c, *extra).reshape((e - s) * K, D)
+    table = torch.empty((R * K, D), device=corpus.device, dtype=torch.float32)
+    for s, e, user, _ in _encoded_users(model, corpus, reps, users, hist, hmask, slot_h, slot_cand, batch_size):
+        table[s * K:e * K] = user.reshape((e - s) * K, D)
     return table
 
 
@@ -206,45 +233,34 @@ def compute_scores_listwise(model, corpus, sizes, batch_size, candidates_per_row
     `candidates_per_row` candidates of one impression (candidate-aware encoders), and ONE nnr_list_scores launch for all scores.
     `sizes`: candidates per impression (contiguous, file order).  check=True verifies that the samples of an impression share their behaviour
     row.  Refused (NnrHipError naming the reason) for encoders whose news representations cannot be cached."""
-    from . import ops
     if not listwise_supported(model):
         raise L.NnrHipError(LISTWISE_REFUSAL % type(model.news_encoder).__name__)
     sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
     if int(sizes.sum()) != corpus.num:
         raise ValueError('listwise evaluation: sizes sum to %d, the corpus holds %d samples' % (int(sizes.sum()), corpus.num))
-    ue = model.user_encoder
-    independent = bool(getattr(ue, 'candidate_independent', False))
+    independent = model.user_encoder.candidate_independent
     plan = list_plan(sizes, None if independent else candidates_per_row)
     t, dev = corpus.t, corpus.device
     if check:
         _check_lists(t, plan, dev)
-    was_training = model.training
-    model.eval()
-    try:
+    with eval_mode(model):
         first = torch.from_numpy(plan.first).to(dev)
         row = torch.from_numpy(plan.row).to(dev)
         if independent:
             users, hist, hmask = t['beh_user'][first], t['beh_history'][first], t['beh_history_mask'][first]
             if dedup_users:
-                H = hist.shape[1]
-                key, inv = torch.unique(torch.cat([users.view(-1, 1), hist.long(), hmask.long()], dim=1), dim=0, return_inverse=True)
-                users, hist, hmask = key[:, 0].contiguous(), key[:, 1:1 + H].to(torch.int32), key[:, 1 + H:] != 0
-                row = inv[torch.from_numpy(plan.imp).to(dev)].to(torch.int32)
+                users, hist, hmask, back = _distinct_rows(users, hist, hmask)
+                row = back[torch.from_numpy(plan.imp).to(dev)].to(torch.int32)
             slots = None
         else:
             rf = first[torch.from_numpy(plan.row_imp).to(dev)]                      # a row reads its impression's behaviour row
             users, hist, hmask = t['beh_user'][rf], t['beh_history'][rf], t['beh_history_mask'][rf]
             slots = torch.from_numpy(plan.row_slots).to(dev)
         R = users.numel()
-        cand = corpus.samples[:, 0].long()
         hist = hist.long()
-        used, inv = torch.unique(torch.cat([hist.reshape(-1), cand]), return_inverse=True)
-        reps = encode_news_table(model, corpus, used)
-        slot_h, slot_c = inv[:hist.numel()].view_as(hist), inv[hist.numel():]
+        used, reps, (slot_h, slot_c) = _news_table(model, corpus, hist, corpus.samples[:, 0].long())
         table = _user_table(model, corpus, reps, users, hist, hmask, slot_h, None if independent else slot_c[slots], batch_size)
         scores = ops.list_scores(table, reps, row.contiguous(), slot_c.to(torch.int32).contiguous(), check=check)
-    finally:
-        model.train(was_training)
     LAST_STATS.update(mode='listwise', user_rows=int(R), per_sample_user_rows=int(corpus.num), encoder_rows=int(used.numel()),
                       candidates_per_row=plan.candidates_per_row)
     return scores
@@ -262,7 +278,7 @@ def recommend_refusal(model):
                 'this model\'s click predictor is %s' % model.click_predictor)
     if not news_reps_cacheable(model):
         return LISTWISE_REFUSAL % type(ne).__name__
-    if not getattr(ue, 'candidate_independent', False):
+    if not ue.candidate_independent:
         return ('recommend needs ONE user vector per behaviour row (candidate_independent: ATT, MHSA, GRU, PUE, SUE_wo_HCA): the user vector of '
                 '%s is a function of the candidate, so a pool-wide search would need one encoder run per (user, news)' % type(ue).__name__)
     return None
@@ -288,29 +304,23 @@ def _pool_rows(name, corpus, rows, pool):
     return rows, pool, V
 
 
-def _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_users, extra=None):
+def _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_users, *extra):
     """What recommend and rank_in_pool hand to their launch (model in eval mode): the distinct news of the histories, the pool and `extra`
-    (news indices, may be None) are encoded once into `reps` (row i = news used[i], ascending), the user encoder runs once per row of `rows`
-    (once per distinct (user, history, mask) row with dedup_users) into `table`; valid marks the pool's rows of reps; exclude holds the
-    table rows of the live history slots with -1 in the dead ones (None unless exclude_history).  back: the user row of every entry of
-    `rows` (None: its own position); slot_x: the rows of reps of `extra`."""
-    t, dev = corpus.t, corpus.device
-    users, hist, hmask = t['beh_user'][rows], t['beh_history'][rows], t['beh_history_mask'][rows] != 0
+    (further vectors of news indices) are encoded once into `reps` (row i = news used[i], ascending), the user encoder runs once per row of
+    `rows` (once per distinct (user, history, mask) row with dedup_users) into `table`; valid marks the pool's rows of reps; exclude holds
+    the table rows of the live history slots with -1 in the dead ones (None unless exclude_history).  back: the user row of every entry of
+    `rows` (None: its own position); slot_x: the rows of reps of each of `extra`."""
+    t = corpus.t
+    users, hist, hmask = t['beh_user'][rows], t['beh_history'][rows].long(), t['beh_history_mask'][rows] != 0
     back = None
     if dedup_users:
-        H = hist.shape[1]
-        key, back = torch.unique(torch.cat([users.view(-1, 1), hist.long(), hmask.long()], dim=1), dim=0, return_inverse=True)
-        users, hist, hmask = key[:, 0].contiguous(), key[:, 1:1 + H], key[:, 1 + H:] != 0
-    hist = hist.long()
-    parts = [hist.reshape(-1), pool] + ([] if extra is None else [extra])
-    used, inv = torch.unique(torch.cat(parts), return_inverse=True)
-    reps = encode_news_table(model, corpus, used)
-    slot_h = inv[:hist.numel()].view_as(hist)
+        users, hist, hmask, back = _distinct_rows(users, hist, hmask)
+    used, reps, (slot_h, slot_p, *slot_x) = _news_table(model, corpus, hist, pool, *extra)
     table = _user_table(model, corpus, reps, users, hist, hmask, slot_h, None, batch_size)
-    valid = torch.zeros(used.numel(), device=dev, dtype=torch.uint8)
-    valid[inv[hist.numel():hist.numel() + pool.numel()]] = 1
+    valid = torch.zeros(used.numel(), device=corpus.device, dtype=torch.uint8)
+    valid[slot_p] = 1
     exclude = torch.where(hmask, slot_h, -1).to(torch.int32).contiguous() if exclude_history else None      # a dead slot is -1
-    return table, reps, used, valid, exclude, back, inv[hist.numel() + pool.numel():]
+    return table, reps, used, valid, exclude, back, slot_x
 
 
 @torch.no_grad()
@@ -322,21 +332,16 @@ def recommend(model, corpus, K, rows=None, pool=None, exclude_history=True, batc
     row (once per distinct (user, history, mask) row with dedup_users), and ONE nnr_topk_scores launch ranks the pool.  1 <= K <= 64.
     Refused (NnrHipError naming the reason, recommend_refusal) for news encoders whose representations cannot be cached, user encoders
     whose vector depends on the candidate, and any click predictor but dot_product."""
-    from . import ops
     why = recommend_refusal(model)
     if why is not None:
         raise L.NnrHipError(why)
     rows, pool, _ = _pool_rows('recommend', corpus, rows, pool)
-    was_training = model.training
-    model.eval()
-    try:
+    with eval_mode(model):
         table, reps, used, valid, exclude, back, _ = _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_users)
         idx, scores = ops.topk_scores(table, reps, K, valid=valid, exclude=exclude, check=check)
         news = torch.where(idx >= 0, used[idx.long().clamp_min(0)], -1)
         if back is not None:
             news, scores = news[back], scores[back]
-    finally:
-        model.train(was_training)
     LAST_STATS.update(mode='recommend', rows=int(rows.numel()), user_rows=int(table.shape[0]), encoder_rows=int(used.numel()),
                       pool=int(pool.numel()), K=int(K))
     return news, scores
@@ -387,7 +392,6 @@ def rank_in_pool(model, corpus, rows, targets, pool=None, exclude_history=True, 
     Both on the device, in the order of `rows`.  metrics: pool_rank_metrics over the counted targets, Python numbers.  Other targets of the
     same row count as ahead of a target when they precede it.  The path is recommend's (news encoded once, the user encoder once per
     distinct row), followed by ONE nnr_pool_ranks launch; refused for the models recommend refuses, with recommend_refusal's words."""
-    from . import ops
     why = recommend_refusal(model)
     if why is not None:
         raise L.NnrHipError(why)
@@ -396,10 +400,8 @@ def rank_in_pool(model, corpus, rows, targets, pool=None, exclude_history=True, 
     targets = _index_list('targets', targets, V, dev, 'rank_in_pool')
     if targets.numel() != rows.numel():
         raise ValueError('rank_in_pool: %d targets for %d rows (one target per entry of rows)' % (targets.numel(), rows.numel()))
-    was_training = model.training
-    model.eval()
-    try:
-        table, reps, used, valid, exclude, back, slot_t = _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_users, targets)
+    with eval_mode(model):
+        table, reps, used, valid, exclude, back, (slot_t,) = _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_users, targets)
         urow = back if back is not None else torch.arange(rows.numel(), device=dev)
         order = torch.argsort(urow, stable=True)                                # the targets grouped by user row
         t_off = torch.zeros(table.shape[0] + 1, device=dev, dtype=torch.int64)
@@ -410,8 +412,6 @@ def rank_in_pool(model, corpus, rows, targets, pool=None, exclude_history=True, 
         ahead[order] = a                                                        # back into the order of `rows`
         pool_size = psz[urow]
         metrics = pool_rank_metrics(ahead, pool_size, ks)
-    finally:
-        model.train(was_training)
     LAST_STATS.update(mode='rank_in_pool', rows=int(rows.numel()), user_rows=int(table.shape[0]), encoder_rows=int(used.numel()),
                       pool=int(pool.numel()), targets=int(targets.numel()))
     return ahead, pool_size, metrics
@@ -428,11 +428,11 @@ def dedup_refusal(model):
     """None when compute_scores_dedup can score `model`, else the reason it cannot."""
     ne, ue = model.news_encoder, model.user_encoder
     name = type(ne).__name__
-    if not getattr(ne, 'cne_gate', False) or getattr(ne, 'batch_independent', False):
+    if not ne.cne_gate or ne.batch_independent:
         return ('de-duplicated evaluation is for the news encoders that pair the sequences of a call by sorted rank (CNE, CNE_wo_CA): %s does '
                 'not (cne_gate) -- %s' % (name, 'its representations are cached per news instead (compute_scores_cached)'
-                                          if getattr(ne, 'batch_independent', False) else 'its dependence on the call is not a pairing'))
-    if getattr(ne, 'tie_order', 'stable') != 'stable':
+                                          if ne.batch_independent else 'its dependence on the call is not a pairing'))
+    if ne.tie_order != 'stable':
         return ('de-duplicated evaluation plans the pairing on the device in the stable order of equal lengths: %s has tie_order=%r, whose '
                 'order is the host sort\'s, call by call' % (name, ne.tie_order))
     if not hasattr(ue, 'encode_user'):
@@ -467,7 +467,6 @@ def compute_scores_dedup(model, corpus, batch_size, window=64, chunk=4096):
     (news, partner, partner) triple encoded once per window of `window` batches, in calls of up to `chunk` sequences.  Exact up to the
     regrouping of the products' rows.  Refused (NnrHipError naming the reason, dedup_refusal) for every model but CNE / CNE_wo_CA with the
     stable tie order and a user encoder that has encode_user."""
-    from . import ops
     from . import news_encoders as NE
     from .model import _DotProductFn
     why = dedup_refusal(model)
@@ -477,15 +476,13 @@ def compute_scores_dedup(model, corpus, batch_size, window=64, chunk=4096):
         raise ValueError('compute_scores_dedup: window=%d' % window)
     if corpus.t['news_title_mask'].shape[0] ** 3 >= 2 ** 63:
         raise L.NnrHipError('compute_scores_dedup packs a triple of news ids into one int64 word: %d news are too many' % corpus.t['news_title_mask'].shape[0])
-    ne, ue = model.news_encoder, model.user_encoder
+    ne = model.news_encoder
     t, dev = corpus.t, corpus.device
     hist, cand = t['beh_history'].contiguous(), corpus.samples[:, 0].contiguous()
     n, H = hist.shape
     V = t['news_title_mask'].shape[0]
     tlen, clen = news_lengths(corpus)
-    was_training = model.training
-    model.eval()
-    try:
+    with eval_mode(model):
         # the memories (final cell states of both streams) of every distinct news: they depend on the news alone
         used = torch.unique(torch.cat([hist.reshape(-1), cand]).long())
         U, H2 = used.numel(), 2 * ne.hidden_dim
@@ -498,13 +495,13 @@ def compute_scores_dedup(model, corpus, batch_size, window=64, chunk=4096):
             for mem, st in zip((mem_t, mem_c), sv['streams']):
                 mem[s:s + sel.numel()] = st['cn'][st['plan'].rank.long()]             # cn is stored by sorted rank
         scores = torch.zeros(n, device=dev, dtype=torch.float32)
-        need_graph = getattr(ue, 'needs_history_graph', False)
         triples = windows = 0
         span = window * batch_size
         for w0 in range(0, n, span):
             cnt = min(span, n - w0)
+            w = slice(w0, w0 + cnt)
             pc_h, pt_h, pc_c, pt_c = ops.cne_pair_triples(hist, cand, tlen, clen, batch_size, w0, cnt, check=w0 == 0)
-            own = torch.cat([hist[w0:w0 + cnt].reshape(-1), cand[w0:w0 + cnt]]).long()
+            own = torch.cat([hist[w].reshape(-1), cand[w]]).long()
             key = torch.stack([own, torch.cat([pc_h.reshape(-1), pc_c]).long(), torch.cat([pt_h.reshape(-1), pt_c]).long()], dim=1)
             word, inv = torch.unique((key[:, 0] * V + key[:, 1]) * V + key[:, 2], return_inverse=True)      # one sortable word per triple
             trip = torch.stack([word // (V * V), word // V % V, word % V], dim=1)
@@ -519,25 +516,12 @@ def compute_scores_dedup(model, corpus, batch_size, window=64, chunk=4096):
                                      (mem_t, row_of[part[:, 2]][pc_.order.long()].contiguous()))
                 rep, _ = NE._cne_fwd_post(ne, sv, False)
                 reps[s:s + part.shape[0]] = rep.view(part.shape[0], -1)
-            slot_h, slot_c = inv[:cnt * H].view(cnt, H), inv[cnt * H:]
-            for start in range(w0, w0 + cnt, batch_size):                            # users and scores: as compute_scores_cached, batch by batch
-                e = min(start + batch_size, w0 + cnt)
-                idx = torch.arange(start, e, device=dev)
-                h = reps[slot_h[start - w0:e - w0]]                                   # [b, H, D]
-                c = reps[slot_c[start - w0:e - w0]].unsqueeze(1)                      # [b, 1, D]
-                hmask = t['beh_history_mask'][idx]
-                graph = cmask = cidx = None
-                if need_graph:
-                    from .corpus import history_graph
-                    graph, cmask, cidx = history_graph(t['news_category'][hist[idx].long()].contiguous(), hmask.contiguous(), corpus.category_num,
-                                                       corpus.norm_name)
-                extra = (model.user_rows(t['beh_user'][idx].long()),) if getattr(ue, 'needs_user_embedding', False) else ()
-                user = ue.encode_user(h, hmask, graph, cmask, cidx, c, *extra)
-                scores[start:e] = _DotProductFn.apply(user, c).squeeze(dim=1)
+            slot_h, slot_c = _split_like(inv, (hist[w], cand[w].view(-1, 1)))
+            # users and scores of the window's samples, in the reference's batches (a window starts on a batch boundary)
+            for s, e, user, c in _encoded_users(model, corpus, reps, t['beh_user'][w], hist[w], t['beh_history_mask'][w], slot_h, slot_c, batch_size):
+                scores[w0 + s:w0 + e] = _DotProductFn.apply(user, c).squeeze(dim=1)
             triples += T
             windows += 1
-    finally:
-        model.train(was_training)
     LAST_STATS.update(mode='dedup', triples=int(triples), distinct_news=int(U), per_sample_rows=int(n * (H + 1)), windows=int(windows))
     return scores
 

@@ -188,7 +188,8 @@ class Model(nn.Module):
         return UserRowsFn.apply(self.user_embedding.weight, user_ID, self.dropout_rate if self.training else 0.0, seed)
 
     def _encode_user(self, user_embedding, *args):
-        if getattr(self.user_encoder, 'needs_user_embedding', False):
+        """encode_user(*args), with the user rows for the encoders that read them: the one place that decides (evaluate.py calls it too)."""
+        if self.user_encoder.needs_user_embedding:
             return self.user_encoder.encode_user(*args, user_embedding)
         return self.user_encoder.encode_user(*args)
 
@@ -201,7 +202,7 @@ class Model(nn.Module):
             ops.wt_prefetch(news_title_text.device)      # W^T copies the backward pass will want, off the critical chain
         ne = self.news_encoder
         if (hasattr(ne, 'forward_pair') and not self.training and not torch.is_grad_enabled() and news_title_text.is_cuda
-                and getattr(ne, 'pad_dedup', True) and ne.tie_order == 'stable' and hasattr(self.user_encoder, 'encode_user')):
+                and ne.pad_dedup and ne.tie_order == 'stable' and hasattr(self.user_encoder, 'encode_user')):
             # inference: the history call without its redundant PAD slots (exact; news_encoders.cne_history_dedup)
             news_representation = ne(news_title_text, news_title_mask, news_title_entity, news_content_text, news_content_mask,
                                      news_content_entity, news_category, news_subCategory, user_embedding)

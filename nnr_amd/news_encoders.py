@@ -41,6 +41,10 @@ def _dp_world():
 
 class NewsEncoder(nn.Module):
     """newsEncoders.py:11-54."""
+    batch_independent = False            # True: a news representation does not depend on the other news of its call (evaluate.news_reps_cacheable)
+    cne_gate = False                     # True: the call's sequences gate each other by sorted rank (CNE, CNE_wo_CA; evaluate.compute_scores_dedup)
+    pad_dedup = True                     # False: Model.forward's inference de-duplication of PAD history slots does not apply
+    tie_order = 'stable'                 # the order of equal lengths where sequences are sorted (the CNE family sets it from the config)
 
     def __init__(self, config, word_table=None):
         super().__init__()

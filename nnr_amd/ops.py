@@ -1376,13 +1376,12 @@ def list_scores(user, reps, row, cand, scores=None, check=True):
     reps [n_reps, D] float32 with unit column stride (any row stride >= D), row / cand int32 [n] -> float32 [n] (written into `scores` when
     given; entries beyond n stay).  The kernel trusts the indices: check=True reads their ranges back (two reductions, one sync) and raises
     before the launch."""
-    n, D = row.numel(), user.shape[1]
-    if user.dim() != 2 or reps.dim() != 2 or reps.shape[1] != D or user.dtype != torch.float32 or reps.dtype != torch.float32:
-        raise L.NnrHipError('list_scores: user [n_user, D] and reps [n_reps, D] must be float32 tables of one width')
+    n_user, n_reps, D, ldu, ldr = _pool_tables('list_scores', user, reps, None, None)[:5]
+    n = row.numel()
     if row.dtype != torch.int32 or cand.dtype != torch.int32 or cand.numel() != n or not (row.is_contiguous() and cand.is_contiguous()):
         raise L.NnrHipError('list_scores: row and cand must be contiguous int32 tensors of one length')
-    if (D > 1 and (user.stride(1) != 1 or reps.stride(1) != 1)) or n < 1 or user.shape[0] < 1 or reps.shape[0] < 1:
-        raise L.NnrHipError('list_scores: empty input or a table whose columns are not adjacent')
+    if n < 1:
+        raise L.NnrHipError('list_scores: empty input (no row / cand pairs)')
     if scores is None:
         scores = torch.empty(n, device=user.device, dtype=torch.float32)
     elif scores.dtype != torch.float32 or scores.numel() < n or not scores.is_contiguous():
@@ -1390,13 +1389,10 @@ def list_scores(user, reps, row, cand, scores=None, check=True):
     if check:
         _p(row), _p(cand)
         lo_r, hi_r, lo_c, hi_c = torch.stack(torch.aminmax(row) + torch.aminmax(cand)).tolist()
-        if lo_r < 0 or hi_r >= user.shape[0] or lo_c < 0 or hi_c >= reps.shape[0]:
+        if lo_r < 0 or hi_r >= n_user or lo_c < 0 or hi_c >= n_reps:
             raise L.NnrHipError('list_scores: row indices %d..%d for %d user rows, cand indices %d..%d for %d news rows'
-                                % (lo_r, hi_r, user.shape[0], lo_c, hi_c, reps.shape[0]))
-    ldu = user.stride(0) if user.shape[0] > 1 else D
-    ldr = reps.stride(0) if reps.shape[0] > 1 else D
-    L.check(L.lib().nnr_list_scores(_p(user), user.shape[0], ldu, _p(reps), reps.shape[0], ldr, _p(row), _p(cand), n, D, _p(scores), _s()),
-            'nnr_list_scores')
+                                % (lo_r, hi_r, n_user, lo_c, hi_c, n_reps))
+    L.check(L.lib().nnr_list_scores(_p(user), n_user, ldu, _p(reps), n_reps, ldr, _p(row), _p(cand), n, D, _p(scores), _s()), 'nnr_list_scores')
     return scores
 
 
@@ -1418,7 +1414,8 @@ def _topk_ws(dev, nbytes):
 
 
 def _pool_tables(name, user, reps, valid, exclude):
-    """The argument checks topk_scores and pool_ranks share, before anything is launched: (n_user, n_reps, D, ldu, ldr, exclude, E, ld_ex)."""
+    """The argument checks list_scores, topk_scores and pool_ranks share, before anything is launched: (n_user, n_reps, D, ldu, ldr, exclude, E,
+    ld_ex)."""
     if user.dim() != 2 or reps.dim() != 2 or reps.shape[1] != user.shape[1] or user.dtype != torch.float32 or reps.dtype != torch.float32:
         raise L.NnrHipError('%s: user [n_user, D] and reps [n_reps, D] must be float32 tables of one width' % name)
     (n_user, D), n_reps = user.shape, reps.shape[0]
@@ -1444,9 +1441,12 @@ def _pool_tables(name, user, reps, valid, exclude):
     return n_user, n_reps, D, ldu, ldr, exclude, E, ld_ex
 
 
-def _finite_tables(name, user, reps):
-    if not bool(torch.isfinite(user).all() & torch.isfinite(reps).all()):
-        raise L.NnrHipError('%s: user and reps must be finite (a NaN or an infinity leaves the order undefined)' % name)
+_NOT_FINITE = '%s: user and reps must be finite (a NaN or an infinity leaves the order undefined)'
+
+
+def _tables_finite(user, reps):
+    """0-dim device bool: both tables are finite (two reductions where they live; the caller reads it back, alone or with its other flags)."""
+    return torch.isfinite(user).all() & torch.isfinite(reps).all()
 
 
 def topk_scores(user, reps, K, valid=None, exclude=None, check=True):
@@ -1460,8 +1460,8 @@ def topk_scores(user, reps, K, valid=None, exclude=None, check=True):
     if not isinstance(K, int) or K < 1:
         raise L.NnrHipError('topk_scores: K = %r (an integer from 1 to 64)' % (K,))
     _p(user), _p(reps), _p(valid), _p(exclude)
-    if check:
-        _finite_tables('topk_scores', user, reps)
+    if check and not bool(_tables_finite(user, reps)):
+        raise L.NnrHipError(_NOT_FINITE % 'topk_scores')
     idx = torch.empty((n_user, K), device=user.device, dtype=torch.int32)
     score = torch.empty((n_user, K), device=user.device, dtype=torch.float32)
     nbytes = L.lib().nnr_topk_workspace_bytes(n_user, n_reps, K)
@@ -1489,14 +1489,13 @@ def pool_ranks(user, reps, t_off, t_news, valid=None, exclude=None, check=True):
     if check:                                               # three reductions where the tensors live, one read-back
         bad_off = (t_off[0] != 0) | (t_off[-1] != T) | (t_off[1:] < t_off[:-1]).any()
         bad_news = ((t_news < 0) | (t_news >= n_reps)).any() if T else torch.zeros_like(bad_off)
-        finite = torch.isfinite(user).all() & torch.isfinite(reps).all()
-        bad_off, bad_news, finite = torch.stack([bad_off.to(user.device), bad_news.to(user.device), finite]).tolist()
+        bad_off, bad_news, finite = torch.stack([bad_off.to(user.device), bad_news.to(user.device), _tables_finite(user, reps)]).tolist()
         if bad_off:
             raise L.NnrHipError('pool_ranks: t_off must be non-decreasing from 0 to the number of targets (%d)' % T)
         if bad_news:
             raise L.NnrHipError('pool_ranks: t_news outside 0 .. %d (the rows of reps)' % (n_reps - 1))
         if not finite:
-            raise L.NnrHipError('pool_ranks: user and reps must be finite (a NaN or an infinity leaves the order undefined)')
+            raise L.NnrHipError(_NOT_FINITE % 'pool_ranks')
     _p(user), _p(reps), _p(valid), _p(exclude), _p(t_off), _p(t_news)
     dev = user.device
     ahead = torch.empty(T, device=dev, dtype=torch.int32)

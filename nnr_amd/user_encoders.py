@@ -24,6 +24,7 @@ class UserEncoder(nn.Module):
     needs_user_embedding = False         # True: encode_user takes the user embedding rows as a seventh argument (model.Model passes them)
     candidate_independent = False        # True: encode_user expands ONE vector per user over the candidates and never reads them (listwise evaluation
                                          # then encodes a user once per impression, evaluate.compute_scores_listwise)
+    needs_history_graph = False          # True: encode_user reads the graph / cluster inputs (evaluate._encoded_users builds them per batch)
 
     def __init__(self, news_encoder: NewsEncoder, config):
         super().__init__()
@@ -478,7 +479,7 @@ def _cluster_layers_initialize(mod):
 
 class SUE(UserEncoder):
     """userEncoders.py:42-98."""
-    needs_history_graph = True           # evaluate.compute_scores_cached builds the graph / cluster inputs for such an encoder
+    needs_history_graph = True           # evaluate._encoded_users builds the graph / cluster inputs for such an encoder
     intra_form = _IntraKeys              # what the cluster pipeline runs as its intra stage (as _CNEAblation states what it keeps)
 
     def __init__(self, news_encoder: NewsEncoder, config):
