@@ -689,6 +689,39 @@ size_t nnr_pool_rank_workspace_bytes(long n_user, long n_reps, long n_target);
 int nnr_pool_ranks(const float* user, long n_user, int ldu, const float* reps, long n_reps, int ldr, int D, const uint8_t* valid,
                    const int* exclude, int E, int ld_ex, const int* t_off, const int* t_news, long n_target, int* ahead, float* t_score,
                    int* pool_size, void* workspace, long workspace_bytes, hipStream_t stream);
+/* The archive form of the two entry points above: a user row is A vectors ("archives", 1 <= A <= 16) and the score of a
+ * pair is their softmax-weighted inner product with the news row, OMAP's click score (userEncoders.py:367-369).  user [n_user][A][D]: archive
+ * a of user u starts at user + u * ldu + a * lda, lda >= D, ldu >= (A - 1) * lda + D.  Everything else -- reps, valid, exclude, the
+ * eligibility rule, the -inf masking, the order, the tie rule, the -1 / -inf tail, t_off, t_news, ahead, pool_size, the workspace (its size
+ * does not depend on A: nnr_topk_workspace_bytes / nnr_pool_rank_workspace_bytes) and the splits -- is the plain entry point's, applied to
+ *   s_a   = the chain  acc = fmaf(user[u, a, d], reps[r, d], acc)  over d ascending from +0           (nnr_topk_scores' score of archive a)
+ *   score = combine(s_0 .. s_{A-1}; scale) = sum_a w_a s_a,  w = softmax_a(scale * s_a).
+ * combine, THE operation sequence (every operation fp32, rounded to nearest once; fma = one rounding; nothing is contracted or reordered):
+ *   m = s_0;  den = 1;  num = s_0;                                             the state after archive 0
+ *   for a = 1 .. A - 1, with s = s_a:
+ *     up = (scale < 0 ? s < m : s > m)                                         s is the new extreme: the state is rescaled to it
+ *     e  = expf(scale * (up ? m - s : s - m))                                  the argument is never positive: no overflow; expf is the
+ *                                                                              runtime's, at most 2 ulp (1 ulp as documented for the device)
+ *     up:      den = fma(den, e, 1);  num = fma(num, e, s);  m = s
+ *     not up:  den = fma(1, e, den);  num = fma(s, e, num)                     (= den + e, and num + s e with one rounding)
+ *   score = num / den                                                          ONE correctly rounded division
+ * m is the running extreme of the archives seen so far (the maximum for scale >= 0), which is the maximum that is subtracted; den and num
+ * are the softmax sums over a ascending, relative to it.  One __device__ function states this sequence; the tile walk (per accumulator
+ * element, one pass over the news tile per archive) and the target pre-pass of nnr_pool_archive_ranks both call it.  So the combined score is
+ * a pure function of the A + 1 rows and scale, to the bit: wherever the rows stand, whatever the strides, the load path (16-byte loads need
+ * lda a multiple of 4 too), the number of news splits, and whether the tile walk or the pre-pass computed it.  Three consequences:
+ *   A = 1: score = s_0 / 1, the bits of nnr_topk_scores for the same rows;
+ *   scale = 0: every e is 1, den = A, score = (s_0 + .. + s_{A-1}) / A summed in ascending a;
+ *   all A archives of a user equal and A in {2, 4}: num = A s_0 exactly, score = s_0.
+ * The scores s_a are finite by contract, as the tables are.
+ * NNR_ERR_ARG, with nothing launched, for everything the plain entry point refuses so and for A < 1, lda < D, ldu < (A - 1) * lda + D or a
+ * scale that is not finite.  NNR_ERR_UNSUPPORTED for A > 16 (csrc/omap.hip's own limit on its archives) and for the plain entry point's cases. */
+int nnr_topk_archive_scores(const float* user, long n_user, int ldu, int A, int lda, float scale, const float* reps, long n_reps, int ldr,
+                            int D, const uint8_t* valid, const int* exclude, int E, int ld_ex, int K, int* idx, float* score, void* workspace,
+                            long workspace_bytes, hipStream_t stream);
+int nnr_pool_archive_ranks(const float* user, long n_user, int ldu, int A, int lda, float scale, const float* reps, long n_reps, int ldr, int D,
+                           const uint8_t* valid, const int* exclude, int E, int ld_ex, const int* t_off, const int* t_news, long n_target,
+                           int* ahead, float* t_score, int* pool_size, void* workspace, long workspace_bytes, hipStream_t stream);
 /* De-duplicated evaluation of the rank-pairing CNE encoders: the pairing plan of every encoder call of a range of
  * reference batches, in one launch.  The reference scores dev samples in batches of batch_size consecutive samples (the last one short) and
  * runs two encoder calls per batch of b samples: the candidate call over the b sequences cand[s] and the history call over the b * H

@@ -174,6 +174,8 @@ SIGNATURES = {
     'nnr_topk_scores': 'i32 ptr i64 i32 ptr i64 i32 i32 ptr ptr i32 i32 i32 ptr ptr ptr i64 stream',
     'nnr_pool_rank_workspace_bytes': 'u64 i64 i64 i64',
     'nnr_pool_ranks': 'i32 ptr i64 i32 ptr i64 i32 i32 ptr ptr i32 i32 ptr ptr i64 ptr ptr ptr ptr i64 stream',
+    'nnr_topk_archive_scores': 'i32 ptr i64 i32 i32 i32 f32 ptr i64 i32 i32 ptr ptr i32 i32 i32 ptr ptr ptr i64 stream',
+    'nnr_pool_archive_ranks': 'i32 ptr i64 i32 i32 i32 f32 ptr i64 i32 i32 ptr ptr i32 i32 ptr ptr i64 ptr ptr ptr ptr i64 stream',
     'nnr_logits_loss_fwd': 'i32 ptr ptr i32 i32 i32 ptr ptr ptr stream',
     'nnr_logits_fwd': 'i32 ptr ptr i32 i32 i32 ptr stream',
     'nnr_nls_loss': 'i32 ptr i32 i32 ptr ptr stream',

@@ -66,6 +66,8 @@ const Entry REGISTRY[] = {
   R(nnr_cne_pair_triples),
   R(nnr_topk_scores),
   R(nnr_pool_ranks),
+  R(nnr_topk_archive_scores),
+  R(nnr_pool_archive_ranks),
 };
 #undef R
 constexpr int NREG = (int)(sizeof(REGISTRY) / sizeof(REGISTRY[0]));

@@ -60,13 +60,35 @@ __device__ __forceinline__ void list_admit(float& ls, int& li, unsigned long lon
   }
 }
 
+// ------------------------------------------------------------------------------------------------ the archive form
+// A user row of the archive entry points is A vectors, lda floats apart; the plain entry points launch the ARCH = false instantiations, which
+// never read this.
+struct Archives { int A, lda; float scale; };
+
+// combine of include/nnr_hip.h, one archive at a time: the state (m, den, num) after archives 0 .. a from the state after 0 .. a - 1 and
+// s = s_a.  THE one statement of the sequence: the tile walk and the target pre-pass both call it, every operation is an explicitly rounded
+// one and contraction is off, so the two sites cannot differ.  `first` (a == 0) is uniform over the launch.
+__device__ __forceinline__ void archive_fold(bool first, float s, float scale, float& m, float& den, float& num) {
+#pragma clang fp contract(off)
+  if (first) { m = s; den = 1.f; num = s; return; }
+  const bool up = scale < 0.f ? s < m : s > m;             // s is the new extreme: the state is rescaled to it; otherwise s joins the state
+  const float e = expf(__fmul_rn(scale, up ? __fsub_rn(m, s) : __fsub_rn(s, m)));
+  den = __fmaf_rn(up ? den : 1.f, e, up ? 1.f : den);
+  num = __fmaf_rn(up ? num : s, e, up ? s : num);
+  m = up ? s : m;
+}
+__device__ __forceinline__ float archive_score(float den, float num) { return __fdiv_rn(num, den); }
+
 // The walk both kernels of this file share: the 64 users from u0 against the news tiles t_begin .. t_end - 1 in ascending order.  For each
 // tile the finished, masked 64 x 128 scores stand in `tile` ([user][news]; -inf over every ineligible position) and fold(n0) is called by
 // all 256 threads behind a barrier; the next tile's first barrier guards `tile` against its readers, so fold needs none of its own.
-template <bool VEC, class Fold>
+// ARCH: a tile is walked once per archive a = 0 .. A - 1 (the news slabs are read again, from L2), each pass leaves the chains s_a in the
+// accumulators and archive_fold takes them into 96 registers of state per lane; the tile that reaches LDS holds the combined scores, and
+// everything behind that point is the plain walk's.  The operand stream never stops: the last slab of a pass prefetches the next pass's first.
+template <bool VEC, bool ARCH, class Fold>
 __device__ __forceinline__ void score_tile_walk(float* tile, const float* __restrict__ user, long n_user, int ldu, const float* __restrict__ reps,
                                                 long n_reps, int ldr, int D, const uint8_t* __restrict__ valid, const int* __restrict__ exclude,
-                                                int E, int ld_ex, long u0, long t_begin, long t_end, Fold&& fold) {
+                                                int E, int ld_ex, long u0, long t_begin, long t_end, const Archives& ar, Fold&& fold) {
   static_assert(TK_STAGE <= TK_TU * TK_TN, "the operand images live inside the score tile");
   float* As = tile;                                         // [k][TK_SA]: As[k * TK_SA + u]
   float* Bs = tile + TK_KS * TK_SA;                         // [k][TK_SB]
@@ -75,7 +97,8 @@ __device__ __forceinline__ void score_tile_walk(float* tile, const float* __rest
 
   // one slab of both operands, global -> registers: 2048 user floats and 4096 news floats over 256 threads
   float pre[24];
-  auto gload = [&](long n0, int k0) {
+  auto gload = [&](long n0, int k0, int a) {
+    const float* __restrict__ ua = ARCH ? user + (long)a * ar.lda : user;
     if (VEC) {                                              // thread: float4 column kq of rows r, r + 32, ...   (D % 4 == 0)
       const int kq = tid & 7, r = tid >> 3, k = k0 + 4 * kq;
 #pragma unroll
@@ -84,7 +107,7 @@ __device__ __forceinline__ void score_tile_walk(float* tile, const float* __rest
         const long row = is_u ? u0 + r + 32 * i : n0 + r + 32 * (i - 2);
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (k < D && row < (is_u ? n_user : n_reps))
-          v = *reinterpret_cast<const float4*>(is_u ? user + row * ldu + k : reps + row * ldr + k);
+          v = *reinterpret_cast<const float4*>(is_u ? ua + row * ldu + k : reps + row * ldr + k);
         pre[4 * i] = v.x; pre[4 * i + 1] = v.y; pre[4 * i + 2] = v.z; pre[4 * i + 3] = v.w;
       }
     } else {                                                // thread: column k of rows r, r + 8, ...
@@ -94,7 +117,7 @@ __device__ __forceinline__ void score_tile_walk(float* tile, const float* __rest
         const bool is_u = i < 8;
         const long row = is_u ? u0 + r + 8 * i : n0 + r + 8 * (i - 8);
         float v = 0.f;
-        if (k < D && row < (is_u ? n_user : n_reps)) v = is_u ? user[row * ldu + k] : reps[row * ldr + k];
+        if (k < D && row < (is_u ? n_user : n_reps)) v = is_u ? ua[row * ldu + k] : reps[row * ldr + k];
         pre[i] = v;
       }
     }
@@ -121,26 +144,44 @@ __device__ __forceinline__ void score_tile_walk(float* tile, const float* __rest
 
   const int wu = (wave & 1) * 32, wn = (wave >> 1) * 64;   // this wave's 32 users x 64 news of the tile
   const int half = lane >> 5, l31 = lane & 31;
-  if (t_begin < t_end) gload(t_begin * TK_TN, 0);
+  const int A = ARCH ? ar.A : 1;
+  if (t_begin < t_end) gload(t_begin * TK_TN, 0, 0);
   for (long t = t_begin; t < t_end; ++t) {
     const long n0 = t * TK_TN;
     f32x16 acc0, acc1;
+    [[maybe_unused]] float m0[16], m1[16], den0[16], den1[16], num0[16], num1[16];   // ARCH: the combine state of this lane's 32 tile elements
+    for (int a = 0; a < A; ++a) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
-    for (int sl = 0; sl < nslab; ++sl) {
-      __syncthreads();                                      // the previous slab's products / the previous tile's fold have read `tile`
-      lstore();
-      __syncthreads();
-      if (sl + 1 < nslab) gload(n0, (sl + 1) * TK_KS);
-      else if (t + 1 < t_end) gload(n0 + TK_TN, 0);
+      for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
+      for (int sl = 0; sl < nslab; ++sl) {
+        __syncthreads();                                    // the previous slab's products / the previous tile's fold have read `tile`
+        lstore();
+        __syncthreads();
+        if (sl + 1 < nslab) gload(n0, (sl + 1) * TK_KS, a);
+        else if (ARCH && a + 1 < A) gload(n0, 0, a + 1);
+        else if (t + 1 < t_end) gload(n0 + TK_TN, 0, 0);
 #pragma unroll
-      for (int s = 0; s < TK_KS / 2; ++s) {                 // A[i = lane & 31][k = lane >> 5], B[k = lane >> 5][j = lane & 31]
-        const int k = 2 * s + half;
-        const float a = As[k * TK_SA + wu + l31];
-        const float b0 = Bs[k * TK_SB + wn + l31], b1 = Bs[k * TK_SB + wn + 32 + l31];
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc1, 0, 0, 0);
+        for (int s = 0; s < TK_KS / 2; ++s) {               // A[i = lane & 31][k = lane >> 5], B[k = lane >> 5][j = lane & 31]
+          const int k = 2 * s + half;
+          const float a_ = As[k * TK_SA + wu + l31];
+          const float b0 = Bs[k * TK_SB + wn + l31], b1 = Bs[k * TK_SB + wn + 32 + l31];
+          acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_, b0, acc0, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_, b1, acc1, 0, 0, 0);
+        }
       }
+      if constexpr (ARCH) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const float s0 = acc0[i], s1 = acc1[i];
+          archive_fold(a == 0, s0, ar.scale, m0[i], den0[i], num0[i]);
+          archive_fold(a == 0, s1, ar.scale, m1[i], den1[i], num1[i]);
+          __builtin_amdgcn_sched_barrier(0);                // two exponentials in flight, not 32: their temporaries would not fit beside the state
+        }
+      }
+    }
+    if constexpr (ARCH) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) { acc0[i] = archive_score(den0[i], num0[i]); acc1[i] = archive_score(den1[i], num1[i]); }
     }
     __syncthreads();                                        // every wave is done with the operand images
 #pragma unroll
@@ -170,11 +211,11 @@ __device__ __forceinline__ void score_tile_walk(float* tile, const float* __rest
   }
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void topk_tile_kernel(const float* __restrict__ user, long n_user, int ldu, const float* __restrict__ reps,
+template <bool VEC, bool ARCH>
+__global__ __launch_bounds__(256, ARCH && VEC ? 2 : 0) void topk_tile_kernel(const float* __restrict__ user, long n_user, int ldu, const float* __restrict__ reps,
                                                         long n_reps, int ldr, int D, const uint8_t* __restrict__ valid,
                                                         const int* __restrict__ exclude, int E, int ld_ex, int K, long user_tiles,
-                                                        int splits, int* __restrict__ out_idx, float* __restrict__ out_score) {
+                                                        int splits, int* __restrict__ out_idx, float* __restrict__ out_score, Archives ar) {
   __shared__ float tile[TK_TU * TK_TN];                     // the score tile [user][news]; before that, the slab's operand images
   __shared__ float lst_s[TK_TU * 64];
   __shared__ int lst_i[TK_TU * 64];
@@ -189,7 +230,7 @@ __global__ __launch_bounds__(256) void topk_tile_kernel(const float* __restrict_
     lst_s[u * 64 + lane] = -INFINITY;
     lst_i[u * 64 + lane] = -1;
   }
-  score_tile_walk<VEC>(tile, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex, u0, t_begin, t_end, [&](long, long n0) {
+  score_tile_walk<VEC, ARCH>(tile, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex, u0, t_begin, t_end, ar, [&](long, long n0) {
     for (int u = wave * 16; u < wave * 16 + 16; ++u) {      // wave-uniform
       if (u0 + u >= n_user) break;
       const float thr = lst_s[u * 64 + K - 1];
@@ -253,12 +294,14 @@ __device__ __forceinline__ unsigned long long rank_key(float s, int r) {
 }
 
 // t_score[j] = the header's chain for (user of j, t_news[j]); ahead[j] = 0 for an eligible target and -1 for an ineligible one (the
-// counters behind it leave a -1 alone).  One thread per target; its user is the last u with t_off[u] <= j.
+// counters behind it leave a -1 alone).  One thread per target; its user is the last u with t_off[u] <= j.  ARCH: one chain per archive,
+// combined by archive_fold as the tile walk combines them.
+template <bool ARCH>
 __global__ __launch_bounds__(256) void pool_rank_target_kernel(const float* __restrict__ user, long n_user, int ldu, const float* __restrict__ reps,
                                                                long n_reps, int ldr, int D, const uint8_t* __restrict__ valid,
                                                                const int* __restrict__ exclude, int E, int ld_ex, const int* __restrict__ t_off,
                                                                const int* __restrict__ t_news, long n_target, int* __restrict__ ahead,
-                                                               float* __restrict__ t_score) {
+                                                               float* __restrict__ t_score, Archives ar) {
   const long j = (long)blockIdx.x * 256 + threadIdx.x;
   if (j >= n_target) return;
   long lo = 0, hi = n_user;                                 // t_off[lo] <= j < t_off[hi] (t_off[0] = 0, t_off[n_user] = n_target)
@@ -272,11 +315,17 @@ __global__ __launch_bounds__(256) void pool_rank_target_kernel(const float* __re
     ahead[j] = -1;
     return;
   }
-  const float* __restrict__ a = user + u * ldu;
   const float* __restrict__ b = reps + r * ldr;
   float acc = 0.f;
-  for (int d = 0; d < D; ++d) acc = __fmaf_rn(a[d], b[d], acc);
-  if (D % TK_KS) acc = __fmaf_rn(0.f, 0.f, acc);            // the tile's zero-filled tail, literally (it turns a -0 into +0 and nothing else)
+  [[maybe_unused]] float m = 0.f, den = 1.f, num = 0.f;
+  for (int k = 0; k < (ARCH ? ar.A : 1); ++k) {
+    const float* __restrict__ a = user + u * ldu + (ARCH ? (long)k * ar.lda : 0);
+    acc = 0.f;
+    for (int d = 0; d < D; ++d) acc = __fmaf_rn(a[d], b[d], acc);
+    if (D % TK_KS) acc = __fmaf_rn(0.f, 0.f, acc);          // the tile's zero-filled tail, literally (it turns a -0 into +0 and nothing else)
+    if constexpr (ARCH) archive_fold(k == 0, acc, ar.scale, m, den, num);
+  }
+  if constexpr (ARCH) acc = archive_score(den, num);
   bool el = !valid || valid[r] != 0;
   for (int e = 0; e < E; ++e) el = el && exclude[u * ld_ex + e] != (int)r;
   t_score[j] = acc;
@@ -287,13 +336,13 @@ __global__ __launch_bounds__(256) void pool_rank_target_kernel(const float* __re
 // ones among them.  A tile's targets are the contiguous range t_off[u0] .. t_off[u0 + 64); position p in it has its key and its counter
 // in LDS while p < PR_CAP and works on global memory beyond that: the counter's own destination, read and written by ONE lane of the wave
 // that owns the user, tile after tile.  Without splits the destination of a counter is ahead[j] itself, where the pre-pass left 0 or -1.
-template <bool VEC>
-__global__ __launch_bounds__(256) void pool_rank_tile_kernel(const float* __restrict__ user, long n_user, int ldu, const float* __restrict__ reps,
+template <bool VEC, bool ARCH>
+__global__ __launch_bounds__(256, ARCH && VEC ? 2 : 0) void pool_rank_tile_kernel(const float* __restrict__ user, long n_user, int ldu, const float* __restrict__ reps,
                                                              long n_reps, int ldr, int D, const uint8_t* __restrict__ valid,
                                                              const int* __restrict__ exclude, int E, int ld_ex, long user_tiles, int splits,
                                                              const int* __restrict__ t_off, const int* __restrict__ t_news,
                                                              const float* __restrict__ t_score, long n_target, int* cnt_t,
-                                                             int* __restrict__ cnt_u) {
+                                                             int* __restrict__ cnt_u, Archives ar) {
   __shared__ float tile[TK_TU * TK_TN];
   __shared__ unsigned long long tg_k[PR_CAP];              // rank_key of the tile's first PR_CAP targets
   __shared__ int tg_c[PR_CAP];                              // and their counters
@@ -321,7 +370,7 @@ __global__ __launch_bounds__(256) void pool_rank_tile_kernel(const float* __rest
   }
   __syncthreads();
   int psz = 0;                                              // lane l of a wave: the eligible entries of its user wave * 16 + l (l < 16)
-  score_tile_walk<VEC>(tile, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex, u0, t_begin, t_end, [&](long t, long n0) {
+  score_tile_walk<VEC, ARCH>(tile, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex, u0, t_begin, t_end, ar, [&](long t, long n0) {
     for (int u = wave * 16; u < wave * 16 + 16; ++u) {      // wave-uniform
       if (u0 + u >= n_user) break;
       const float c0 = tile[u * TK_TN + lane], c1 = tile[u * TK_TN + 64 + lane];
@@ -376,19 +425,34 @@ __global__ __launch_bounds__(256) void pool_rank_merge_kernel(const int* __restr
 }
 }  // namespace
 
+
 extern "C" size_t nnr_pool_rank_workspace_bytes(long n_user, long n_reps, long n_target) {
   if (n_user < 1 || n_reps < 1 || n_target < 0 || n_user >= INT_MAX || n_reps > INT_MAX || n_target > INT_MAX) return 0;
   const int splits = topk_splits(n_user, n_reps);
   return splits > 1 ? (size_t)(n_target + n_user) * splits * sizeof(int) : 0;
 }
 
-extern "C" int nnr_pool_ranks(const float* user, long n_user, int ldu, const float* reps, long n_reps, int ldr, int D, const uint8_t* valid,
-                              const int* exclude, int E, int ld_ex, const int* t_off, const int* t_news, long n_target, int* ahead,
-                              float* t_score, int* pool_size, void* workspace, long workspace_bytes, hipStream_t stream) {
+extern "C" size_t nnr_topk_workspace_bytes(long n_user, long n_reps, int K) {
+  if (n_user < 1 || n_reps < 1 || K < 1 || K > 64) return 0;
+  const int splits = topk_splits(n_user, n_reps);
+  return splits > 1 ? (size_t)n_user * splits * K * (sizeof(float) + sizeof(int)) : 0;
+}
+
+namespace {
+// What the archive entry points check beyond their plain counterparts (A > 16 is refused behind the plain argument checks)
+bool archives_ok(int ldu, int A, int lda, float scale, int D) {
+  return A >= 1 && D >= 1 && lda >= D && (long)ldu >= (long)(A - 1) * lda + D && scale - scale == 0.f;
+}
+
+// The body of nnr_pool_ranks (ARCH = false: `ar` is not read by any kernel) and of nnr_pool_archive_ranks
+template <bool ARCH>
+int pool_ranks_run(const float* user, long n_user, int ldu, const Archives& ar, const float* reps, long n_reps, int ldr, int D,
+                   const uint8_t* valid, const int* exclude, int E, int ld_ex, const int* t_off, const int* t_news, long n_target, int* ahead,
+                   float* t_score, int* pool_size, void* workspace, long workspace_bytes, hipStream_t stream) {
   if (!user || !reps || !pool_size || !t_off) return NNR_ERR_ARG;
   if (n_user < 1 || n_reps < 1 || D < 1 || ldu < D || ldr < D || E < 0 || ld_ex < E || (E > 0 && !exclude) || n_target < 0) return NNR_ERR_ARG;
   if (n_target > 0 && (!t_news || !ahead || !t_score)) return NNR_ERR_ARG;
-  if (n_user >= INT_MAX || n_reps > INT_MAX || n_target > INT_MAX) return NNR_ERR_UNSUPPORTED;
+  if (n_user >= INT_MAX || n_reps > INT_MAX || n_target > INT_MAX || (ARCH && ar.A > 16)) return NNR_ERR_UNSUPPORTED;
   const int splits = topk_splits(n_user, n_reps);
   const size_t need = nnr_pool_rank_workspace_bytes(n_user, n_reps, n_target);
   if (need > 0 && (!workspace || workspace_bytes < 0 || (size_t)workspace_bytes < need || ((uintptr_t)workspace & 3))) return NNR_ERR_ARG;
@@ -396,21 +460,21 @@ extern "C" int nnr_pool_ranks(const float* user, long n_user, int ldu, const flo
   if (user_tiles * splits > INT_MAX) return NNR_ERR_UNSUPPORTED;
   if (!exclude) E = 0;
   if (n_target > 0) {
-    hipLaunchKernelGGL(pool_rank_target_kernel, dim3((unsigned)((n_target + 255) / 256)), dim3(256), 0, stream, user, n_user, ldu, reps, n_reps,
-                       ldr, D, valid, exclude, E, ld_ex, t_off, t_news, n_target, ahead, t_score);
+    hipLaunchKernelGGL(pool_rank_target_kernel<ARCH>, dim3((unsigned)((n_target + 255) / 256)), dim3(256), 0, stream, user, n_user, ldu, reps,
+                       n_reps, ldr, D, valid, exclude, E, ld_ex, t_off, t_news, n_target, ahead, t_score, ar);
     NNR_CHECK_LAUNCH();
   }
   int* ws = reinterpret_cast<int*>(workspace);
   int* cnt_t = splits > 1 ? ws : ahead;
   int* cnt_u = splits > 1 ? ws + (size_t)n_target * splits : pool_size;
-  const bool vec = D % 4 == 0 && ldu % 4 == 0 && ldr % 4 == 0 && al16(user) && al16(reps);
+  const bool vec = D % 4 == 0 && ldu % 4 == 0 && ldr % 4 == 0 && al16(user) && al16(reps) && (!ARCH || ar.lda % 4 == 0);
   const dim3 grid((unsigned)(user_tiles * splits));
   if (vec)
-    hipLaunchKernelGGL(pool_rank_tile_kernel<true>, grid, dim3(256), 0, stream, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex,
-                       user_tiles, splits, t_off, t_news, t_score, n_target, cnt_t, cnt_u);
+    hipLaunchKernelGGL((pool_rank_tile_kernel<true, ARCH>), grid, dim3(256), 0, stream, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E,
+                       ld_ex, user_tiles, splits, t_off, t_news, t_score, n_target, cnt_t, cnt_u, ar);
   else
-    hipLaunchKernelGGL(pool_rank_tile_kernel<false>, grid, dim3(256), 0, stream, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex,
-                       user_tiles, splits, t_off, t_news, t_score, n_target, cnt_t, cnt_u);
+    hipLaunchKernelGGL((pool_rank_tile_kernel<false, ARCH>), grid, dim3(256), 0, stream, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E,
+                       ld_ex, user_tiles, splits, t_off, t_news, t_score, n_target, cnt_t, cnt_u, ar);
   NNR_CHECK_LAUNCH();
   if (splits > 1) {
     hipLaunchKernelGGL(pool_rank_merge_kernel, dim3((unsigned)((n_target + n_user + 255) / 256)), dim3(256), 0, stream, ws, n_target, n_user,
@@ -420,18 +484,13 @@ extern "C" int nnr_pool_ranks(const float* user, long n_user, int ldu, const flo
   return NNR_OK;
 }
 
-extern "C" size_t nnr_topk_workspace_bytes(long n_user, long n_reps, int K) {
-  if (n_user < 1 || n_reps < 1 || K < 1 || K > 64) return 0;
-  const int splits = topk_splits(n_user, n_reps);
-  return splits > 1 ? (size_t)n_user * splits * K * (sizeof(float) + sizeof(int)) : 0;
-}
-
-extern "C" int nnr_topk_scores(const float* user, long n_user, int ldu, const float* reps, long n_reps, int ldr, int D, const uint8_t* valid,
-                               const int* exclude, int E, int ld_ex, int K, int* idx, float* score, void* workspace, long workspace_bytes,
-                               hipStream_t stream) {
+// The body of nnr_topk_scores (ARCH = false) and of nnr_topk_archive_scores
+template <bool ARCH>
+int topk_run(const float* user, long n_user, int ldu, const Archives& ar, const float* reps, long n_reps, int ldr, int D, const uint8_t* valid,
+             const int* exclude, int E, int ld_ex, int K, int* idx, float* score, void* workspace, long workspace_bytes, hipStream_t stream) {
   if (!user || !reps || !idx || !score) return NNR_ERR_ARG;
   if (n_user < 1 || n_reps < 1 || D < 1 || ldu < D || ldr < D || E < 0 || ld_ex < E || (E > 0 && !exclude) || K < 1) return NNR_ERR_ARG;
-  if (K > 64 || n_reps > INT_MAX) return NNR_ERR_UNSUPPORTED;
+  if (K > 64 || n_reps > INT_MAX || (ARCH && ar.A > 16)) return NNR_ERR_UNSUPPORTED;
   const int splits = topk_splits(n_user, n_reps);
   const size_t need = nnr_topk_workspace_bytes(n_user, n_reps, K);
   if (need > 0 && (!workspace || workspace_bytes < 0 || (size_t)workspace_bytes < need || ((uintptr_t)workspace & 3))) return NNR_ERR_ARG;
@@ -442,14 +501,14 @@ extern "C" int nnr_topk_scores(const float* user, long n_user, int ldu, const fl
   int* t_idx = splits > 1 ? ws_idx : idx;
   float* t_score = splits > 1 ? ws_score : score;
   if (!exclude) E = 0;
-  const bool vec = D % 4 == 0 && ldu % 4 == 0 && ldr % 4 == 0 && al16(user) && al16(reps);
+  const bool vec = D % 4 == 0 && ldu % 4 == 0 && ldr % 4 == 0 && al16(user) && al16(reps) && (!ARCH || ar.lda % 4 == 0);
   const dim3 grid((unsigned)(user_tiles * splits));
   if (vec)
-    hipLaunchKernelGGL(topk_tile_kernel<true>, grid, dim3(256), 0, stream, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex, K,
-                       user_tiles, splits, t_idx, t_score);
+    hipLaunchKernelGGL((topk_tile_kernel<true, ARCH>), grid, dim3(256), 0, stream, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex,
+                       K, user_tiles, splits, t_idx, t_score, ar);
   else
-    hipLaunchKernelGGL(topk_tile_kernel<false>, grid, dim3(256), 0, stream, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex, K,
-                       user_tiles, splits, t_idx, t_score);
+    hipLaunchKernelGGL((topk_tile_kernel<false, ARCH>), grid, dim3(256), 0, stream, user, n_user, ldu, reps, n_reps, ldr, D, valid, exclude, E, ld_ex,
+                       K, user_tiles, splits, t_idx, t_score, ar);
   NNR_CHECK_LAUNCH();
   if (splits > 1) {
     hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((n_user + 3) / 4)), dim3(256), 0, stream, ws_score, ws_idx, n_user, splits, K, idx,
@@ -457,4 +516,36 @@ extern "C" int nnr_topk_scores(const float* user, long n_user, int ldu, const fl
     NNR_CHECK_LAUNCH();
   }
   return NNR_OK;
+}
+}  // namespace
+
+extern "C" int nnr_pool_ranks(const float* user, long n_user, int ldu, const float* reps, long n_reps, int ldr, int D, const uint8_t* valid,
+                              const int* exclude, int E, int ld_ex, const int* t_off, const int* t_news, long n_target, int* ahead,
+                              float* t_score, int* pool_size, void* workspace, long workspace_bytes, hipStream_t stream) {
+  return pool_ranks_run<false>(user, n_user, ldu, Archives{1, 0, 0.f}, reps, n_reps, ldr, D, valid, exclude, E, ld_ex, t_off, t_news, n_target,
+                               ahead, t_score, pool_size, workspace, workspace_bytes, stream);
+}
+
+extern "C" int nnr_pool_archive_ranks(const float* user, long n_user, int ldu, int A, int lda, float scale, const float* reps, long n_reps,
+                                      int ldr, int D, const uint8_t* valid, const int* exclude, int E, int ld_ex, const int* t_off,
+                                      const int* t_news, long n_target, int* ahead, float* t_score, int* pool_size, void* workspace,
+                                      long workspace_bytes, hipStream_t stream) {
+  if (!archives_ok(ldu, A, lda, scale, D)) return NNR_ERR_ARG;
+  return pool_ranks_run<true>(user, n_user, ldu, Archives{A, lda, scale}, reps, n_reps, ldr, D, valid, exclude, E, ld_ex, t_off, t_news, n_target,
+                              ahead, t_score, pool_size, workspace, workspace_bytes, stream);
+}
+
+extern "C" int nnr_topk_scores(const float* user, long n_user, int ldu, const float* reps, long n_reps, int ldr, int D, const uint8_t* valid,
+                               const int* exclude, int E, int ld_ex, int K, int* idx, float* score, void* workspace, long workspace_bytes,
+                               hipStream_t stream) {
+  return topk_run<false>(user, n_user, ldu, Archives{1, 0, 0.f}, reps, n_reps, ldr, D, valid, exclude, E, ld_ex, K, idx, score, workspace,
+                         workspace_bytes, stream);
+}
+
+extern "C" int nnr_topk_archive_scores(const float* user, long n_user, int ldu, int A, int lda, float scale, const float* reps, long n_reps,
+                                       int ldr, int D, const uint8_t* valid, const int* exclude, int E, int ld_ex, int K, int* idx, float* score,
+                                       void* workspace, long workspace_bytes, hipStream_t stream) {
+  if (!archives_ok(ldu, A, lda, scale, D)) return NNR_ERR_ARG;
+  return topk_run<true>(user, n_user, ldu, Archives{A, lda, scale}, reps, n_reps, ldr, D, valid, exclude, E, ld_ex, K, idx, score, workspace,
+                        workspace_bytes, stream);
 }

@@ -270,17 +270,22 @@ def compute_scores_listwise(model, corpus, sizes, batch_size, candidates_per_row
 # Every form above scores (impression, candidate) pairs that the behaviours file chose.  recommend answers the other question: the K news of
 # a pool that the model ranks highest for a user.  With cacheable news representations, ONE user vector per row and the dot-product head
 # that is [users, D] x [news, D] -> [users, K], which nnr_topk_scores computes without the [users, news] scores ever existing.
-def recommend_refusal(model):
-    """None when recommend can serve `model`, else the reason it cannot."""
+# OMAP is candidate-aware only behind its K archives (pool_archives): the same product once per archive, combined per pair (nnr_topk_archive_scores).
+def recommend_refusal(model, archives=False):
+    """None when recommend can serve `model`, else the reason it cannot.  archives: the caller's `archives` keyword -- True admits a
+    pool_archives user encoder (OMAP), whose pool is ranked on its candidate-free archives; False, the default, keeps the answer recommend
+    has always given for it."""
     ne, ue = model.news_encoder, model.user_encoder
     if getattr(model, 'click_predictor', 'dot_product') != 'dot_product':
         return ('recommend ranks a pool by inner products of one user vector with the news representations (the dot_product click predictor): '
                 'this model\'s click predictor is %s' % model.click_predictor)
     if not news_reps_cacheable(model):
         return LISTWISE_REFUSAL % type(ne).__name__
-    if not ue.candidate_independent:
-        return ('recommend needs ONE user vector per behaviour row (candidate_independent: ATT, MHSA, GRU, PUE, SUE_wo_HCA): the user vector of '
-                '%s is a function of the candidate, so a pool-wide search would need one encoder run per (user, news)' % type(ue).__name__)
+    if not ue.candidate_independent and not (archives and ue.pool_archives):
+        return ('recommend needs ONE user vector per behaviour row (candidate_independent: ATT, MHSA, GRU, PUE, SUE_wo_HCA) or, with '
+                'archives=True, candidate-free archives whose inner products give the score (pool_archives: OMAP): the user vector of %s is a '
+                'function of the candidate, so a pool-wide search would need one encoder run per (user, news)%s'
+                % (type(ue).__name__, ' -- unless it is ranked on its archives: pass archives=True' if ue.pool_archives else ''))
     return None
 
 
@@ -304,10 +309,32 @@ def _pool_rows(name, corpus, rows, pool):
     return rows, pool, V
 
 
-def _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_users, *extra):
+def _archive_table(model, reps, hmask, slot_h, batch_size):
+    """The archive table [R, A * D] of a pool_archives encoder (OMAP) for R behaviour rows (hmask [R, H]; slot_h [R, H]: the rows of `reps` of
+    the history news): row r holds the A archives of encode_archives, one after the other; `batch_size` rows per encode_archives call."""
+    ue, (R, D) = model.user_encoder, (hmask.shape[0], reps.shape[1])
+    table = None
+    for s in range(0, R, batch_size):
+        e = min(s + batch_size, R)
+        arch = ue.encode_archives(reps[slot_h[s:e]], hmask[s:e].contiguous())             # [r, A, D]
+        if table is None:
+            table = torch.empty((R, arch.shape[1] * D), device=reps.device, dtype=torch.float32)
+        table[s:e] = arch.reshape(e - s, -1)
+    return table
+
+
+def _archive_args(model, archives):
+    """The archive keywords of ops.topk_scores / ops.pool_ranks for `model` under the caller's `archives` keyword: none for an encoder of one
+    vector per row."""
+    ue = model.user_encoder
+    return dict(archives=int(ue.OMAP_head_num), scale=float(ue.archive_scale)) if archives and ue.pool_archives else {}
+
+
+def _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_users, archives, *extra):
     """What recommend and rank_in_pool hand to their launch (model in eval mode): the distinct news of the histories, the pool and `extra`
     (further vectors of news indices) are encoded once into `reps` (row i = news used[i], ascending), the user encoder runs once per row of
-    `rows` (once per distinct (user, history, mask) row with dedup_users) into `table`; valid marks the pool's rows of reps; exclude holds
+    `rows` (once per distinct (user, history, mask) row with dedup_users) into `table` (one vector per row; for a pool_archives encoder its A
+    archives per row, [rows, A * D], from one encode_archives call per batch of distinct rows); valid marks the pool's rows of reps; exclude holds
     the table rows of the live history slots with -1 in the dead ones (None unless exclude_history).  back: the user row of every entry of
     `rows` (None: its own position); slot_x: the rows of reps of each of `extra`."""
     t = corpus.t
@@ -316,7 +343,10 @@ def _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_u
     if dedup_users:
         users, hist, hmask, back = _distinct_rows(users, hist, hmask)
     used, reps, (slot_h, slot_p, *slot_x) = _news_table(model, corpus, hist, pool, *extra)
-    table = _user_table(model, corpus, reps, users, hist, hmask, slot_h, None, batch_size)
+    if archives and model.user_encoder.pool_archives:
+        table = _archive_table(model, reps, hmask, slot_h, batch_size)
+    else:
+        table = _user_table(model, corpus, reps, users, hist, hmask, slot_h, None, batch_size)
     valid = torch.zeros(used.numel(), device=corpus.device, dtype=torch.uint8)
     valid[slot_p] = 1
     exclude = torch.where(hmask, slot_h, -1).to(torch.int32).contiguous() if exclude_history else None      # a dead slot is -1
@@ -324,26 +354,29 @@ def _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_u
 
 
 @torch.no_grad()
-def recommend(model, corpus, K, rows=None, pool=None, exclude_history=True, batch_size=256, dedup_users=True, check=True):
+def recommend(model, corpus, K, rows=None, pool=None, exclude_history=True, batch_size=256, dedup_users=True, check=True, archives=False):
     """(news int64 [R, K], scores float32 [R, K]) on the device: for each of the behaviour rows `rows` of `corpus` (default: all) the K news of
     `pool` (news indices; default: every news of the corpus but PAD news 0) with the largest click scores, best first, equal scores by
     ascending position in the sorted table of distinct news (= ascending news index); -1 / -inf where the pool ran out.  exclude_history: a
     news in a live history slot of the row is not recommended to it.  The distinct news are encoded once, the user encoder runs once per
     row (once per distinct (user, history, mask) row with dedup_users), and ONE nnr_topk_scores launch ranks the pool.  1 <= K <= 64.
+    archives=True: a pool_archives encoder (OMAP) is served too -- a row is its A archives and the launch is nnr_topk_archive_scores: the
+    click score as the softmax-weighted sum over the archives' inner products.  Without it such a model is refused as
+    every candidate-aware one, which is what recommend did before the archive form existed; other models are served the same either way.
     Refused (NnrHipError naming the reason, recommend_refusal) for news encoders whose representations cannot be cached, user encoders
-    whose vector depends on the candidate, and any click predictor but dot_product."""
-    why = recommend_refusal(model)
+    whose vector depends on the candidate other than through such archives, and any click predictor but dot_product."""
+    why = recommend_refusal(model, archives)
     if why is not None:
         raise L.NnrHipError(why)
     rows, pool, _ = _pool_rows('recommend', corpus, rows, pool)
     with eval_mode(model):
-        table, reps, used, valid, exclude, back, _ = _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_users)
-        idx, scores = ops.topk_scores(table, reps, K, valid=valid, exclude=exclude, check=check)
+        table, reps, used, valid, exclude, back, _ = _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_users, archives)
+        idx, scores = ops.topk_scores(table, reps, K, valid=valid, exclude=exclude, check=check, **_archive_args(model, archives))
         news = torch.where(idx >= 0, used[idx.long().clamp_min(0)], -1)
         if back is not None:
             news, scores = news[back], scores[back]
     LAST_STATS.update(mode='recommend', rows=int(rows.numel()), user_rows=int(table.shape[0]), encoder_rows=int(used.numel()),
-                      pool=int(pool.numel()), K=int(K))
+                      pool=int(pool.numel()), K=int(K), archives=_archive_args(model, archives).get('archives', 1))
     return news, scores
 
 
@@ -384,15 +417,17 @@ def pool_rank_metrics(ahead, pool_size, ks=(5, 10)):
 
 
 @torch.no_grad()
-def rank_in_pool(model, corpus, rows, targets, pool=None, exclude_history=True, ks=(5, 10), batch_size=256, dedup_users=True, check=True):
+def rank_in_pool(model, corpus, rows, targets, pool=None, exclude_history=True, ks=(5, 10), batch_size=256, dedup_users=True, check=True,
+                 archives=False):
     """(ahead int32 [R], pool_size int32 [R], metrics) for the behaviour rows `rows` of `corpus` (repeats allowed) and one target news index per
     entry of `rows`: ahead[i] = the number of eligible news of `pool` that the model ranks before targets[i] for rows[i] -- the number of
     entries recommend's list would hold before it, with recommend's pool, history exclusion and tie order --, -1 when the target is itself
     not eligible for the row (outside the pool, or in a live history slot with exclude_history); pool_size[i] = the row's eligible news.
     Both on the device, in the order of `rows`.  metrics: pool_rank_metrics over the counted targets, Python numbers.  Other targets of the
     same row count as ahead of a target when they precede it.  The path is recommend's (news encoded once, the user encoder once per
-    distinct row), followed by ONE nnr_pool_ranks launch; refused for the models recommend refuses, with recommend_refusal's words."""
-    why = recommend_refusal(model)
+    distinct row), followed by ONE nnr_pool_ranks launch (nnr_pool_archive_ranks for OMAP with archives=True, as in recommend); refused for
+    the models recommend refuses, with recommend_refusal's words."""
+    why = recommend_refusal(model, archives)
     if why is not None:
         raise L.NnrHipError(why)
     rows, pool, V = _pool_rows('rank_in_pool', corpus, rows, pool)
@@ -401,19 +436,19 @@ def rank_in_pool(model, corpus, rows, targets, pool=None, exclude_history=True, 
     if targets.numel() != rows.numel():
         raise ValueError('rank_in_pool: %d targets for %d rows (one target per entry of rows)' % (targets.numel(), rows.numel()))
     with eval_mode(model):
-        table, reps, used, valid, exclude, back, (slot_t,) = _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_users, targets)
+        table, reps, used, valid, exclude, back, (slot_t,) = _pool_inputs(model, corpus, rows, pool, exclude_history, batch_size, dedup_users, archives, targets)
         urow = back if back is not None else torch.arange(rows.numel(), device=dev)
         order = torch.argsort(urow, stable=True)                                # the targets grouped by user row
         t_off = torch.zeros(table.shape[0] + 1, device=dev, dtype=torch.int64)
         t_off[1:] = torch.cumsum(torch.bincount(urow, minlength=table.shape[0]), dim=0)
         a, _, psz = ops.pool_ranks(table, reps, t_off.to(torch.int32), slot_t[order].to(torch.int32).contiguous(), valid=valid, exclude=exclude,
-                                   check=check)
+                                   check=check, **_archive_args(model, archives))
         ahead = torch.empty_like(a)
         ahead[order] = a                                                        # back into the order of `rows`
         pool_size = psz[urow]
         metrics = pool_rank_metrics(ahead, pool_size, ks)
     LAST_STATS.update(mode='rank_in_pool', rows=int(rows.numel()), user_rows=int(table.shape[0]), encoder_rows=int(used.numel()),
-                      pool=int(pool.numel()), targets=int(targets.numel()))
+                      pool=int(pool.numel()), targets=int(targets.numel()), archives=_archive_args(model, archives).get('archives', 1))
     return ahead, pool_size, metrics
 
 

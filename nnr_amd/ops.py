@@ -1449,14 +1449,59 @@ def _tables_finite(user, reps):
     return torch.isfinite(user).all() & torch.isfinite(reps).all()
 
 
-def topk_scores(user, reps, K, valid=None, exclude=None, check=True):
+def _archive_tables(name, user, reps, valid, exclude, archives, lda):
+    """The archive form's user table (nnr_topk_archive_scores, include/nnr_hip.h) as _pool_tables sees it: `user` is [n_user, A, D] (unit
+    stride along D, any stride lda >= D between archives) or [n_user, >= (A - 1) * lda + D] with archive a of a row at columns a * lda ..
+    (lda defaults to D).  Returns (_pool_tables' tuple with the archive-aware ldu, lda, the [n_user, A, D] view that the launch reads)."""
+    A = archives
+    if not isinstance(A, int) or isinstance(A, bool) or A < 1:
+        raise L.NnrHipError('%s: archives = %r (an integer from 1 to 16)' % (name, A))
+    D = reps.shape[1] if reps.dim() == 2 else -1
+    if user.dim() == 3 and tuple(user.shape[1:]) == (A, D) and lda in (None, user.stride(1)):
+        lda = user.stride(1) if A > 1 else D
+        first = user[:, 0, :]
+    elif user.dim() == 2 and D >= 1 and (D if lda is None else lda) >= D and user.shape[1] >= (A - 1) * (D if lda is None else lda) + D:
+        lda = D if lda is None else int(lda)
+        first = user[:, :D]
+    else:
+        raise L.NnrHipError('%s: with archives = %d the user table is [n_user, %d, D] or [n_user, (archives - 1) * lda + D and more] with '
+                            'lda >= D = the width of reps (got %r, lda %r, reps %r)' % (name, A, A, tuple(user.shape), lda, tuple(reps.shape)))
+    t = _pool_tables(name, first, reps, valid, exclude)
+    n_user, D, ldu = t[0], t[2], t[3]
+    if n_user == 1:
+        ldu = (A - 1) * lda + D
+    if lda < D or ldu < (A - 1) * lda + D:
+        raise L.NnrHipError('%s: overlapping archives (lda %d, row stride %d for %d archives of width %d)' % (name, lda, ldu, A, D))
+    return t[:3] + (ldu,) + t[4:], lda, first.as_strided((n_user, A, D), (ldu, lda, 1))
+
+
+def _archive_scale(name, scale):
+    scale = float(scale)
+    if scale != scale or scale in (float('inf'), float('-inf')):
+        raise L.NnrHipError('%s: scale = %r is not finite' % (name, scale))
+    return scale
+
+
+_ARCHIVES_UNSUPPORTED = 'archives = %d is unsupported beyond 16 (the OMAP kernels\' own limit on their archives); '
+
+
+def topk_scores(user, reps, K, valid=None, exclude=None, check=True, archives=1, lda=None, scale=0.0):
     """(idx int32 [n_user, K], score float32 [n_user, K]): for every user row the K eligible rows of `reps` with the largest <user, reps row>,
     by score descending, equal scores by ascending row; idx = -1 / score = -inf where fewer than K rows are eligible (nnr_topk_scores,
     include/nnr_hip.h, which states the summation order).  user [n_user, D] and reps [n_reps, D] float32 with unit column stride (any row stride
     >= D); valid: bool / uint8 [n_reps], nonzero = in the pool, or None; exclude: int32 [n_user, E] (unit column stride) of rows a user must
     not get, entries outside 0 .. n_reps - 1 (a -1 pad) ignored, or None.  1 <= K <= 64.  The [n_user, n_reps] scores never exist.  The
-    tables are finite by contract: check=True verifies that (two reductions, one sync) and raises before the launch."""
-    n_user, n_reps, D, ldu, ldr, exclude, E, ld_ex = _pool_tables('topk_scores', user, reps, valid, exclude)
+    tables are finite by contract: check=True verifies that (two reductions, one sync) and raises before the launch.
+    archives = A > 1 (or a 3-D user table): the archive form, nnr_topk_archive_scores -- a user row is A vectors ([n_user, A, D], or
+    [n_user, A * D] with the archives `lda` = D columns apart) and the score of a pair is sum_a w_a <user[u, a], reps row> with
+    w = softmax_a(scale * <user[u, a], reps row>), by the operation sequence the header states.  With archives == 1 and a 2-D table the
+    plain entry point is called, exactly as without these keywords."""
+    arch = type(archives) is not int or archives != 1 or user.dim() == 3
+    if arch:
+        (n_user, n_reps, D, ldu, ldr, exclude, E, ld_ex), lda, user = _archive_tables('topk_scores', user, reps, valid, exclude, archives, lda)
+        scale = _archive_scale('topk_scores', scale)
+    else:
+        n_user, n_reps, D, ldu, ldr, exclude, E, ld_ex = _pool_tables('topk_scores', user, reps, valid, exclude)
     if not isinstance(K, int) or K < 1:
         raise L.NnrHipError('topk_scores: K = %r (an integer from 1 to 64)' % (K,))
     _p(user), _p(reps), _p(valid), _p(exclude)
@@ -1466,20 +1511,31 @@ def topk_scores(user, reps, K, valid=None, exclude=None, check=True):
     score = torch.empty((n_user, K), device=user.device, dtype=torch.float32)
     nbytes = L.lib().nnr_topk_workspace_bytes(n_user, n_reps, K)
     ws = _topk_ws(user.device, nbytes)
+    if arch:
+        L.check(L.lib().nnr_topk_archive_scores(_p(user), n_user, ldu, archives, lda, scale, _p(reps), n_reps, ldr, D, _p(_u8(valid)), _p(exclude),
+                                                E, ld_ex, K, _p(idx), _p(score), _p(ws), nbytes, _s()), 'nnr_topk_archive_scores',
+                unsupported=_ARCHIVES_UNSUPPORTED % archives + 'so are K = %d beyond 64 and 2^31 news rows and more' % K)
+        return idx, score
     L.check(L.lib().nnr_topk_scores(_p(user), n_user, ldu, _p(reps), n_reps, ldr, D, _p(_u8(valid)), _p(exclude), E, ld_ex, K, _p(idx), _p(score),
                                     _p(ws), nbytes, _s()), 'nnr_topk_scores', unsupported='K = %d is unsupported beyond 64 (a running list is one entry per lane of a wave), as are 2^31 news rows and more' % K)
     return idx, score
 
 
-def pool_ranks(user, reps, t_off, t_news, valid=None, exclude=None, check=True):
+def pool_ranks(user, reps, t_off, t_news, valid=None, exclude=None, check=True, archives=1, lda=None, scale=0.0):
     """(ahead int32 [T], t_score float32 [T], pool_size int32 [n_user]): where the targets land when each user's whole pool is ranked
     (nnr_pool_ranks, include/nnr_hip.h).  user, reps, valid and exclude as for topk_scores, with its eligibility rule.  t_off: int32
     [n_user + 1], non-decreasing from 0 to T; t_news: int32 [T], rows of `reps`; entries t_off[u] .. t_off[u + 1] - 1 are the targets of user
     row u (none, many, repeats).  ahead[j] = the number of eligible rows that topk_scores would place before target j (greater score, or equal
     score and smaller row), -1 when the target is itself ineligible for its user; t_score[j] = its score, with the bits topk_scores returns;
     pool_size[u] = the user's eligible rows.  check=True verifies that the tables are finite, t_off is ordered from 0 to T and t_news lies
-    inside the table (reductions on the device, one sync) and raises before the launch."""
-    n_user, n_reps, D, ldu, ldr, exclude, E, ld_ex = _pool_tables('pool_ranks', user, reps, valid, exclude)
+    inside the table (reductions on the device, one sync) and raises before the launch.  archives, lda, scale: the archive form
+    (nnr_pool_archive_ranks), with topk_scores' table layout and score; archives == 1 with a 2-D table calls the plain entry point."""
+    arch = type(archives) is not int or archives != 1 or user.dim() == 3
+    if arch:
+        (n_user, n_reps, D, ldu, ldr, exclude, E, ld_ex), lda, user = _archive_tables('pool_ranks', user, reps, valid, exclude, archives, lda)
+        scale = _archive_scale('pool_ranks', scale)
+    else:
+        n_user, n_reps, D, ldu, ldr, exclude, E, ld_ex = _pool_tables('pool_ranks', user, reps, valid, exclude)
     if (t_off.dtype != torch.int32 or t_news.dtype != torch.int32 or t_off.dim() != 1 or t_news.dim() != 1
             or not (t_off.is_contiguous() and t_news.is_contiguous())):
         raise L.NnrHipError('pool_ranks: t_off and t_news must be contiguous int32 vectors')
@@ -1503,6 +1559,12 @@ def pool_ranks(user, reps, t_off, t_news, valid=None, exclude=None, check=True):
     pool_size = torch.empty(n_user, device=dev, dtype=torch.int32)
     nbytes = L.lib().nnr_pool_rank_workspace_bytes(n_user, n_reps, T)
     ws = _topk_ws(dev, nbytes)
+    if arch:
+        L.check(L.lib().nnr_pool_archive_ranks(_p(user), n_user, ldu, archives, lda, scale, _p(reps), n_reps, ldr, D, _p(_u8(valid)), _p(exclude),
+                                               E, ld_ex, _p(t_off), _p(t_news) if T else None, T, _p(ahead) if T else None,
+                                               _p(t_score) if T else None, _p(pool_size), _p(ws), nbytes, _s()), 'nnr_pool_archive_ranks',
+                unsupported=_ARCHIVES_UNSUPPORTED % archives + 'so are 2^31 user rows, news rows or targets and more')
+        return ahead, t_score, pool_size
     L.check(L.lib().nnr_pool_ranks(_p(user), n_user, ldu, _p(reps), n_reps, ldr, D, _p(_u8(valid)), _p(exclude), E, ld_ex, _p(t_off),
                                    _p(t_news) if T else None, T, _p(ahead) if T else None, _p(t_score) if T else None, _p(pool_size), _p(ws),
                                    nbytes, _s()), 'nnr_pool_ranks', unsupported='2^31 user rows, news rows or targets and more are unsupported')

@@ -25,6 +25,9 @@ class UserEncoder(nn.Module):
     candidate_independent = False        # True: encode_user expands ONE vector per user over the candidates and never reads them (listwise evaluation
                                          # then encodes a user once per impression, evaluate.compute_scores_listwise)
     needs_history_graph = False          # True: encode_user reads the graph / cluster inputs (evaluate._encoded_users builds them per batch)
+    pool_archives = False                # True: the click score of a (user, news) pair is a softmax-weighted sum over the inner products of the
+                                         # news with A candidate-free vectors per user (encode_archives, archive_scale): with archives=True evaluate.recommend
+                                         # and rank_in_pool rank a whole pool for such an encoder although it is not candidate_independent
 
     def __init__(self, news_encoder: NewsEncoder, config):
         super().__init__()
@@ -709,24 +712,30 @@ class CATT(UserEncoder):
         return _CandAttnFn.apply(history_embedding, candidate_news_representation, self, user_history_mask)
 
 
+def _omap_forward(mod, hist, cand, mask):
+    """nnr_omap_fwd for hist [B, H, D], cand [B, N, D], mask [B, H] or None: (x, c, mask as passed on, alpha, Y, beta, R, gamma, out, sizes)."""
+    B, H, D = hist.shape
+    N, K = cand.shape[1], mod.OMAP_head_num
+    x = hist if hist.stride(2) == 1 and hist.stride(0) == H * hist.stride(1) else hist.contiguous()
+    c = cand.contiguous()
+    if mask is not None:
+        mask = (mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0).contiguous()
+    W = mod.W.detach()
+    f32 = dict(device=x.device, dtype=torch.float32)
+    alpha, Y, beta = torch.empty((B, H, H), **f32), torch.empty((B, H, D), **f32), torch.empty((B, H, K), **f32)
+    R, gamma, out = torch.empty((B, K, D), **f32), torch.empty((B, N, K), **f32), torch.empty((B, N, D), **f32)
+    ops.omap_fwd(x, c, mask, W, B, N, H, D, K, alpha, Y, beta, R, gamma, out)
+    return x, c, mask, alpha, Y, beta, R, gamma, out, (B, N, H, D, K)
+
+
 class _OmapFn(torch.autograd.Function):
     """hist [B, H, D], cand [B, N, D], mask [B, H] -> [B, N, D] on the kernels of csrc/omap.hip (three launches forward, four backward).  alpha,
     Y = X + alpha X, beta, the archives and gamma are saved; dW goes straight into W.grad."""
 
     @staticmethod
     def forward(ctx, hist, cand, mod, mask):
-        B, H, D = hist.shape
-        N, K = cand.shape[1], mod.OMAP_head_num
-        x = hist if hist.stride(2) == 1 and hist.stride(0) == H * hist.stride(1) else hist.contiguous()
-        c = cand.contiguous()
-        if mask is not None:
-            mask = (mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0).contiguous()
-        W = mod.W.detach()
-        f32 = dict(device=x.device, dtype=torch.float32)
-        alpha, Y, beta = torch.empty((B, H, H), **f32), torch.empty((B, H, D), **f32), torch.empty((B, H, K), **f32)
-        R, gamma, out = torch.empty((B, K, D), **f32), torch.empty((B, N, K), **f32), torch.empty((B, N, D), **f32)
-        ops.omap_fwd(x, c, mask, W, B, N, H, D, K, alpha, Y, beta, R, gamma, out)
-        ctx.mod, ctx.saved = mod, (x, c, mask, alpha, Y, beta, R, gamma, (B, N, H, D, K))
+        x, c, mask, alpha, Y, beta, R, gamma, out, sizes = _omap_forward(mod, hist, cand, mask)
+        ctx.mod, ctx.saved = mod, (x, c, mask, alpha, Y, beta, R, gamma, sizes)
         return out
 
     @staticmethod
@@ -765,7 +774,11 @@ class OMAP(UserEncoder):
     the heads, one user vector per candidate from a softmax over the archives.  Observable quirks kept: a padded history row has beta = 1/K and
     adds Y[i] / K to every archive; a user without history has alpha = 1/H; masked scores pass no gradient.  In train mode every call
     rewrites `auxiliary_loss` = coefficient * ||(W^T W) o (J_K - I_K)||_F (a 0-dim tensor that carries its own backward); in eval mode it is
-    left as it was.  state_dict: W (J_k / I_k are plain attributes, as in the reference)."""
+    left as it was.  state_dict: W (J_k / I_k are plain attributes, as in the reference).
+    pool_archives: the user vector is gamma R with gamma = softmax_k(<R_k, n> / scalar), so the click score <gamma R, n> is
+    sum_k gamma_k <R_k, n>: a function of the candidate's inner products with the K archives, which do not depend on it (encode_archives;
+    archive_scale = 1 / scalar).  evaluate.recommend / rank_in_pool rank a whole pool on that form when asked to (archives=True)."""
+    pool_archives = True
 
     def __init__(self, news_encoder: NewsEncoder, config):
         super().__init__(news_encoder, config)
@@ -773,6 +786,7 @@ class OMAP(UserEncoder):
         self.OMAP_head_num = int(config.OMAP_head_num)
         self.HiFi_Ark_regularizer_coefficient = float(config.HiFi_Ark_regularizer_coefficient)
         self.scalar = math.sqrt(float(self.news_embedding_dim))
+        self.archive_scale = 1.0 / self.scalar
         self.W = nn.parameter.Parameter(torch.zeros([self.news_embedding_dim, self.OMAP_head_num]))
         self.J_k = torch.ones([self.OMAP_head_num, self.OMAP_head_num])
         self.I_k = torch.eye(self.OMAP_head_num)
@@ -786,6 +800,16 @@ class OMAP(UserEncoder):
         if self.training:
             self.auxiliary_loss = _OmapRegFn.apply(self.W, self)
         return user_representation
+
+    @torch.no_grad()
+    def encode_archives(self, history_embedding, user_history_mask):
+        """The archives R [B, K, D] that encode_user computes for this history [B, H, D] and mask [B, H], with its bits: the forward entry
+        point on one blank candidate per user (R never reads the candidates, and its summation order depends on neither N nor B), the
+        quirks included (a padded row adds Y[i] / K to every archive; a user without history has alpha = 1 / H).  No autograd, and
+        `auxiliary_loss` stays as it was."""
+        B, _, D = history_embedding.shape
+        blank = torch.zeros((B, 1, D), device=history_embedding.device, dtype=torch.float32)
+        return _omap_forward(self, history_embedding.detach(), blank, user_history_mask)[6]
 
 
 class PUE(UserEncoder):
