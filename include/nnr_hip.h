@@ -76,14 +76,13 @@ typedef struct nnr_gemm_args {
   int k_chunk;              /* > 0: like split_k but with fixed-size slices of k_chunk reduction rows (multiple of 32): the number of
                                live slices follows the device-side K; atomicAdd into a pre-zeroed / running C */
   float* colsum_out;        /* trans_a only: colsum_out[m] += sum_k A[k][m]  (fused bias gradient, f32 atomics) */
-  int tile;                 /* 0 auto, 1: 256x80, 2: 64x80, 3: 128x208, 4: 128x80, 5: 128x80 with BK=32, 6: 64x80 with BK=64,
-                             * 7: 16x80 skinny (K split over the waves; plain NT / NN launches only) */
+  int tile;                 /* 0: the library chooses (csrc/gemm.hip: choose_tile); else a row of csrc/gemm.hip's tile table kTiles, which states
+                             * each id's kernel, shape and what it accepts (nnr_gemm_tile_info lists the rows): 2 3 4 5 6 register-staged,
+                             * 7 skinny, 9 15 16 LDS-DMA NT, 20 26 27 30 32 LDS-DMA TN, 50 51 bf16x3 NT.  NNR_ERR_ARG when the row refuses the launch */
   /* filled by the library */
   uint32_t drop_thresh;
   float drop_scale;
   int vec_epi;
-  int sched;                /* token-reduction (split-K) launches: bits 0-1 how workgroups are dealt to the XCDs, bits 2-7 / 8+ tuning
-                             * overrides of the device-side slice count (workgroup target / stages per slice; 0 = defaults) */
   /* reproducible split-K (trans_a = trans_b = 1, split_k > 1, N % 4 == 0): with `slab` set, slice z STORES its partial M x N result to
    * slab[z] and a second launch adds the live slices in slice order into C (and the fused column sums into colsum_out): no f32
    * atomics inside the reduction, bit-identical gradients from run to run (config.py:125-130).  slab_floats >= split_k * (M * N + M). */
@@ -107,6 +106,14 @@ typedef struct nnr_gemm_args {
 } nnr_gemm_args;
 
 int nnr_gemm_f32(const nnr_gemm_args* args, hipStream_t stream);
+/* Host-only: the tile id nnr_gemm_f32 would launch for these arguments (0: an empty product, nothing runs), or the negative code with which it
+ * would refuse them.  Dereferences none of the data pointers. */
+int nnr_gemm_tile_for(const nnr_gemm_args* args);
+/* Host-only: row `index` (0, 1, ... until NNR_ERR_ARG) of the tile table for one operand layout.  dims[6] = id, rows, cols, reduction depth of a
+ * stage, stage buffers, workgroups per CU the kernel is built for (0: no launch bound); suffix: the live profile's family is
+ * gemm_<nt | nn | tn>_<suffix>; kernel: the instantiation as rocprofv3 prints it ("" for the skinny tile, which picks its wave count per launch).
+ * cap >= 64 bytes each.  NNR_ERR_UNSUPPORTED: the row has no kernel for this layout. */
+int nnr_gemm_tile_info(int index, int trans_a, int trans_b, int* dims, char* suffix, char* kernel, int cap);
 /* w [rows, cols] (row stride ld) -> three bf16 images out3[i * img_stride + r * ldo + c] with w == image0 + image1 + image2 EXACTLY (columns
  * cols .. ldo-1 zero).  For nnr_gemm_args.B3 (experimental tile 50); weights change once per optimizer step. */
 int nnr_split_bf16x3(const float* w, int rows, int cols, int ld, int ldo, void* out3, long img_stride, hipStream_t stream);

@@ -1,7 +1,9 @@
 """ctypes binding of libnnr_hip.so (include/nnr_hip.h).  No torch types cross the boundary: only raw device
 pointers, sizes and the HIP stream handle.  The product path has NO fallback: if the library is missing or a call
 fails, an exception is raised."""
+import collections
 import ctypes as C
+import itertools
 import os
 import subprocess
 
@@ -20,7 +22,11 @@ class GemmArgs(C.Structure):
                 ('ldmul', ci), ('resid', vp), ('ldres', ci), ('accumulate', ci), ('atomic', ci), ('c_idx', vp),
                 ('split_k', ci), ('rowdot_w', vp), ('rowdot_out', vp), ('batch', ci), ('strideA', cl), ('strideB', cl),
                 ('strideC', cl), ('stride_aux', cl), ('stride_res', cl), ('k_chunk', ci), ('colsum_out', vp), ('tile', ci), ('drop_thresh', cu32),
-                ('drop_scale', cf), ('vec_epi', ci), ('sched', ci), ('slab', vp), ('slab_floats', cl), ('slab_mode', ci), ('pre_add', vp), ('ldpre', ci), ('gate_bwd', ci), ('B3', vp), ('b3_stride', cl), ('ldb3', ci)]
+                ('drop_scale', cf), ('vec_epi', ci), ('slab', vp), ('slab_floats', cl), ('slab_mode', ci), ('pre_add', vp), ('ldpre', ci), ('gate_bwd', ci), ('B3', vp), ('b3_stride', cl), ('ldb3', ci)]
+
+
+GemmTile = collections.namedtuple('GemmTile', 'rows cols bk stages occ suffix kernels')
+NNR_ERR_ARG, NNR_ERR_UNSUPPORTED = -1, -3
 
 
 class LstmProblem(C.Structure):
@@ -60,6 +66,8 @@ class PoolArgs(C.Structure):
 SIGNATURES = {
     'nnr_version': 'i32',
     'nnr_gemm_f32': 'i32 GemmArgs stream',
+    'nnr_gemm_tile_for': 'i32 GemmArgs',
+    'nnr_gemm_tile_info': 'i32 i32 i32 i32 ptr cstr cstr i32',
     'nnr_split_bf16x3': 'i32 ptr i32 i32 i32 i32 ptr i64 stream',
     'nnr_seq_plan': 'i32 ptr ptr i32 i32 ptr ptr ptr ptr ptr ptr ptr ptr ptr ptr ptr stream',
     'nnr_seq_plan_pair': 'i32 ptr ptr i32 ptr ptr i32 i32 ptr ptr ptr ptr ptr ptr ptr ptr ptr ptr ptr stream',
@@ -277,6 +285,31 @@ def lib():
     return _lib
 
 
+_tiles = None
+
+
+def gemm_tiles():
+    """csrc/gemm.hip's tile table, read once: {tile id: GemmTile}.  `kernels` maps each operand layout the row has kernels for ('nt', 'nn',
+    'tn') to the instantiation as rocprofv3 prints it ('' for the skinny tile); the live profile's family is 'gemm_<layout>_<suffix>'."""
+    global _tiles
+    if _tiles is None:
+        tiles, dims, suffix, kernel = {}, (ci * 6)(), C.create_string_buffer(64), C.create_string_buffer(64)
+        for index in itertools.count():
+            kernels = {}
+            for lay, ta, tb in (('nt', 0, 0), ('nn', 0, 1), ('tn', 1, 1)):
+                rc = lib().nnr_gemm_tile_info(index, ta, tb, dims, suffix, kernel, 64)
+                if rc == 0:
+                    kernels[lay] = kernel.value.decode()
+                elif rc != NNR_ERR_UNSUPPORTED:
+                    break
+            else:
+                tiles[dims[0]] = GemmTile(*dims[1:], suffix.value.decode(), kernels)
+                continue
+            break                           # NNR_ERR_ARG: past the last row
+        _tiles = tiles
+    return _tiles
+
+
 def build_id():
     """Identity of the kernels that are running: sha256 over the sources libnnr_hip.so is built from (csrc/*.hip, common.h, the
     header) and, separately, over the loaded binary.  profiles/pmc_traffic.json carries both: counter traffic collected on another
@@ -293,7 +326,6 @@ def build_id():
     return {'src_sha256': h.hexdigest()[:16], 'lib_sha256': lib_hash}
 
 
-NNR_ERR_ARG, NNR_ERR_UNSUPPORTED = -1, -3
 CALLS = [0]          # C-ABI calls checked so far (bench.py reports calls per step; each is one or a few kernel launches)
 
 

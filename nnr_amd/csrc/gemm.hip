@@ -16,6 +16,7 @@
 //   (embedding gradient), split-K with atomics for the token-reduction GEMMs, dynamic token count read from
 //   device memory (no host sync).
 #include "common.h"
+#include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 
@@ -497,14 +498,6 @@ __device__ __forceinline__ void lds_dma16(const float* gsrc, unsigned lds_dst) {
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
-__device__ __forceinline__ void set_prio_dyn(unsigned p) {      // s_setprio takes an immediate
-  switch (p & 3) {
-    case 0: __builtin_amdgcn_s_setprio(0); break;
-    case 1: __builtin_amdgcn_s_setprio(1); break;
-    case 2: __builtin_amdgcn_s_setprio(2); break;
-    default: __builtin_amdgcn_s_setprio(3); break;
-  }
-}
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
@@ -518,15 +511,8 @@ __device__ __forceinline__ void wait_stages(int ahead) {
   }
 }
 
-template <int TM, int TN, int BK, int NS, int OCC, int PRIO = 0>
+template <int TM, int TN, int BK, int NS, int OCC>
 __global__ __launch_bounds__(256, OCC) void gemm_nt_pipe_kernel(nnr_gemm_args g) {
-  // PRIO 1: static, distinct wave priorities for the workgroups that (most likely) share a CU.  With equal priorities the SIMD
-  // interleaves the MFMAs of its resident waves instruction by instruction, so they all reach their per-stage wait + barrier +
-  // fragment-read phase together and the matrix pipe idles through it; with distinct priorities one wave runs its stage at full
-  // rate while the others queue, and the phases stay staggered.
-  if (PRIO == 1) set_prio_dyn(blockIdx.x >> 8);
-  if (PRIO == 2) set_prio_dyn(blockIdx.x >> 5);
-  if (PRIO == 3) set_prio_dyn(blockIdx.x);
   constexpr int BM = 64 * TM, BN = 16 * TN, ROWS = BM + BN;
   constexpr int KQ = BK / 4, NKG = BK / 16;             // 16-byte chunks per row; 16-deep k-groups per stage
   constexpr int RPI = 64 / KQ;                          // tile rows one DMA instruction covers (1 KiB)
@@ -621,7 +607,7 @@ __global__ __launch_bounds__(256, OCC) void gemm_nt_pipe_kernel(nnr_gemm_args g)
   // wholly beyond N (2 of 5 at N = 200: 13 % of the launch's matrix work; 1 of 5 at N = 300, 3 of 5 at N = 900: 5 %) only ever multiplied clamped rows into
   // columns that are never stored.  Those workgroups take a second instantiation of the stage loop that skips them (uniform branches per tile); every
   // accumulator that IS stored sees the same MFMAs in the same order: results are bit-identical.
-  const int nv = (g.sched & 1) ? min(TN, (N - n0 + 15) >> 4) : TN;      // (g.sched bit 0: set by the launcher, kNtRagged)
+  const int nv = min(TN, (N - n0 + 15) >> 4);
   auto run = [&](auto full_tag) {
     constexpr bool FULL = decltype(full_tag)::value;
     for (int s = 0; s < S; ++s) {
@@ -802,8 +788,8 @@ __global__ __launch_bounds__(256, OCC) void gemm_nt_pipe2_kernel(nnr_gemm_args g
   // Ragged last column block / reduction tail (round 5; see gemm_nt_pipe_kernel): the workgroups of a last column block with nv < TN live 16-column tiles run a
   // second instantiation of the loop that skips the dead tiles; the last stage only multiplies the 16-deep k-groups / MFMA steps that hold a k < K (K = 900: 4 live k in the last stage, its second group is skipped).
   // Skipped MFMAs only ever added exact zeros / fed columns that are never stored: results are bit-identical.
-  const int nv = (g.sched & 1) ? min(TN, (N - n0 + 15) >> 4) : TN;
-  const int klast = (g.sched & 1) ? K - (S - 1) * BK : BK;         // valid reduction depth of the last stage (1 .. 32)
+  const int nv = min(TN, (N - n0 + 15) >> 4);
+  const int klast = K - (S - 1) * BK;         // valid reduction depth of the last stage (1 .. 32)
   auto run = [&](auto full_tag) {
     constexpr bool FULL = decltype(full_tag)::value;
     auto rd = [&](int s, int kg, f32x4 (&a)[TM], f32x4 (&b)[TN]) {
@@ -910,14 +896,9 @@ __global__ __launch_bounds__(256, OCC) void gemm_nt_pipe2_kernel(nnr_gemm_args g
   gemm_epilogue<TM, TN>(g, acc, lds, C, m0, n0, M, N, z);
 }
 
-// g.sched bit 0 of the NT pipe kernels: skip the empty fragments of a ragged last column block / reduction tail
-constexpr int kNtRagged = 1;
-
 template <int TM, int TN, int NS, int OCC>
-int launch_pipe2(const nnr_gemm_args& g0, hipStream_t s) {
+int launch_pipe2(const nnr_gemm_args& g, hipStream_t s) {
   constexpr int BM = 64 * TM, BN = 16 * TN;
-  nnr_gemm_args g = g0;
-  g.sched = kNtRagged;
   const int nbm = (g.M + BM - 1) / BM, nbn = (g.N + BN - 1) / BN;
   dim3 grid(nbm * nbn, 1, g.batch > 1 ? g.batch : 1), block(256);
   hipLaunchKernelGGL((gemm_nt_pipe2_kernel<TM, TN, NS, OCC>), grid, block, 0, s, g);
@@ -925,14 +906,12 @@ int launch_pipe2(const nnr_gemm_args& g0, hipStream_t s) {
   return NNR_OK;
 }
 
-template <int TM, int TN, int BK, int NS, int OCC, int PRIO = 0>
-int launch_pipe(const nnr_gemm_args& g0, hipStream_t s) {
+template <int TM, int TN, int BK, int NS, int OCC>
+int launch_pipe(const nnr_gemm_args& g, hipStream_t s) {
   constexpr int BM = 64 * TM, BN = 16 * TN;
-  nnr_gemm_args g = g0;
-  g.sched = kNtRagged;
   const int nbm = (g.M + BM - 1) / BM, nbn = (g.N + BN - 1) / BN;
   dim3 grid(nbm * nbn, 1, g.batch > 1 ? g.batch : 1), block(256);
-  hipLaunchKernelGGL((gemm_nt_pipe_kernel<TM, TN, BK, NS, OCC, PRIO>), grid, block, 0, s, g);
+  hipLaunchKernelGGL((gemm_nt_pipe_kernel<TM, TN, BK, NS, OCC>), grid, block, 0, s, g);
   NNR_CHECK_LAUNCH();
   return NNR_OK;
 }
@@ -1172,24 +1151,54 @@ int launch_bx3(const nnr_gemm_args& g, hipStream_t s) {
 // workgroup or two, rounded so that eff x nblk is a whole number of waves of resident workgroups (400 x 400 x 77 k tokens: 1 000
 // workgroups on 768 slots = 379 us, 740 or 1 520 = 279 / 293 us).  Shared by the kernels and by the slab reduction (same arithmetic,
 // same K: they agree on which slices exist).
-__device__ __forceinline__ int tn_eff_slices(int split_k, int sched, int K, int nblk, int slots) {
-  const int deal_mode = sched & 3;
-  const int want_wg = ((sched >> 2) & 63) ? ((sched >> 2) & 63) * 64 : 512;      // workgroups wanted at least (tuning knob, default 512)
-  const int slice_stages = (sched >> 8) ? (sched >> 8) : 96;                     // stages per slice aimed at (tuning knob)
+__device__ __forceinline__ int tn_eff_slices(int split_k, int K, int nblk, int slots) {
+  constexpr int want_wg = 512;          // workgroups wanted at least
+  constexpr int slice_stages = 96;      // stages per slice aimed at
   const int ktiles = (K + 15) / 16;
   const int want = (want_wg + nblk - 1) / nblk;
-  int eff = max(1, min(min(split_k, max(want, ktiles / slice_stages)), max(1, ktiles / 12)));
-  if (deal_mode != 2) {
-    const int W = eff * nblk, wv = W / slots;
-    const int target = W < slots ? slots : (((W - wv * slots) * 2 < slots) ? wv * slots : (wv + 1) * slots);
-    eff = max(1, min(target / nblk, min(split_k, max(1, ktiles / 12))));
-  }
-  return eff;
+  const int eff = max(1, min(min(split_k, max(want, ktiles / slice_stages)), max(1, ktiles / 12)));
+  const int W = eff * nblk, wv = W / slots;
+  const int target = W < slots ? slots : (((W - wv * slots) * 2 < slots) ? wv * slots : (wv + 1) * slots);
+  return max(1, min(target / nblk, min(split_k, max(1, ktiles / 12))));
 }
 
-template <int TM, int TN, int NS, int OCC, int PRIO = 0>
+// blockIdx -> (tile, reduction slice) of the LDS-DMA TN kernels; false: this workgroup has nothing to do.  The host sizes split_k for the
+// CAPACITY of the token buffers; the live reduction length (device side) is typically a fifth of it: use only as many slices (eff) as keep a
+// slice long enough to amortise its prologue and its atomic epilogue (~96 stages) while still giving every CU a workgroup or two; the surplus
+// workgroups exit.
+// With split-K the grid is 1-D and the eff x nblk workgroups, in slice-major order, are dealt to the XCDs in eight CONTIGUOUS
+// runs (XCD = blockIdx.x % 8 under round-robin placement; speed only): all tiles of a slice run on one XCD (a slice that
+// straddles a run boundary on two), so a token row of A and of B is pulled into one L2 instead of into every L2 whose
+// workgroups touch it -- 4-5x the operand bytes at the fabric counters for the 400 x 400 and 832 x 200 shapes when the tiles of
+// a slice are spread round-robin (profiles/pmc_traffic.json, round 2 first collection).
+__device__ __forceinline__ bool tn_place(int split_k, int K, int nbn, int nblk, int slots, int& bm, int& bn, int& z, int& kbeg, int& kend) {
+  constexpr int BK = 16;
+  int v;
+  z = 0;
+  kbeg = 0, kend = K;
+  if (split_k > 1) {
+    const int ktiles = (K + BK - 1) / BK;
+    const int eff = tn_eff_slices(split_k, K, nblk, slots);
+    const int W = eff * nblk, per = (W + 7) >> 3;
+    const int L = blockIdx.x, x = L & 7, slot = L >> 3;
+    const int lin = x * per + slot;
+    if (slot >= per || lin >= W) return false;
+    z = lin / nblk;
+    v = lin - z * nblk;
+    const int per_k = (ktiles + eff - 1) / eff;
+    kbeg = z * per_k * BK;
+    kend = min(K, kbeg + per_k * BK);
+    if (kbeg >= kend) return false;
+  } else {
+    const int b = blockIdx.x, q = nblk >> 3, rem = nblk & 7, x = b & 7, slot = b >> 3;
+    v = x * q + min(x, rem) + slot;
+  }
+  bm = v / nbn, bn = v - bm * nbn;
+  return true;
+}
+
+template <int TM, int TN, int NS, int OCC>
 __global__ __launch_bounds__(256, OCC) void gemm_tn_pipe_kernel(nnr_gemm_args g) {
-  if (PRIO == 1) set_prio_dyn((blockIdx.x + gridDim.x * blockIdx.z) >> 8);
   constexpr int BK = 16, BM = 64 * TM, BN = 16 * TN;
   constexpr int PA = BM, PB = BN <= 64 ? 64 : (BN <= 128 ? 128 : 256);
   constexpr int RA = 256 / PA, RB = 256 / PB;          // token rows per DMA instruction
@@ -1208,41 +1217,8 @@ __global__ __launch_bounds__(256, OCC) void gemm_tn_pipe_kernel(nnr_gemm_args g)
   if (g.dyn_dim == 2) K = min(K, *g.dyn_dev);
   const int nbm = (M + BM - 1) / BM, nbn = (N + BN - 1) / BN;
   const int nblk = nbm * nbn;
-  // blockIdx -> (tile, reduction slice).  The host sizes split_k for the CAPACITY of the token buffers; the live reduction length
-  // (device side) is typically a fifth of it: use only as many slices (eff) as keep a slice long enough to amortise its prologue
-  // and its atomic epilogue (~96 stages) while still giving every CU a workgroup or two; the surplus workgroups exit.
-  // With split-K the grid is 1-D and the eff x nblk workgroups, in slice-major order, are dealt to the XCDs in eight CONTIGUOUS
-  // runs (XCD = blockIdx.x % 8 under round-robin placement; speed only): all tiles of a slice run on one XCD (a slice that
-  // straddles a run boundary on two), so a token row of A and of B is pulled into one L2 instead of into every L2 whose
-  // workgroups touch it -- 4-5x the operand bytes at the fabric counters for the 400 x 400 and 832 x 200 shapes when the tiles of
-  // a slice are spread round-robin (profiles/pmc_traffic.json, round 2 first collection).  deal_mode 0 = that spread layout (A/B).
-  int v, z = 0;
-  int kbeg = 0, kend = K;
-  if (g.split_k > 1) {
-    const int deal_mode = g.sched & 3;                // set by the launcher
-    const int ktiles = (K + BK - 1) / BK;
-    const int eff = tn_eff_slices(g.split_k, g.sched, K, nblk, OCC * 256);
-    if (deal_mode) {
-      const int W = eff * nblk, per = (W + 7) >> 3;
-      const int L = blockIdx.x, x = L & 7, slot = L >> 3;
-      const int lin = x * per + slot;
-      if (slot >= per || lin >= W) return;
-      z = lin / nblk;
-      v = lin - z * nblk;
-    } else {
-      z = blockIdx.x / nblk;
-      v = blockIdx.x - z * nblk;
-      if (z >= eff) return;
-    }
-    const int per_k = (ktiles + eff - 1) / eff;
-    kbeg = z * per_k * BK;
-    kend = min(K, kbeg + per_k * BK);
-    if (kbeg >= kend) return;
-  } else {
-    const int b = blockIdx.x, q = nblk >> 3, rem = nblk & 7, x = b & 7, slot = b >> 3;
-    v = x * q + min(x, rem) + slot;
-  }
-  const int bm = v / nbn, bn = v - bm * nbn;
+  int bm, bn, z, kbeg, kend;
+  if (!tn_place(g.split_k, K, nbn, nblk, OCC * 256, bm, bn, z, kbeg, kend)) return;
   const int m0 = bm * BM, n0 = bn * BN;
   const float* __restrict__ A = g.A;
   const float* __restrict__ B = g.B;
@@ -1384,18 +1360,12 @@ __global__ __launch_bounds__(256, OCC) void gemm_tn_pipe_kernel(nnr_gemm_args g)
   gemm_epilogue<TM, TN>(g, acc, lds, g.slab_mode ? g.C + (long)z * M * N : g.C, m0, n0, M, N, z);
 }
 
-// g.sched of the split-K token reductions, as the kernels and the slab reduction read it: deal mode 1 (the tiles of a slice on one XCD),
-// default workgroup target (512) and stages per slice (96)
-constexpr int kTnSched = 1;
-
-template <int TM, int TN, int NS, int OCC, int PRIO = 0>
+template <int TM, int TN, int NS, int OCC>
 int launch_tn_pipe(const nnr_gemm_args& g, hipStream_t s) {
   constexpr int BM = 64 * TM, BN = 16 * TN;
   const int nbm = (g.M + BM - 1) / BM, nbn = (g.N + BN - 1) / BN;
   dim3 grid(g.split_k > 1 ? nbm * nbn * ((g.split_k + 7) / 8) * 8 : nbm * nbn), block(256);      // split-K: slices are dealt to XCDs (see the kernel)
-  nnr_gemm_args gg = g;
-  gg.sched = kTnSched;
-  hipLaunchKernelGGL((gemm_tn_pipe_kernel<TM, TN, NS, OCC, PRIO>), grid, block, 0, s, gg);
+  hipLaunchKernelGGL((gemm_tn_pipe_kernel<TM, TN, NS, OCC>), grid, block, 0, s, g);
   NNR_CHECK_LAUNCH();
   return NNR_OK;
 }
@@ -1441,41 +1411,8 @@ __global__ __launch_bounds__(256, OCC) void gemm_tn_pipe2_kernel(nnr_gemm_args g
   if (g.dyn_dim == 2) K = min(K, *g.dyn_dev);
   const int nbm = (M + BM - 1) / BM, nbn = (N + BN - 1) / BN;
   const int nblk = nbm * nbn;
-  // blockIdx -> (tile, reduction slice).  The host sizes split_k for the CAPACITY of the token buffers; the live reduction length
-  // (device side) is typically a fifth of it: use only as many slices (eff) as keep a slice long enough to amortise its prologue
-  // and its atomic epilogue (~96 stages) while still giving every CU a workgroup or two; the surplus workgroups exit.
-  // With split-K the grid is 1-D and the eff x nblk workgroups, in slice-major order, are dealt to the XCDs in eight CONTIGUOUS
-  // runs (XCD = blockIdx.x % 8 under round-robin placement; speed only): all tiles of a slice run on one XCD (a slice that
-  // straddles a run boundary on two), so a token row of A and of B is pulled into one L2 instead of into every L2 whose
-  // workgroups touch it -- 4-5x the operand bytes at the fabric counters for the 400 x 400 and 832 x 200 shapes when the tiles of
-  // a slice are spread round-robin (profiles/pmc_traffic.json, round 2 first collection).  deal_mode 0 = that spread layout (A/B).
-  int v, z = 0;
-  int kbeg = 0, kend = K;
-  if (g.split_k > 1) {
-    const int deal_mode = g.sched & 3;                // set by the launcher
-    const int ktiles = (K + BK - 1) / BK;
-    const int eff = tn_eff_slices(g.split_k, g.sched, K, nblk, OCC * 256);
-    if (deal_mode) {
-      const int W = eff * nblk, per = (W + 7) >> 3;
-      const int L = blockIdx.x, x = L & 7, slot = L >> 3;
-      const int lin = x * per + slot;
-      if (slot >= per || lin >= W) return;
-      z = lin / nblk;
-      v = lin - z * nblk;
-    } else {
-      z = blockIdx.x / nblk;
-      v = blockIdx.x - z * nblk;
-      if (z >= eff) return;
-    }
-    const int per_k = (ktiles + eff - 1) / eff;
-    kbeg = z * per_k * BK;
-    kend = min(K, kbeg + per_k * BK);
-    if (kbeg >= kend) return;
-  } else {
-    const int b = blockIdx.x, q = nblk >> 3, rem = nblk & 7, x = b & 7, slot = b >> 3;
-    v = x * q + min(x, rem) + slot;
-  }
-  const int bm = v / nbn, bn = v - bm * nbn;
+  int bm, bn, z, kbeg, kend;
+  if (!tn_place(g.split_k, K, nbn, nblk, OCC * 256, bm, bn, z, kbeg, kend)) return;
   const int m0 = bm * BM, n0 = bn * BN;
   const float* __restrict__ A = g.A;
   const float* __restrict__ B = g.B;
@@ -1653,9 +1590,7 @@ int launch_tn_pipe2(const nnr_gemm_args& g, hipStream_t s) {
   constexpr int BM = 64 * TM, BN = 16 * TN;
   const int nbm = (g.M + BM - 1) / BM, nbn = (g.N + BN - 1) / BN;
   dim3 grid(g.split_k > 1 ? nbm * nbn * ((g.split_k + 7) / 8) * 8 : nbm * nbn), block(256);      // split-K: slices are dealt to XCDs (see the kernel)
-  nnr_gemm_args gg = g;
-  gg.sched = kTnSched;
-  hipLaunchKernelGGL((gemm_tn_pipe2_kernel<TM, TN, NS, OCC>), grid, block, 0, s, gg);
+  hipLaunchKernelGGL((gemm_tn_pipe2_kernel<TM, TN, NS, OCC>), grid, block, 0, s, g);
   NNR_CHECK_LAUNCH();
   return NNR_OK;
 }
@@ -1810,14 +1745,14 @@ int launch_skinny(const nnr_gemm_args& g, hipStream_t s) {
 // most two such launches per step -- the two encoder calls of the plugin API -- and two addends into a zeroed buffer commute).
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ slab, const float* __restrict__ cs_slab, float* __restrict__ C,
                                                             int ldc, float* __restrict__ colsum_out, int M, int N, int K, const int* __restrict__ dyn_dev,
-                                                            int split_k, int sched, int nblk, int slots, int bk, int kind) {
+                                                            int split_k, int nblk, int slots, int bk, int kind) {
   if (dyn_dev) K = min(K, *dyn_dev);
   int live;
   const int ktiles = (K + bk - 1) / bk;
   if (ktiles <= 0) {
     live = 0;
   } else if (kind == 1) {
-    const int eff = tn_eff_slices(split_k, sched, K, nblk, slots);
+    const int eff = tn_eff_slices(split_k, K, nblk, slots);
     const int per_k = (ktiles + eff - 1) / eff;
     live = min(eff, (ktiles + per_k - 1) / per_k);
   } else {
@@ -1854,42 +1789,68 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 
 }  // namespace
 
-// tile id -> (rows, columns, stage depth, workgroups per CU the kernel is built for, 1 = LDS-DMA TN tile with the device-side slice count)
-static bool tile_shape(int tile, int* bm, int* bn, int* bk, int* occ, int* kind) {
-  struct T { int tile, bm, bn, bk, occ, kind; };
-  static const T tab[] = {{2, 64, 80, 16, 1, 0}, {3, 128, 208, 16, 1, 0}, {4, 128, 80, 16, 1, 0}, {5, 128, 80, 32, 1, 0}, {6, 64, 80, 64, 1, 0},
-                          {20, 128, 80, 16, 3, 1}, {26, 128, 80, 16, 3, 1}, {27, 128, 208, 16, 2, 1}, {30, 128, 160, 16, 2, 1}, {32, 64, 208, 16, 2, 1}};
-  for (const T& t : tab)
-    if (t.tile == tile) { *bm = t.bm; *bn = t.bn; *bk = t.bk; *occ = t.occ; *kind = t.kind; return true; }
-  return false;
+// ------------------------------------------------------------------------------------------------ the tile table
+// One row per tile id (nnr_gemm_args.tile): what the id means is stated HERE only.  nnr_gemm_f32 launches through the row, the slab reduction
+// reads its shape, nnr_gemm_tile_info hands the rows to the host side (nnr_amd/_lib.py:gemm_tiles -- ops.tn_tile's shapes, the profile's
+// family names and profile.KERNEL_OF's kernel names), and the header's comment on `tile` points here.
+enum TileFamily { kRegStaged, kSkinny, kNtPipe, kNtPipe2, kNtBx3, kTnPipe, kTnPipe2 };
+struct TileRow {
+  int id;
+  TileFamily family;
+  int bm, bn, bk;           // rows, columns and reduction depth of a stage
+  int stages, occ;          // stage buffers; workgroups per CU the kernel is built for (0: no launch bound)
+  const char* suffix;       // the profile's family name is gemm_<nt | nn | tn>_<suffix>
+  const char* kernel;       // the instantiation as rocprofv3 prints it (register-staged: formatted from the row and the transposes; skinny: none,
+                            // launch_skinny picks the wave count per launch)
+  bool (*ok)(const nnr_gemm_args&);
+  int (*launch)(const nnr_gemm_args&, hipStream_t);
+};
+static bool skinny_ok(const nnr_gemm_args& g) {
+  if (g.pre_add || g.gate_bwd) return false;
+  return !(g.trans_a || g.a_idx || g.b_idx || g.c_idx || g.dyn_dev || g.split_k > 1 || g.k_chunk > 0 || g.rowdot_w || g.colsum_out || g.atomic ||
+           (g.drop_target != 0 && g.drop_target != 3));
 }
+// the template arguments are written once: they give the row's shape numbers, its kernel name and its launcher
+#define NNR_REG(ID, TM, TN, BK, SUFFIX) \
+  {ID, kRegStaged, 64 * TM, 16 * TN, BK, 2, 0, SUFFIX, nullptr, [](const nnr_gemm_args&) { return true; }, launch_cfg<TM, TN, BK>}
+#define NNR_NT1(ID, TM, TN, BK, NS, OCC, SUFFIX, OK) \
+  {ID, kNtPipe, 64 * TM, 16 * TN, BK, NS, OCC, SUFFIX, "gemm_nt_pipe_kernel<" #TM ", " #TN ", " #BK ", " #NS ", " #OCC ">", OK, launch_pipe<TM, TN, BK, NS, OCC>}
+#define NNR_BX3(ID, TM, TN, NS, OCC, SUFFIX) \
+  {ID, kNtBx3, 64 * TM, 16 * TN, 32, NS, OCC, SUFFIX, "gemm_nt_bx3_kernel<" #TM ", " #TN ", " #NS ">", bx3_ok, launch_bx3<TM, TN, NS>}
+#define NNR_PIPE(ID, FAMILY, KERNEL, LAUNCH, BK, TM, TN, NS, OCC, SUFFIX, OK) /* gen-2 NT (BK 32) and both TN loops (BK 16) */ \
+  {ID, FAMILY, 64 * TM, 16 * TN, BK, NS, OCC, SUFFIX, #KERNEL "<" #TM ", " #TN ", " #NS ", " #OCC ">", OK, LAUNCH<TM, TN, NS, OCC>}
+static const TileRow kTiles[] = {
+    NNR_REG(2, 1, 5, 16, "64x80"),         //  64 x 80
+    NNR_REG(3, 2, 13, 16, "128x208"),      // 128 x 208 (whole rows in one wave: fused row-dot)
+    NNR_REG(4, 2, 5, 16, "128x80"),        // 128 x 80 (4 waves/SIMD: more workgroups in flight per CU)
+    NNR_REG(5, 2, 5, 32, "128x80k32"),     // 128 x 80, BK = 32: half the barriers per FLOP, 3 workgroups per CU
+    NNR_REG(6, 1, 5, 64, "64x80k64"),      //  64 x 80, BK = 64: latency-bound small launches (few stages, 74 KB LDS)
+    {7, kSkinny, 16, 80, 16, 1, 0, "16x80skinny", nullptr, skinny_ok, launch_skinny},      // 16 x 80, K split over the waves (plain NT / NN launches only)
+    NNR_PIPE(9, kNtPipe2, gemm_nt_pipe2_kernel, launch_pipe2, 32, 2, 5, 3, 2, "pipe2_128x80", [](const nnr_gemm_args& g) { return pipe_ok(g) && !g.a_idx; }),      // gen-2 loop, 128 x 80, 3 x 26 KB stages, 2 workgroups / CU
+    NNR_NT1(15, 2, 5, 16, 3, 4, "pipe128x80", pipe_ok),        // 128 x 80, BK 16, 3 x 13 KB stages, 4 workgroups / CU
+    NNR_NT1(16, 2, 5, 16, 2, 5, "pipe128x80s2", pipe_ok),      // 128 x 80, BK 16, 2 stages, 5-6 workgroups / CU
+    NNR_PIPE(20, kTnPipe, gemm_tn_pipe_kernel, launch_tn_pipe, 16, 2, 5, 3, 3, "pipe128x80", tn_pipe_ok), // TN 128 x 80, 3 x 16 KB stages
+    NNR_PIPE(26, kTnPipe2, gemm_tn_pipe2_kernel, launch_tn_pipe2, 16, 2, 5, 3, 3, "pipe2_128x80", [](const nnr_gemm_args& g) { return tn_pipe_ok(g) && !g.b_idx; }),      // gen-2 TN 128 x 80 (no gather)
+    NNR_PIPE(27, kTnPipe2, gemm_tn_pipe2_kernel, launch_tn_pipe2, 16, 2, 13, 3, 2, "pipe2_128x208", tn_pipe_ok), // gen-2 TN 128 x 208
+    NNR_PIPE(30, kTnPipe2, gemm_tn_pipe2_kernel, launch_tn_pipe2, 16, 2, 10, 3, 2, "pipe2_128x160", tn_pipe_ok), // gen-2 TN 128 x 160 (N = 300 in two column blocks)
+    NNR_PIPE(32, kTnPipe2, gemm_tn_pipe2_kernel, launch_tn_pipe2, 16, 1, 13, 3, 2, "pipe2_64x208", tn_pipe_ok), // gen-2 TN 64 x 208, 3 x 20 KB stages: row tiles of 64 fit M = 200 / 400 / 832
+                                                               // (256 / 448 / 832 rows of MFMA work instead of 256 / 512 / 896)
+    NNR_BX3(50, 2, 5, 2, 2, "bx3_128x80"),                     // bf16x3 NT 128 x 80 (needs args.B3: pre-split weights)
+    NNR_BX3(51, 1, 5, 2, 3, "bx3_64x80"),                      // ... 64 x 80: 2 x 23 KB stages, 3 workgroups / CU
+};
+#undef NNR_REG
+#undef NNR_NT1
+#undef NNR_BX3
+#undef NNR_PIPE
 
-static int dispatch_tile(int tile, const nnr_gemm_args& g, hipStream_t stream) {
-  switch (tile) {
-    case 2: return launch_cfg<1, 5, 16>(g, stream);    //  64 x 80
-    case 3: return launch_cfg<2, 13, 16>(g, stream);   // 128 x 208 (whole rows in one wave: fused row-dot)
-    case 4: return launch_cfg<2, 5, 16>(g, stream);    // 128 x 80 (4 waves/SIMD: more workgroups in flight per CU)
-    case 5: return launch_cfg<2, 5, 32>(g, stream);   // 128 x 80, BK = 32: half the barriers per FLOP, 3 workgroups per CU
-    case 6: return launch_cfg<1, 5, 64>(g, stream);   //  64 x 80, BK = 64: latency-bound small launches (few stages, 74 KB LDS)
-    case 9:  if (!pipe_ok(g) || g.a_idx) return NNR_ERR_ARG; return launch_pipe2<2, 5, 3, 2>(g, stream);    // gen-2 loop, 128 x 80, 3 x 26 KB stages, 2 workgroups / CU
-    case 15: if (!pipe_ok(g)) return NNR_ERR_ARG; return launch_pipe<2, 5, 16, 3, 4>(g, stream);   // 128 x 80, BK 16, 3 x 13 KB stages, 4 workgroups / CU
-    case 16: if (!pipe_ok(g)) return NNR_ERR_ARG; return launch_pipe<2, 5, 16, 2, 5>(g, stream);   // 128 x 80, BK 16, 2 stages, 5-6 workgroups / CU
-    case 20: if (!tn_pipe_ok(g)) return NNR_ERR_ARG; return launch_tn_pipe<2, 5, 3, 3>(g, stream);   // TN 128 x 80, 3 x 16 KB stages
-    case 26: if (!tn_pipe_ok(g) || g.b_idx) return NNR_ERR_ARG; return launch_tn_pipe2<2, 5, 3, 3>(g, stream);    // gen-2 TN 128 x 80 (no gather)
-    case 27: if (!tn_pipe_ok(g)) return NNR_ERR_ARG; return launch_tn_pipe2<2, 13, 3, 2>(g, stream);              // gen-2 TN 128 x 208
-    case 30: if (!tn_pipe_ok(g)) return NNR_ERR_ARG; return launch_tn_pipe2<2, 10, 3, 2>(g, stream);              // gen-2 TN 128 x 160 (N = 300 in two column blocks)
-    case 50: if (!bx3_ok(g)) return NNR_ERR_ARG; return launch_bx3<2, 5, 2>(g, stream);           // bf16x3 NT 128 x 80 (needs args.B3: pre-split weights)
-    case 51: if (!bx3_ok(g)) return NNR_ERR_ARG; return launch_bx3<1, 5, 2>(g, stream);        // ... 64 x 80: 2 x 23 KB stages, 3 workgroups / CU
-    case 32: if (!tn_pipe_ok(g)) return NNR_ERR_ARG; return launch_tn_pipe2<1, 13, 3, 2>(g, stream);              // gen-2 TN 64 x 208, 3 x 20 KB stages: row tiles of 64 fit M = 200 / 400 / 832
-                                                                                                                  // (256 / 448 / 832 rows of MFMA work instead of 256 / 512 / 896)
-    case 7:
-      if (g.pre_add || g.gate_bwd) return NNR_ERR_ARG;
-      if (g.trans_a || g.a_idx || g.b_idx || g.c_idx || g.dyn_dev || g.split_k > 1 || g.k_chunk > 0 || g.rowdot_w || g.colsum_out || g.atomic ||
-          (g.drop_target != 0 && g.drop_target != 3)) return NNR_ERR_ARG;
-      return launch_skinny(g, stream);
-    default: return NNR_ERR_ARG;
-  }
+static const TileRow* tile_row(int tile) {
+  for (const TileRow& t : kTiles)
+    if (t.id == tile) return &t;
+  return nullptr;
 }
+// operand layouts a family has kernels for: bit 0 NT (trans_a = trans_b = 0), bit 1 NN (trans_b), bit 2 TN (both); (A^T, B[N,K]) never occurs
+static int family_layouts(TileFamily f) { return f == kRegStaged ? 7 : f == kSkinny ? 3 : (f == kTnPipe || f == kTnPipe2) ? 4 : 1; }
+static int layout_bit(int trans_a, int trans_b) { return trans_a ? (trans_b ? 4 : 0) : (trans_b ? 2 : 1); }
 
 extern "C" int nnr_split_bf16x3(const float* w, int rows, int cols, int ld, int ldo, void* out3, long img_stride, hipStream_t stream) {
   if (!w || !out3 || rows <= 0 || cols <= 0 || ld < cols || ldo < cols || (ldo & 7) || img_stride < (long)rows * ldo) return NNR_ERR_ARG;
@@ -1900,11 +1861,51 @@ extern "C" int nnr_split_bf16x3(const float* w, int rows, int cols, int ld, int 
   return NNR_OK;
 }
 
-extern "C" int nnr_gemm_f32(const nnr_gemm_args* a, hipStream_t stream) {
+// the automatic choice (tile == 0), on the normalised arguments
+static int choose_tile(const nnr_gemm_args& g) {
+  int tile;
+  const long wg128 = (long)((g.M + 127) / 128) * ((g.N + 79) / 80) * (g.k_chunk > 0 ? (g.K + g.k_chunk - 1) / g.k_chunk : (g.split_k > 1 ? g.split_k : (g.batch > 1 ? g.batch : 1)));
+  const long wg64 = (long)((g.M + 63) / 64) * ((g.N + 79) / 80) * (g.split_k > 1 ? g.split_k : (g.batch > 1 ? g.batch : 1));
+  const bool plain = !g.trans_a && !g.a_idx && !g.b_idx && !g.c_idx && !g.dyn_dev && g.split_k <= 1 && g.k_chunk <= 0 && !g.rowdot_w &&
+                     !g.colsum_out && !g.atomic && (g.drop_target == 0 || g.drop_target == 3) && !g.pre_add && !g.gate_bwd;
+  if (g.rowdot_w) tile = 3;
+  else if (plain && wg64 <= 512 && g.K >= 64) tile = 7;   // small row-parallel launch: 16 x 80 tiles, K split over the 4 waves
+  else if (pipe_ok(g) && !g.a_idx && g.K >= 800 && wg64 > 512) {
+    tile = 9;              // long reductions (dX: K = 1664, SUE: K = 900): the
+                           // software-pipelined loop with the lean DMA issue, 2 workgroups / CU (130 vs 112 TF, 93 vs 79 TF)
+  }
+  else if (pipe_ok(g) && (g.dyn_dev || wg128 >= 640)) tile = 15;   // GPU-filling NT: LDS-DMA staged 128 x 80, BK 16, 4 workgroups / CU
+                           // (112 vs 98 TF on the 131 072-row CNE shapes, tools/gemm_pipe_bench.py)
+  else if (pipe_ok(g) && wg64 > 512 && g.K >= 128) tile = 16;      // mid-size NT (SUE: 4 352 x 900 x 900): same tile, two 13 KB stages,
+                           // 5-6 workgroups / CU cover the round trips (79 vs 65-72 TF)
+  else if (wg64 <= 512 && !g.dyn_dev && g.k_chunk <= 0 && g.K >= 128 && !g.trans_a) tile = 6;   // (not for TN: the small weight-gradient
+                           // launches run on the leaf stream BESIDE the recurrence, whose workgroups hold 98 KB of LDS per CU; a 74 KB tile cannot
+                           // move in next to them and waits for free CUs, the 19 KB tile can: 12.60 vs 12.70 ms/step)   // at most 2 workgroups per CU: nothing hides the
+                           // memory round trip each k-stage pays with a one-stage prefetch -> BK = 64, 4x fewer stages
+  else if (g.M <= 512 || (wg128 < 640 && !g.dyn_dev)) tile = 2;   // too few 128-row tiles to fill 256 CUs x 4: use 64-row tiles
+  else if (g.trans_a) tile = 2;   // TN (token-reduction dW): callers pick the LDS-DMA tiles 20 / 24 explicitly (their split-K factor
+                                  // depends on the tile); this is the register-staged fallback
+  else if (!g.trans_a && !g.trans_b) tile = 5;   // NT that the pipelined kernel cannot take (unaligned operands)
+  else tile = 4;           // NN with a K-major B (activations on both sides, or a weight the caller did not transpose)
+  return tile;
+}
+
+// What a call launches: the normalised arguments, the caller's C / colsum_out of a slab launch, and the table row (nullptr: an empty product,
+// nothing runs).  nnr_gemm_f32 launches exactly this and nnr_gemm_tile_for answers from it, so the two cannot differ.
+struct GemmPlan {
+  nnr_gemm_args g;
+  float* slab_C;
+  float* slab_cs;
+  int slab_ldc;
+  const TileRow* row;
+};
+static int gemm_plan(const nnr_gemm_args* a, GemmPlan* p) {
+  *p = GemmPlan{};
   if (!a || !a->A || !a->B) return NNR_ERR_ARG;
   if (!a->C && !a->rowdot_out && !a->aux_out) return NNR_ERR_ARG;
   if (a->M <= 0 || a->N <= 0 || a->K <= 0) return NNR_OK;
-  nnr_gemm_args g = *a;
+  nnr_gemm_args& g = p->g;
+  g = *a;
   g.drop_thresh = nnr_drop_thresh(g.drop_target ? g.drop_p : 0.f);
   g.drop_scale = (g.drop_target && g.drop_p > 0.f) ? 1.f / (1.f - g.drop_p) : 1.f;
   if (g.drop_thresh == 0u) g.drop_target = 0;
@@ -1927,54 +1928,55 @@ extern "C" int nnr_gemm_f32(const nnr_gemm_args* a, hipStream_t stream) {
     if (g.gate_bwd && (!g.C || !g.aux_out || !g.mul || !g.resid || g.bias || g.rowvec || g.act || g.drop_target || g.accumulate || g.rowdot_w)) return NNR_ERR_ARG;
   }
   // reproducible split-K: the slices store into the caller's slab, a second launch adds them in slice order (splitk_reduce_kernel)
-  float* slab_C = nullptr;
-  float* slab_cs = nullptr;
-  int slab_ldc = 0;
   if (g.slab != nullptr) {
     if (!(g.trans_a && g.trans_b) || g.split_k <= 1 || g.k_chunk > 0 || g.c_idx || (g.N & 3) || (((uintptr_t)g.slab) & 15) || !g.C || g.accumulate == 2 ||
         g.slab_floats < (long)g.split_k * ((long)g.M * g.N + g.M))
       return NNR_ERR_ARG;
-    slab_C = g.C; slab_ldc = g.ldc; slab_cs = g.colsum_out;
+    p->slab_C = g.C; p->slab_ldc = g.ldc; p->slab_cs = g.colsum_out;
     g.C = g.slab; g.ldc = g.N; g.atomic = 0; g.accumulate = 0; g.slab_mode = 1; g.vec_epi = 1;
     if (g.colsum_out) g.colsum_out = g.slab + (long)g.split_k * g.M * g.N;
   } else {
     g.slab_mode = 0;
   }
-  int tile = g.tile;
-  if (tile == 0) {
-    const long wg128 = (long)((g.M + 127) / 128) * ((g.N + 79) / 80) * (g.k_chunk > 0 ? (g.K + g.k_chunk - 1) / g.k_chunk : (g.split_k > 1 ? g.split_k : (g.batch > 1 ? g.batch : 1)));
-    const long wg64 = (long)((g.M + 63) / 64) * ((g.N + 79) / 80) * (g.split_k > 1 ? g.split_k : (g.batch > 1 ? g.batch : 1));
-    const bool plain = !g.trans_a && !g.a_idx && !g.b_idx && !g.c_idx && !g.dyn_dev && g.split_k <= 1 && g.k_chunk <= 0 && !g.rowdot_w &&
-                       !g.colsum_out && !g.atomic && (g.drop_target == 0 || g.drop_target == 3) && !g.pre_add && !g.gate_bwd;
-    if (g.rowdot_w) tile = 3;
-    else if (plain && wg64 <= 512 && g.K >= 64) tile = 7;   // small row-parallel launch: 16 x 80 tiles, K split over the 4 waves
-    else if (pipe_ok(g) && !g.a_idx && g.K >= 800 && wg64 > 512) {
-      tile = 9;              // long reductions (dX: K = 1664, SUE: K = 900): the
-                             // software-pipelined loop with the lean DMA issue, 2 workgroups / CU (130 vs 112 TF, 93 vs 79 TF)
-    }
-    else if (pipe_ok(g) && (g.dyn_dev || wg128 >= 640)) tile = 15;   // GPU-filling NT: LDS-DMA staged 128 x 80, BK 16, 4 workgroups / CU
-                             // (112 vs 98 TF on the 131 072-row CNE shapes, tools/gemm_pipe_bench.py)
-    else if (pipe_ok(g) && wg64 > 512 && g.K >= 128) tile = 16;      // mid-size NT (SUE: 4 352 x 900 x 900): same tile, two 13 KB stages,
-                             // 5-6 workgroups / CU cover the round trips (79 vs 65-72 TF)
-    else if (wg64 <= 512 && !g.dyn_dev && g.k_chunk <= 0 && g.K >= 128 && !g.trans_a) tile = 6;   // (not for TN: the small weight-gradient
-                             // launches run on the leaf stream BESIDE the recurrence, whose workgroups hold 98 KB of LDS per CU; a 74 KB tile cannot
-                             // move in next to them and waits for free CUs, the 19 KB tile can: 12.60 vs 12.70 ms/step)   // at most 2 workgroups per CU: nothing hides the
-                             // memory round trip each k-stage pays with a one-stage prefetch -> BK = 64, 4x fewer stages
-    else if (g.M <= 512 || (wg128 < 640 && !g.dyn_dev)) tile = 2;   // too few 128-row tiles to fill 256 CUs x 4: use 64-row tiles
-    else if (g.trans_a) tile = 2;   // TN (token-reduction dW): callers pick the LDS-DMA tiles 20 / 24 explicitly (their split-K factor
-                                    // depends on the tile); this is the register-staged fallback
-    else if (!g.trans_a && !g.trans_b) tile = 5;   // NT that the pipelined kernel cannot take (unaligned operands)
-    else tile = 4;           // NN with a K-major B (activations on both sides, or a weight the caller did not transpose)
-  }
-  const int rc = dispatch_tile(tile, g, stream);
+  const TileRow* row = tile_row(g.tile == 0 ? choose_tile(g) : g.tile);
+  // (the fused row-dot needs whole rows in one column block)
+  if (!row || !(family_layouts(row->family) & layout_bit(g.trans_a, g.trans_b)) || !row->ok(g) || (g.rowdot_w && g.N > row->bn)) return NNR_ERR_ARG;
+  p->row = row;
+  return NNR_OK;
+}
+
+extern "C" int nnr_gemm_tile_for(const nnr_gemm_args* args) {
+  GemmPlan p;
+  const int rc = gemm_plan(args, &p);
+  return rc != NNR_OK ? rc : (p.row ? p.row->id : 0);
+}
+
+extern "C" int nnr_gemm_tile_info(int index, int trans_a, int trans_b, int* dims, char* suffix, char* kernel, int cap) {
+  if (index < 0 || index >= (int)(sizeof(kTiles) / sizeof(kTiles[0])) || !dims || !suffix || !kernel || cap < 64) return NNR_ERR_ARG;
+  const TileRow& t = kTiles[index];
+  if (!(family_layouts(t.family) & layout_bit(trans_a, trans_b))) return NNR_ERR_UNSUPPORTED;
+  const int d[6] = {t.id, t.bm, t.bn, t.bk, t.stages, t.occ};
+  for (int i = 0; i < 6; ++i) dims[i] = d[i];
+  snprintf(suffix, cap, "%s", t.suffix);
+  if (t.family == kRegStaged) snprintf(kernel, cap, "gemm_kernel<%d, %d, %s, %s, %d>", t.bm / 64, t.bn / 16, trans_a ? "true" : "false", trans_b ? "true" : "false", t.bk);
+  else snprintf(kernel, cap, "%s", t.kernel ? t.kernel : "");
+  return NNR_OK;
+}
+
+extern "C" int nnr_gemm_f32(const nnr_gemm_args* a, hipStream_t stream) {
+  GemmPlan p;
+  int rc = gemm_plan(a, &p);
+  if (rc != NNR_OK || !p.row) return rc;
+  const nnr_gemm_args& g = p.g;
+  rc = p.row->launch(g, stream);
   if (rc != NNR_OK || !g.slab_mode) return rc;
-  int bm, bn, bk, occ, kind;
-  if (!tile_shape(tile, &bm, &bn, &bk, &occ, &kind)) return NNR_ERR_ARG;
-  const int nblk = ((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn);
+  const TileRow& t = *p.row;
+  const int nblk = ((g.M + t.bm - 1) / t.bm) * ((g.N + t.bn - 1) / t.bn);
   const long mn4 = ((long)g.M * g.N) >> 2;
   const int blocks = (int)(mn4 / 256 + 1 > 2048 ? 2048 : mn4 / 256 + 1);
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)g.slab, (const float*)g.colsum_out, slab_C, slab_ldc, slab_cs,
-                     g.M, g.N, g.K, g.dyn_dim == 2 ? g.dyn_dev : (const int*)nullptr, g.split_k, kTnSched, nblk, occ * 256, bk, kind);
+  // (kind 1: the LDS-DMA TN tiles count their slices on the device)
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)g.slab, (const float*)g.colsum_out, p.slab_C, p.slab_ldc, p.slab_cs,
+                     g.M, g.N, g.K, g.dyn_dim == 2 ? g.dyn_dev : (const int*)nullptr, g.split_k, nblk, t.occ * 256, t.bk, (t.family == kTnPipe || t.family == kTnPipe2) ? 1 : 0);
   NNR_CHECK_LAUNCH();
   return NNR_OK;
 }

@@ -422,6 +422,11 @@ def lstm_prefetch(dev, lstms, H, E):
         _on_leaf(dev, jobs, launch)
 
 
+def _tn_sized(tile, target):
+    t = L.gemm_tiles()[tile or 2]        # (0: the library chooses; its register-staged fallback for TN is the 64 x 80 tile 2)
+    return tile, t.rows, t.cols, target
+
+
 def tn_tile(M, N, K, gather=False):
     """Tile of a token-reduction (weight-gradient) GEMM C[M,N] += A[K,M]^T B[K,N] and the tile dims its split-K factor is sized
     for: the LDS-DMA staged tiles of csrc/gemm.hip (gemm_tn_pipe_kernel) as (tile id, rows, cols, workgroups to aim for).  Measured
@@ -429,18 +434,18 @@ def tn_tile(M, N, K, gather=False):
     68 -> 86, 400x400 75 -> 82, 200x400 62 -> 73 (128x208); short reductions stay on the register-staged 64x80 tile.  (The 53 KB
     128 x 80 tile everywhere lost to the 78 KB 128 x 208 one for N = 200 / 400 once the recurrence held 120-130 KB: 11.43 vs 11.38 ms.)"""
     if K >= 2048 and M >= 512 and N >= 512 and not gather and not ((M & 3) or (N & 3)):
-        return 26, 128, 80, 2048          # SUE's 900 x 900 x 4 352 weight gradients: 8 slices of 544 rows instead of 12 of 363 on the 64 x 80 tile
+        return _tn_sized(26, 2048)            # SUE's 900 x 900 x 4 352 weight gradients: 8 slices of 544 rows instead of 12 of 363 on the 64 x 80 tile
     if K < 8192 or (M & 3) or (N & 3) or (M >= 512 and N >= 512):
-        return 0, 64, 80, 2048
+        return _tn_sized(0, 2048)
     if not gather and M >= 1024 and 160 < N <= 320:
-        return 30, 128, 160, 2048         # dW_ih (1664 x 300): operand counter traffic 2.0x -> 1.5x -- A (d gates) is fetched twice, not 4x
+        return _tn_sized(30, 2048)            # 128 x 160: dW_ih (1664 x 300): operand counter traffic 2.0x -> 1.5x -- A (d gates) is fetched twice, not 4x
     if N <= 208 or (N > 320 and N <= 416):
         if gather or M % 128 != 0:
-            return 32, 64, 208, 640       # gen-2 loop, 64 x 208: M = 200 / 400 / 832 in 4 / 7 / 13 row tiles (256 / 448 / 832 rows of MFMA work, not 256 / 512 / 896)
-        return 27, 128, 208, 640          # gen-2 loop, 128 x 208 (one token row per DMA instruction: takes gathered rows)
+            return _tn_sized(32, 640)         # gen-2 loop, 64 x 208: M = 200 / 400 / 832 in 4 / 7 / 13 row tiles (256 / 448 / 832 rows of MFMA work, not 256 / 512 / 896)
+        return _tn_sized(27, 640)             # gen-2 loop, 128 x 208 (one token row per DMA instruction: takes gathered rows)
     if gather:
-        return 20, 128, 80, 2048          # gathered rows wider than 208 columns (dW_hh at --hidden_dim 212..256): tile 26 has no gather path
-    return 26, 128, 80, 2048             # gen-2 loop, 128 x 80
+        return _tn_sized(20, 2048)            # 128 x 80: gathered rows wider than 208 columns (dW_hh at --hidden_dim 212..256): tile 26 has no gather path
+    return _tn_sized(26, 2048)                # gen-2 loop, 128 x 80
 
 
 def split_for(m, n, k, tile_m=64, tile_n=80, target_blocks=2048, kmin=256):
@@ -524,6 +529,15 @@ def _bx3_wanted(A, B, M, N, K, lda, ldb, trans_a, trans_b, a_idx, b_idx, c_idx, 
             and (K | lda | ldb) & 3 == 0 and (A.data_ptr() | B.data_ptr()) & 15 == 0 and (drop is None or drop[0] in (3, 4) or drop[1] <= 0.0))
 
 
+def gemm_family(g):
+    """The live profile's kernel family of the launch nnr_gemm_f32 makes for the filled argument struct `g`: asked of the library
+    (nnr_gemm_tile_for -- the function the launch itself chooses with), named from its tile table."""
+    t = L.lib().nnr_gemm_tile_for(C.byref(g))
+    L.check(min(t, 0), 'nnr_gemm_f32', counted=False)
+    tiles = L.gemm_tiles()
+    return 'gemm_%s_%s' % ('tn' if g.trans_a else ('nn' if g.trans_b else 'nt'), tiles[t].suffix if t in tiles else 'tile%d' % t)
+
+
 def gemm(A, B, C_=None, *, M, N, K, lda, ldb, ldc=0, trans_a=False, trans_b=False, dyn=None, dyn_dim=0, a_idx=None, b_idx=None,
          drop=None, alpha=1.0, bias=None, rowvec=None, ldrv=0, rowvec_map=None, act=0, aux_out=None, ldaux=0, mul=None, ldmul=0,
          resid=None, ldres=0, accumulate=False, atomic=False, c_idx=None, split_k=1, rowdot_w=None, rowdot_out=None, batch=1,
@@ -604,33 +618,7 @@ def gemm(A, B, C_=None, *, M, N, K, lda, ldb, ldc=0, trans_a=False, trans_b=Fals
     if not _prof.active():
         L.check(L.lib().nnr_gemm_f32(C.byref(g), _s()), 'nnr_gemm_f32')
         return
-    pipe_nt = (not trans_a and not trans_b and b_idx is None and split_k <= 1 and k_chunk <= 0 and rowdot_w is None and colsum_out is None
-               and (drop is None or drop[0] in (3, 4) or drop[1] <= 0.0) and (K | lda | ldb) & 3 == 0 and (A.data_ptr() | B.data_ptr()) & 15 == 0)
-    wg128 = ((M + 127) // 128) * ((N + 79) // 80) * (split_k if split_k > 1 else max(1, batch)) * (1 if k_chunk <= 0 else max(1, K // k_chunk))
-    # mirror of the library's tile choice (csrc/gemm.hip:nnr_gemm_f32), only to NAME the kernel family in the live profile
-    wg64 = ((M + 63) // 64) * ((N + 79) // 80) * (split_k if split_k > 1 else max(1, batch))
-    if tile:
-        t = tile
-    elif rowdot_w is not None:
-        t = 3
-    elif (not trans_a and a_idx is None and b_idx is None and c_idx is None and dyn is None and split_k <= 1 and k_chunk <= 0
-          and colsum_out is None and not atomic and wg64 <= 512 and K >= 64 and drop is None):
-        t = 7
-    elif pipe_nt and a_idx is None and K >= 800 and wg64 > 512:
-        t = 9
-    elif pipe_nt and (dyn is not None or wg128 >= 640):
-        t = 15
-    elif pipe_nt and wg64 > 512 and K >= 128:
-        t = 16
-    elif wg64 <= 512 and dyn is None and k_chunk <= 0 and K >= 128:
-        t = 6
-    elif M <= 512 or (wg128 < 640 and dyn is None) or trans_a:
-        t = 2
-    else:
-        t = 5 if not trans_b else 4
-    fam = 'gemm_%s_%s' % ('tn' if trans_a else ('nn' if trans_b else 'nt'),
-                          {2: '64x80', 3: '128x208', 4: '128x80', 5: '128x80k32', 6: '64x80k64', 7: '16x80skinny', 9: 'pipe2_128x80', 15: 'pipe128x80', 16: 'pipe128x80s2',
-                           20: 'pipe128x80', 26: 'pipe2_128x80', 27: 'pipe2_128x208', 30: 'pipe2_128x160', 32: 'pipe2_64x208', 50: 'bx3_128x80', 51: 'bx3_64x80'}.get(t, 'tile%d' % t))
+    fam = gemm_family(g)
 
     def flops(vals=None, M=M, N=N, K=K, dyn=dyn, dyn_dim=dyn_dim, batch=batch):
         # vals: {data_ptr of a device-side size: its value at the time of the launch} (replayed launches: the size buffers are
@@ -691,9 +679,9 @@ def linear_bwd_weight(dy, x, dw, dyn=None, rows=None, db=None, small_lds=False, 
     N, K = dw.shape
     t, bm, bn, target = tn_tile(N, K, R)
     if small_lds:
-        t, bm, bn, target = 2, 64, 80, 2048
+        t, bm, bn, target = _tn_sized(2, 2048)
     if t and ((dy.stride(0) | x.stride(0)) & 3 or (dy.data_ptr() | x.data_ptr()) & 15):
-        t, bm, bn, target = 0, 64, 80, 2048
+        t, bm, bn, target = _tn_sized(0, 2048)
     gemm(dy, x, dw, M=N, N=K, K=R, lda=dy.stride(0), ldb=x.stride(0), ldc=dw.stride(0), trans_a=True, trans_b=True,
          atomic=True, dyn=dyn, dyn_dim=2, colsum_out=db, split_k=split_for(N, K, R, bm, bn, target), tile=t, **kw)
 

@@ -3,6 +3,7 @@ launch (the kernels run on torch's current stream, so torch.cuda.Event sees them
 launch (true dims, not the padded tile dims; data-dependent token counts are read back from device memory after the
 timed region).  Families map 1:1 to kernel symbols, so the rocprofv3 --kernel-trace --stats averages under profiles/
 can be compared directly."""
+import functools
 import os
 
 import torch
@@ -10,21 +11,20 @@ import torch
 _on = False
 _records = []          # (family, start, end, flops_fn)
 
-KERNEL_OF = {
-    'gemm_nt_256x80': 'gemm_kernel<4, 5, false, false, 16>', 'gemm_nn_256x80': 'gemm_kernel<4, 5, false, true, 16>',
-    'gemm_tn_256x80': 'gemm_kernel<4, 5, true, true, 16>', 'gemm_nt_64x80': 'gemm_kernel<1, 5, false, false, 16>',
-    'gemm_nn_64x80': 'gemm_kernel<1, 5, false, true, 16>', 'gemm_tn_64x80': 'gemm_kernel<1, 5, true, true, 16>',
-    'gemm_nt_128x208': 'gemm_kernel<2, 13, false, false, 16>', 'gemm_nt_128x80': 'gemm_kernel<2, 5, false, false, 16>', 'gemm_nt_128x80k32': 'gemm_kernel<2, 5, false, false, 32>',
-    'gemm_nt_64x80k64': 'gemm_kernel<1, 5, false, false, 64>', 'gemm_nn_64x80k64': 'gemm_kernel<1, 5, false, true, 64>',
-    'gemm_tn_64x80k64': 'gemm_kernel<1, 5, true, true, 64>',
-    'gemm_nt_pipe128x80': 'gemm_nt_pipe_kernel<2, 5, 16, 3, 4, 0>', 'gemm_nt_pipe128x80s2': 'gemm_nt_pipe_kernel<2, 5, 16, 2, 5, 0>',
-    'gemm_nt_bx3_128x80': 'gemm_nt_bx3_kernel<2, 5, 2>', 'gemm_nt_bx3_64x80': 'gemm_nt_bx3_kernel<1, 5, 2>',
-    'gemm_nt_pipe2_128x80': 'gemm_nt_pipe2_kernel<2, 5, 3, 2>', 'gemm_nt_pipe2_128x64': 'gemm_nt_pipe2_kernel<2, 4, 3, 2>',
-    'gemm_tn_pipe2_128x80': 'gemm_tn_pipe2_kernel<2, 5, 3, 3>', 'gemm_tn_pipe2_128x208': 'gemm_tn_pipe2_kernel<2, 13, 3, 2>', 'gemm_tn_pipe2_128x160': 'gemm_tn_pipe2_kernel<2, 10, 3, 2>', 'gemm_tn_pipe2_64x208': 'gemm_tn_pipe2_kernel<1, 13, 3, 2>',
-    'gemm_tn_pipe128x80': 'gemm_tn_pipe_kernel<2, 5, 3, 3, 0>', 'gemm_tn_pipe128x208': 'gemm_tn_pipe_kernel<2, 13, 3, 2, 0>',
-    'gemm_nn_128x80': 'gemm_kernel<2, 5, false, true, 16>', 'gemm_tn_128x80': 'gemm_kernel<2, 5, true, true, 16>', 'lstm_fwd': 'lstm_fwd_pair_kernel<13>', 'lstm_bwd': 'lstm_bwd_pair_kernel<13, true>',
-    'gru_fwd': 'gru_fwd_kernel<13>', 'gru_bwd': 'gru_bwd_kernel<13>',
-}
+@functools.lru_cache(maxsize=None)
+def kernels():
+    """family -> kernel symbol as rocprofv3 prints it (also readable as profile.KERNEL_OF).  The GEMM families come from the library's tile
+    table (csrc/gemm.hip: kTiles), so this is made on first use: the library has to be built by then."""
+    from . import _lib
+    d = {'lstm_fwd': 'lstm_fwd_pair_kernel<13>', 'lstm_bwd': 'lstm_bwd_pair_kernel<13, true>', 'gru_fwd': 'gru_fwd_kernel<13>', 'gru_bwd': 'gru_bwd_kernel<13>'}
+    d.update(('gemm_%s_%s' % (lay, t.suffix), k) for t in _lib.gemm_tiles().values() for lay, k in t.kernels.items() if k)
+    return d
+
+
+def __getattr__(name):
+    if name == 'KERNEL_OF':
+        return kernels()
+    raise AttributeError(name)
 
 
 _enabled, _every = False, 1
@@ -310,7 +310,7 @@ def weight_gradient_traffic():
     res = {}
     tot_op = tot_hbm = 0.0
     for family, d in tn_operand_bytes().items():
-        hbm = pmc_traffic(KERNEL_OF.get(family, family))
+        hbm = pmc_traffic(kernels().get(family, family))
         if hbm and d['launches']:
             op = d['bytes'] / d['launches']
             res[family] = {'operand_mb_per_launch': round(op / 1e6, 1), 'counter_mb_per_launch': round(hbm / 1e6, 1), 'ratio': round(hbm / op, 2)}
@@ -331,11 +331,11 @@ def roofline(peak_tflops, sampled_steps=None, ms_per_step=None):
     ach = d['flops'] / (d['ms'] * 1e-3) / 1e12 if d['ms'] > 0 else 0.0
     return {
         'bound': 'mfma', 'achieved': round(ach, 3), 'peak': peak_tflops, 'unit': 'TFLOP/s', 'frac': round(ach / peak_tflops, 4),
-        'traffic': pmc_traffic(KERNEL_OF.get(name, name)), 'traffic_source': 'profiles/pmc_traffic.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes '
+        'traffic': pmc_traffic(kernels().get(name, name)), 'traffic_source': 'profiles/pmc_traffic.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes '
         'of this command (PMC cannot be collected inside the timed run), FETCH_SIZE x2 per the gfx950 note; quoted only when the file\'s build_id equals the running build: ' + _PMC.get('why', ''),
         'algorithmic_bytes_per_launch': (lambda b: None if b is None else round(b))(operand_bytes(name)),
-        'traffic_over_algorithmic': (lambda t, b: None if not (t and b) else round(t / b, 2))(pmc_traffic(KERNEL_OF.get(name, name)), operand_bytes(name)),
-        'kernel': KERNEL_OF.get(name, name), 'family': name, 'launches': d['launches'],
+        'traffic_over_algorithmic': (lambda t, b: None if not (t and b) else round(t / b, 2))(pmc_traffic(kernels().get(name, name)), operand_bytes(name)),
+        'kernel': kernels().get(name, name), 'family': name, 'launches': d['launches'],
         'avg_launch_us': round(1000 * d['ms'] / max(1, d['launches']), 2),
         'share_of_instrumented_time': round(d['ms'] / total_ms, 3),
         'families': {k: {'ms': round(v['ms'], 3), 'tflops': round(v['flops'] / (v['ms'] * 1e-3) / 1e12, 2) if v['ms'] > 0 else 0.0,
